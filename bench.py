@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- iterations/sec of the 2D->3D style-transfer optimisation step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,8 +15,12 @@ region (`--no-hoist` recomputes them every step like the reference does).  Scali
 every rank renders 8 views of the SAME texture, so the job does N*8 views per step;
 `value` counts 8-view iterations per second over the whole job (= steps/s * N).
 
-Prints ONE JSON line (rank 0).
-  roofline       the dominant kernel (the Winograd conv launches, ~80 % of the step) against the fp32-MFMA peak:
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times K steps and prints the headline (`value`,
+`ms_per_step` = wall time of the timed region / K, losses, configuration).  --dump-outputs DIR also writes what the last
+timed step computed (loss, optimised tensors and their gradients, rendered views) as DIR/<name>.npy; the inputs are
+seeded, so two builds run with the same arguments can be compared file by file.  --full adds, after the timed region,
+the measurements below (each needs further steps or runs of its own) and, with N > 1, the collective checks and timing:
+  roofline      the dominant kernel (the Winograd conv launches, ~80 % of the step) against the fp32-MFMA peak:
                  achieved = MFMA flops ISSUED (16 multiplies per 2x2 outputs, i.e. 16/36 of the direct convolution's
                  count) / HIP-event time on the launch stream, so frac <= 1 by construction; the direct-convolution
                  equivalent rate is reported separately as alg_equiv_tflops.
@@ -168,6 +172,26 @@ def time_ms(fn, reps=20, warm=3):
     return a.elapsed_time(b) / reps
 
 
+DUMP_BYTES = 64 * 10 ** 6           # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """arrays: name -> float32 / float64 numpy array, written as out_dir/<name>.npy.  Smallest first, each gets an equal
+    share of what is left of DUMP_BYTES; an array larger than its share is replaced by a fixed sample of its elements
+    (flat indices drawn with seed 0, sorted), so runs with the same arguments write the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].nbytes)
+    budget = DUMP_BYTES
+    for i, (name, a) in enumerate(items):
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        share = budget // (len(items) - i) - 128                # an .npy header is 128 bytes
+        if a.nbytes > share:
+            idx = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        budget -= a.nbytes + 128
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -178,9 +202,13 @@ def main():
     ap.add_argument("--mesh", choices=["cow", "bob", "teapot"], default="cow")
     ap.add_argument("--style", type=int, choices=[1, 3, 4, 5], default=1)
     ap.add_argument("--no-hoist", action="store_true", help="recompute content renders + VGG targets every step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--profile-kernels", action="store_true", help="per-kernel HIP events also when --gpus > 1")
-    ap.add_argument("--layers", action="store_true", help="add the per-layer table to the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure per-kernel times, rooflines, the CPU baseline and (N > 1) the "
+                         "collectives; off by default: a plain run times the steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--profile-kernels", action="store_true", help="with --full: per-kernel HIP events also when --gpus > 1")
+    ap.add_argument("--layers", action="store_true", help="with --full: add the per-layer table to the JSON line")
     ap.add_argument("--target", choices=["texture", "mesh", "both"], default="texture",
                     help="optimization_target (BASELINE configs[1] = texture; configs[4] = both)")
     ap.add_argument("--approach", choices=["second", "first_a", "first_b"], default="second",
@@ -194,6 +222,10 @@ def main():
     args = ap.parse_args()
     if args.approach != "second" and (args.gpus > 1 or args.background != "white" or args.no_hoist):
         raise SystemExit("bench.py: --approach first_a / first_b are single-GPU variants with the default backgrounds")
+    if (args.layers or args.profile_kernels) and not args.full:
+        raise SystemExit("bench.py: --layers / --profile-kernels add to the measurements of --full; pass --full as well")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     from st3d import launch as st3d_launch
     if not st3d_launch.under_launcher():
@@ -258,6 +290,7 @@ def main():
 
     content_tensors = content_targets()
     content_each_step = args.no_hoist or bg == "noise"  # the content VGG forward to conv4_2 cannot be (or is not) hoisted
+    kept = {} if args.dump_outputs else None             # --dump-outputs: the views the last step rendered
 
     def step_second():          # second_approach.py:145-190
         optimizer.zero_grad()
@@ -265,6 +298,8 @@ def main():
         mesh = U.build_mesh(out["verts_uvs"], out["faces_uvs"], texture_map, out["verts"], out["faces"])
         cur, masks = U.render_meshes(renderer, mesh, my_cams)
         cur = U.apply_background(cur, masks, background_type=bg, background=style_tensors)
+        if kept is not None:
+            kept["rendered"] = cur
         loss = L.compute_second_approach_loss(cur, content, style_tensors, vgg, 1e6, 1.0, out["verts"], verts, mesh,
                                               reg_weights, args.target, batch_denom=global_views)
         loss.backward()
@@ -297,6 +332,8 @@ def main():
         optimizer.zero_grad()
         mesh = U.build_mesh(out["verts_uvs"], out["faces_uvs"], texture_map, out["verts"], out["faces"])
         rendered, cov = U.render_meshes(renderer, mesh, my_cams)
+        if kept is not None:
+            kept["rendered"] = rendered
         loss = L.compute_first_approach_loss(rendered=rendered, masks=cov, target_rendered=targets_b, verts=out["verts"],
                                              target_verts=verts, mesh=mesh, weights=reg_weights, opt_type=args.target,
                                              batch_denom=global_views)
@@ -314,10 +351,11 @@ def main():
     comm = {}
     if world > 1:       # RCCL builds its communicator lazily on the first collective: keep that out of the timed steps even at --warmup 0
         torch.distributed.all_reduce(torch.zeros(texture_map.numel(), device=device))
-        comm = st3d_optim.comm_info(device)         # backend, ranks that answered a SUM of ones, RCCL version
-        ids = [None] * world
-        torch.distributed.all_gather_object(ids, "%s #%d" % (torch.cuda.get_device_name(device), device.index))
-        comm["devices_seen"] = ids
+        if args.full:
+            comm = st3d_optim.comm_info(device)         # backend, ranks that answered a SUM of ones, RCCL version
+            ids = [None] * world
+            torch.distributed.all_gather_object(ids, "%s #%d" % (torch.cuda.get_device_name(device), device.index))
+            comm["devices_seen"] = ids
     first_loss = None
     for _ in range(args.warmup):
         loss = step()
@@ -338,25 +376,43 @@ def main():
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     median_ms = per_step[len(per_step) // 2]
     final_loss, first_step_loss = float(loss.detach()), float(first_loss)
+    outputs = None
+    if args.dump_outputs and rank == 0:
+        # what the caller of the last timed step holds: the optimised tensors after its update, their gradients, and the
+        # views it rendered (this rank's shard); the loss follows below, summed over the ranks like final_loss
+        outputs = {"rendered": kept.get("rendered")}
+        if args.approach == "first_a":
+            outputs.update(pixels=pixels, pixels_grad=pixels.grad)
+        else:
+            outputs.update(texture=texture_map, texture_grad=texture_map.grad)
+            if args.target != "texture":
+                outputs.update(verts=out["verts"], verts_grad=out["verts"].grad)
+        outputs = {k: v.detach().float().cpu().numpy() for k, v in outputs.items() if v is not None}
     collectives_per_step = optimizer.collectives / float(max(args.warmup + args.steps, 1))
     allreduce_ms = allreduce_ms_min = None
     if world > 1:
-        # the one collective of the step (the flat gradient buffer of all optimised tensors), timed on its own right after
-        # the timed region (same message size, same stream)
-        g = torch.zeros(sum(q.numel() for q in optimizer.params), device=device)
-        allreduce_ms = time_ms(lambda: torch.distributed.all_reduce(g), reps=20, warm=3)
-        t = torch.tensor([elapsed, dev_ms, median_ms, allreduce_ms, -allreduce_ms], device=device, dtype=torch.float64)
+        if args.full:
+            # the one collective of the step (the flat gradient buffer of all optimised tensors), timed on its own right
+            # after the timed region (same message size, same stream)
+            g = torch.zeros(sum(q.numel() for q in optimizer.params), device=device)
+            allreduce_ms = time_ms(lambda: torch.distributed.all_reduce(g), reps=20, warm=3)
+        t = torch.tensor([elapsed, dev_ms, median_ms] + ([allreduce_ms, -allreduce_ms] if args.full else []), device=device,
+                         dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        elapsed, dev_ms, median_ms, allreduce_ms, allreduce_ms_min = (float(x) for x in t)
-        allreduce_ms_min = -allreduce_ms_min
+        elapsed, dev_ms, median_ms = (float(x) for x in t[:3])
+        if args.full:
+            allreduce_ms, allreduce_ms_min = float(t[3]), -float(t[4])
         lt = torch.tensor([final_loss, first_step_loss], device=device, dtype=torch.float64)
         torch.distributed.all_reduce(lt)
         final_loss, first_step_loss = float(lt[0]), float(lt[1])
+    if outputs is not None:
+        outputs["loss"] = np.array(final_loss, dtype=np.float64)
+        dump_outputs(args.dump_outputs, outputs)
 
     kernels, layers = None, None
     nprof = 5
     wino = os.environ.get("ST3D_CONV") != "direct"
-    if args.profile_kernels or world == 1:
+    if args.full and (args.profile_kernels or world == 1):
         # per-launch HIP events (recorded by libst3d on the stream the kernels are launched on) over nprof further
         # steps of the same loop, right after the timed region
         launches = []
@@ -481,105 +537,106 @@ def main():
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        s2 = (S / 512.0) ** 2
-        # algorithmic and issued MFMA flops of one step on this GPU
-        f_alg_step = sum(conv_alg_flops(m, S, Bv) for m, *_ in CONVS) * 2 + sum(gram_alg_flops(m, S, Bv) for m in STYLE_TAPS) * 2
-        if content_each_step:
-            f_alg_step += sum(conv_alg_flops(m, S, Bv) for m, *_ in CONVS if m <= 21)
-        f_wino_alg = sum(conv_alg_flops(m, S, Bv) for m, *_ in CONVS if m != 0) * 2
-        if content_each_step:
-            f_wino_alg += sum(conv_alg_flops(m, S, Bv) for m, *_ in CONVS if 0 < m <= 21)
-        wfams = ("conv_fwd", "conv_dgrad", "conv43_fwd", "conv43_dgrad")
-        if kernels and any(f in kernels for f in wfams):
-            # what the Winograd launches of a step actually issued: per launch F(2x2,3x3) = 16/36, F(4x4,3x3) = 36/144 of the
-            # direct count, as tagged by the plan's profile (conv_* / conv43_* families)
-            f_conv_issued_measured = sum(kernels[f]["_issued_flops"] for f in wfams if f in kernels)
-        else:
-            f_conv_issued_measured = None
-        f_issued_step = ((f_conv_issued_measured if f_conv_issued_measured is not None else f_wino_alg * (16.0 / 36.0)) if wino
-                         else f_wino_alg + 2 * conv_alg_flops(0, S, Bv)) \
-            + sum(gram_fwd_issued_flops(m, S, Bv) + gram_alg_flops(m, S, Bv) for m in STYLE_TAPS)
-        if os.environ.get("ST3D_TAP0_FUSED") != "0":
-            f_issued_step += 2.0 * 32 * 64 * S * S * Bv        # conv1_1's input gradient as an MFMA product (csrc/tap0.hip)
-        step_s = dev_ms / args.steps * 1e-3
         std_cfg = (S == 512 and Bv == 8 and not content_each_step and wino and args.mesh == "cow" and args.target == "texture"
                    and args.approach == "second")
-        traffic, tpath = {}, ""
-        if std_cfg:
-            import glob
-            tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))     # newest round last
-            if tfiles:
-                tpath = tfiles[-1]
-                with open(tpath) as fh:
-                    traffic = json.load(fh)
-        tsrc = ("committed rocprofv3 PMC passes %s (FETCH_SIZE raw + WRITE_SIZE per launch; gfx950 under-reports 16-B/lane "
-                "read streams by up to 2x), not re-measured in this run" % os.path.relpath(tpath, ROOT)) if traffic else None
-        step_roofline = {
-            "bound": "mfma", "achieved": round(f_issued_step / step_s / 1e12, 3), "peak": PEAK_FP32_MFMA / 1e12, "unit": "TFLOP/s",
-            "frac": round(f_issued_step / step_s / PEAK_FP32_MFMA, 4),
-            "alg_equiv_tflops": round(f_alg_step / step_s / 1e12, 3),
-            "traffic": (traffic["fetch_bytes_raw_per_step"] + traffic["write_bytes_per_step"]) if traffic else None,
-            "traffic_source": tsrc,
-            "note": "whole step per GPU (renders, losses, Adam and host gaps included): MFMA flops issued per step (%.1f GF: "
-                    "Winograd convs 16/36 (F(2x2,3x3)) or 36/144 (F(4x4,3x3)) of the direct count, Gram forward upper tiles only) over the HIP-event time of the "
-                    "timed region (%.3f ms/step); alg_equiv_tflops prices the same time with the direct-convolution count of "
-                    "SURVEY.md 8d (%.1f GF/step)" % (f_issued_step / 1e9, dev_ms / args.steps, f_alg_step / 1e9)}
-        roofline = step_roofline
-        if kernels and sum(kernels.get(f, {}).get("ms_per_step", 0) for f in wfams) > 0 and args.approach != "first_b":
-            # the dominant kernel: the Winograd conv launches (forward + input-gradient, both tile sizes), priced together
-            kms = sum(kernels[f]["ms_per_step"] for f in wfams if f in kernels)
-            kn = sum(kernels[f]["launches_per_step"] for f in wfams if f in kernels)
-            f_conv_alg = sum(kernels[f]["_alg_flops"] for f in wfams if f in kernels)
-            f_conv_issued = f_conv_issued_measured if wino else f_conv_alg
-            n43 = sum(kernels[f]["launches_per_step"] for f in ("conv43_fwd", "conv43_dgrad") if f in kernels)
-            ktraffic = None
-            if traffic and kn == traffic.get("wino_kernel_launches_per_step"):
-                ktraffic = (traffic["wino_fetch_bytes_raw_per_step"] + traffic["wino_write_bytes_per_step"]) / kn
-            roofline = {
-                "bound": "mfma", "achieved": round(f_conv_issued / (kms * 1e-3) / 1e12, 3), "peak": PEAK_FP32_MFMA / 1e12,
-                "unit": "TFLOP/s", "frac": round(f_conv_issued / (kms * 1e-3) / PEAK_FP32_MFMA, 4),
-                "traffic": ktraffic, "traffic_source": tsrc if ktraffic else None,
-                "alg_equiv_tflops": round(f_conv_alg / (kms * 1e-3) / 1e12, 3),
-                # the number earlier rounds reported as `frac`, when every launch was F(2x2,3x3): 16/36 of the direct count
-                # over the same time / peak.  Above 1 once launches run F(4x4,3x3) -- a comparison across rounds, not a roofline
-                "f23_equiv_of_peak": round(f_conv_alg * 16.0 / 36.0 / (kms * 1e-3) / PEAK_FP32_MFMA, 4),
-                "kernel": (("wino43_kernel (csrc/wino43.hip, F(4x4,3x3): %d launches)" % n43 if n43 else "")
-                           + (" + " if n43 and kn > n43 else "")
-                           + ("wino4_kernel (csrc/wino.hip, F(2x2,3x3): %d launches)" % (kn - n43) if kn > n43 else ""))
-                          if wino else "conv3x3_kernel (csrc/conv.hip)",
-                "launches_per_step": kn, "avg_launch_ms": round(kms / kn, 4), "ms_per_step": round(kms, 4),
-                "share_of_step": round(kms / (dev_ms / args.steps), 4),
-                "flops_per_launch_issued": round(f_conv_issued / kn), "flops_per_launch_alg": round(f_conv_alg / kn),
-                "note": "achieved = MFMA flops ISSUED by these launches (Winograd F(2x2,3x3): 16 multiplies per 2x2 outputs = "
-                        "16/36, F(4x4,3x3): 36 per 4x4 outputs = 36/144 of the 2*9*Cin*Cout per output pixel of the direct "
-                        "convolutions they replace, forward + "
-                        "input-gradient of every VGG conv but conv1_1: %.1f GF issued, %.1f GF algorithmic per step) / their "
-                        "HIP-event time on the launch stream over %d steps after the timed region; frac = matrix-pipe "
-                        "utilisation.  alg_equiv_tflops = the direct-convolution count over the same time (may exceed the "
-                        "peak; it is not a roofline fraction); f23_equiv_of_peak = the round-1/2 `frac` metric (every launch "
-                        "priced as F(2x2,3x3)) for comparison across rounds." % (f_conv_issued / 1e9, f_conv_alg / 1e9, nprof)}
-        if args.approach == "first_b" and kernels:
-            # phase B of the first approach has no VGG: the step IS the HBM/latency-bound render + scatter kernels.  Its
-            # roofline is HBM: algorithmic bytes of SURVEY.md 8d per kernel over the kernel's own (standalone, back-to-back)
-            # time; the dominant one is the rasteriser.  step_roofline prices all of them over the measured step, host gaps included.
-            names = [k for k in ("raster_fwd", "shade_fwd", "masked_mse",
-                                  "shade_bwd_with_bary" if "shade_bwd_with_bary" in kernels else "shade_bwd_texture_scatter",
-                                  "raster_bwd_vertex_scatter", "project_verts_bwd", "mesh_regularisers", "adam") if k in kernels]
-            kb = {k: kernels[k]["alg_gbps"] * 1e9 * kernels[k]["ms_per_call"] * 1e-3 for k in names}
-            ksum_ms = sum(kernels[k]["ms_per_call"] for k in names)
-            dom = max(names, key=lambda k: kernels[k]["ms_per_call"])
-            step_roofline = {"bound": "hbm", "achieved": round(sum(kb.values()) / step_s / 1e9, 1), "peak": PEAK_HBM / 1e9, "unit": "GB/s",
-                             "frac": round(sum(kb.values()) / step_s / PEAK_HBM, 4), "traffic": None,
-                             "kernel_ms_sum_standalone": round(ksum_ms, 4), "device_ms_per_step": round(step_s * 1e3, 4),
-                             "host_or_launch_bound_share": round(max(0.0, 1.0 - ksum_ms / (step_s * 1e3)), 3),
-                             "note": "algorithmic bytes of the step's kernels (%s) over the HIP-event time of the timed region; "
-                                     "the difference between that time and the kernels' standalone sum is launch / host time "
-                                     "(Python autograd + ~12 launches per step)" % ", ".join(names)}
-            roofline = {"bound": "hbm", "kernel": dom + " (csrc/raster.hip: face setup + coarse bins + 16x16-pixel tiles)" if dom == "raster_fwd" else dom,
-                        "achieved": kernels[dom]["alg_gbps"], "peak": PEAK_HBM / 1e9, "unit": "GB/s", "frac": kernels[dom]["hbm_frac"],
-                        "traffic": None, "avg_launch_ms": kernels[dom]["ms_per_call"],
-                        "note": "the longest kernel of a phase-B step, timed alone on this step's inputs; latency-bound "
-                                "(tile lists, per-pixel face walks), not a stream"}
+        roofline = step_roofline = None
+        if args.full:
+            # algorithmic and issued MFMA flops of one step on this GPU
+            f_alg_step = sum(conv_alg_flops(m, S, Bv) for m, *_ in CONVS) * 2 + sum(gram_alg_flops(m, S, Bv) for m in STYLE_TAPS) * 2
+            if content_each_step:
+                f_alg_step += sum(conv_alg_flops(m, S, Bv) for m, *_ in CONVS if m <= 21)
+            f_wino_alg = sum(conv_alg_flops(m, S, Bv) for m, *_ in CONVS if m != 0) * 2
+            if content_each_step:
+                f_wino_alg += sum(conv_alg_flops(m, S, Bv) for m, *_ in CONVS if 0 < m <= 21)
+            wfams = ("conv_fwd", "conv_dgrad", "conv43_fwd", "conv43_dgrad")
+            if kernels and any(f in kernels for f in wfams):
+                # what the Winograd launches of a step actually issued: per launch F(2x2,3x3) = 16/36, F(4x4,3x3) = 36/144 of the
+                # direct count, as tagged by the plan's profile (conv_* / conv43_* families)
+                f_conv_issued_measured = sum(kernels[f]["_issued_flops"] for f in wfams if f in kernels)
+            else:
+                f_conv_issued_measured = None
+            f_issued_step = ((f_conv_issued_measured if f_conv_issued_measured is not None else f_wino_alg * (16.0 / 36.0)) if wino
+                             else f_wino_alg + 2 * conv_alg_flops(0, S, Bv)) \
+                + sum(gram_fwd_issued_flops(m, S, Bv) + gram_alg_flops(m, S, Bv) for m in STYLE_TAPS)
+            if os.environ.get("ST3D_TAP0_FUSED") != "0":
+                f_issued_step += 2.0 * 32 * 64 * S * S * Bv        # conv1_1's input gradient as an MFMA product (csrc/tap0.hip)
+            step_s = dev_ms / args.steps * 1e-3
+            traffic, tpath = {}, ""
+            if std_cfg:
+                import glob
+                tfiles = sorted(glob.glob(os.path.join(ROOT, "profiles", "r*_pmc_traffic.json")))     # newest round last
+                if tfiles:
+                    tpath = tfiles[-1]
+                    with open(tpath) as fh:
+                        traffic = json.load(fh)
+            tsrc = ("committed rocprofv3 PMC passes %s (FETCH_SIZE raw + WRITE_SIZE per launch; gfx950 under-reports 16-B/lane "
+                    "read streams by up to 2x), not re-measured in this run" % os.path.relpath(tpath, ROOT)) if traffic else None
+            step_roofline = {
+                "bound": "mfma", "achieved": round(f_issued_step / step_s / 1e12, 3), "peak": PEAK_FP32_MFMA / 1e12, "unit": "TFLOP/s",
+                "frac": round(f_issued_step / step_s / PEAK_FP32_MFMA, 4),
+                "alg_equiv_tflops": round(f_alg_step / step_s / 1e12, 3),
+                "traffic": (traffic["fetch_bytes_raw_per_step"] + traffic["write_bytes_per_step"]) if traffic else None,
+                "traffic_source": tsrc,
+                "note": "whole step per GPU (renders, losses, Adam and host gaps included): MFMA flops issued per step (%.1f GF: "
+                        "Winograd convs 16/36 (F(2x2,3x3)) or 36/144 (F(4x4,3x3)) of the direct count, Gram forward upper tiles only) over the HIP-event time of the "
+                        "timed region (%.3f ms/step); alg_equiv_tflops prices the same time with the direct-convolution count of "
+                        "SURVEY.md 8d (%.1f GF/step)" % (f_issued_step / 1e9, dev_ms / args.steps, f_alg_step / 1e9)}
+            roofline = step_roofline
+            if kernels and sum(kernels.get(f, {}).get("ms_per_step", 0) for f in wfams) > 0 and args.approach != "first_b":
+                # the dominant kernel: the Winograd conv launches (forward + input-gradient, both tile sizes), priced together
+                kms = sum(kernels[f]["ms_per_step"] for f in wfams if f in kernels)
+                kn = sum(kernels[f]["launches_per_step"] for f in wfams if f in kernels)
+                f_conv_alg = sum(kernels[f]["_alg_flops"] for f in wfams if f in kernels)
+                f_conv_issued = f_conv_issued_measured if wino else f_conv_alg
+                n43 = sum(kernels[f]["launches_per_step"] for f in ("conv43_fwd", "conv43_dgrad") if f in kernels)
+                ktraffic = None
+                if traffic and kn == traffic.get("wino_kernel_launches_per_step"):
+                    ktraffic = (traffic["wino_fetch_bytes_raw_per_step"] + traffic["wino_write_bytes_per_step"]) / kn
+                roofline = {
+                    "bound": "mfma", "achieved": round(f_conv_issued / (kms * 1e-3) / 1e12, 3), "peak": PEAK_FP32_MFMA / 1e12,
+                    "unit": "TFLOP/s", "frac": round(f_conv_issued / (kms * 1e-3) / PEAK_FP32_MFMA, 4),
+                    "traffic": ktraffic, "traffic_source": tsrc if ktraffic else None,
+                    "alg_equiv_tflops": round(f_conv_alg / (kms * 1e-3) / 1e12, 3),
+                    # the number earlier rounds reported as `frac`, when every launch was F(2x2,3x3): 16/36 of the direct count
+                    # over the same time / peak.  Above 1 once launches run F(4x4,3x3) -- a comparison across rounds, not a roofline
+                    "f23_equiv_of_peak": round(f_conv_alg * 16.0 / 36.0 / (kms * 1e-3) / PEAK_FP32_MFMA, 4),
+                    "kernel": (("wino43_kernel (csrc/wino43.hip, F(4x4,3x3): %d launches)" % n43 if n43 else "")
+                               + (" + " if n43 and kn > n43 else "")
+                               + ("wino4_kernel (csrc/wino.hip, F(2x2,3x3): %d launches)" % (kn - n43) if kn > n43 else ""))
+                              if wino else "conv3x3_kernel (csrc/conv.hip)",
+                    "launches_per_step": kn, "avg_launch_ms": round(kms / kn, 4), "ms_per_step": round(kms, 4),
+                    "share_of_step": round(kms / (dev_ms / args.steps), 4),
+                    "flops_per_launch_issued": round(f_conv_issued / kn), "flops_per_launch_alg": round(f_conv_alg / kn),
+                    "note": "achieved = MFMA flops ISSUED by these launches (Winograd F(2x2,3x3): 16 multiplies per 2x2 outputs = "
+                            "16/36, F(4x4,3x3): 36 per 4x4 outputs = 36/144 of the 2*9*Cin*Cout per output pixel of the direct "
+                            "convolutions they replace, forward + "
+                            "input-gradient of every VGG conv but conv1_1: %.1f GF issued, %.1f GF algorithmic per step) / their "
+                            "HIP-event time on the launch stream over %d steps after the timed region; frac = matrix-pipe "
+                            "utilisation.  alg_equiv_tflops = the direct-convolution count over the same time (may exceed the "
+                            "peak; it is not a roofline fraction); f23_equiv_of_peak = the round-1/2 `frac` metric (every launch "
+                            "priced as F(2x2,3x3)) for comparison across rounds." % (f_conv_issued / 1e9, f_conv_alg / 1e9, nprof)}
+            if args.approach == "first_b" and kernels:
+                # phase B of the first approach has no VGG: the step IS the HBM/latency-bound render + scatter kernels.  Its
+                # roofline is HBM: algorithmic bytes of SURVEY.md 8d per kernel over the kernel's own (standalone, back-to-back)
+                # time; the dominant one is the rasteriser.  step_roofline prices all of them over the measured step, host gaps included.
+                names = [k for k in ("raster_fwd", "shade_fwd", "masked_mse",
+                                      "shade_bwd_with_bary" if "shade_bwd_with_bary" in kernels else "shade_bwd_texture_scatter",
+                                      "raster_bwd_vertex_scatter", "project_verts_bwd", "mesh_regularisers", "adam") if k in kernels]
+                kb = {k: kernels[k]["alg_gbps"] * 1e9 * kernels[k]["ms_per_call"] * 1e-3 for k in names}
+                ksum_ms = sum(kernels[k]["ms_per_call"] for k in names)
+                dom = max(names, key=lambda k: kernels[k]["ms_per_call"])
+                step_roofline = {"bound": "hbm", "achieved": round(sum(kb.values()) / step_s / 1e9, 1), "peak": PEAK_HBM / 1e9, "unit": "GB/s",
+                                 "frac": round(sum(kb.values()) / step_s / PEAK_HBM, 4), "traffic": None,
+                                 "kernel_ms_sum_standalone": round(ksum_ms, 4), "device_ms_per_step": round(step_s * 1e3, 4),
+                                 "host_or_launch_bound_share": round(max(0.0, 1.0 - ksum_ms / (step_s * 1e3)), 3),
+                                 "note": "algorithmic bytes of the step's kernels (%s) over the HIP-event time of the timed region; "
+                                         "the difference between that time and the kernels' standalone sum is launch / host time "
+                                         "(Python autograd + ~12 launches per step)" % ", ".join(names)}
+                roofline = {"bound": "hbm", "kernel": dom + " (csrc/raster.hip: face setup + coarse bins + 16x16-pixel tiles)" if dom == "raster_fwd" else dom,
+                            "achieved": kernels[dom]["alg_gbps"], "peak": PEAK_HBM / 1e9, "unit": "GB/s", "frac": kernels[dom]["hbm_frac"],
+                            "traffic": None, "avg_launch_ms": kernels[dom]["ms_per_call"],
+                            "note": "the longest kernel of a phase-B step, timed alone on this step's inputs; latency-bound "
+                                    "(tile lists, per-pixel face walks), not a stream"}
         tgt = {"texture": "texture-only optimisation", "mesh": "vertex optimisation", "both": "joint vertex + texture optimisation"}[args.target]
         cfg_name = "BASELINE.json configs[1]" if std_cfg else "variant of BASELINE.json configs[1]"
         loop = {"second": "second_approach loop body", "first_a": "first_approach phase A = style_transfer() loop on the views' pixels, no renderer",
@@ -608,9 +665,9 @@ def main():
                        "targets_hoisted": hoisted,
                        "parallelism": "views sharded dp%d, RCCL all-reduce of the texture gradient" % world},
             "first_step_loss": first_step_loss, "final_loss": final_loss,
-            "roofline": roofline,
-            "step_roofline": step_roofline,
         }
+        if args.full:
+            res.update(roofline=roofline, step_roofline=step_roofline)
         if allreduce_ms is not None:
             res.update(comm)
             res["collectives_per_step"] = collectives_per_step
@@ -624,7 +681,7 @@ def main():
             res["kernels"] = kernels
         if layers and args.layers:
             res["layers"] = layers
-        if not args.no_cpu_baseline and world == 1 and args.approach == "second":
+        if args.full and not args.no_cpu_baseline and world == 1 and args.approach == "second":
             try:
                 # like for like with the CPU leg, which executes the step as the reference does (content re-rendered and its
                 # VGG forward redone every step, second_approach.py:157-166): the same on the GPU, 20 steps after the timed

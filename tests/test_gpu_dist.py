@@ -117,8 +117,8 @@ def test_bench_gpus_2_launches_its_own_ranks_and_reports_what_ran(target, n_para
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "MASTER_ADDR")}
     env["ST3D_DIST_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-           "--size", "256", "--views", "2", "--target", target]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline", "--size", "256", "--views", "2", "--target", target]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     out = [ln for ln in r.stdout.splitlines() if ln.strip()]

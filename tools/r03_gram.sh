@@ -1,12 +1,13 @@
 #!/bin/bash
 set -x
-cd /root/repo
-timeout -k 10 600 python -m pytest tests/test_gpu_kernels.py -x -q -k "gram" > gpurun_out/r3_gram_test.log 2>&1 || { tail -30 gpurun_out/r3_gram_test.log; exit 1; }
-tail -3 gpurun_out/r3_gram_test.log
-run() { timeout -k 10 300 python bench.py --steps 60 --no-cpu-baseline > gpurun_out/r3g_$1.json 2>gpurun_out/r3g_$1.err || { tail -20 gpurun_out/r3g_$1.err; exit 1; }
+cd "$(dirname "$0")/.."
+export OUT=${OUT:-out}; mkdir -p "$OUT"
+timeout -k 10 600 python -m pytest tests/test_gpu_kernels.py -x -q -k "gram" > $OUT/r3_gram_test.log 2>&1 || { tail -30 $OUT/r3_gram_test.log; exit 1; }
+tail -3 $OUT/r3_gram_test.log
+run() { timeout -k 10 300 python bench.py --full --steps 60 --no-cpu-baseline > $OUT/r3g_$1.json 2>$OUT/r3g_$1.err || { tail -20 $OUT/r3g_$1.err; exit 1; }
 python - $1 <<'P'
-import json,sys
-d=json.load(open("gpurun_out/r3g_%s.json"%sys.argv[1])); k=d["kernels"]
+import json,os,sys
+d=json.load(open(os.environ["OUT"] + "/r3g_%s.json"%sys.argv[1])); k=d["kernels"]
 print(sys.argv[1], d["ms_per_step"], d["roofline"]["frac"], "gram_fwd", k["gram_fwd"]["ms_per_step"], "final", d["final_loss"], flush=True)
 P
 }

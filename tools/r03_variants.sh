@@ -1,10 +1,11 @@
 #!/bin/bash
 set -x
-cd /root/repo
-run() { n=$1; shift; timeout -k 10 400 python bench.py --no-cpu-baseline "$@" > gpurun_out/r3v_$n.json 2>gpurun_out/r3v_$n.err || { tail -20 gpurun_out/r3v_$n.err; exit 1; }
+cd "$(dirname "$0")/.."
+export OUT=${OUT:-out}; mkdir -p "$OUT"
+run() { n=$1; shift; timeout -k 10 400 python bench.py --full --no-cpu-baseline "$@" > $OUT/r3v_$n.json 2>$OUT/r3v_$n.err || { tail -20 $OUT/r3v_$n.err; exit 1; }
 python - $n <<'P'
-import json,sys
-d=json.load(open("gpurun_out/r3v_%s.json"%sys.argv[1]))
+import json,os,sys
+d=json.load(open(os.environ["OUT"] + "/r3v_%s.json"%sys.argv[1]))
 print(sys.argv[1], d["metric"], d["value"], d["ms_per_step"], "roofline", d["roofline"].get("kernel"), d["roofline"]["frac"], "step", d["step_roofline"]["frac"], d["step_roofline"].get("host_or_launch_bound_share"), flush=True)
 print("   ", {k: (v.get("ms_per_step", v.get("ms_per_call"))) for k, v in d.get("kernels", {}).items()}, flush=True)
 P

@@ -3,13 +3,14 @@
 # each.  Run on the GPU box from the repo root, variants as VAR=value tokens ("-" = defaults):
 #   bash tools/wino_sched_ab.sh "- ST3D_WINO_SCHED=1 ST3D_WINO_BARRIER_MID=1 -"
 set -e
+export OUT=${OUT:-out}; mkdir -p "$OUT"
 for v in ${1:-- ST3D_WINO_SCHED=1}; do
   touch 2d-to-3d-style-transfer_amd/csrc/wino.hip
   if [ "$v" = "-" ]; then python 2d-to-3d-style-transfer_amd/build.py --jobs 16 > /dev/null; else env "$v" python 2d-to-3d-style-transfer_amd/build.py --jobs 16 > /dev/null; fi
-  python bench.py --steps ${STEPS:-60} --no-cpu-baseline --layers > gpurun_out/sched.json 2> /dev/null
+  python bench.py --full --steps ${STEPS:-60} --no-cpu-baseline --layers > "$OUT/sched.json" 2> /dev/null
   python - "$v" <<'P'
-import json, sys
-d = json.load(open("gpurun_out/sched.json"))
+import json, os, sys
+d = json.load(open(os.path.join(os.environ["OUT"], "sched.json")))
 k = d["kernels"]
 f = [l["ms"] for l in d["layers"] if l["family"] == "conv_fwd"]
 g = [l["ms"] for l in d["layers"] if l["family"] == "conv_dgrad"]

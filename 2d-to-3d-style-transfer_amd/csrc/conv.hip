@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvArgs a) {
             const int e = tid + i * 256;
             const int ci = e / XS;
             bool ok = ((xvalid >> i) & 1u) && (ci0 + ci) < a.Cin;
-            if (MODE != 0) ok = ok && (xa[i] > 0.f);                 // ReLU gate
+            if (MODE != 0) ok = ok && !(xa[i] <= 0.f);               // ReLU gate (open on NaN, like threshold_backward)
             if (MODE == 2) ok = ok && (xi[i] == xpos[i]);            // max-unpool gate
             Xs[e] = ok ? xv[i] : 0.f;
         }
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_kernel(const ConvArgs a) {
                 const int py = y0 + wn * NT + q;
                 if (py < H && px < W) {
                     float v = acc[m][q][r] + bsum;
-                    if (a.relu) v = v > 0.f ? v : 0.f;
+                    if (a.relu) v = __builtin_elementwise_maximum(v, 0.f);    // NaN-propagating (torch.relu(nan) = nan)
                     yout[(size_t)co * HW + (size_t)py * W + px] = v;
                 }
             }
@@ -312,8 +312,8 @@ __global__ __launch_bounds__(256) void dgrad_small_kernel(const float *__restric
             if (e < ITEMS) {
                 const int ci = e / ((SG_TH + 2) * ROW4), rem = e - ci * ((SG_TH + 2) * ROW4), r = rem / ROW4, l = rem - r * ROW4;
                 f32x4 v;
-                v.x = ra[j].x > 0.f ? rg[j].x : 0.f; v.y = ra[j].y > 0.f ? rg[j].y : 0.f;
-                v.z = ra[j].z > 0.f ? rg[j].z : 0.f; v.w = ra[j].w > 0.f ? rg[j].w : 0.f;
+                v.x = !(ra[j].x <= 0.f) ? rg[j].x : 0.f; v.y = !(ra[j].y <= 0.f) ? rg[j].y : 0.f;
+                v.z = !(ra[j].z <= 0.f) ? rg[j].z : 0.f; v.w = !(ra[j].w <= 0.f) ? rg[j].w : 0.f;
                 *reinterpret_cast<f32x4 *>(&tile[ci][r][4 * l]) = v;
             }
         }
@@ -433,7 +433,8 @@ __global__ __launch_bounds__(256, 2) void conv_small_fwd_kernel(const float *__r
 #pragma unroll
             for (int j = 0; j < SF_CG; ++j) {
                 f32x4 o = {acc[j][0], acc[j][1], acc[j][2], acc[j][3]};
-                if (relu) { o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f); }
+                if (relu) { o.x = __builtin_elementwise_maximum(o.x, 0.f); o.y = __builtin_elementwise_maximum(o.y, 0.f);
+                            o.z = __builtin_elementwise_maximum(o.z, 0.f); o.w = __builtin_elementwise_maximum(o.w, 0.f); }
                 *reinterpret_cast<f32x4 *>(y + ((size_t)n * Cout + cg + j) * HW + (size_t)oy * W + ox) = o;
             }
         }

@@ -190,7 +190,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int bx, const
                     for (int q = 0; q < NT; ++q) {
                         unsigned mk = 0;
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) mk |= (pg[((r & 3) + 8 * (r >> 2)) * LB + q * 32] > 0.f ? 1u : 0u) << r;
+                        for (int r = 0; r < 16; ++r) mk |= (!(pg[((r & 3) + 8 * (r >> 2)) * LB + q * 32] <= 0.f) ? 1u : 0u) << r;     // open on NaN
                         gmask[m][q] = mk;
                     }
                 }
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgs g) 
                     unsigned mk = 0;
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        mk |= (Bs[((r & 3) + 8 * (r >> 2) + 4 * lhi) * LB + wn * 32 + l31] > 0.f ? 1u : 0u) << r;
+                        mk |= (!(Bs[((r & 3) + 8 * (r >> 2) + 4 * lhi) * LB + wn * 32 + l31] <= 0.f) ? 1u : 0u) << r;
                     gmask[m] = mk;
                 }
         }

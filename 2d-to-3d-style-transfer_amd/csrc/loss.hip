@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256) void axpy_diff_kernel(const float *__restrict_
         const float ai = a[i];
         const float v = coef * (ai - b[i]);
         const float t = accumulate ? g[i] + v : v;
-        g[i] = (gate && !(ai > 0.f)) ? 0.f : t;
+        g[i] = (gate && ai <= 0.f) ? 0.f : t;          // open on NaN, like threshold_backward
     }
 }
 
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void range_kernel(const float *__restrict__ t,
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const float v = t[i];
-        acc += fmaxf(v - 1.0f, 0.f) + fmaxf(-v, 0.f);
+        acc += __builtin_elementwise_maximum(v - 1.0f, 0.f) + __builtin_elementwise_maximum(-v, 0.f);   // NaN stays NaN, as torch.relu
         if (g) g[i] = v > 1.0f ? 1.0f : (v < 0.f ? -1.0f : 0.f);
     }
     block_store_partial(acc, partials);

@@ -111,7 +111,7 @@ __global__ __launch_bounds__(256, J == 2 ? 3 : 4) void conv1_bwd_gemm_kernel(con
             const float a2 = A2s[t * 64 + lane];
 #pragma unroll
             for (int j = 0; j < J; ++j) {
-                const float b = Fv[t][j] > 0.f ? acc1[j][t >> 4][t & 15] : 0.f;     // ReLU gate of relu1_1
+                const float b = !(Fv[t][j] <= 0.f) ? acc1[j][t >> 4][t & 15] : 0.f;     // ReLU gate of relu1_1 (open on NaN)
                 acc2[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, b, acc2[j], 0, 0, 0);
             }
         }

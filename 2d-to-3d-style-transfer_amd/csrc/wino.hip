@@ -51,7 +51,7 @@ struct WinoArgs {
     unsigned long long *dbg;   // diagnostic builds only (DBG != 0): per-wave phase cycle sums
     const float *gate;    // wino4_kernel: (N,Cout,H,W) or nullptr; outputs are zeroed where gate <= 0 (the consumer's ReLU gate,
                           // applied by the producer so that the consumer streams ONE operand: see st3d_wino_dgrad_chain)
-    const float *addt;    // with gate: outputs become gate > 0 ? y + addc * (gate - addt) : 0 -- the content-loss gradient
+    const float *addt;    // with gate: outputs become !(gate <= 0) ? y + addc * (gate - addt) : 0 -- the content-loss gradient
     float addc;           // addc * (activation - target) (losses.py:24-28) lands in the same store; nullptr = none
 };
 
@@ -196,10 +196,10 @@ __global__ __launch_bounds__(NT4, MH == 1 ? 3 : 2) void wino4_kernel(const WinoA
             for (int jj = 0; jj < 4; ++jj) {
                 float v;
                 if (MODE == 0) v = xv[i][jj];
-                if (MODE == 1) v = (xa[i][jj] > 0.f) ? xv[i][jj] : 0.f;
+                if (MODE == 1) v = !(xa[i][jj] <= 0.f) ? xv[i][jj] : 0.f;      // gates open on NaN, like threshold_backward
                 if (MODE == 2) {
                     const unsigned ib = (xi[i] >> (8 * (jj >> 1))) & 0xffu;
-                    v = (xp[i][jj >> 1] > 0.f && ib == (rowbit[i] | (jj & 1))) ? xg[i][jj >> 1] : 0.f;
+                    v = (!(xp[i][jj >> 1] <= 0.f) && ib == (rowbit[i] | (jj & 1))) ? xg[i][jj >> 1] : 0.f;
                 }
                 if (MODE == 3) {
                     const unsigned ib = (xi[i] >> (8 * (jj >> 1))) & 0xffu;
@@ -471,7 +471,7 @@ __global__ __launch_bounds__(NT4, MH == 1 ? 3 : 2) void wino4_kernel(const WinoA
         if (a.yidx) ryi = __builtin_amdgcn_make_buffer_rsrc(a.yidx + (size_t)n * a.Cout * HpWp, 0, (unsigned)(a.Cout * HpWp), 0x00020000);
         if (inb) vp = (unsigned)((((size_t)co0 + (tid >> 4)) * HpWp + (size_t)(oy >> 1) * Wp + (ox >> 1)) * 4);
     }
-    const float relu_floor = a.relu ? 0.f : -__builtin_inff();      // ReLU as max(v, floor) with a wave-uniform floor
+    const float relu_floor = a.relu ? 0.f : -__builtin_inff();      // ReLU as maximum(v, floor) with a wave-uniform floor
     __syncthreads();
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
@@ -491,7 +491,7 @@ __global__ __launch_bounds__(NT4, MH == 1 ? 3 : 2) void wino4_kernel(const WinoA
             for (int jj = 0; jj < 2; ++jj) {
                 float v0 = z[jj][0][t] + z[jj][1][t] + z[jj][2][t] + bsum;
                 float v1 = z[jj][1][t] - z[jj][2][t] - z[jj][3][t] + bsum;
-                if (GATE == 0) { v0 = __builtin_fmaxf(v0, relu_floor); v1 = __builtin_fmaxf(v1, relu_floor); }     // one v_max each (gated launches are input-gradients: no ReLU)
+                if (GATE == 0) { v0 = __builtin_elementwise_maximum(v0, relu_floor); v1 = __builtin_elementwise_maximum(v1, relu_floor); }     // one v_maximum3 each, NaN-propagating (gated launches are input-gradients: no ReLU)
                 y[t][0][jj] = v0; y[t][1][jj] = v1;
             }
         if (DBG == 3 && y[0][0][0] != 12345.678f) continue;       // diagnostic: whole epilogue but no global stores
@@ -510,8 +510,8 @@ __global__ __launch_bounds__(NT4, MH == 1 ? 3 : 2) void wino4_kernel(const WinoA
             if (GATE >= 1) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    q0[e] = gq[it][0][e] > 0.f ? q0[e] : 0.f;
-                    q1[e] = gq[it][1][e] > 0.f ? q1[e] : 0.f;
+                    q0[e] = !(gq[it][0][e] <= 0.f) ? q0[e] : 0.f;
+                    q1[e] = !(gq[it][1][e] <= 0.f) ? q1[e] : 0.f;
                 }
             }
             // the item's channel step goes into the VECTOR offset and the scalar offset stays 0: with an SGPR scalar offset

@@ -79,7 +79,7 @@ struct Wino43Args {
     uint8_t *yidx;        // EPI 1: argmax
     int N, Cin, Cout, H, W, relu, tiles_x, tiles_y, n_ct;
     const float *gate;    // (N,Cout,H,W) or nullptr: outputs are zeroed where gate <= 0 (the consumer's ReLU gate, see wino.hip)
-    const float *addt;    // with gate: outputs become gate > 0 ? y + addc * (gate - addt) : 0
+    const float *addt;    // with gate: outputs become !(gate <= 0) ? y + addc * (gate - addt) : 0
     float addc;
     int xpc;                        // XCDs per cout tile (slots are renumbered XCD-major, see wino43_body); 1 = as dealt
     unsigned magic_x, magic_y;      // floor(2^32 / tiles_x) + 1, likewise tiles_y: pix / tiles_x = umulhi(pix, magic_x) for pix * tiles_x < 2^32 (tiles_x >= 2)
@@ -367,7 +367,7 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
         ryp = __builtin_amdgcn_make_buffer_rsrc(a.yp + (size_t)n * a.Cout * HpWp, 0, (unsigned)(a.Cout * HpWp * 4), 0x00020000);
         if (a.yidx) ryi = __builtin_amdgcn_make_buffer_rsrc(a.yidx + (size_t)n * a.Cout * HpWp, 0, (unsigned)(a.Cout * HpWp), 0x00020000);
     }
-    const float relu_floor = a.relu ? 0.f : -__builtin_inff();
+    const float relu_floor = a.relu ? 0.f : -__builtin_inff();      // ReLU as maximum(v, floor): NaN-propagating, one v_maximum3
     // the reader's bias and the consumer's ReLU gate (GATE >= 1) of a half are requested two passes before they are used
     // (one workgroup per CU: an exposed HBM round trip idles the whole CU)
     unsigned vo = kOob;
@@ -456,7 +456,7 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     float v = rowv[i][j] + bsum;
-                    if (GATE == 0) v = __builtin_fmaxf(v, relu_floor);
+                    if (GATE == 0) v = __builtin_elementwise_maximum(v, relu_floor);
                     rowv[i][j] = v;
                 }
                 if (GATE >= 1) {
@@ -473,7 +473,7 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
                         }
                     }
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) rowv[i][j] = g[j] > 0.f ? rowv[i][j] : 0.f;
+                    for (int j = 0; j < 4; ++j) rowv[i][j] = !(g[j] <= 0.f) ? rowv[i][j] : 0.f;     // open on NaN
                 }
                 // Non-temporal stores (and gate reads, above): what a tile writes is read next by ANOTHER kernel, out of the
                 // memory-side cache at best -- kept out of L2 it leaves the XCD's 4 MB to the filter operands and the patch rows

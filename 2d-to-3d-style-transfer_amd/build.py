@@ -27,6 +27,7 @@ SOURCES = {
     "raster.hip": ["-ffp-contract=off"],
     "shade.hip": ["-ffp-contract=off"],
     "soft.hip": ["-ffp-contract=off"],
+    "lighting.hip": ["-ffp-contract=off"],
     "conv.hip": ["-fno-slp-vectorize"],   # the VALU conv1_1 kernels: SLP-packed v_pk_fma needs register-pair shuffles
     "wino.hip": ["-fno-slp-vectorize"],   # SLP-packed f32 (v_pk_*) needs register shuffles that cost matrix-pipe time
     "wino43.hip": ["-fno-slp-vectorize"],  # (with SLP packing the nine-layer sum is 0.8 % faster, but the re-associated column transform
@@ -49,7 +50,8 @@ def _newer(src, dst, extra=()):
 
 def build(force=False, jobs=4, verbose=True):
     os.makedirs(OBJDIR, exist_ok=True)
-    hdrs = (os.path.join(CSRC, "common.h"), os.path.join(CSRC, "det.h"), os.path.join(CSRC, "lab", "wino8.inc"),
+    hdrs = (os.path.join(CSRC, "common.h"), os.path.join(CSRC, "det.h"), os.path.join(CSRC, "phong.h"),
+            os.path.join(CSRC, "lab", "wino8.inc"),
             os.path.join(HERE, "..", "include", "st3d.h"), os.path.abspath(__file__))
     todo = []
     objs = []

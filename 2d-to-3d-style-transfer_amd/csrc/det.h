@@ -84,4 +84,16 @@ __attribute__((unused)) static __global__ __launch_bounds__(256) void det_abs_su
     if (threadIdx.x == 0) partials[blockIdx.x] = t;
 }
 
+// the same with every term scaled by `scale` (the lit texture scatters: contributions are |g| times a lighting factor <= scale;
+// a non-finite scale poisons the bound like a non-finite gradient)
+__attribute__((unused)) static __global__ __launch_bounds__(256) void det_abs_sum_scaled_kernel(const float *__restrict__ x, size_t n, float scale,
+                                                                                                float *__restrict__ partials) {
+    __shared__ float s4[4];
+    float acc = 0.f;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) acc += fabsf(x[i]);
+    const float t = det_block_sum(acc, s4);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t * scale;
+}
+
 }  // namespace st3d_det

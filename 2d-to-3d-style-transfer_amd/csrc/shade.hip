@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "det.h"
+#include "phong.h"
 
 namespace {
 
@@ -58,11 +59,14 @@ __device__ __forceinline__ Blend blend_k1(float dist, float z) {
     return o;
 }
 
+// LIT 1: the texel is lit first (phong.h): colour = ad * texel + sp replaces it in the blend
+template <int LIT = 0>
 __global__ __launch_bounds__(256) void shade_fwd_kernel(const int32_t *__restrict__ p2f, const float *__restrict__ bary,
                                                         const float *__restrict__ zbuf, const float *__restrict__ dists,
                                                         const float *__restrict__ uvs, const int32_t *__restrict__ fuv,
                                                         const float *__restrict__ tex, int B, int S, int T,
-                                                        float *__restrict__ rgb, float *__restrict__ mask) {
+                                                        float *__restrict__ rgb, float *__restrict__ mask,
+                                                        const st3d_phong::LitArgs la = {}) {
     const size_t HW = (size_t)S * S;
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)B * HW) return;
@@ -82,6 +86,8 @@ __global__ __launch_bounds__(256) void shade_fwd_kernel(const int32_t *__restric
     const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
     const float *t00 = tex + ((size_t)q.r0 * T + q.x0) * 3, *t01 = tex + ((size_t)q.r0 * T + q.x1) * 3;
     const float *t10 = tex + ((size_t)q.r1 * T + q.x0) * 3, *t11 = tex + ((size_t)q.r1 * T + q.x1) * 3;
+    float ad[3] = {1.f, 1.f, 1.f}, sp[3] = {0.f, 0.f, 0.f};
+    if (LIT) st3d_phong::phong_fwd(la, (int)b, f, b0, b1, b2, ad, sp);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         float t = 0.f;
@@ -89,6 +95,7 @@ __global__ __launch_bounds__(256) void shade_fwd_kernel(const int32_t *__restric
         if (q.vy0 && q.vx1) t += t01[c] * w01;
         if (q.vy1 && q.vx0) t += t10[c] * w10;
         if (q.vy1 && q.vx1) t += t11[c] * w11;
+        if (LIT) t = ad[c] * t + sp[c];
         o[c * HW] = (bl.wnum * t + bl.delta * 1.0f) / bl.denom;
     }
     mask[i] = ((1.0f - (1.0f - bl.prob)) > 0.f) ? 1.f : 0.f;
@@ -104,14 +111,17 @@ constexpr int kTexSlots = 2048;          // >= 4 x 256 footprint corners: the pr
 // DET 0: float LDS table + float global atomics (fast default).  DET 1: the same binning in 64-bit fixed point (LDS and
 // global integer atomics; `gtex` is then the int64 accumulator array and `det` holds the power-of-two scale): bitwise
 // reproducible whatever the order (det.h).
-template <int DET>
+// LIT 1: colour = ad * texel + sp (phong.h) -- the texture / uv factor of a channel becomes g k ad_c, and with la.grad_np the
+// lighting's own d/dN, d/dP go to grad_np (per pixel) and, through N = sum b_i n_i and P = sum b_i v_i, into gbary.
+template <int DET, int LIT = 0>
 __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict__ grad_rgb, const int32_t *__restrict__ p2f,
                                                         const float *__restrict__ bary, const float *__restrict__ zbuf,
                                                         const float *__restrict__ dists, const float *__restrict__ uvs,
                                                         const int32_t *__restrict__ fuv, const float *__restrict__ tex,
                                                         int B, int S, int T, int tiles_x, float *__restrict__ gtex,
                                                         float *__restrict__ guv, float *__restrict__ gbary,
-                                                        const st3d_det::DetHeader *__restrict__ det) {
+                                                        const st3d_det::DetHeader *__restrict__ det,
+                                                        const st3d_phong::LitArgs la = {}) {
     typedef typename std::conditional<DET != 0, unsigned long long, float>::type acc_t;
     __shared__ int s_key[kTexSlots];
     __shared__ acc_t s_acc[kTexSlots][3];
@@ -145,7 +155,28 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
         const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
         const int e00 = q.r0 * T + q.x0, e01 = q.r0 * T + q.x1, e10 = q.r1 * T + q.x0, e11 = q.r1 * T + q.x1;
         const float *g = grad_rgb + (size_t)b * 3 * HW + p;
-        const float gk[3] = {g[0] * k, g[HW] * k, g[2 * HW] * k};
+        const float gk0[3] = {g[0] * k, g[HW] * k, g[2 * HW] * k};
+        float ad[3] = {1.f, 1.f, 1.f}, sp[3] = {0.f, 0.f, 0.f};
+        if (LIT) st3d_phong::phong_fwd(la, b, f, b0, b1, b2, ad, sp);
+        const float gk[3] = {LIT ? gk0[0] * ad[0] : gk0[0], LIT ? gk0[1] * ad[1] : gk0[1], LIT ? gk0[2] * ad[2] : gk0[2]};
+        if (LIT && la.grad_np) {
+            // d colour_c / d ad_c = texel_c, d colour_c / d sp_c = 1
+            float g_ad[3], g_sp[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                float t = 0.f;
+                if (q.vy0 && q.vx0) t += tex[(size_t)e00 * 3 + c] * w00;
+                if (q.vy0 && q.vx1) t += tex[(size_t)e01 * 3 + c] * w01;
+                if (q.vy1 && q.vx0) t += tex[(size_t)e10 * 3 + c] * w10;
+                if (q.vy1 && q.vx1) t += tex[(size_t)e11 * 3 + c] * w11;
+                g_ad[c] = gk0[c] * t;
+                g_sp[c] = gk0[c];
+            }
+            st3d_phong::F3 gN = {0.f, 0.f, 0.f}, gP = {0.f, 0.f, 0.f};
+            if (la.kind != st3d_phong::kAmbient) st3d_phong::phong_bwd(la, b, f, b0, b1, b2, g_ad, g_sp, gN, gP);
+            float *o = la.grad_np + 6 * i;
+            o[0] = gN.x; o[1] = gN.y; o[2] = gN.z; o[3] = gP.x; o[4] = gP.y; o[5] = gP.z;
+        }
         if (want_uv) {
             float gix = 0.f, giy = 0.f;
 #pragma unroll
@@ -162,6 +193,16 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
                 gbary[3 * i] = gu * uvs[2 * u0] + gv * uvs[2 * u0 + 1];
                 gbary[3 * i + 1] = gu * uvs[2 * u1] + gv * uvs[2 * u1 + 1];
                 gbary[3 * i + 2] = gu * uvs[2 * u2] + gv * uvs[2 * u2 + 1];
+                if (LIT && la.grad_np && la.kind != st3d_phong::kAmbient) {     // + dN/db_i = n_i, dP/db_i = v_i
+                    const float *gnp = la.grad_np + 6 * i;
+                    const st3d_phong::F3 gN = st3d_phong::f3(gnp), gP = st3d_phong::f3(gnp + 3);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {
+                        const int vj = la.faces[3 * f + j];
+                        gbary[3 * i + j] += st3d_phong::dot3(gN, st3d_phong::f3(la.normals + 3 * vj)) +
+                                            st3d_phong::dot3(gP, st3d_phong::f3(la.verts + 3 * vj));
+                    }
+                }
             }
         }
         if (gtex) {
@@ -292,6 +333,79 @@ extern "C" int st3d_apply_background(const float *img, const float *mask, const 
     const size_t n = (size_t)B * 3 * S * S;
     background_kernel<<<st3d::cdiv((long)n, 256), 256, 0, st3d::as_stream(stream)>>>(img, mask, bg, bg_batch, B,
                                                                                    (size_t)S * S, out);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------ lit shading (phong.h)
+namespace {
+st3d_phong::LitArgs lit_args(const float *verts, const float *normals, const int32_t *faces, const float *R, const float *trans,
+                             const float *light, int n_lights, int kind, float *grad_np) {
+    st3d_phong::LitArgs la;
+    la.verts = verts; la.normals = normals; la.faces = faces; la.R = R; la.T = trans; la.light = light;
+    la.n_lights = n_lights; la.kind = kind; la.grad_np = grad_np;
+    return la;
+}
+}  // namespace
+
+extern "C" int st3d_shade_lit_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                                  const float *verts_uvs, const int32_t *faces_uvs, const float *texture, int B, int S, int T,
+                                  int F, int VT, const float *verts, const float *normals, const int32_t *faces, const float *R,
+                                  const float *trans, const float *light, int n_lights, int kind, float *rgb, float *mask,
+                                  st3d_stream_t stream) {
+    ST3D_CHECK_ARG(pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture && rgb && mask);
+    ST3D_CHECK_ARG(faces && R && trans && light && (n_lights == 1 || n_lights == B));
+    ST3D_CHECK_ARG(kind >= st3d_phong::kAmbient && kind <= st3d_phong::kHeadlight);
+    ST3D_CHECK_ARG(kind == st3d_phong::kAmbient || (verts && normals));
+    ST3D_CHECK_ARG(B > 0 && S > 0 && T > 1 && F > 0 && VT > 0);
+    const size_t n = (size_t)B * S * S;
+    shade_fwd_kernel<1><<<st3d::cdiv((long)n, 256), 256, 0, st3d::as_stream(stream)>>>(
+        pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, rgb, mask,
+        lit_args(verts, normals, faces, R, trans, light, n_lights, kind, nullptr));
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+extern "C" int st3d_shade_lit_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                                  const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                                  int B, int S, int T, int F, int VT, const float *verts, const float *normals,
+                                  const int32_t *faces, const float *R, const float *trans, const float *light, int n_lights,
+                                  int kind, float weight_bound, float *grad_texture, float *grad_bary, float *grad_np,
+                                  void *workspace, size_t workspace_bytes, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(grad_rgb && pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture);
+    ST3D_CHECK_ARG(faces && R && trans && light && (n_lights == 1 || n_lights == B));
+    ST3D_CHECK_ARG(kind >= st3d_phong::kAmbient && kind <= st3d_phong::kHeadlight);
+    ST3D_CHECK_ARG(kind == st3d_phong::kAmbient || (verts && normals));
+    ST3D_CHECK_ARG(grad_texture || grad_bary);
+    ST3D_CHECK_ARG(!grad_bary == !grad_np);
+    ST3D_CHECK_ARG(B > 0 && S > 0 && T > 1 && F > 0 && VT > 0 && weight_bound >= 0.f);
+    hipStream_t s = st3d::as_stream(stream);
+    const int tiles = (S + 15) / 16;
+    const st3d_phong::LitArgs la = lit_args(verts, normals, faces, R, trans, light, n_lights, kind, grad_np);
+    if (!workspace) {
+        shade_bwd_kernel<0, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs,
+                                                                       faces_uvs, texture, B, S, T, tiles, grad_texture, nullptr,
+                                                                       grad_bary, nullptr, la);
+        ST3D_LAUNCH_CHECK();
+        return ST3D_OK;
+    }
+    // fixed point: every texture contribution is |g| k ad_c w <= |g| weight_bound (k, w <= 1; weight_bound >= max ad_c)
+    ST3D_CHECK_ARG(grad_texture);
+    ST3D_CHECK_ARG(workspace_bytes >= st3d_shade_bwd_det_workspace_bytes(T) && ((uintptr_t)workspace & 15) == 0);
+    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
+    float *partials = st3d_det::partials_of(workspace);
+    long long *acc = st3d_det::accum_of(workspace, kDetPartials);
+    const size_t npx = (size_t)B * 3 * S * S, nacc = (size_t)T * T * 3;
+    st3d_det::det_abs_sum_scaled_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, npx, weight_bound, partials);
+    ST3D_LAUNCH_CHECK();
+    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kDetPartials, hdr);
+    ST3D_LAUNCH_CHECK();
+    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    shade_bwd_kernel<1, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs,
+                                                                   texture, B, S, T, tiles, reinterpret_cast<float *>(acc), nullptr,
+                                                                   grad_bary, hdr, la);
+    ST3D_LAUNCH_CHECK();
+    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_texture);
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "det.h"
+#include "phong.h"
 
 namespace {
 
@@ -322,11 +323,14 @@ struct SoftArgs {
 // no slot within kSoftProbe steps (K layers can touch more texels than the table holds) goes to global memory directly.
 constexpr int kSoftTexSlots = 2048, kSoftProbe = 24;
 
-template <int MODE, int DET = 0>
+// LIT 1: every layer's texel is lit first (phong.h: colour = ad * texel + sp) and that colour enters the blend; backward as
+// in shade_bwd_kernel<DET, 1> per layer (texture factor g kw ad_c, d/dN and d/dP per fragment into la.grad_np and gbary).
+template <int MODE, int DET = 0, int LIT = 0>
 __global__ __launch_bounds__(256) void soft_shade_kernel(const SoftArgs a, float *__restrict__ rgb, float *__restrict__ alpha_out,
                                                          const float *__restrict__ grad_rgb, float *__restrict__ gtex,
                                                          float *__restrict__ gbary, float *__restrict__ gz, float *__restrict__ gd,
-                                                         int tiles_x, const st3d_det::DetHeader *__restrict__ det) {
+                                                         int tiles_x, const st3d_det::DetHeader *__restrict__ det,
+                                                         const st3d_phong::LitArgs la = {}) {
     typedef typename std::conditional<DET != 0, unsigned long long, float>::type acc_t;
     __shared__ int s_key[MODE == 1 ? kSoftTexSlots : 1];
     __shared__ acc_t s_acc[MODE == 1 ? kSoftTexSlots : 1][3];
@@ -408,6 +412,8 @@ __global__ __launch_bounds__(256) void soft_shade_kernel(const SoftArgs a, float
         const float *t00 = a.tex + ((size_t)q.r0 * T + q.x0) * 3, *t01 = a.tex + ((size_t)q.r0 * T + q.x1) * 3;
         const float *t10 = a.tex + ((size_t)q.r1 * T + q.x0) * 3, *t11 = a.tex + ((size_t)q.r1 * T + q.x1) * 3;
         float t[3];
+        float ad[3] = {1.f, 1.f, 1.f}, sp[3] = {0.f, 0.f, 0.f};
+        if (LIT) st3d_phong::phong_fwd(la, (int)b, f, b0, b1, b2, ad, sp);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             float s = 0.f;
@@ -415,7 +421,7 @@ __global__ __launch_bounds__(256) void soft_shade_kernel(const SoftArgs a, float
             if (q.vy0 && q.vx1) s += t01[c] * w01;
             if (q.vy1 && q.vx0) s += t10[c] * w10;
             if (q.vy1 && q.vx1) s += t11[c] * w11;
-            t[c] = s;
+            t[c] = LIT ? ad[c] * s + sp[c] : s;
         }
         wsum += w; c0 += w * t[0]; c1 += w * t[1]; c2 += w * t[2];
     }
@@ -460,9 +466,12 @@ __global__ __launch_bounds__(256) void soft_shade_kernel(const SoftArgs a, float
         const float kw = w / denom;           // d rgb / d colour_k
         const float gc[3] = {g0, g1, g2};
         const float rr[3] = {r0, r1, r2};
+        float ad[3] = {1.f, 1.f, 1.f}, sp[3] = {0.f, 0.f, 0.f};
+        if (LIT) st3d_phong::phong_fwd(la, (int)b, f, b0, b1, b2, ad, sp);
+        float g_ad[3] = {0.f, 0.f, 0.f}, g_sp[3] = {0.f, 0.f, 0.f};
         float gix = 0.f, giy = 0.f, dw = 0.f;
         if (binned) {
-            const float gk3[3] = {g0 * kw, g1 * kw, g2 * kw};
+            const float gk3[3] = {LIT ? g0 * kw * ad[0] : g0 * kw, LIT ? g1 * kw * ad[1] : g1 * kw, LIT ? g2 * kw * ad[2] : g2 * kw};
             if (q.vy0 && q.vx0) deposit((int)(o00 / 3), gk3, w00);
             if (q.vy0 && q.vx1) deposit((int)(o01 / 3), gk3, w01);
             if (q.vy1 && q.vx0) deposit((int)(o10 / 3), gk3, w10);
@@ -477,15 +486,32 @@ __global__ __launch_bounds__(256) void soft_shade_kernel(const SoftArgs a, float
             if (q.vy1 && q.vx0) t10 = a.tex[o10 + c];
             if (q.vy1 && q.vx1) t11 = a.tex[o11 + c];
             const float tc = t00 * w00 + t01 * w01 + t10 * w10 + t11 * w11;
-            dw += gc[c] * (tc - rr[c]) / denom;
-            gix += gck * ((t01 - t00) * q.wy0 + (t11 - t10) * q.wy1);
-            giy += gck * ((t10 - t00) * q.wx0 + (t11 - t01) * q.wx1);
+            const float col = LIT ? ad[c] * tc + sp[c] : tc;
+            const float gcl = LIT ? gck * ad[c] : gck;
+            if (LIT) { g_ad[c] = gck * tc; g_sp[c] = gck; }
+            dw += gc[c] * (col - rr[c]) / denom;
+            gix += gcl * ((t01 - t00) * q.wy0 + (t11 - t10) * q.wy1);
+            giy += gcl * ((t10 - t00) * q.wx0 + (t11 - t01) * q.wx1);
         }
         if (gbary) {
             const float gu = q.cx ? 0.f : gix * (float)(T - 1), gv = q.cy ? 0.f : giy * (float)(T - 1);
             gbary[3 * (i * K + k)] = gu * a.uvs[2 * u0] + gv * a.uvs[2 * u0 + 1];
             gbary[3 * (i * K + k) + 1] = gu * a.uvs[2 * u1] + gv * a.uvs[2 * u1 + 1];
             gbary[3 * (i * K + k) + 2] = gu * a.uvs[2 * u2] + gv * a.uvs[2 * u2 + 1];
+            if (LIT && la.grad_np) {
+                st3d_phong::F3 gN = {0.f, 0.f, 0.f}, gP = {0.f, 0.f, 0.f};
+                if (la.kind != st3d_phong::kAmbient) {
+                    st3d_phong::phong_bwd(la, (int)b, f, b0, b1, b2, g_ad, g_sp, gN, gP);
+#pragma unroll
+                    for (int j = 0; j < 3; ++j) {          // dN/db_j = n_j, dP/db_j = v_j (original face: clipped slots too)
+                        const int vj = la.faces[3 * f + j];
+                        gbary[3 * (i * K + k) + j] += st3d_phong::dot3(gN, st3d_phong::f3(la.normals + 3 * vj)) +
+                                                      st3d_phong::dot3(gP, st3d_phong::f3(la.verts + 3 * vj));
+                    }
+                }
+                float *o = la.grad_np + 6 * (i * K + k);
+                o[0] = gN.x; o[1] = gN.y; o[2] = gN.z; o[3] = gP.x; o[4] = gP.y; o[5] = gP.z;
+            }
         }
         // w = prob * exp((z_inv - z_max)/gamma)
         const float dprob = dw * e;
@@ -932,6 +958,83 @@ extern "C" int st3d_raster_soft_bwd_det(const float *grad_bary, const float *gra
                                                                   reinterpret_cast<float *>(acc), frag_slot, z_clip, hdr, nullptr);
     ST3D_LAUNCH_CHECK();
     st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 0, grad_verts_ndc);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+// ------------------------------------------------------------------------------------------ lit shading (phong.h)
+namespace {
+st3d_phong::LitArgs soft_lit_args(const float *verts, const float *normals, const int32_t *faces, const float *R,
+                                  const float *trans, const float *light, int n_lights, int kind, float *grad_np) {
+    st3d_phong::LitArgs la;
+    la.verts = verts; la.normals = normals; la.faces = faces; la.R = R; la.T = trans; la.light = light;
+    la.n_lights = n_lights; la.kind = kind; la.grad_np = grad_np;
+    return la;
+}
+}  // namespace
+
+extern "C" int st3d_shade_soft_lit_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                                       const float *verts_uvs, const int32_t *faces_uvs, const float *texture, int B, int S,
+                                       int T, int K, float sigma, float gamma, const float *background, const float *verts,
+                                       const float *normals, const int32_t *faces, const float *R, const float *trans,
+                                       const float *light, int n_lights, int kind, float *rgb, float *alpha,
+                                       st3d_stream_t stream) {
+    ST3D_CHECK_ARG(pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture && background && rgb && alpha);
+    ST3D_CHECK_ARG(faces && R && trans && light && (n_lights == 1 || n_lights == B));
+    ST3D_CHECK_ARG(kind >= st3d_phong::kAmbient && kind <= st3d_phong::kHeadlight);
+    ST3D_CHECK_ARG(kind == st3d_phong::kAmbient || (verts && normals));
+    ST3D_CHECK_ARG(B > 0 && S > 0 && T > 1 && K >= 1 && sigma > 0.f && gamma > 0.f);
+    SoftArgs a{pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, K, sigma, gamma, background[0],
+               background[1], background[2]};
+    const size_t n = (size_t)B * S * S;
+    soft_shade_kernel<0, 0, 1><<<st3d::cdiv((long)n, 256), 256, 0, st3d::as_stream(stream)>>>(
+        a, rgb, alpha, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr,
+        soft_lit_args(verts, normals, faces, R, trans, light, n_lights, kind, nullptr));
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+extern "C" int st3d_shade_soft_lit_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                                       const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                                       int B, int S, int T, int K, float sigma, float gamma, const float *background,
+                                       const float *verts, const float *normals, const int32_t *faces, const float *R,
+                                       const float *trans, const float *light, int n_lights, int kind, float weight_bound,
+                                       float *grad_texture, float *grad_bary, float *grad_zbuf, float *grad_dists,
+                                       float *grad_np, void *workspace, size_t workspace_bytes, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(grad_rgb && pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture && background);
+    ST3D_CHECK_ARG(faces && R && trans && light && (n_lights == 1 || n_lights == B));
+    ST3D_CHECK_ARG(kind >= st3d_phong::kAmbient && kind <= st3d_phong::kHeadlight);
+    ST3D_CHECK_ARG(kind == st3d_phong::kAmbient || (verts && normals));
+    ST3D_CHECK_ARG(grad_texture || grad_bary || grad_zbuf || grad_dists);
+    ST3D_CHECK_ARG(!grad_np == !grad_bary);
+    ST3D_CHECK_ARG(B > 0 && S > 0 && T > 1 && K >= 1 && sigma > 0.f && gamma > 0.f && weight_bound >= 0.f);
+    hipStream_t s = st3d::as_stream(stream);
+    SoftArgs a{pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, K, sigma, gamma, background[0],
+               background[1], background[2]};
+    const st3d_phong::LitArgs la = soft_lit_args(verts, normals, faces, R, trans, light, n_lights, kind, grad_np);
+    const int tiles = (S + 15) / 16;
+    if (!workspace) {
+        soft_shade_kernel<1, 0, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(a, nullptr, nullptr, grad_rgb, grad_texture, grad_bary,
+                                                                          grad_zbuf, grad_dists, tiles, nullptr, la);
+        ST3D_LAUNCH_CHECK();
+        return ST3D_OK;
+    }
+    // fixed point: every texture contribution is |g| kw ad_c w <= |g| weight_bound
+    ST3D_CHECK_ARG(grad_texture);
+    ST3D_CHECK_ARG(workspace_bytes >= st3d_shade_soft_bwd_det_workspace_bytes(T) && ((uintptr_t)workspace & 15) == 0);
+    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
+    float *partials = st3d_det::partials_of(workspace);
+    long long *acc = st3d_det::accum_of(workspace, kSoftDetPartials);
+    const size_t npx = (size_t)B * 3 * S * S, nacc = (size_t)T * T * 3;
+    st3d_det::det_abs_sum_scaled_kernel<<<kSoftDetPartials, 256, 0, s>>>(grad_rgb, npx, weight_bound, partials);
+    ST3D_LAUNCH_CHECK();
+    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kSoftDetPartials, hdr);
+    ST3D_LAUNCH_CHECK();
+    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    soft_shade_kernel<1, 1, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(a, nullptr, nullptr, grad_rgb, reinterpret_cast<float *>(acc),
+                                                                      grad_bary, grad_zbuf, grad_dists, tiles, hdr, la);
+    ST3D_LAUNCH_CHECK();
+    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_texture);
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }

@@ -15,13 +15,14 @@ import torch.nn.functional as F
 
 from . import io as st3d_io
 from . import optim as st3d_optim
-from .render import (AmbientLights, FoVPerspectiveCameras, MeshRasterizer, MeshRenderer, RasterizationSettings,
-                     SoftPhongShader)
+from .render import (AmbientLights, DirectionalLights, FoVPerspectiveCameras, HeadLights, Materials, MeshRasterizer,
+                     MeshRenderer, PointLights, RasterizationSettings, SoftPhongShader)
 
-Flag = namedtuple("Flag", "name type default help choices", defaults=(None,))
+Flag = namedtuple("Flag", "name type default help choices nargs", defaults=(None, None))
 
 _BACKGROUNDS = ['noise', 'style', 'white']
 _TARGETS = ['texture', 'mesh', 'both']
+_LIGHTS = ['ambient', 'point', 'directional', 'headlight']
 
 # name, type, default and choices are the reference's (first_approach.py:23-45, second_approach.py:23-42); note
 # `type=bool` flags keep argparse's "any non-empty string is True" behaviour of the reference.
@@ -49,6 +50,10 @@ SHARED_FLAGS = [
     Flag("verts_lr", float, None, "separate Adam step size for the vertices when both are optimised (notes.txt:29 of the reference)"),
     Flag("checkpoint_every", int, 0, "write <output_path>/checkpoint.pt (parameters + Adam state) every N epochs/batches; 0 = never"),
     Flag("resume", str, None, "checkpoint.pt to continue from"),
+    Flag("lights", str, "ambient", "shading of every render: white ambient (the reference's), a point or directional light "
+         "(PyTorch3D's default colours), or a point light at each view's camera", _LIGHTS),
+    Flag("light_xyz", float, [0.0, 1.0, 0.0], "location of the point light / direction towards the directional light", None, 3),
+    Flag("shininess", float, 64.0, "Phong exponent of the material (lit runs)"),
 ]
 
 # regularisers the reference defines but never switches on (losses.py:48-65, notes.txt:36,39); weight 0 = off
@@ -65,8 +70,27 @@ def make_parser(extra_flags):
         kw = {"type": fl.type, "default": fl.default, "help": fl.help}
         if fl.choices:
             kw["choices"] = fl.choices
+        if fl.nargs:
+            kw["nargs"] = fl.nargs
         parser.add_argument("--" + fl.name, **kw)
     return parser
+
+
+def make_lights(args, device):
+    """--lights / --light_xyz / --shininess -> (lights, materials) of every render of the run (current and content
+    renders, final_render/).  'ambient' is the reference's white AmbientLights, rendered exactly as before."""
+    kind = getattr(args, "lights", "ambient")
+    if kind == "ambient":
+        return AmbientLights(device=device), None
+    materials = Materials(shininess=float(args.shininess), device=device)
+    xyz = (tuple(float(x) for x in args.light_xyz),)
+    if kind == "point":
+        return PointLights(location=xyz, device=device), materials
+    if kind == "directional":
+        return DirectionalLights(direction=xyz, device=device), materials
+    if kind == "headlight":
+        return HeadLights(device=device), materials
+    raise ValueError(f"unknown --lights {kind!r}")
 
 
 def load_scene(obj_path, size, resize_texture, device):
@@ -166,9 +190,10 @@ class Run:
 
         cams = FoVPerspectiveCameras(device=self.device)
         settings = RasterizationSettings(image_size=args.size, blur_radius=0.0, faces_per_pixel=1)
+        lights, materials = make_lights(args, self.device)
         self.renderer = MeshRenderer(rasterizer=MeshRasterizer(cameras=cams, raster_settings=settings),
-                                     shader=SoftPhongShader(device=self.device, cameras=cams,
-                                                            lights=AmbientLights(device=self.device)))
+                                     shader=SoftPhongShader(device=self.device, cameras=cams, lights=lights,
+                                                            materials=materials))
         self.say("Loading model...")
         self.vgg = _u.get_vgg(weights=args.vgg_weights)
 

@@ -306,6 +306,118 @@ def raster_soft_bwd(grads, p2f, verts_ndc, faces_i32, clip_bary, perspective_cor
     return g
 
 
+# ------------------------------------------------------------------ Phong lighting (csrc/phong.h, csrc/lighting.hip)
+# `lit` below is st3d.render.LitSetup: verts (V,3), normals (V,3) or None, faces_i32, R (B,3,3), T (B,3), block (n,24),
+# kind, weight_bound (see include/st3d.h)
+def vertex_normals(verts, faces_i32, incidence):
+    """-> (normals (V,3), unnormalised sums (V,3)); incidence = (inc_off (V+1), inc_ref (3F)) int32."""
+    verts = _f32c(verts)
+    V, F = verts.shape[0], faces_i32.shape[0]
+    dev = verts.device
+    scratch = torch.empty((_lib.load().st3d_vertex_normals_scratch_floats(F),), dtype=F32, device=dev)
+    n = torch.empty((V, 3), dtype=F32, device=dev)
+    m = torch.empty((V, 3), dtype=F32, device=dev)
+    call("st3d_vertex_normals", dptr(verts), dptr(faces_i32, I32), V, F, dptr(incidence[0], I32), dptr(incidence[1], I32),
+         dptr(scratch), dptr(n), dptr(m), stream_ptr())
+    return n, m
+
+
+def vertex_normals_bwd(verts, faces_i32, incidence, unnormalised, grad_normals, grad_pos, out):
+    """out (V,3) += grad_pos (or nothing) + d/dverts <grad_normals, normals(verts)>."""
+    verts = _f32c(verts)
+    V, F = verts.shape[0], faces_i32.shape[0]
+    scratch = torch.empty((_lib.load().st3d_vertex_normals_scratch_floats(F),), dtype=F32, device=verts.device)
+    call("st3d_vertex_normals_bwd", dptr(verts), dptr(faces_i32, I32), V, F, dptr(incidence[0], I32), dptr(incidence[1], I32),
+         dptr(unnormalised, F32), dptr(grad_normals.contiguous(), F32), dptr(grad_pos.contiguous(), F32) if grad_pos is not None
+         else None, dptr(scratch), dptr(out, F32), stream_ptr())
+    return out
+
+
+def _lit_ptrs(lit):
+    return (dptr(lit.verts, F32) if lit.normals is not None else None, dptr(lit.normals, F32) if lit.normals is not None else None,
+            dptr(lit.faces_i32, I32), dptr(lit.R, F32), dptr(lit.T, F32), dptr(lit.block, F32), lit.block.shape[0], lit.kind)
+
+
+def shade_lit_fwd(frag, verts_uvs, faces_uvs_i32, texture, lit):
+    p2f, zbuf, bary, dists = frag
+    B, S, _ = p2f.shape
+    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
+    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
+    call("st3d_shade_lit_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
+         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, texture.shape[0], faces_uvs_i32.shape[0], verts_uvs.shape[0],
+         *_lit_ptrs(lit), dptr(rgb), dptr(mask), stream_ptr())
+    return rgb, mask
+
+
+def shade_lit_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, lit, want_texture=True, want_geometry=False):
+    """-> (grad_texture (T,T,3) | None, grad_bary (B,S,S,3) | None, grad_np (B,S,S,6) | None)"""
+    p2f, zbuf, bary, dists = frag
+    B, S, _ = p2f.shape
+    T = texture.shape[0]
+    dev = p2f.device
+    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
+    gb = torch.empty((B, S, S, 3), dtype=F32, device=dev) if want_geometry else None
+    gnp = torch.empty((B, S, S, 6), dtype=F32, device=dev) if want_geometry else None
+    ws, nb = None, 0
+    if _DETERMINISTIC and gt is not None:
+        nb = _lib.load().st3d_shade_bwd_det_workspace_bytes(T)
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
+    call("st3d_shade_lit_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
+         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, faces_uvs_i32.shape[0],
+         verts_uvs.shape[0], *_lit_ptrs(lit), float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gnp), dptr(ws), nb,
+         stream_ptr())
+    return gt, gb, gnp
+
+
+def shade_soft_lit_fwd(frag, verts_uvs, faces_uvs_i32, texture, lit, sigma=1e-4, gamma=1e-4, background=(1.0, 1.0, 1.0)):
+    p2f, zbuf, bary, dists = frag
+    B, S, _, K = p2f.shape
+    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
+    alpha = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
+    call("st3d_shade_soft_lit_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
+         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, texture.shape[0], K, float(sigma), float(gamma), _bg3(background),
+         *_lit_ptrs(lit), dptr(rgb), dptr(alpha), stream_ptr())
+    return rgb, alpha
+
+
+def shade_soft_lit_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, lit, sigma=1e-4, gamma=1e-4,
+                       background=(1.0, 1.0, 1.0), want_texture=True, want_geometry=True):
+    """-> (grad_texture | None, (grad_bary, grad_zbuf, grad_dists) | None, grad_np (B,S,S,K,6) | None)"""
+    p2f, zbuf, bary, dists = frag
+    B, S, _, K = p2f.shape
+    T = texture.shape[0]
+    dev = p2f.device
+    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
+    gb = torch.empty((B, S, S, K, 3), dtype=F32, device=dev) if want_geometry else None
+    gz = torch.empty((B, S, S, K), dtype=F32, device=dev) if want_geometry else None
+    gd = torch.empty((B, S, S, K), dtype=F32, device=dev) if want_geometry else None
+    gnp = torch.empty((B, S, S, K, 6), dtype=F32, device=dev) if want_geometry else None
+    ws, nb = None, 0
+    if _DETERMINISTIC and gt is not None:
+        nb = _lib.load().st3d_shade_soft_bwd_det_workspace_bytes(T)
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
+    call("st3d_shade_soft_lit_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
+         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, K, float(sigma),
+         float(gamma), _bg3(background), *_lit_ptrs(lit), float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gz), dptr(gd),
+         dptr(gnp), dptr(ws), nb, stream_ptr())
+    return gt, ((gb, gz, gd) if want_geometry else None), gnp
+
+
+def phong_scatter(grad_np, p2f, bary, faces_i32, V):
+    """grad_np (B,S,S[,K],6) -> (2,V,3): d/d(vertex positions), d/d(vertex normals), summed over the views."""
+    B, S = p2f.shape[0], p2f.shape[1]
+    K = p2f.shape[3] if p2f.dim() == 4 else 1
+    dev = p2f.device
+    out = torch.empty((2, V, 3), dtype=F32, device=dev)
+    ws, nb = None, 0
+    if _DETERMINISTIC:
+        nb = _lib.load().st3d_phong_scatter_workspace_bytes(B, V, S)
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
+    call("st3d_phong_scatter", dptr(grad_np, F32), dptr(p2f, I32), dptr(bary, F32), dptr(faces_i32, I32), B, V,
+         faces_i32.shape[0], S, K, dptr(out), dptr(ws), nb, stream_ptr())
+    return out
+
+
 def apply_background(img, mask, bg=None):
     B, _, S, _ = img.shape
     out = torch.empty_like(img)

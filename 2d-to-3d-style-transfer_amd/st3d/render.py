@@ -10,8 +10,17 @@ raster, fused shade) and the backward is one launch (texture scatter).
 The reference's own configuration (blur_radius=0, faces_per_pixel=1, default BlendParams;
 first_approach.py:107) runs on the specialised hard kernels.  Any other RasterizationSettings /
 BlendParams (K <= 8 faces per pixel, blur_radius > 0, clipped barycentrics, sigma/gamma/background)
-runs on the general soft rasteriser + softmax blend (csrc/soft.hip).  Lights:
-AmbientLights only; cameras: FoV perspective with default fov/znear/zfar.
+runs on the general soft rasteriser + softmax blend (csrc/soft.hip).  Cameras: FoV
+perspective with default fov/znear/zfar.
+
+Lights: AmbientLights, PointLights, DirectionalLights (N = 1 or one per view) and Materials, as SoftPhongShader
+(phong_shading) lights them, on both kernel families, forward and backward (csrc/phong.h, csrc/lighting.hip):
+vertex normals n_v = normalize(sum of (v2 - v1) x (v0 - v1) over v's faces); per fragment N = sum b_i n_i,
+P = sum b_i v_i; L = location - P (point) or direction; D = kd Ld relu(n.l); r = -l + 2 (n.l) n,
+e = normalize(C - P) with C the camera centre, Sp = ks Ls (relu(e.r) [n.l > 0])^shininess, A = ka La;
+colour = (A + D) texel + Sp replaces the texel in the blend.  lights=None means white AmbientLights -- today's unlit
+render on the unchanged kernels (PyTorch3D's own default is PointLights(); the one deliberate divergence).  No
+gradient flows to lights, materials or cameras (a parameter with requires_grad raises).
 """
 import math
 
@@ -272,11 +281,233 @@ class BlendParams:
             raise ValueError("sigma and gamma must be positive")
 
 
+# ------------------------------------------------------------------------ lights and materials (csrc/phong.h)
+
+
+def _param(value, what, device):
+    """PyTorch3D light / material parameter -> (N,3) float32 tensor on `device`.  No gradient flows to lights or materials:
+    a tensor that asks for one is refused instead of silently getting none."""
+    if isinstance(value, torch.Tensor) and value.requires_grad:
+        raise NotImplementedError(f"{what}: gradients to lights and materials are not implemented (requires_grad=True)")
+    t = torch.as_tensor(value, dtype=torch.float32)
+    t = t.reshape(1, 3) if t.dim() <= 1 else t
+    if t.dim() != 2 or t.shape[1] != 3 or t.shape[0] < 1:
+        raise ValueError(f"{what} must have shape (N, 3), got {tuple(t.shape)}")
+    return t.to(device)
+
+
+def _batch(*params):
+    """the common N of (N,3) parameters (each N is 1 or that N)"""
+    n = max(p.shape[0] for p in params)
+    if any(p.shape[0] not in (1, n) for p in params):
+        raise ValueError("light / material parameters must all have N = 1 or the same N")
+    return n
+
+
 class AmbientLights:
+    """PyTorch3D AmbientLights: ambient_color (N,3), no diffuse or specular light.  White with default Materials is today's
+    unlit render (the specialised ambient kernels); any other colour scales the texel per channel."""
+
     def __init__(self, ambient_color=((1.0, 1.0, 1.0),), device="cpu"):
-        c = torch.as_tensor(ambient_color, dtype=torch.float32).reshape(-1)
-        if not torch.allclose(c, torch.ones(3)):
-            raise NotImplementedError("only the default white ambient light is supported")
+        self.device = torch.device(device)
+        self.ambient_color = _param(ambient_color, "ambient_color", self.device)
+        self.diffuse_color = torch.zeros_like(self.ambient_color)
+        self.specular_color = torch.zeros_like(self.ambient_color)
+        _batch(self.ambient_color)
+
+    def _params(self):
+        return (self.ambient_color, self.diffuse_color, self.specular_color, torch.zeros_like(self.ambient_color))
+
+
+class PointLights:
+    """PyTorch3D PointLights (defaults: ambient 0.5, diffuse 0.3, specular 0.2, location (0, 1, 0)); N = 1 or one per view."""
+    KIND = 1
+
+    def __init__(self, ambient_color=((0.5, 0.5, 0.5),), diffuse_color=((0.3, 0.3, 0.3),),
+                 specular_color=((0.2, 0.2, 0.2),), location=((0.0, 1.0, 0.0),), device="cpu"):
+        self.device = torch.device(device)
+        self.ambient_color = _param(ambient_color, "ambient_color", self.device)
+        self.diffuse_color = _param(diffuse_color, "diffuse_color", self.device)
+        self.specular_color = _param(specular_color, "specular_color", self.device)
+        self.location = _param(location, "location", self.device)
+        _batch(*self._params())
+
+    def _params(self):
+        return (self.ambient_color, self.diffuse_color, self.specular_color, self.location)
+
+
+class DirectionalLights:
+    """PyTorch3D DirectionalLights (same colours as PointLights, direction (0, 1, 0) pointing TOWARDS the light)."""
+    KIND = 2
+
+    def __init__(self, ambient_color=((0.5, 0.5, 0.5),), diffuse_color=((0.3, 0.3, 0.3),),
+                 specular_color=((0.2, 0.2, 0.2),), direction=((0.0, 1.0, 0.0),), device="cpu"):
+        self.device = torch.device(device)
+        self.ambient_color = _param(ambient_color, "ambient_color", self.device)
+        self.diffuse_color = _param(diffuse_color, "diffuse_color", self.device)
+        self.specular_color = _param(specular_color, "specular_color", self.device)
+        self.direction = _param(direction, "direction", self.device)
+        _batch(*self._params())
+
+    def _params(self):
+        return (self.ambient_color, self.diffuse_color, self.specular_color, self.direction)
+
+
+class HeadLights(PointLights):
+    """A PointLights at every view's own camera centre (the CLIs' --lights headlight): the kernels take the location from
+    the view's R and T, so it follows the views through batching and sharding.  Colours as PointLights."""
+    KIND = 3
+
+    def __init__(self, ambient_color=((0.5, 0.5, 0.5),), diffuse_color=((0.3, 0.3, 0.3),),
+                 specular_color=((0.2, 0.2, 0.2),), device="cpu"):
+        super().__init__(ambient_color, diffuse_color, specular_color, ((0.0, 0.0, 0.0),), device)
+
+
+class Materials:
+    """PyTorch3D Materials (defaults: ambient = diffuse = specular = (1, 1, 1), shininess 64)."""
+
+    def __init__(self, ambient_color=((1.0, 1.0, 1.0),), diffuse_color=((1.0, 1.0, 1.0),),
+                 specular_color=((1.0, 1.0, 1.0),), shininess=64, device="cpu"):
+        self.device = torch.device(device)
+        self.ambient_color = _param(ambient_color, "ambient_color", self.device)
+        self.diffuse_color = _param(diffuse_color, "diffuse_color", self.device)
+        self.specular_color = _param(specular_color, "specular_color", self.device)
+        if isinstance(shininess, torch.Tensor) and shininess.requires_grad:
+            raise NotImplementedError("shininess: gradients to lights and materials are not implemented (requires_grad=True)")
+        self.shininess = torch.as_tensor(shininess, dtype=torch.float32).reshape(-1).to(self.device)
+        _batch(self.ambient_color, self.diffuse_color, self.specular_color, self.shininess[:, None].expand(-1, 3))
+
+
+_LIGHT_FLOATS = 24          # include/st3d.h: the light block layout
+_PACK_CACHE = {}
+
+
+class Lighting:
+    """What the lit kernels need of a (lights, materials) pair: the packed block (n,24) on the device, the kind
+    (0 ambient only, 1 point, 2 directional, 3 headlight) and the bound of the lighting factor (A + D) for the fixed-point
+    texture scatter."""
+
+    def __init__(self, block, kind, weight_bound):
+        self.block, self.kind, self.weight_bound = block, kind, weight_bound
+
+    @property
+    def n(self):
+        return self.block.shape[0]
+
+
+def _tensors_of(lights, materials):
+    ts = list(lights._params())
+    if materials is not None:
+        ts += [materials.ambient_color, materials.diffuse_color, materials.specular_color, materials.shininess]
+    return ts
+
+
+def lighting_of(lights, materials, device):
+    """(lights, materials) -> None for today's unlit kernels (lights None, or white AmbientLights with absent or default
+    Materials: those render bit for bit as before), else a Lighting.  Packed once per object pair and cached on the
+    identity and version of its tensors: steady state costs no host work."""
+    if lights is None:
+        return None
+    if not isinstance(lights, (AmbientLights, PointLights, DirectionalLights)):
+        raise NotImplementedError(f"{type(lights).__name__} is not implemented (AmbientLights, PointLights, DirectionalLights)")
+    ts = _tensors_of(lights, materials)
+    if any(t.requires_grad for t in ts):
+        raise NotImplementedError("gradients to lights and materials are not implemented (a parameter has requires_grad=True)")
+    key = (id(lights), id(materials), tuple((t.data_ptr(), t._version) for t in ts), str(device))
+    hit = _PACK_CACHE.get(key)
+    if hit is not None:
+        return hit[0]
+    mat = materials if materials is not None else Materials()
+    la, ld, ls, pos = (t.detach().cpu() for t in lights._params())
+    ka, kd, ks = (t.detach().cpu() for t in (mat.ambient_color, mat.diffuse_color, mat.specular_color))
+    sh = mat.shininess.detach().cpu()[:, None]
+    n = _batch(la, ld, ls, pos, ka, kd, ks, sh.expand(-1, 3))
+    kind = 0 if isinstance(lights, AmbientLights) else lights.KIND
+    if kind == 0 and bool((la == 1).all()) and bool((ka == 1).all()):
+        out = None                                         # white ambient x default ambient material: the unlit kernels
+    else:
+        block = torch.zeros((n, _LIGHT_FLOATS), dtype=torch.float32)
+        for j, t in enumerate((la, ld, ls, pos, ka, kd, ks)):
+            block[:, 3 * j:3 * j + 3] = t.expand(n, 3)
+        block[:, 21] = sh[:, 0].expand(n)
+        bound = float(((ka * la).abs() + (kd * ld).abs()).max())
+        out = Lighting(block.to(device), kind, bound if math.isfinite(bound) else float("nan"))
+    if len(_PACK_CACHE) > 64:
+        _PACK_CACHE.clear()
+    _PACK_CACHE[key] = (out, lights, materials)            # keep the keyed objects alive: their ids stay unique
+    return out
+
+
+_INCIDENCE_CACHE = {}
+
+
+def vertex_incidence(faces_i32, V):
+    """vertex -> (face, corner) incidence in CSR form: inc_off (V+1) and inc_ref (3F) = face * 3 + corner, every entry once,
+    ascending within each vertex (the fixed order of the vertex-normal gathers).  Built once per topology."""
+    key = (faces_i32.data_ptr(), tuple(faces_i32.shape), faces_i32._version, int(V), str(faces_i32.device))
+    hit = _INCIDENCE_CACHE.get(key)
+    if hit is None:
+        idx = faces_i32.reshape(-1).to(torch.int64)
+        ref = torch.argsort(idx, stable=True)
+        off = torch.zeros(V + 1, dtype=torch.int64, device=idx.device)
+        off[1:] = torch.cumsum(torch.bincount(idx, minlength=V), 0)
+        if len(_INCIDENCE_CACHE) > 64:
+            _INCIDENCE_CACHE.clear()
+        hit = ((off.to(torch.int32).contiguous(), ref.to(torch.int32).contiguous()), faces_i32)
+        _INCIDENCE_CACHE[key] = hit
+    return hit[0]
+
+
+_NORMAL_CACHE = {}
+
+
+def _vertex_normals(verts, v32, faces_i32, incidence):
+    """-> (normals, unnormalised sums) of the mesh; cached on the vertices' identity and version when they are not being
+    optimised (texture-only runs compute them once)."""
+    key = None
+    if not verts.requires_grad:
+        key = (v32.data_ptr(), v32._version, tuple(v32.shape), faces_i32.data_ptr(), str(v32.device))
+        hit = _NORMAL_CACHE.get(key)
+        if hit is not None:
+            return hit[0]
+    out = ops.vertex_normals(v32, faces_i32, incidence)
+    if key is not None:
+        if len(_NORMAL_CACHE) > 16:
+            _NORMAL_CACHE.clear()
+        _NORMAL_CACHE[key] = (out, v32, faces_i32)
+    return out
+
+
+class LitSetup:
+    """Per-render arguments of the lit kernels (st3d.ops.shade_lit_*)."""
+
+    def __init__(self, lighting, verts, faces_i32, R, T, normals=None, unnormalised=None, incidence=None):
+        self.block, self.kind, self.weight_bound = lighting.block, lighting.kind, lighting.weight_bound
+        self.verts, self.faces_i32, self.R, self.T = verts, faces_i32, R.to(torch.float32).contiguous(), \
+            T.to(torch.float32).contiguous()
+        self.normals, self.unnormalised, self.incidence = normals, unnormalised, incidence
+
+
+def _lit_setup(lighting, verts_in, v, faces_i32, R, T):
+    if lighting is None:
+        return None
+    if lighting.n not in (1, R.shape[0]):
+        raise ValueError(f"lights have N = {lighting.n} entries; a batch of {R.shape[0]} views takes N = 1 or N = "
+                         f"{R.shape[0]}")
+    if lighting.kind == 0:
+        return LitSetup(lighting, v, faces_i32, R, T)
+    inc = vertex_incidence(faces_i32, v.shape[0])
+    n, m = _vertex_normals(verts_in, v, faces_i32, inc)
+    return LitSetup(lighting, v, faces_i32, R, T, n, m, inc)
+
+
+def _lit_vertex_grad(lit, gverts, gnp, p2f, bary):
+    """gverts (V,3) += the lighting's direct world-space terms: d/dP and, through the vertex normals, d/dN"""
+    if lit.kind == 0:
+        return gverts
+    V = lit.verts.shape[0]
+    s = ops.phong_scatter(gnp, p2f, bary, lit.faces_i32, V)
+    return ops.vertex_normals_bwd(lit.verts, lit.faces_i32, lit.incidence, lit.unnormalised, s[1], s[0], gverts)
 
 
 class MeshRasterizer:
@@ -285,9 +516,13 @@ class MeshRasterizer:
 
 
 class SoftPhongShader:
+    """PyTorch3D SoftPhongShader: lights (None = white AmbientLights -- PyTorch3D's own default is PointLights(); this is
+    the one deliberate divergence, it keeps the reference's unlit renders) and materials (None = Materials())."""
+
     def __init__(self, device="cpu", cameras=None, lights=None, materials=None, blend_params=None, **kw):
-        self.cameras, self.lights = cameras, lights
+        self.cameras, self.lights, self.materials = cameras, lights, materials
         self.blend_params = blend_params if blend_params is not None else BlendParams()
+        lighting_of(lights, materials, device)      # validate now (N, requires_grad)
 
 
 class _RenderFn(torch.autograd.Function):
@@ -295,7 +530,7 @@ class _RenderFn(torch.autograd.Function):
     when the vertices need a gradient, shade d/d(bary) -> raster backward -> projection backward."""
 
     @staticmethod
-    def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S):
+    def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, lighting=None):
         v = verts.detach().to(torch.float32).contiguous()
         tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
         if tex.shape[0] != tex.shape[1]:
@@ -304,7 +539,11 @@ class _RenderFn(torch.autograd.Function):
         ndc = ops.project_verts(v, R, T)
         # (no near-plane watch here: render_views has looked at the vertices' depths before choosing these kernels)
         frag = ops.raster_fwd(ndc, faces_i32, S)
-        rgb, mask = ops.shade_fwd(frag, uvs, faces_uvs_i32, tex)
+        ctx.lit = _lit_setup(lighting, verts, v, faces_i32, R, T)
+        if ctx.lit is None:
+            rgb, mask = ops.shade_fwd(frag, uvs, faces_uvs_i32, tex)
+        else:
+            rgb, mask = ops.shade_lit_fwd(frag, uvs, faces_uvs_i32, tex, ctx.lit)
         ctx.frag, ctx.uvs, ctx.fuv, ctx.tex = frag, uvs, faces_uvs_i32, tex
         ctx.tex_shape = tex_map.shape
         ctx.geom = (v, ndc, faces_i32, R, T)
@@ -321,6 +560,17 @@ class _RenderFn(torch.autograd.Function):
     def _backward(ctx, grad_rgb, _grad_mask):
         need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         gtex = gverts = None
+        if ctx.lit is not None and (need_v or need_t):
+            gt, gbary, gnp = ops.shade_lit_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit,
+                                               want_texture=need_t, want_geometry=need_v)
+            if need_t:
+                gtex = gt.reshape(ctx.tex_shape)
+            if need_v:
+                v, ndc, faces_i32, R, T = ctx.geom
+                gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
+                gverts = ops.project_verts_bwd(v, R, T, gndc)
+                gverts = _lit_vertex_grad(ctx.lit, gverts, gnp, ctx.frag[0], ctx.frag[2]).reshape(ctx.verts_shape)
+            return gverts, gtex, None, None, None, None, None, None, None
         if need_v or need_t:
             res = ops.shade_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, want_bary=need_v,
                                 want_texture=need_t)
@@ -331,7 +581,7 @@ class _RenderFn(torch.autograd.Function):
                 v, ndc, faces_i32, R, T = ctx.geom
                 gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
                 gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
-        return gverts, gtex, None, None, None, None, None, None
+        return gverts, gtex, None, None, None, None, None, None, None
 
 
 class _SoftRenderFn(torch.autograd.Function):
@@ -341,7 +591,7 @@ class _SoftRenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, K, blur, clip, sigma, gamma, bg,
-                cull=False, persp=True, z_clip=None):
+                cull=False, persp=True, z_clip=None, lighting=None):
         v = verts.detach().to(torch.float32).contiguous()
         tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
         if tex.shape[0] != tex.shape[1]:
@@ -352,7 +602,11 @@ class _SoftRenderFn(torch.autograd.Function):
         ctx.slots = frag[4] if z_clip is not None else None
         ctx.z_clip = z_clip
         frag = frag[:4]
-        rgb, alpha = ops.shade_soft_fwd(frag, uvs, faces_uvs_i32, tex, sigma, gamma, bg)
+        ctx.lit = _lit_setup(lighting, verts, v, faces_i32, R, T)
+        if ctx.lit is None:
+            rgb, alpha = ops.shade_soft_fwd(frag, uvs, faces_uvs_i32, tex, sigma, gamma, bg)
+        else:
+            rgb, alpha = ops.shade_soft_lit_fwd(frag, uvs, faces_uvs_i32, tex, ctx.lit, sigma, gamma, bg)
         ctx.persp = persp
         ctx.frag, ctx.uvs, ctx.fuv, ctx.tex = frag, uvs, faces_uvs_i32, tex
         ctx.blend = (sigma, gamma, bg)
@@ -373,15 +627,23 @@ class _SoftRenderFn(torch.autograd.Function):
         gtex = gverts = None
         if need_v or need_t:
             sigma, gamma, bg = ctx.blend
-            gt, geo = ops.shade_soft_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, sigma, gamma, bg,
-                                         want_texture=need_t, want_geometry=need_v)
+            gnp = None
+            if ctx.lit is None:
+                gt, geo = ops.shade_soft_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, sigma, gamma, bg,
+                                             want_texture=need_t, want_geometry=need_v)
+            else:
+                gt, geo, gnp = ops.shade_soft_lit_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit,
+                                                      sigma, gamma, bg, want_texture=need_t, want_geometry=need_v)
             if need_t:
                 gtex = gt.reshape(ctx.tex_shape)
             if need_v:
                 v, ndc, faces_i32, R, T = ctx.geom
                 gndc = ops.raster_soft_bwd(geo, ctx.frag[0], ndc, faces_i32, ctx.clip, ctx.persp, ctx.slots, ctx.z_clip)
-                gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
-        return (gverts, gtex) + (None,) * 15
+                gverts = ops.project_verts_bwd(v, R, T, gndc)
+                if ctx.lit is not None:
+                    gverts = _lit_vertex_grad(ctx.lit, gverts, gnp, ctx.frag[0], ctx.frag[2])
+                gverts = gverts.reshape(ctx.verts_shape)
+        return (gverts, gtex) + (None,) * 16
 
 
 def uses_hard_path(raster_settings, blend_params):
@@ -420,20 +682,22 @@ def reaches_near_plane(verts, R, T, z_clip):
     return near
 
 
-def render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None):
+def render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None, lights=None, materials=None):
     """``_render_views`` inside a named range (``ST3D_ROCTX=1``: rocprofv3 --marker-trace shows the step's phases)."""
     with ops.trace("render"):
-        return _render_views(meshes, R, T, image_size, raster_settings, blend_params)
+        return _render_views(meshes, R, T, image_size, raster_settings, blend_params, lights, materials)
 
 
-def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None):
+def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None, lights=None, materials=None):
     """All B views in one batch of launches -> (rgb (B,3,S,S), coverage (B,1,S,S)).  Coverage is the 0/1 mask under
     the reference's hard settings (whichever kernels render them) and softmax_rgb_blend's alpha under soft settings;
-    both satisfy ``coverage > 0`` == covered."""
+    both satisfy ``coverage > 0`` == covered.  lights / materials: the shading (lighting_of: None = today's unlit
+    kernels); both kernel families light, so a batch rerouted to the clipping kernels keeps its lighting."""
     tex = meshes.textures
     dev = meshes.device
     rs, bp = raster_settings, blend_params
     R, T = R.to(dev), T.to(dev)
+    lighting = lighting_of(lights, materials, dev)
     hard_settings = uses_hard_path(rs, bp)
     if hard_settings and (ops.near_plane_triggered() or
                           reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT)):
@@ -447,13 +711,13 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
     if uses_hard_path(rs, bp):
         # K=1, blur 0: the blend weight cancels and the pixel is the sampled texel itself
         return _RenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
-                               tex.faces_uvs_i32(), R, T, int(image_size))
+                               tex.faces_uvs_i32(), R, T, int(image_size), lighting)
     bp = bp if bp is not None else BlendParams()
     rs = rs if rs is not None else RasterizationSettings(image_size=image_size)
     rgb, alpha = _SoftRenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
                                      tex.faces_uvs_i32(), R, T, int(image_size), rs.faces_per_pixel,
                                      rs.blur_radius, rs.clip_barycentric_coords, bp.sigma, bp.gamma, bp.background_color,
-                                     rs.cull_backfaces, rs.perspective_correct, rs.z_clip)
+                                     rs.cull_backfaces, rs.perspective_correct, rs.z_clip, lighting)
     if hard_settings:
         # the caller asked for the hard configuration and is handed what the hard path hands out: the 0/1 coverage mask
         # (alpha of a K = 1 / blur 0 blend is in [0.5, 1) on covered pixels; the reference thresholds it, utils.py:72)
@@ -477,15 +741,18 @@ class MeshRenderer:
     def is_hard(self):
         return uses_hard_path(self.rasterizer.raster_settings, getattr(self.shader, "blend_params", None))
 
-    def render(self, meshes_world, cameras=None):
-        """-> (rgb (n,3,S,S), coverage (n,1,S,S)) under this renderer's raster settings and blend params."""
+    def render(self, meshes_world, cameras=None, lights=None, materials=None):
+        """-> (rgb (n,3,S,S), coverage (n,1,S,S)) under this renderer's raster settings, blend params and shading;
+        lights / materials given here replace the shader's for this call (as PyTorch3D's ``renderer(mesh, lights=...)``)."""
         cameras = cameras if cameras is not None else self.rasterizer.cameras
         R, T = join_cameras(cameras)
+        lights = lights if lights is not None else getattr(self.shader, "lights", None)
+        materials = materials if materials is not None else getattr(self.shader, "materials", None)
         return render_views(meshes_world, R, T, self.image_size, self.rasterizer.raster_settings,
-                            getattr(self.shader, "blend_params", None))
+                            getattr(self.shader, "blend_params", None), lights, materials)
 
-    def __call__(self, meshes_world, cameras=None, **kw):
-        rgb, cov = self.render(meshes_world, cameras)
+    def __call__(self, meshes_world, cameras=None, lights=None, materials=None, **kw):
+        rgb, cov = self.render(meshes_world, cameras, lights, materials)
         # hard path: alpha of softmax_rgb_blend with K=1 is in [0.5,1) on covered pixels, 0 elsewhere; only
         # (alpha > 0) is ever consumed (utils.py:72), so the 0/1 mask stands in for it.  Soft path: the real alpha.
         return torch.cat([rgb, cov], dim=1).permute(0, 2, 3, 1)

@@ -192,6 +192,66 @@ int st3d_raster_soft_bwd_det(const float *grad_bary, const float *grad_zbuf, con
                              int S, int K, int clip_bary, int perspective_correct, const int32_t *frag_slot, float z_clip,
                              float *grad_verts_ndc, void *workspace, size_t workspace_bytes, st3d_stream_t stream);
 
+/* ---- Phong lighting (PyTorch3D SoftPhongShader with PointLights / DirectionalLights / AmbientLights and Materials;
+ * csrc/phong.h holds the per-fragment formulas, csrc/lighting.hip the mesh side).  World space throughout: vertex normals
+ * n_v = m_v / max(|m_v|, 1e-6), m_v = sum over v's faces of (v2 - v1) x (v0 - v1); per fragment N = sum b_i n_i,
+ * P = sum b_i v_i, camera centre C = -T R^T (from R, T of the view); colour = (A + D) * texel + Sp replaces the texel in
+ * the blend (no clamping; the background is not lit).
+ *
+ * Light block: n_lights (1, or B = one per view) entries of 24 floats:
+ *   [0..2] ambient_color  [3..5] diffuse_color  [6..8] specular_color  [9..11] location (point) / direction (directional)
+ *   [12..14] material ambient  [15..17] material diffuse  [18..20] material specular  [21] shininess  [22..23] unused
+ * kind: 0 ambient only (colour = ka La texel; verts / normals may be NULL), 1 point, 2 directional, 3 point light at each
+ * view's camera centre (headlight; [9..11] unused).
+ *
+ * Incidence list of the vertex normals: inc_off (V+1), inc_ref (3F) = face * 3 + corner, ascending within each vertex. */
+size_t st3d_vertex_normals_scratch_floats(int F);
+/* normals (V,3) and the unnormalised sums m (V,3) the backward needs; scratch >= st3d_vertex_normals_scratch_floats */
+int st3d_vertex_normals(const float *verts, const int32_t *faces, int V, int F, const int32_t *inc_off,
+                        const int32_t *inc_ref, float *scratch, float *normals, float *unnormalised, st3d_stream_t stream);
+/* grad_verts (V,3) += grad_pos (may be NULL) + d/dverts of <grad_normals, normals(verts)> */
+int st3d_vertex_normals_bwd(const float *verts, const int32_t *faces, int V, int F, const int32_t *inc_off,
+                            const int32_t *inc_ref, const float *unnormalised, const float *grad_normals,
+                            const float *grad_pos, float *scratch, float *grad_verts, st3d_stream_t stream);
+/* st3d_shade_fwd with lighting (R (B,3,3), trans (B,3): the cameras of the views) */
+int st3d_shade_lit_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                       const float *verts_uvs, const int32_t *faces_uvs, const float *texture, int B, int S, int T,
+                       int F, int VT, const float *verts, const float *normals, const int32_t *faces, const float *R,
+                       const float *trans, const float *light, int n_lights, int kind, float *rgb, float *mask,
+                       st3d_stream_t stream);
+/* -> grad_texture (T,T,3) accumulated (may be NULL), grad_bary (B,S,S,3) and grad_np (B,S,S,6) = per pixel d/dN, d/dP
+ * (both or neither).  workspace NULL: float atomics; else (>= st3d_shade_bwd_det_workspace_bytes(T), 16-byte aligned,
+ * grad_texture given) the fixed-point scatter of st3d_shade_bwd_det, its bound scaled by weight_bound >= max_c (A + D)_c
+ * (e.g. max over entries and channels of |ka La| + |kd Ld|). */
+int st3d_shade_lit_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                       const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                       int B, int S, int T, int F, int VT, const float *verts, const float *normals,
+                       const int32_t *faces, const float *R, const float *trans, const float *light, int n_lights,
+                       int kind, float weight_bound, float *grad_texture, float *grad_bary, float *grad_np,
+                       void *workspace, size_t workspace_bytes, st3d_stream_t stream);
+/* the same for the general soft kernels (per layer: grad_np (B,S,S,K,6)); det workspace
+ * >= st3d_shade_soft_bwd_det_workspace_bytes(T) */
+int st3d_shade_soft_lit_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                            const float *verts_uvs, const int32_t *faces_uvs, const float *texture, int B, int S,
+                            int T, int K, float sigma, float gamma, const float *background, const float *verts,
+                            const float *normals, const int32_t *faces, const float *R, const float *trans,
+                            const float *light, int n_lights, int kind, float *rgb, float *alpha,
+                            st3d_stream_t stream);
+int st3d_shade_soft_lit_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                            const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                            int B, int S, int T, int K, float sigma, float gamma, const float *background,
+                            const float *verts, const float *normals, const int32_t *faces, const float *R,
+                            const float *trans, const float *light, int n_lights, int kind, float weight_bound,
+                            float *grad_texture, float *grad_bary, float *grad_zbuf, float *grad_dists,
+                            float *grad_np, void *workspace, size_t workspace_bytes, st3d_stream_t stream);
+/* grad_np of the lit backward (K layers per pixel, K = 1 for the specialised path) -> out (2,V,3) = [d/d(vertex
+ * positions), d/d(vertex normals)] through N = sum b_i n_i, P = sum b_i v_i, summed over the views (world space); out is
+ * overwritten.  workspace NULL: float atomics; else (>= st3d_phong_scatter_workspace_bytes) bitwise reproducible. */
+size_t st3d_phong_scatter_workspace_bytes(int B, int V, int S);
+int st3d_phong_scatter(const float *grad_np, const int32_t *pix_to_face, const float *bary, const int32_t *faces,
+                       int B, int V, int F, int S, int K, float *out, void *workspace, size_t workspace_bytes,
+                       st3d_stream_t stream);
+
 /* apply_background, utils.py:19-30: out = img*mask + bg*(1-mask); bg (B,3,S,S) or, with
  * bg_batch == 1, one (3,S,S) image broadcast over the batch.  Optional grad path is the
  * same kernel applied to the gradient with bg = NULL (out = g*mask). */

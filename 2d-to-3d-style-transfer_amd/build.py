@@ -28,6 +28,7 @@ SOURCES = {
     "shade.hip": ["-ffp-contract=off"],
     "soft.hip": ["-ffp-contract=off"],
     "lighting.hip": ["-ffp-contract=off"],
+    "silhouette.hip": ["-ffp-contract=off"],   # its alpha is compared bit for bit with soft.hip's
     "conv.hip": ["-fno-slp-vectorize"],   # the VALU conv1_1 kernels: SLP-packed v_pk_fma needs register-pair shuffles
     "wino.hip": ["-fno-slp-vectorize"],   # SLP-packed f32 (v_pk_*) needs register shuffles that cost matrix-pipe time
     "wino43.hip": ["-fno-slp-vectorize"],  # (with SLP packing the nine-layer sum is 0.8 % faster, but the re-associated column transform

@@ -46,6 +46,10 @@ struct TraceRange {
         if (r_ != ST3D_OK) return r_;                                                    \
     } while (0)
 
+// loss.hip: loss_out[0] += scale * (sum of partials[0..np) in index order, in fp64) -- the second stage of every ordered
+// two-stage reduction; np <= st3d_reduce_partials()
+int finish_partials(const float *partials, int np, float scale, float *loss_out, hipStream_t stream);
+
 constexpr int kWave = 64;
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

@@ -237,6 +237,13 @@ inline int grid_for(size_t n) {
 
 extern "C" int st3d_reduce_partials(void) { return NPART; }
 
+// the finishing reduction for kernels of other files that write their own per-workgroup partials (silhouette.hip)
+int st3d::finish_partials(const float *partials, int np, float scale, float *loss_out, hipStream_t stream) {
+    finish_kernel<<<1, 256, 0, stream>>>(partials, np, scale, loss_out);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
 extern "C" int st3d_sqdiff_sum(const float *a, const float *b, size_t n, size_t nb, float scale, float *D, float *partials,
                                float *loss_out, st3d_stream_t stream) {
     ST3D_CHECK_ARG(a && b && partials && loss_out);

@@ -53,13 +53,13 @@ def main(argv=None):
             continue
         run.say(f"\nBatch {vb.index}")
         n_local = vb.hi - vb.lo
-        targets = cams = None
+        targets = cams = outline = None
         if n_local:
             cams = run.cameras[vb.lo:vb.hi]
             style = run.style_image.expand(n_local, -1, -1, -1)
             with torch.no_grad():
-                img, cov = render_meshes(run.renderer, run.content_mesh, cams)
-                content = apply_background(img, cov, background_type=args.content_background, background=style)
+                img, outline = render_meshes(run.renderer, run.content_mesh, cams)    # outline: --silhouette_weight's target
+                content = apply_background(img, outline, background_type=args.content_background, background=style)
                 start = _phase_a_start(run, args, content, cams, style)
             # phase A: the whole batch is stylised at once; the result may leave [0,1], hence the clamp
             targets = finalize_tensor(style_transfer(start, content, style, run.vgg, steps=args.n_style_transfer_steps,
@@ -78,6 +78,10 @@ def main(argv=None):
                                                    verts=run.opt['verts'], target_verts=run.original_verts, mesh=mesh,
                                                    weights=run.loss_weights, opt_type=args.optimization_target,
                                                    batch_denom=vb.size)     # image term -> share of the batch mean
+                # the masked MSE is masked by the CURRENT render's coverage and cannot see the outline move; this term can
+                outline_term = run.silhouette_term(mesh, cams, outline, vb.size)
+                if torch.is_tensor(outline_term):
+                    loss = loss + outline_term
                 loss.backward()
             else:
                 loss = run.idle_contribution()

@@ -9,11 +9,14 @@ features and style Grams (reference :18-25) do not depend on the optimised param
 cached on the tensors' identity/version, i.e. recomputed exactly when the caller passes new or
 modified content/style images.
 """
+import math
+
 import torch
 from torch.nn import functional as F  # noqa: F401  (star-import surface of the reference module)
 
 from st3d import mesh_losses as _mesh_losses
 from st3d import ops as _ops
+from st3d import render as _render
 from st3d import vgg as _vgg
 from st3d.mesh_losses import mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency  # noqa: F401
 from style_transfer import *  # noqa: F401,F403  (the reference does the same, losses.py:5)
@@ -103,6 +106,68 @@ def _l2_to(x, ref, want_grad=True):
         return _ops.sqdiff_sum(x, ref.reshape(x.shape), scale=1.0 / x.numel()), None
     loss, diff = _ops.sqdiff_sum(x, ref.reshape(x.shape), scale=1.0 / x.numel(), want_diff=True)
     return loss, diff * (2.0 / x.numel())
+
+
+class _SilhouetteLossFn(torch.autograd.Function):
+    """verts -> scale * sum (alpha - target)^2 over this call's views: project, general raster, then ONE fused launch that
+    reduces the loss and writes d loss / d dists (alpha never reaches memory).  backward: raster backward of the stored
+    grad_dists and the projection backward, scaled by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, verts, faces_i32, R, T, target, S, K, blur, clip, sigma, cull, persp, z_clip, scale):
+        v = verts.detach().to(torch.float32).contiguous()
+        ndc = _ops.project_verts(v, R, T)
+        p2f, _zbuf, _bary, dists, slots = _ops.raster_soft_fwd(ndc, faces_i32, S, K, blur, clip, cull, persp, z_clip)
+        loss, gd = _ops.silhouette_loss(p2f, dists, target, sigma, scale, want_grad=verts.requires_grad)
+        ctx.saved = (gd, p2f, slots, v, ndc, faces_i32, R, T, clip, persp, z_clip)
+        ctx.verts_shape = verts.shape
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        gd, p2f, slots, v, ndc, faces_i32, R, T, clip, persp, z_clip = ctx.saved
+        gverts = None
+        if gd is not None and ctx.needs_input_grad[0]:
+            gndc = _ops.raster_soft_bwd((None, None, gd), p2f, ndc, faces_i32, clip, persp, slots, z_clip)
+            gverts = (_ops.project_verts_bwd(v, R, T, gndc) * grad_out).reshape(ctx.verts_shape)
+        return (gverts,) + (None,) * 13
+
+
+SILHOUETTE_FACES_PER_PIXEL = 8
+
+
+def silhouette_blur_radius(sigma):
+    """PyTorch3D's silhouette-fitting tutorial: blur_radius = log(1 / 1e-4 - 1) * sigma (faces whose sigmoid falls below
+    1e-4 are not rasterised)."""
+    return math.log(1.0 / 1e-4 - 1.0) * float(sigma)
+
+
+def compute_silhouette_loss(renderer_or_settings, mesh, cameras, target_masks, sigma=1e-4, batch_denom=None):
+    """mean over views and pixels of (alpha - target)^2, alpha = SoftSilhouetteShader's (sigmoid_alpha_blend with
+    BlendParams(sigma)): the image-space term that holds the OUTLINE when the vertices move.  target_masks (n,1,S,S), e.g.
+    the 0/1 coverage of the content renders.  The silhouette pass takes image size, culling, perspective correction and the
+    clipping depth from the renderer (or RasterizationSettings) given and rasterises with faces_per_pixel = 8 -- the
+    kernels' maximum; PyTorch3D's tutorial uses 50 -- and blur_radius = log(1 / 1e-4 - 1) * sigma, the tutorial's rule.
+    batch_denom: the GLOBAL batch the mean divides by when the views are sharded over ranks (default: this call's views).
+    The mesh needs no textures.  Gradients flow to the vertices only."""
+    rs = getattr(getattr(renderer_or_settings, "rasterizer", None), "raster_settings", renderer_or_settings)
+    if not isinstance(rs, _render.RasterizationSettings):
+        raise TypeError("compute_silhouette_loss takes a MeshRenderer or RasterizationSettings")
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be positive")
+    verts = mesh.verts_packed()
+    if not verts.is_cuda or not target_masks.is_cuda:
+        raise RuntimeError("st3d runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
+    R, T = _render.join_cameras(cameras)
+    n, S = R.shape[0], rs.image_size
+    if target_masks.numel() != n * S * S:
+        raise ValueError(f"target_masks must be ({n},1,{S},{S}), got {tuple(target_masks.shape)}")
+    scale = 1.0 / (float(S) * float(S) * float(batch_denom if batch_denom is not None else n))
+    with _ops.trace("silhouette_loss"):
+        return _SilhouetteLossFn.apply(verts, mesh.faces_i32(), R.to(verts.device), T.to(verts.device),
+                                       target_masks.detach().to(torch.float32), S, SILHOUETTE_FACES_PER_PIXEL,
+                                       silhouette_blur_radius(sigma), True, float(sigma), rs.cull_backfaces,
+                                       rs.perspective_correct, rs.z_clip, scale)
 
 
 class _MaskedMseFn(torch.autograd.Function):

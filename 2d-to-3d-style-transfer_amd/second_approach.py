@@ -55,13 +55,13 @@ def main(argv=None):
             cams = run.cameras[vb.lo:vb.hi]
             style = run.style_image.expand(vb.hi - vb.lo, -1, -1, -1)
 
-            content = content_of_batch.get(vb.index) if reuse_content else None
+            content, outline = content_of_batch.get(vb.index, (None, None)) if reuse_content else (None, None)
             if content is None:
                 with torch.no_grad():
-                    img, cov = render_meshes(run.renderer, run.content_mesh, cams)
-                    content = apply_background(img, cov, background_type=args.content_background, background=style)
+                    img, outline = render_meshes(run.renderer, run.content_mesh, cams)
+                    content = apply_background(img, outline, background_type=args.content_background, background=style)
                 if reuse_content:
-                    content_of_batch[vb.index] = content
+                    content_of_batch[vb.index] = (content, outline)     # the content's 0/1 coverage: --silhouette_weight's target
 
             mesh = run.current_mesh()
             img, cov = render_meshes(run.renderer, mesh, cams)
@@ -74,6 +74,9 @@ def main(argv=None):
             extra = run.regularisers(current, cov, mesh, vb.hi - vb.lo, vb.size)
             if torch.is_tensor(extra):              # every weight is 0 by default: nothing is added, as in the reference
                 loss = loss + extra
+            outline_term = run.silhouette_term(mesh, cams, outline, vb.size)
+            if torch.is_tensor(outline_term):
+                loss = loss + outline_term
 
             if args.save_every and steps_done % args.save_every == 0:
                 run.save_views(current, vb.lo)          # encoded by worker threads, off the step's critical path

@@ -54,6 +54,9 @@ SHARED_FLAGS = [
          "(PyTorch3D's default colours), or a point light at each view's camera", _LIGHTS),
     Flag("light_xyz", float, [0.0, 1.0, 0.0], "location of the point light / direction towards the directional light", None, 3),
     Flag("shininess", float, 64.0, "Phong exponent of the material (lit runs)"),
+    Flag("silhouette_weight", float, 0.0, "weight of the silhouette term that holds the outline of the content mesh when the "
+         "vertices move (optimization_target mesh / both); 0 = off"),
+    Flag("silhouette_sigma", float, 1e-4, "sigma of the soft silhouette (SoftSilhouetteShader's BlendParams.sigma)"),
 ]
 
 # regularisers the reference defines but never switches on (losses.py:48-65, notes.txt:36,39); weight 0 = off
@@ -64,8 +67,27 @@ REGULARISER_FLAGS = [
 ]
 
 
+def check_args(args):
+    """What the flags rule out together, found when they are read -- before any GPU work.  -> None or the complaint."""
+    if getattr(args, "silhouette_weight", 0.0) and getattr(args, "optimization_target", None) == 'texture':
+        return ("--silhouette_weight needs --optimization_target mesh or both: with 'texture' the vertices do not move and "
+                "the term would be a constant")
+    if not getattr(args, "silhouette_sigma", 1e-4) > 0.0:
+        return "--silhouette_sigma must be positive"
+    return None
+
+
+class _Parser(argparse.ArgumentParser):
+    def parse_args(self, args=None, namespace=None):
+        parsed = super().parse_args(args, namespace)
+        complaint = check_args(parsed)
+        if complaint:
+            self.error(complaint)
+        return parsed
+
+
 def make_parser(extra_flags):
-    parser = argparse.ArgumentParser()
+    parser = _Parser()
     for fl in list(extra_flags) + SHARED_FLAGS:
         kw = {"type": fl.type, "default": fl.default, "help": fl.help}
         if fl.choices:
@@ -319,6 +341,17 @@ class Run:
         if getattr(a, "texture_l2_weight", 0.0):
             total = total + (a.texture_l2_weight / self.world) * _l.texture_l2_loss(mesh, self.original_map)
         return total
+
+    def silhouette_term(self, mesh, cams, target, batch_size):
+        """--silhouette_weight x this rank's share of the batch mean of (soft silhouette of `mesh` - target)^2; target = the
+        0/1 coverage of the content renders of the same views.  An image term like tv_weight: divided by the GLOBAL batch,
+        nothing on a rank without views, and with weight 0 (the default) nothing runs at all."""
+        import losses as _l
+        a = self.args
+        if not getattr(a, "silhouette_weight", 0.0) or cams is None or len(cams) == 0:
+            return 0
+        return a.silhouette_weight * _l.compute_silhouette_loss(self.renderer, mesh, cams, target,
+                                                                sigma=a.silhouette_sigma, batch_denom=batch_size)
 
     def export(self, mesh):
         """final_render/view_k.png from 12 turntable cameras + final.obj/.mtl/.png (first_approach.py:219-225)."""

@@ -306,6 +306,50 @@ def raster_soft_bwd(grads, p2f, verts_ndc, faces_i32, clip_bary, perspective_cor
     return g
 
 
+# ------------------------------------------------------------------ silhouette (csrc/silhouette.hip)
+def _check_sigma(sigma):
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be positive")
+    return float(sigma)
+
+
+def silhouette_fwd(p2f, dists, sigma=1e-4):
+    """sigmoid_alpha_blend's alpha of the fragments (p2f, dists) (B,S,S,K) -> (B,1,S,S); no texture, UVs or barycentrics."""
+    sigma = _check_sigma(sigma)
+    B, S, _, K = p2f.shape
+    alpha = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
+    call("st3d_silhouette_fwd", dptr(p2f, I32), dptr(dists, F32), B, S, K, sigma, dptr(alpha), stream_ptr())
+    return alpha
+
+
+def silhouette_bwd(grad_alpha, p2f, dists, sigma=1e-4, out=None):
+    """grad_alpha (B,1,S,S) -> grad_dists (B,S,S,K); `out`: an existing grad_dists the result is ADDED to."""
+    sigma = _check_sigma(sigma)
+    B, S, _, K = p2f.shape
+    acc = 1
+    if out is None:
+        out = torch.empty((B, S, S, K), dtype=F32, device=p2f.device)
+        acc = 0
+    call("st3d_silhouette_bwd", dptr(grad_alpha.contiguous(), F32), dptr(p2f, I32), dptr(dists, F32), B, S, K, sigma, acc,
+         dptr(out, F32), stream_ptr())
+    return out
+
+
+def silhouette_loss(p2f, dists, target, sigma=1e-4, scale=1.0, want_grad=True):
+    """-> (loss (1,) = scale * sum (alpha - target)^2, grad_dists (B,S,S,K) | None) in one pass; target (B,1,S,S)."""
+    sigma = _check_sigma(sigma)
+    B, S, _, K = p2f.shape
+    if target.numel() != B * S * S:
+        raise ValueError(f"target must hold {B}x1x{S}x{S} values, got {tuple(target.shape)}")
+    dev = p2f.device
+    parts = torch.empty((_lib.load().st3d_reduce_partials(),), dtype=F32, device=dev)
+    out = torch.zeros((1,), dtype=F32, device=dev)
+    gd = torch.empty((B, S, S, K), dtype=F32, device=dev) if want_grad else None
+    call("st3d_silhouette_loss", dptr(p2f, I32), dptr(dists, F32), dptr(target.contiguous(), F32), B, S, K, sigma, float(scale),
+         dptr(gd), dptr(parts), dptr(out), stream_ptr())
+    return out, gd
+
+
 # ------------------------------------------------------------------ Phong lighting (csrc/phong.h, csrc/lighting.hip)
 # `lit` below is st3d.render.LitSetup: verts (V,3), normals (V,3) or None, faces_i32, R (B,3,3), T (B,3), block (n,24),
 # kind, weight_bound (see include/st3d.h)

@@ -21,6 +21,10 @@ e = normalize(C - P) with C the camera centre, Sp = ks Ls (relu(e.r) [n.l > 0])^
 colour = (A + D) texel + Sp replaces the texel in the blend.  lights=None means white AmbientLights -- today's unlit
 render on the unchanged kernels (PyTorch3D's own default is PointLights(); the one deliberate divergence).  No
 gradient flows to lights, materials or cameras (a parameter with requires_grad raises).
+
+Silhouettes: SoftSilhouetteShader (sigmoid_alpha_blend: alpha = 1 - prod_k (1 - sigmoid(-dists_k / sigma))) renders alpha
+alone, without a texture, and alpha -- its own and SoftPhongShader's under soft settings -- is differentiable in the
+vertices through the signed edge distance (csrc/silhouette.hip); losses.compute_silhouette_loss is the fused loss on it.
 """
 import math
 
@@ -525,6 +529,56 @@ class SoftPhongShader:
         lighting_of(lights, materials, device)      # validate now (N, requires_grad)
 
 
+class SoftSilhouetteShader:
+    """PyTorch3D SoftSilhouetteShader (blending.sigmoid_alpha_blend): the renderer returns (n,S,S,4) with RGB = 1 and
+    alpha = 1 - prod_k (1 - sigmoid(-dists_k / sigma)) over the K nearest faces in channel 3.  Only blend_params.sigma is
+    read; no texture is needed.  It always renders on the general rasteriser (near-plane clipping included), whatever the
+    raster settings: at K = 1 / blur 0 alpha is sigmoid(-d / sigma) in [0.5, 1) on covered pixels.  alpha is differentiable
+    in the vertices (csrc/silhouette.hip).  K <= 8 faces per pixel (PyTorch3D's silhouette tutorial uses 50)."""
+
+    def __init__(self, blend_params=None, **kw):
+        self.blend_params = blend_params if blend_params is not None else BlendParams()
+
+
+class _SilhouetteFn(torch.autograd.Function):
+    """verts -> alpha (B,1,S,S): project, general raster, silhouette_fwd; backward silhouette_bwd -> raster_soft_bwd with
+    d/d(dists) alone -> project_verts_bwd."""
+
+    @staticmethod
+    def forward(ctx, verts, faces_i32, R, T, S, K, blur, clip, sigma, cull, persp, z_clip):
+        v = verts.detach().to(torch.float32).contiguous()
+        ndc = ops.project_verts(v, R, T)
+        p2f, _zbuf, _bary, dists, slots = ops.raster_soft_fwd(ndc, faces_i32, S, K, blur, clip, cull, persp, z_clip)
+        ctx.frag, ctx.slots = (p2f, dists), slots
+        ctx.args = (clip, sigma, persp, z_clip)
+        ctx.geom = (v, ndc, faces_i32, R, T)
+        ctx.verts_shape = verts.shape
+        return ops.silhouette_fwd(p2f, dists, sigma)
+
+    @staticmethod
+    def backward(ctx, grad_alpha):
+        with ops.trace("render_backward"):
+            gverts = None
+            if ctx.needs_input_grad[0]:
+                clip, sigma, persp, z_clip = ctx.args
+                v, ndc, faces_i32, R, T = ctx.geom
+                gd = ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[1], sigma)
+                gndc = ops.raster_soft_bwd((None, None, gd), ctx.frag[0], ndc, faces_i32, clip, persp, ctx.slots, z_clip)
+                gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
+            return (gverts,) + (None,) * 11
+
+
+def render_silhouette(meshes, R, T, image_size, raster_settings=None, blend_params=None):
+    """SoftSilhouetteShader's alpha (B,1,S,S) of all B views; the mesh needs no textures."""
+    dev = meshes.device
+    rs = raster_settings if raster_settings is not None else RasterizationSettings(image_size=image_size)
+    bp = blend_params if blend_params is not None else BlendParams()
+    with ops.trace("render"):
+        return _SilhouetteFn.apply(meshes.verts_packed(), meshes.faces_i32(), R.to(dev), T.to(dev), int(image_size),
+                                   rs.faces_per_pixel, rs.blur_radius, rs.clip_barycentric_coords, bp.sigma,
+                                   rs.cull_backfaces, rs.perspective_correct, rs.z_clip)
+
+
 class _RenderFn(torch.autograd.Function):
     """(verts, texture_map) -> (rgb (B,3,S,S), mask (B,1,S,S)); backward = texture scatter and,
     when the vertices need a gradient, shade d/d(bary) -> raster backward -> projection backward."""
@@ -587,7 +641,9 @@ class _RenderFn(torch.autograd.Function):
 class _SoftRenderFn(torch.autograd.Function):
     """General path: K faces per pixel, blur_radius, softmax_rgb_blend -> (rgb (B,3,S,S), alpha (B,1,S,S)).
     Gradients flow from rgb to the texture and, through barycentrics, depth and the signed edge distance, to
-    the vertices; alpha is returned without a gradient (the reference only ever thresholds it, utils.py:72)."""
+    the vertices; a gradient for alpha joins them through the signed edge distance (silhouette_bwd accumulates into the
+    grad_dists of the RGB backward before the one raster backward).  Without one the launches are those of the RGB
+    backward alone (the reference only ever thresholds alpha, utils.py:72)."""
 
     @staticmethod
     def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, K, blur, clip, sigma, gamma, bg,
@@ -613,18 +669,27 @@ class _SoftRenderFn(torch.autograd.Function):
         ctx.clip = clip
         ctx.tex_shape, ctx.verts_shape = tex_map.shape, verts.shape
         ctx.geom = (v, ndc, faces_i32, R, T)
-        ctx.mark_non_differentiable(alpha)
+        ctx.set_materialize_grads(False)        # an output nobody differentiates arrives as None, not as zeros
         return rgb, alpha
 
     @staticmethod
-    def backward(ctx, grad_rgb, _grad_alpha):
+    def backward(ctx, grad_rgb, grad_alpha):
         with ops.trace("render_backward"):
-            return _SoftRenderFn._backward(ctx, grad_rgb, _grad_alpha)
+            return _SoftRenderFn._backward(ctx, grad_rgb, grad_alpha)
 
     @staticmethod
-    def _backward(ctx, grad_rgb, _grad_alpha):
+    def _backward(ctx, grad_rgb, grad_alpha):
         need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         gtex = gverts = None
+        if grad_rgb is None:
+            # only alpha carries a gradient (or nothing does): no RGB backward, no texture gradient
+            if need_v and grad_alpha is not None:
+                v, ndc, faces_i32, R, T = ctx.geom
+                gd = ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[3], ctx.blend[0])
+                gndc = ops.raster_soft_bwd((None, None, gd), ctx.frag[0], ndc, faces_i32, ctx.clip, ctx.persp, ctx.slots,
+                                           ctx.z_clip)
+                gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
+            return (gverts, gtex) + (None,) * 16
         if need_v or need_t:
             sigma, gamma, bg = ctx.blend
             gnp = None
@@ -638,6 +703,8 @@ class _SoftRenderFn(torch.autograd.Function):
                 gtex = gt.reshape(ctx.tex_shape)
             if need_v:
                 v, ndc, faces_i32, R, T = ctx.geom
+                if grad_alpha is not None:      # d alpha / d dists joins the RGB backward's grad_dists
+                    ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[3], sigma, out=geo[2])
                 gndc = ops.raster_soft_bwd(geo, ctx.frag[0], ndc, faces_i32, ctx.clip, ctx.persp, ctx.slots, ctx.z_clip)
                 gverts = ops.project_verts_bwd(v, R, T, gndc)
                 if ctx.lit is not None:
@@ -739,6 +806,8 @@ class MeshRenderer:
 
     @property
     def is_hard(self):
+        if isinstance(self.shader, SoftSilhouetteShader):
+            return False
         return uses_hard_path(self.rasterizer.raster_settings, getattr(self.shader, "blend_params", None))
 
     def render(self, meshes_world, cameras=None, lights=None, materials=None):
@@ -746,6 +815,10 @@ class MeshRenderer:
         lights / materials given here replace the shader's for this call (as PyTorch3D's ``renderer(mesh, lights=...)``)."""
         cameras = cameras if cameras is not None else self.rasterizer.cameras
         R, T = join_cameras(cameras)
+        if isinstance(self.shader, SoftSilhouetteShader):       # RGB = 1, alpha = sigmoid_alpha_blend's; nothing is lit
+            alpha = render_silhouette(meshes_world, R, T, self.image_size, self.rasterizer.raster_settings,
+                                      self.shader.blend_params)
+            return torch.ones((alpha.shape[0], 3) + tuple(alpha.shape[2:]), dtype=alpha.dtype, device=alpha.device), alpha
         lights = lights if lights is not None else getattr(self.shader, "lights", None)
         materials = materials if materials is not None else getattr(self.shader, "materials", None)
         return render_views(meshes_world, R, T, self.image_size, self.rasterizer.raster_settings,

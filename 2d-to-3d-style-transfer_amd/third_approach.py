@@ -36,7 +36,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     run = Run(args, lr=args.mse_lr, image_dir="2d_style_transfer")
     mesh = run.opt['optimizable_mesh']
-    content_of_batch = {}
+    content_of_batch, outline_of_batch = {}, {}
 
     run.say("Starting optimization...")
     for rnd in tqdm(range(run.progress, args.n_rounds), desc="Round", disable=not run.main):
@@ -51,6 +51,7 @@ def main(argv=None):
                         img, cov = render_meshes(run.renderer, run.content_mesh, cams)
                         content_of_batch[vb.index] = apply_background(img, cov, background_type=args.content_background,
                                                                       background=style)
+                        outline_of_batch[vb.index] = cov        # the content's 0/1 coverage: --silhouette_weight's target
                     img, cov = render_meshes(run.renderer, run.current_mesh(), cams)
                     start = apply_background(img, cov, background_type=args.current_background, background=style)
                 targets = finalize_tensor(style_transfer(start, content_of_batch[vb.index], style, run.vgg,
@@ -68,6 +69,9 @@ def main(argv=None):
                                                        verts=run.opt['verts'], target_verts=run.original_verts, mesh=mesh,
                                                        weights=run.loss_weights, opt_type=args.optimization_target,
                                                        batch_denom=vb.size)
+                    outline_term = run.silhouette_term(mesh, cams, outline_of_batch[vb.index], vb.size)
+                    if torch.is_tensor(outline_term):
+                        loss = loss + outline_term
                     loss.backward()
                 else:
                     loss = run.idle_contribution()

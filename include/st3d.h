@@ -192,6 +192,29 @@ int st3d_raster_soft_bwd_det(const float *grad_bary, const float *grad_zbuf, con
                              int S, int K, int clip_bary, int perspective_correct, const int32_t *frag_slot, float z_clip,
                              float *grad_verts_ndc, void *workspace, size_t workspace_bytes, st3d_stream_t stream);
 
+/* ---- silhouette (csrc/silhouette.hip): PyTorch3D's SoftSilhouetteShader on the fragments of st3d_raster_soft_fwd.  The
+ * reference never builds one (it only thresholds alpha, utils.py:72); this is the image-space anchor PyTorch3D offers
+ * for the runs that move the mesh.  Over the K <= 8 layers of a pixel, skipping pix_to_face_k < 0:
+ *   prob_k = sigmoid(-dists_k / sigma),  alpha = 1 - prod_k (1 - prob_k),
+ *   d alpha / d dists_k = -prob_k * prod_j (1 - prob_j) / sigma.
+ * alpha equals st3d_shade_soft_fwd's bit for bit.  pix_to_face, dists, grad_dists are (B,S,S,K); alpha, grad_alpha and
+ * target are (B,1,S,S); sigma > 0. */
+/* pytorch3d.renderer.blending.sigmoid_alpha_blend(colors, fragments, blend_params)[..., 3] (SoftSilhouetteShader.forward) */
+int st3d_silhouette_fwd(const int32_t *pix_to_face, const float *dists, int B, int S, int K, float sigma, float *alpha,
+                        st3d_stream_t stream);
+/* autograd's backward of sigmoid_alpha_blend for its alpha channel: grad_dists = (accumulate ? grad_dists : 0) +
+ * grad_alpha * d alpha / d dists; empty layers get 0 (accumulate: are left alone) */
+int st3d_silhouette_bwd(const float *grad_alpha, const int32_t *pix_to_face, const float *dists, int B, int S, int K,
+                        float sigma, int accumulate, float *grad_dists, st3d_stream_t stream);
+/* ((sigmoid_alpha_blend(...)[..., 3] - target) ** 2).sum() * scale and its backward to dists in one pass (neither alpha nor
+ * its gradient goes to memory): loss_out[0] += scale * sum (alpha - target)^2 by the ordered two-stage reduction (partials:
+ * st3d_reduce_partials() floats; bitwise reproducible), grad_dists (may be NULL) = 2 * scale * (alpha - target) *
+ * d alpha / d dists -- bit for bit what st3d_silhouette_bwd gives for grad_alpha = 2 * scale * (st3d_silhouette_fwd - target).
+ * scale carries the weight, 1 / S^2 and the GLOBAL batch denominator. */
+int st3d_silhouette_loss(const int32_t *pix_to_face, const float *dists, const float *target, int B, int S, int K,
+                         float sigma, float scale, float *grad_dists, float *partials, float *loss_out,
+                         st3d_stream_t stream);
+
 /* ---- Phong lighting (PyTorch3D SoftPhongShader with PointLights / DirectionalLights / AmbientLights and Materials;
  * csrc/phong.h holds the per-fragment formulas, csrc/lighting.hip the mesh side).  World space throughout: vertex normals
  * n_v = m_v / max(|m_v|, 1e-6), m_v = sum over v's faces of (v2 - v1) x (v0 - v1); per fragment N = sum b_i n_i,

@@ -659,6 +659,36 @@ def sqdiff_sum(a, b, scale=1.0, want_diff=False):
     return (out, D) if want_diff else out
 
 
+class _SqdiffItem(ctypes.Structure):
+    _fields_ = [("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("D", ctypes.c_void_p), ("n", ctypes.c_size_t),
+                ("nb", ctypes.c_size_t), ("scale", ctypes.c_float), ("slot", ctypes.c_int)]
+
+
+def sqdiff_sum_multi(items, zero_first, combine, style_weight, content_weight, out=None):
+    """Up to 8 squared-difference sums in one launch pair (st3d_sqdiff_sum_multi).  items: (a, b, scale, slot, want_diff)
+    each; b is broadcast when it is shorter (a.numel() % b.numel() == 0).  Item k adds scale * sum((a - b)^2) into
+    out[slot]; zero_first clears the three slots first; combine then sets out[0] = content_weight * out[1] +
+    style_weight * out[2].  -> (out (3,) [total, content, style], [D or None per item])."""
+    if not 0 < len(items) <= 8:
+        raise ValueError("st3d_sqdiff_sum_multi takes 1 to 8 items")
+    dev = items[0][0].device
+    if out is None:
+        out = torch.zeros((3,), dtype=F32, device=dev)
+    arr = (_SqdiffItem * len(items))()
+    keep, diffs = [], []
+    for it, (a, b, scale, slot, want_diff) in zip(arr, items):
+        a, b = a.contiguous(), b.contiguous()
+        D = torch.empty_like(a) if want_diff else None
+        keep += [a, b]
+        diffs.append(D)
+        it.a, it.b, it.D = dptr(a, F32), dptr(b, F32), dptr(D)
+        it.n, it.nb, it.scale, it.slot = a.numel(), b.numel(), float(scale), int(slot)
+    parts = torch.empty((len(items) * _lib.load().st3d_reduce_partials(),), dtype=F32, device=dev)
+    call("st3d_sqdiff_sum_multi", arr, len(items), dptr(parts), dptr(out, F32), 1 if zero_first else 0, 1 if combine else 0,
+         float(style_weight), float(content_weight), stream_ptr())
+    return out, diffs
+
+
 def masked_mse(rendered, target, mask, want_grad=True):
     B, _, S, _ = rendered.shape
     parts = torch.empty((_lib.load().st3d_reduce_partials(),), dtype=F32, device=rendered.device)

@@ -29,6 +29,7 @@ SOURCES = {
     "soft.hip": ["-ffp-contract=off"],
     "lighting.hip": ["-ffp-contract=off"],
     "silhouette.hip": ["-ffp-contract=off"],   # its alpha is compared bit for bit with soft.hip's
+    "silraster.hip": ["-ffp-contract=off"],    # its alpha is compared bit for bit with silhouette.hip's on soft.hip's fragments
     "conv.hip": ["-fno-slp-vectorize"],   # the VALU conv1_1 kernels: SLP-packed v_pk_fma needs register-pair shuffles
     "wino.hip": ["-fno-slp-vectorize"],   # SLP-packed f32 (v_pk_*) needs register shuffles that cost matrix-pipe time
     "wino43.hip": ["-fno-slp-vectorize"],  # (with SLP packing the nine-layer sum is 0.8 % faster, but the re-associated column transform
@@ -52,6 +53,7 @@ def _newer(src, dst, extra=()):
 def build(force=False, jobs=4, verbose=True):
     os.makedirs(OBJDIR, exist_ok=True)
     hdrs = (os.path.join(CSRC, "common.h"), os.path.join(CSRC, "det.h"), os.path.join(CSRC, "phong.h"),
+            os.path.join(CSRC, "softgeom.h"),
             os.path.join(CSRC, "lab", "wino8.inc"),
             os.path.join(HERE, "..", "include", "st3d.h"), os.path.abspath(__file__))
     todo = []

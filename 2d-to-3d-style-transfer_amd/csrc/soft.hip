@@ -15,31 +15,13 @@
 #include "common.h"
 #include "det.h"
 #include "phong.h"
+#include "softgeom.h"
 
 namespace {
 
-constexpr float kEps = 1e-8f;
 constexpr int TILE = 16;
 constexpr int LIST_CAP = 512;
 constexpr float kBlendEps = 1e-10f, kZnear = 1.0f, kZfar = 100.0f;
-
-__device__ __forceinline__ float pix_to_ndc(int i, int S) { return -1.0f + (2.0f * (float)i + 1.0f) / (float)S; }
-__device__ __forceinline__ float edge_fn(float px, float py, float ax, float ay, float bx, float by) {
-    return (px - ax) * (by - ay) - (py - ay) * (bx - ax);
-}
-__device__ __forceinline__ float pld2(float px, float py, float ax, float ay, float bx, float by) {
-    const float bax = bx - ax, bay = by - ay;
-    const float l2 = bax * bax + bay * bay;
-    if (l2 <= kEps) {
-        const float dx = px - bx, dy = py - by;
-        return dx * dx + dy * dy;
-    }
-    float t = (bax * (px - ax) + bay * (py - ay)) / l2;
-    t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-    const float qx = ax + t * bax, qy = ay + t * bay;
-    const float dx = qx - px, dy = qy - py;
-    return dx * dx + dy * dy;
-}
 
 // ------------------------------------------------------------------------------------------ near-plane clipping
 // PyTorch3D clips every mesh against z = z_clip_value (znear / 2 for perspective cameras) before rasterising

@@ -133,7 +133,47 @@ class _SilhouetteLossFn(torch.autograd.Function):
         return (gverts,) + (None,) * 13
 
 
+class _SilhouetteRasterLossFn(torch.autograd.Function):
+    """The same loss on the silhouette rasteriser (csrc/silraster.hip) at faces_per_pixel K = 1..64: project, ONE raster pass
+    from the face records to the loss (no fragments, alpha never reaches memory), backward from the saved per-pixel state
+    (keep, the cut, alpha - target: 16 bytes per pixel whatever K is) to the vertices.  Projected vertices and face records
+    are recomputed in the backward rather than kept."""
+
+    @staticmethod
+    def forward(ctx, verts, faces_i32, R, T, target, K, blur, clip, sigma, cull, persp, z_clip, scale):
+        v = verts.detach().to(torch.float32).contiguous()
+        ndc = _ops.project_verts(v, R, T)
+        loss, state = _ops.silraster_loss(ndc, faces_i32, target, K, blur, sigma, scale, clip, cull, persp, z_clip)
+        ctx.saved = (state if verts.requires_grad else None, v, faces_i32, R, T)
+        ctx.settings = (blur, clip, sigma, cull, persp, z_clip, scale)
+        ctx.verts_shape = verts.shape
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        state, v, faces_i32, R, T = ctx.saved
+        blur, clip, sigma, cull, persp, z_clip, scale = ctx.settings
+        gverts = None
+        if state is not None and ctx.needs_input_grad[0]:
+            ndc = _ops.project_verts(v, R, T)
+            gndc = _ops.silraster_bwd(state, ndc, faces_i32, blur, sigma, None, 2.0 * scale, clip, cull, persp, z_clip)
+            gverts = (_ops.project_verts_bwd(v, R, T, gndc) * grad_out).reshape(ctx.verts_shape)
+        return (gverts,) + (None,) * 12
+
+
 SILHOUETTE_FACES_PER_PIXEL = 8
+SILHOUETTE_RASTER_MAX_FACES_PER_PIXEL = _ops.SILRASTER_MAX_FACES_PER_PIXEL      # 64
+
+
+def check_silhouette_faces_per_pixel(faces_per_pixel):
+    """None (the general rasteriser at K = 8) or an integer 1..64 (the silhouette rasteriser at that K); else ValueError"""
+    if faces_per_pixel is None:
+        return None
+    k = faces_per_pixel
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= SILHOUETTE_RASTER_MAX_FACES_PER_PIXEL:
+        raise ValueError(f"faces_per_pixel must be None or an integer in 1..{SILHOUETTE_RASTER_MAX_FACES_PER_PIXEL}, "
+                         f"got {faces_per_pixel!r}")
+    return k
 
 
 def silhouette_blur_radius(sigma):
@@ -142,14 +182,19 @@ def silhouette_blur_radius(sigma):
     return math.log(1.0 / 1e-4 - 1.0) * float(sigma)
 
 
-def compute_silhouette_loss(renderer_or_settings, mesh, cameras, target_masks, sigma=1e-4, batch_denom=None):
+def compute_silhouette_loss(renderer_or_settings, mesh, cameras, target_masks, sigma=1e-4, batch_denom=None,
+                            faces_per_pixel=None):
     """mean over views and pixels of (alpha - target)^2, alpha = SoftSilhouetteShader's (sigmoid_alpha_blend with
     BlendParams(sigma)): the image-space term that holds the OUTLINE when the vertices move.  target_masks (n,1,S,S), e.g.
     the 0/1 coverage of the content renders.  The silhouette pass takes image size, culling, perspective correction and the
     clipping depth from the renderer (or RasterizationSettings) given and rasterises with faces_per_pixel = 8 -- the
     kernels' maximum; PyTorch3D's tutorial uses 50 -- and blur_radius = log(1 / 1e-4 - 1) * sigma, the tutorial's rule.
     batch_denom: the GLOBAL batch the mean divides by when the views are sharded over ranks (default: this call's views).
-    The mesh needs no textures.  Gradients flow to the vertices only."""
+    The mesh needs no textures.  Gradients flow to the vertices only.
+    faces_per_pixel: None = the path above, bit for bit.  An integer 1..64 (PyTorch3D's tutorial: 50) = the silhouette
+    rasteriser (csrc/silraster.hip) at that K: same semantics -- at K = 8 the same alpha and loss bit for bit --, no
+    fragments in memory, 16 bytes per pixel kept for the backward.  Anything else: ValueError."""
+    faces_per_pixel = check_silhouette_faces_per_pixel(faces_per_pixel)
     rs = getattr(getattr(renderer_or_settings, "rasterizer", None), "raster_settings", renderer_or_settings)
     if not isinstance(rs, _render.RasterizationSettings):
         raise TypeError("compute_silhouette_loss takes a MeshRenderer or RasterizationSettings")
@@ -164,6 +209,11 @@ def compute_silhouette_loss(renderer_or_settings, mesh, cameras, target_masks, s
         raise ValueError(f"target_masks must be ({n},1,{S},{S}), got {tuple(target_masks.shape)}")
     scale = 1.0 / (float(S) * float(S) * float(batch_denom if batch_denom is not None else n))
     with _ops.trace("silhouette_loss"):
+        if faces_per_pixel is not None:
+            return _SilhouetteRasterLossFn.apply(verts, mesh.faces_i32(), R.to(verts.device), T.to(verts.device),
+                                                 target_masks.detach().to(torch.float32).reshape(n, 1, S, S), faces_per_pixel,
+                                                 silhouette_blur_radius(sigma), True, float(sigma), rs.cull_backfaces,
+                                                 rs.perspective_correct, rs.z_clip, scale)
         return _SilhouetteLossFn.apply(verts, mesh.faces_i32(), R.to(verts.device), T.to(verts.device),
                                        target_masks.detach().to(torch.float32), S, SILHOUETTE_FACES_PER_PIXEL,
                                        silhouette_blur_radius(sigma), True, float(sigma), rs.cull_backfaces,

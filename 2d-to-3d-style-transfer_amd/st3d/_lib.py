@@ -63,6 +63,13 @@ SIGNATURES = {
     "st3d_silhouette_bwd": (c_int, [c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_float, c_int, c_f32p, c_stream]),
     "st3d_silhouette_loss": (c_int, [c_i32p, c_f32p, c_f32p, c_int, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_f32p,
                                      c_stream]),
+    "st3d_silraster_fwd": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_float, c_f32p, c_f32p,
+                                   c_stream]),
+    "st3d_silraster_loss": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_float, c_f32p, c_float,
+                                    c_f32p, c_f32p, c_f32p, c_stream]),
+    "st3d_silraster_bwd_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "st3d_silraster_bwd": (c_int, [c_f32p, c_f32p, c_i32p, c_int, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_float,
+                                   c_float, c_f32p, c_f32p, c_float, c_f32p, ctypes.c_void_p, c_size, c_stream]),
     "st3d_vertex_normals_scratch_floats": (c_size, [c_int]),
     "st3d_vertex_normals": (c_int, [c_f32p, c_i32p, c_int, c_int, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_stream]),
     "st3d_vertex_normals_bwd": (c_int, [c_f32p, c_i32p, c_int, c_int, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,

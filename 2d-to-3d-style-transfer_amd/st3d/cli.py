@@ -57,6 +57,8 @@ SHARED_FLAGS = [
     Flag("silhouette_weight", float, 0.0, "weight of the silhouette term that holds the outline of the content mesh when the "
          "vertices move (optimization_target mesh / both); 0 = off"),
     Flag("silhouette_sigma", float, 1e-4, "sigma of the soft silhouette (SoftSilhouetteShader's BlendParams.sigma)"),
+    Flag("silhouette_faces_per_pixel", int, None, "faces per pixel of the silhouette term, 1..64, on the silhouette rasteriser "
+         "(PyTorch3D's silhouette tutorial uses 50); unset = the general rasteriser at 8"),
 ]
 
 # regularisers the reference defines but never switches on (losses.py:48-65, notes.txt:36,39); weight 0 = off
@@ -74,6 +76,9 @@ def check_args(args):
                 "the term would be a constant")
     if not getattr(args, "silhouette_sigma", 1e-4) > 0.0:
         return "--silhouette_sigma must be positive"
+    k = getattr(args, "silhouette_faces_per_pixel", None)
+    if k is not None and not 1 <= k <= 64:
+        return "--silhouette_faces_per_pixel must be in 1..64"
     return None
 
 
@@ -351,7 +356,8 @@ class Run:
         if not getattr(a, "silhouette_weight", 0.0) or cams is None or len(cams) == 0:
             return 0
         return a.silhouette_weight * _l.compute_silhouette_loss(self.renderer, mesh, cams, target,
-                                                                sigma=a.silhouette_sigma, batch_denom=batch_size)
+                                                                sigma=a.silhouette_sigma, batch_denom=batch_size,
+                                                                faces_per_pixel=getattr(a, "silhouette_faces_per_pixel", None))
 
     def export(self, mesh):
         """final_render/view_k.png from 12 turntable cameras + final.obj/.mtl/.png (first_approach.py:219-225)."""

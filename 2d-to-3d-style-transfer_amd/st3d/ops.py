@@ -350,6 +350,86 @@ def silhouette_loss(p2f, dists, target, sigma=1e-4, scale=1.0, want_grad=True):
     return out, gd
 
 
+# ------------------------------------------------------------------ silhouette rasteriser (csrc/silraster.hip)
+SILRASTER_MAX_FACES_PER_PIXEL = 64
+
+
+def _check_silraster_k(K):
+    if isinstance(K, bool) or int(K) != K or not 1 <= int(K) <= SILRASTER_MAX_FACES_PER_PIXEL:
+        raise ValueError(f"faces_per_pixel must be an integer in 1..{SILRASTER_MAX_FACES_PER_PIXEL}, got {K!r}")
+    return int(K)
+
+
+def _silraster_records(verts_ndc, faces_i32, perspective_correct, z_clip):
+    """the two clipped records per face of st3d_face_setup_clip (B*F*96 bytes; recomputed in the backward, never kept)"""
+    B, V, _ = verts_ndc.shape
+    F = faces_i32.shape[0]
+    nb = _lib.load().st3d_clip_records_bytes(B, F)
+    rec = torch.empty((nb // 4,), dtype=F32, device=verts_ndc.device)
+    call("st3d_face_setup_clip", dptr(verts_ndc, F32), dptr(faces_i32, I32), B, V, F, float(z_clip),
+         1 if perspective_correct else 0, dptr(rec), nb, stream_ptr())
+    return rec
+
+
+def _silraster_common(S, blur_radius, clip_bary, cull_backfaces, perspective_correct):
+    return (int(S), float(blur_radius), 1 if clip_bary else 0, 1 if cull_backfaces else 0, 1 if perspective_correct else 0)
+
+
+def silraster_fwd(verts_ndc, faces_i32, S, K, blur_radius, sigma=1e-4, clip_bary=True, cull_backfaces=False,
+                  perspective_correct=True, z_clip=0.5):
+    """SoftSilhouetteShader's alpha at faces_per_pixel K = 1..64 without fragments: -> (alpha (B,1,S,S), state (3,B,S,S));
+    state (12 bytes per pixel whatever K is) is what silraster_bwd needs."""
+    K, sigma = _check_silraster_k(K), _check_sigma(sigma)
+    B, F, dev = verts_ndc.shape[0], faces_i32.shape[0], verts_ndc.device
+    rec = _silraster_records(verts_ndc, faces_i32, perspective_correct, z_clip)
+    S, blur, clip, cull, persp = _silraster_common(S, blur_radius, clip_bary, cull_backfaces, perspective_correct)
+    alpha = torch.empty((B, 1, S, S), dtype=F32, device=dev)
+    state = torch.empty((3, B, S, S), dtype=F32, device=dev)
+    call("st3d_silraster_fwd", dptr(rec), B, F, S, K, blur, clip, cull, persp, sigma, dptr(alpha), dptr(state), stream_ptr())
+    return alpha, state
+
+
+def silraster_loss(verts_ndc, faces_i32, target, K, blur_radius, sigma=1e-4, scale=1.0, clip_bary=True, cull_backfaces=False,
+                   perspective_correct=True, z_clip=0.5):
+    """-> (loss (1,) = scale * sum (alpha - target)^2, state (4,B,S,S)) in one raster pass; target (B,1,S,S).  alpha does
+    not reach memory; plane 3 of state is alpha - target, which silraster_bwd(grad_scale = 2 * scale) turns into d/d verts."""
+    K, sigma = _check_silraster_k(K), _check_sigma(sigma)
+    B, F, dev = verts_ndc.shape[0], faces_i32.shape[0], verts_ndc.device
+    if target.dim() != 4 or target.shape[0] != B or target.shape[2] != target.shape[3] or target.numel() != B * target.shape[2] ** 2:
+        raise ValueError(f"target must be ({B},1,S,S), got {tuple(target.shape)}")
+    rec = _silraster_records(verts_ndc, faces_i32, perspective_correct, z_clip)
+    S, blur, clip, cull, persp = _silraster_common(target.shape[2], blur_radius, clip_bary, cull_backfaces, perspective_correct)
+    state = torch.empty((4, B, S, S), dtype=F32, device=dev)
+    parts = torch.empty((_lib.load().st3d_reduce_partials(),), dtype=F32, device=dev)
+    out = torch.zeros((1,), dtype=F32, device=dev)
+    call("st3d_silraster_loss", dptr(rec), B, F, S, K, blur, clip, cull, persp, sigma, dptr(target.contiguous(), F32),
+         float(scale), dptr(state), dptr(parts), dptr(out), stream_ptr())
+    return out, state
+
+
+def silraster_bwd(state, verts_ndc, faces_i32, blur_radius, sigma=1e-4, grad_alpha=None, grad_scale=1.0, clip_bary=True,
+                  cull_backfaces=False, perspective_correct=True, z_clip=0.5):
+    """d/d verts_ndc (B,V,3) of silraster_fwd (grad_alpha (B,1,S,S)) or of silraster_loss (grad_alpha None, grad_scale =
+    2 * scale) from the saved state; the raster settings must be the forward's."""
+    sigma = _check_sigma(sigma)
+    B, V, _ = verts_ndc.shape
+    F, dev = faces_i32.shape[0], verts_ndc.device
+    if state.dim() != 4 or state.shape[0] != (3 if grad_alpha is not None else 4) or state.shape[1] != B:
+        raise ValueError(f"state {tuple(state.shape)} does not belong to this call")
+    rec = _silraster_records(verts_ndc, faces_i32, perspective_correct, z_clip)
+    S, blur, clip, cull, persp = _silraster_common(state.shape[2], blur_radius, clip_bary, cull_backfaces, perspective_correct)
+    g = torch.empty((B, V, 3), dtype=F32, device=dev)
+    ws, nb = None, 0
+    if _DETERMINISTIC:
+        nb = _lib.load().st3d_silraster_bwd_workspace_bytes(B, V, S)
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
+    ga = grad_alpha.to(F32).contiguous() if grad_alpha is not None else None
+    call("st3d_silraster_bwd", dptr(rec), dptr(verts_ndc, F32), dptr(faces_i32, I32), B, V, F, S, blur, clip, cull, persp,
+         float(z_clip), sigma, dptr(state, F32), dptr(ga, F32) if ga is not None else None, float(grad_scale), dptr(g),
+         dptr(ws) if ws is not None else None, nb, stream_ptr())
+    return g
+
+
 # ------------------------------------------------------------------ Phong lighting (csrc/phong.h, csrc/lighting.hip)
 # `lit` below is st3d.render.LitSetup: verts (V,3), normals (V,3) or None, faces_i32, R (B,3,3), T (B,3), block (n,24),
 # kind, weight_bound (see include/st3d.h)

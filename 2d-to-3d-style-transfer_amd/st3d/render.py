@@ -272,6 +272,14 @@ class RasterizationSettings:
                 and self.perspective_correct and not self.cull_backfaces and self.z_clip_value is None)
 
 
+class SilhouetteRasterizationSettings(RasterizationSettings):
+    """RasterizationSettings for the silhouette rasteriser (csrc/silraster.hip): faces_per_pixel up to 64 (PyTorch3D's
+    silhouette tutorial uses 50), because that rasteriser goes from the faces to alpha without keeping fragments.  Only a
+    MeshRenderer with a SoftSilhouetteShader accepts them; every other shader needs each fragment's depth and colour and
+    stays at RasterizationSettings' 8."""
+    MAX_FACES_PER_PIXEL = 64
+
+
 class BlendParams:
     """PyTorch3D BlendParams (sigma, gamma, background_color) for softmax_rgb_blend."""
 
@@ -534,7 +542,9 @@ class SoftSilhouetteShader:
     alpha = 1 - prod_k (1 - sigmoid(-dists_k / sigma)) over the K nearest faces in channel 3.  Only blend_params.sigma is
     read; no texture is needed.  It always renders on the general rasteriser (near-plane clipping included), whatever the
     raster settings: at K = 1 / blur 0 alpha is sigmoid(-d / sigma) in [0.5, 1) on covered pixels.  alpha is differentiable
-    in the vertices (csrc/silhouette.hip).  K <= 8 faces per pixel (PyTorch3D's silhouette tutorial uses 50)."""
+    in the vertices (csrc/silhouette.hip).  K <= 8 faces per pixel with RasterizationSettings; with
+    SilhouetteRasterizationSettings the renderer uses the silhouette rasteriser (csrc/silraster.hip), K <= 64 (PyTorch3D's
+    silhouette tutorial uses 50)."""
 
     def __init__(self, blend_params=None, **kw):
         self.blend_params = blend_params if blend_params is not None else BlendParams()
@@ -568,12 +578,45 @@ class _SilhouetteFn(torch.autograd.Function):
             return (gverts,) + (None,) * 11
 
 
+class _SilhouetteRasterFn(torch.autograd.Function):
+    """verts -> alpha (B,1,S,S) on the silhouette rasteriser (csrc/silraster.hip, K = 1..64): project, one raster pass to
+    alpha; backward from the saved per-pixel state (keep and the cut: 12 bytes per pixel whatever K is) to the vertices.
+    Projected vertices and face records are recomputed in the backward rather than kept."""
+
+    @staticmethod
+    def forward(ctx, verts, faces_i32, R, T, S, K, blur, clip, sigma, cull, persp, z_clip):
+        v = verts.detach().to(torch.float32).contiguous()
+        ndc = ops.project_verts(v, R, T)
+        alpha, state = ops.silraster_fwd(ndc, faces_i32, S, K, blur, sigma, clip, cull, persp, z_clip)
+        ctx.saved = (state if verts.requires_grad else None, v, faces_i32, R, T)
+        ctx.settings = (blur, clip, sigma, cull, persp, z_clip)
+        ctx.verts_shape = verts.shape
+        return alpha
+
+    @staticmethod
+    def backward(ctx, grad_alpha):
+        with ops.trace("render_backward"):
+            gverts = None
+            state, v, faces_i32, R, T = ctx.saved
+            if state is not None and ctx.needs_input_grad[0]:
+                blur, clip, sigma, cull, persp, z_clip = ctx.settings
+                ndc = ops.project_verts(v, R, T)
+                gndc = ops.silraster_bwd(state, ndc, faces_i32, blur, sigma, grad_alpha, 1.0, clip, cull, persp, z_clip)
+                gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
+            return (gverts,) + (None,) * 11
+
+
 def render_silhouette(meshes, R, T, image_size, raster_settings=None, blend_params=None):
-    """SoftSilhouetteShader's alpha (B,1,S,S) of all B views; the mesh needs no textures."""
+    """SoftSilhouetteShader's alpha (B,1,S,S) of all B views; the mesh needs no textures.  SilhouetteRasterizationSettings
+    select the silhouette rasteriser (no fragments, faces_per_pixel up to 64)."""
     dev = meshes.device
     rs = raster_settings if raster_settings is not None else RasterizationSettings(image_size=image_size)
     bp = blend_params if blend_params is not None else BlendParams()
     with ops.trace("render"):
+        if isinstance(rs, SilhouetteRasterizationSettings):
+            return _SilhouetteRasterFn.apply(meshes.verts_packed(), meshes.faces_i32(), R.to(dev), T.to(dev), int(image_size),
+                                             rs.faces_per_pixel, rs.blur_radius, rs.clip_barycentric_coords, bp.sigma,
+                                             rs.cull_backfaces, rs.perspective_correct, rs.z_clip)
         return _SilhouetteFn.apply(meshes.verts_packed(), meshes.faces_i32(), R.to(dev), T.to(dev), int(image_size),
                                    rs.faces_per_pixel, rs.blur_radius, rs.clip_barycentric_coords, bp.sigma,
                                    rs.cull_backfaces, rs.perspective_correct, rs.z_clip)
@@ -763,6 +806,9 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
     tex = meshes.textures
     dev = meshes.device
     rs, bp = raster_settings, blend_params
+    if isinstance(rs, SilhouetteRasterizationSettings):
+        raise NotImplementedError("SilhouetteRasterizationSettings render on the silhouette rasteriser, which produces alpha "
+                                  "only: they need a SoftSilhouetteShader")
     R, T = R.to(dev), T.to(dev)
     lighting = lighting_of(lights, materials, dev)
     hard_settings = uses_hard_path(rs, bp)
@@ -798,6 +844,10 @@ class MeshRenderer:
     ``render`` and skips the RGBA repack."""
 
     def __init__(self, rasterizer, shader):
+        if isinstance(getattr(rasterizer, "raster_settings", None), SilhouetteRasterizationSettings) \
+                and not isinstance(shader, SoftSilhouetteShader):
+            raise NotImplementedError("SilhouetteRasterizationSettings render on the silhouette rasteriser, which produces "
+                                      "alpha only: they need a SoftSilhouetteShader, got " + type(shader).__name__)
         self.rasterizer, self.shader = rasterizer, shader
 
     @property

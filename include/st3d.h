@@ -215,6 +215,38 @@ int st3d_silhouette_loss(const int32_t *pix_to_face, const float *dists, const f
                          float sigma, float scale, float *grad_dists, float *partials, float *loss_out,
                          st3d_stream_t stream);
 
+/* ---- silhouette rasteriser (csrc/silraster.hip): SoftSilhouetteShader at faces_per_pixel K = 1..64 without fragments in
+ * memory.  face_records are st3d_face_setup_clip's (two per face, st3d_clip_records_bytes).  Per pixel: the candidates are
+ * the records that pass ref_rasterize_k3's tests (oracle/raster_ref.c), of a quadrilateral split by the near plane the half
+ * nearer in the image plane counts, the K nearest by (depth, record index) are the fragments, and
+ *   prob_k = sigmoid(-d_k / sigma),  keep = prod_k (1 - prob_k) in depth order,  alpha = 1 - keep
+ * -- at K <= 8 bit for bit st3d_silhouette_fwd on st3d_raster_soft_fwd's fragments.  `state` is what the backward needs,
+ * planes of B*S*S floats: keep, the depth and the record index (int bits) of the last fragment taken, and for the fused
+ * loss alpha - target: 12 / 16 bytes per pixel whatever K is.  alpha and target are (B,1,S,S); sigma > 0;
+ * blur_radius >= 0.  A candidate with a NaN depth or distance makes its pixel's keep, alpha and gradient NaN. */
+/* rasterize_meshes(faces_per_pixel=K, blur_radius, clip_barycentric_coords, cull_backfaces, perspective_correct, z_clip_value)
+ * + blending.sigmoid_alpha_blend(...)[..., 3]; state: 3 planes */
+int st3d_silraster_fwd(const float *face_records, int B, int F, int S, int K, float blur_radius, int clip_bary,
+                       int cull_backfaces, int perspective_correct, float sigma, float *alpha, float *state,
+                       st3d_stream_t stream);
+/* the same followed by ((alpha - target) ** 2).sum() * scale: loss_out[0] += that, by st3d_silhouette_loss's ordered
+ * reduction (partials: st3d_reduce_partials() floats; bitwise reproducible, and bit for bit st3d_silhouette_loss's value
+ * where alpha is).  alpha does not reach memory; state: 4 planes */
+int st3d_silraster_loss(const float *face_records, int B, int F, int S, int K, float blur_radius, int clip_bary,
+                        int cull_backfaces, int perspective_correct, float sigma, const float *target, float scale, float *state,
+                        float *partials, float *loss_out, st3d_stream_t stream);
+/* autograd's backward of the two above down to the projected vertices (rasterize_meshes' backward for dists +
+ * sigmoid_alpha_blend's): grad_verts_ndc (B,V,3) = sum over the fragments of upstream * (-prob * keep / sigma) * d d / d verts
+ * (nearest edge, first minimum, projection parameter constant; through the cut points on clipped faces, z_clip as given to
+ * st3d_face_setup_clip).  upstream = grad_alpha (B,1,S,S), or with grad_alpha NULL grad_scale * (plane 3 of the fused loss's
+ * state), grad_scale = 2 * scale.  workspace (st3d_silraster_bwd_workspace_bytes, 16-byte aligned): 64-bit fixed-point
+ * accumulation after a bound pass, bitwise reproducible; NULL: float atomics.  No gradient to cameras. */
+size_t st3d_silraster_bwd_workspace_bytes(int B, int V, int S);
+int st3d_silraster_bwd(const float *face_records, const float *verts_ndc, const int32_t *faces, int B, int V, int F, int S,
+                       float blur_radius, int clip_bary, int cull_backfaces, int perspective_correct, float z_clip, float sigma,
+                       const float *state, const float *grad_alpha, float grad_scale, float *grad_verts_ndc, void *workspace,
+                       size_t workspace_bytes, st3d_stream_t stream);
+
 /* ---- Phong lighting (PyTorch3D SoftPhongShader with PointLights / DirectionalLights / AmbientLights and Materials;
  * csrc/phong.h holds the per-fragment formulas, csrc/lighting.hip the mesh side).  World space throughout: vertex normals
  * n_v = m_v / max(|m_v|, 1e-6), m_v = sum over v's faces of (v2 - v1) x (v0 - v1); per fragment N = sum b_i n_i,

@@ -36,6 +36,7 @@ SOURCES = {
                                            #  moves the 200-step G5 trajectory past its 1e-4 early-step bound: 1.2e-4)
     "gram.hip": [],
     "tap0.hip": [],
+    "need.hip": [],
     "loss.hip": ["-ffp-contract=off"],
     "mesh.hip": [],
     "plan.hip": [],

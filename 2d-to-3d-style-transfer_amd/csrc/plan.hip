@@ -178,7 +178,13 @@ struct st3d_plan {
     hipGraphExec_t gexec;
     hipStream_t cap_stream;
     float *g_in, *g_grad, *g_loss;
-    struct { int n, denom, want_grad, warm; float sw, cw; } gkey;
+    uint8_t *g_mask;
+    struct { int n, denom, want_grad, warm, masked; float sw, cw; } gkey;
+    // need lists of st3d_plan_loss_masked (need.hip), rebuilt by every masked call; nullptr where the size has none
+    int need_levels;           // levels that exist at this size, capped by ST3D_NEED_DEPTH
+    uint8_t *need_seg, *need_flags;
+    size_t need_flags_bytes;
+    int *need_list[2], *need_cnt;
 };
 
 namespace {
@@ -220,7 +226,10 @@ struct Scope {   // HIP-event bracket around one kernel family (only when profil
 // F_CONV_*: the Winograd launches; F_CONVX_*: the convs Winograd does not cover (conv1_1, odd shapes, ST3D_CONV=direct)
 // F_CONV43_*: the launches that ran Winograd F(4x4,3x3) (wino43.hip: 2.25 instead of 4 MFMA-multiplies per output)
 enum { F_CONV_FWD = 0, F_CONV_DGRAD = 1, F_POOL = 2, F_GRAM_FWD = 3, F_GRAM_BWD = 4, F_ELEM = 5, F_CONVX_FWD = 6, F_CONVX_DGRAD = 7,
-       F_CONV43_FWD = 8, F_CONV43_DGRAD = 9 };
+       F_CONV43_FWD = 8, F_CONV43_DGRAD = 9,
+       // launches that ran over a need list: a fraction of the full launch's work, so not priced as one
+       F_CONV43_DGRAD_NEED = 10, F_CONVX_DGRAD_NEED = 11, F_GRAM_BWD_NEED = 12 };
+static_assert(F_GRAM_BWD_NEED + 1 == ST3D_PROFILE_FAMILIES, "profile families");
 
 // F(4x4,3x3) for this GEMM?  K = channels reduced over (Cin forward, Cout for the input gradient), M = channels produced
 bool use_wino43(const st3d_vgg *v, int cs, int K, int M, int H, int W) {
@@ -312,14 +321,26 @@ bool dgrad_is_wino(const st3d_plan *p, int cs) {
 // one input-gradient launch of conv slot cs: g (gradient w.r.t. the conv's post-ReLU output, or w.r.t. the output of
 // the pool behind it when pooled) -> dst (gradient w.r.t. the conv's input).  pregated: g is already zero where the gate
 // this launch would apply is closed; out_gate: zero dst where this tensor is <= 0 (the next link's gate, Winograd only)
+// tile_list / n_active: compute the listed output tiles only (F(4x4,3x3) launches; anything else is an error, not a
+// silent full launch: the caller has already skipped the work above on the strength of it)
 int dgrad_step(st3d_plan *p, int cs, const float *g, bool g_is_pooled, int pool_of_g, float *dst, int n, hipStream_t s,
-               bool pregated = false, const float *out_gate = nullptr, const float *add_target = nullptr, float add_coef = 0.f) {
+               bool pregated = false, const float *out_gate = nullptr, const float *add_target = nullptr, float add_coef = 0.f,
+               const int *tile_list = nullptr, const int *n_active = nullptr) {
     const int m = kConvIdx[cs];
     const int H = p->H[m], W = p->W[m];
     const bool wino = dgrad_is_wino(p, cs);
     // F(4x4,3x3) takes an already gated gradient only (what the producer-gated chain hands on)
     const bool w43 = wino && pregated && use_wino43(p->vgg, cs, kConvCout[cs], kConvCin[cs], H, W);
-    Scope sc(p, w43 ? F_CONV43_DGRAD : (wino ? F_CONV_DGRAD : F_CONVX_DGRAD), s, m);
+    if (tile_list && !w43) {
+        st3d::set_error("st3d_plan_loss_masked: the input gradient of module %d is not an F(4x4,3x3) launch", m);
+        return ST3D_E_STATE;
+    }
+    Scope sc(p, tile_list ? F_CONV43_DGRAD_NEED : w43 ? F_CONV43_DGRAD : (wino ? F_CONV_DGRAD : F_CONVX_DGRAD), s, m);
+    if (tile_list) {
+        ST3D_TRY(st3d_wino43_dgrad_chain_tiles(g, g_is_pooled ? p->pidx[pool_of_g] : nullptr, p->vgg->u6d[cs], out_gate, add_target,
+                                               add_coef, dst, n, kConvCin[cs], kConvCout[cs], H, W, tile_list, n_active, s));
+        return ST3D_OK;
+    }
     if (w43) {
         ST3D_TRY(st3d_wino43_dgrad_chain(g, g_is_pooled ? p->pidx[pool_of_g] : nullptr, p->vgg->u6d[cs], out_gate, add_target,
                                          add_coef, dst, n, kConvCin[cs], kConvCout[cs], H, W, s));
@@ -361,6 +382,7 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     p->gbuf[0] = p->gbuf[1] = nullptr; p->content_target = nullptr; p->gram_ws = nullptr; p->partials = nullptr;
     p->have_content = p->have_style = false; p->style_batch = 0; p->last_n = 0; p->prof = false;
     p->use_graph = 0; p->gexec = nullptr; p->cap_stream = nullptr; p->g_in = p->g_grad = p->g_loss = nullptr; memset(&p->gkey, 0, sizeof(p->gkey));
+    p->g_mask = nullptr; p->need_levels = 0; p->need_seg = p->need_flags = nullptr; p->need_flags_bytes = 0; p->need_list[0] = p->need_list[1] = nullptr; p->need_cnt = nullptr;
     memset(p->fam_ms, 0, sizeof(p->fam_ms)); memset(p->fam_n, 0, sizeof(p->fam_n));
     int rc = ST3D_OK;
     int C = 3, H = S, W = S;
@@ -404,6 +426,23 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     if (rc == ST3D_OK) rc = dev_alloc(p, &p->g_in, (size_t)B * 3 * S * S);
     if (rc == ST3D_OK) rc = dev_alloc(p, &p->g_grad, (size_t)B * 3 * S * S);
     if (rc == ST3D_OK) rc = dev_alloc(p, &p->g_loss, (size_t)4);
+    // ST3D_NEED_DEPTH=k: how many of the bottom launches a need mask may thin out (0 none, 1 the relu1_1 pass, 2 + the
+    // conv1_2 input gradient, 3 + the conv2_1 input gradient = the default: each level measured to pay)
+    const char *nd = getenv("ST3D_NEED_DEPTH");
+    p->need_levels = st3d_need_levels(S);
+    if (nd && atoi(nd) >= 0 && atoi(nd) < p->need_levels) p->need_levels = atoi(nd);
+    if (p->need_levels >= 1 && rc == ST3D_OK) {
+        rc = dev_alloc(p, &p->g_mask, (size_t)B * S * S);
+        if (rc == ST3D_OK) rc = dev_alloc(p, &p->need_seg, (size_t)B * S * (S / 64));
+        if (rc == ST3D_OK) rc = dev_alloc(p, &p->need_cnt, (size_t)2);
+        p->need_flags_bytes = st3d_need_workspace_bytes(B, S);
+        if (rc == ST3D_OK && p->need_levels >= 2) rc = dev_alloc(p, &p->need_flags, p->need_flags_bytes);
+        for (int l = 0; l < 2 && l + 2 <= p->need_levels && rc == ST3D_OK; ++l) {
+            int rows = 0, cols = 0;
+            st3d_wino43_tile_geometry(S >> l, S >> l, &rows, &cols);
+            rc = dev_alloc(p, &p->need_list[l], (size_t)B * ((S >> l) / rows) * ((S >> l) / cols));
+        }
+    }
     if (rc != ST3D_OK) { st3d_plan_destroy(p); return rc; }
     *out = p;
     return ST3D_OK;
@@ -427,6 +466,12 @@ extern "C" int st3d_plan_destroy(st3d_plan *p) {
     if (p->g_in) (void)hipFree(p->g_in);
     if (p->g_grad) (void)hipFree(p->g_grad);
     if (p->g_loss) (void)hipFree(p->g_loss);
+    if (p->g_mask) (void)hipFree(p->g_mask);
+    if (p->need_seg) (void)hipFree(p->need_seg);
+    if (p->need_flags) (void)hipFree(p->need_flags);
+    if (p->need_cnt) (void)hipFree(p->need_cnt);
+    for (int l = 0; l < 2; ++l)
+        if (p->need_list[l]) (void)hipFree(p->need_list[l]);
     if (p->gexec) (void)hipGraphExecDestroy(p->gexec);
     if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
     for (auto &e : p->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -511,7 +556,7 @@ extern "C" int st3d_plan_set_style(st3d_plan *p, const float *style, int style_b
 }
 
 static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
-                             float content_weight, float *loss_out, float *grad_current, hipStream_t s);
+                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, hipStream_t s);
 
 extern "C" int st3d_plan_graph(st3d_plan *p, int enable) {
     ST3D_CHECK_ARG(p);
@@ -523,7 +568,15 @@ extern "C" int st3d_plan_graph(st3d_plan *p, int enable) {
 
 extern "C" int st3d_plan_loss(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
                               float content_weight, float *loss_out, float *grad_current, st3d_stream_t stream) {
+    return st3d_plan_loss_masked(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, nullptr, stream);
+}
+
+extern "C" int st3d_plan_loss_masked(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
+                                     float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask,
+                                     st3d_stream_t stream) {
     ST3D_CHECK_ARG(p && current && loss_out);
+    ST3D_CHECK_ARG(((uintptr_t)need_mask & 15) == 0);
+    if (!grad_current || p->need_levels < 1) need_mask = nullptr;      // nothing to thin out: the ordinary call
     ST3D_CHECK_ARG(n > 0 && n <= p->B && batch_denom >= n);
     if (!p->have_content || !p->have_style) {
         st3d::set_error("st3d_plan_loss: content/style targets not set");
@@ -531,28 +584,30 @@ extern "C" int st3d_plan_loss(st3d_plan *p, const float *current, int n, int bat
     }
     ST3D_CHECK_ARG(p->style_batch == 1 || p->style_batch == n);
     hipStream_t s = st3d::as_stream(stream);
-    if (!p->use_graph || p->prof) return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, s);
+    if (!p->use_graph || p->prof)
+        return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, s);
 
     // ---- graph replay
     const size_t img = (size_t)n * 3 * p->S * p->S;
-    const int want_grad = grad_current ? 1 : 0;
+    const int want_grad = grad_current ? 1 : 0, masked = need_mask ? 1 : 0;
     const bool same = p->gexec && p->gkey.n == n && p->gkey.denom == batch_denom && p->gkey.want_grad == want_grad &&
-                      p->gkey.sw == style_weight && p->gkey.cw == content_weight;
+                      p->gkey.masked == masked && p->gkey.sw == style_weight && p->gkey.cw == content_weight;
     if (!same) {
         if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
         const bool warm = p->gkey.warm && p->gkey.n == n && p->gkey.denom == batch_denom && p->gkey.want_grad == want_grad &&
-                          p->gkey.sw == style_weight && p->gkey.cw == content_weight;
-        p->gkey.n = n; p->gkey.denom = batch_denom; p->gkey.want_grad = want_grad; p->gkey.sw = style_weight; p->gkey.cw = content_weight;
+                          p->gkey.masked == masked && p->gkey.sw == style_weight && p->gkey.cw == content_weight;
+        p->gkey.n = n; p->gkey.denom = batch_denom; p->gkey.want_grad = want_grad; p->gkey.masked = masked;
+        p->gkey.sw = style_weight; p->gkey.cw = content_weight;
         if (!warm) {            // first call with these parameters: run it plainly (loads every code object, nothing to capture yet)
             p->gkey.warm = 1;
-            return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, s);
+            return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, s);
         }
         hipGraph_t graph = nullptr;
         // captured on a stream of the plan's own: the caller's stream is usually the (uncapturable) default stream
         if (!p->cap_stream) ST3D_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
         ST3D_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
         const int rc = plan_loss_enqueue(p, p->g_in, n, batch_denom, style_weight, content_weight, p->g_loss,
-                                         want_grad ? p->g_grad : nullptr, p->cap_stream);
+                                         want_grad ? p->g_grad : nullptr, masked ? p->g_mask : nullptr, p->cap_stream);
         const hipError_t e = hipStreamEndCapture(p->cap_stream, &graph);
         if (rc != ST3D_OK || e != hipSuccess || !graph) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -564,6 +619,7 @@ extern "C" int st3d_plan_loss(st3d_plan *p, const float *current, int n, int bat
         if (ei != hipSuccess) { p->gexec = nullptr; st3d::set_error("st3d_plan_loss: hipGraphInstantiate: %s", hipGetErrorString(ei)); return ST3D_E_HIP; }
     }
     ST3D_HIP(hipMemcpyAsync(p->g_in, current, img * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (masked) ST3D_HIP(hipMemcpyAsync(p->g_mask, need_mask, (size_t)n * p->S * p->S, hipMemcpyDeviceToDevice, s));
     ST3D_HIP(hipGraphLaunch(p->gexec, s));
     ST3D_HIP(hipMemcpyAsync(loss_out, p->g_loss, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (grad_current) ST3D_HIP(hipMemcpyAsync(grad_current, p->g_grad, img * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -572,7 +628,7 @@ extern "C" int st3d_plan_loss(st3d_plan *p, const float *current, int n, int bat
 }
 
 static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
-                             float content_weight, float *loss_out, float *grad_current, hipStream_t s) {
+                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, hipStream_t s) {
     {
         st3d::TraceRange tr("vgg_forward");
         ST3D_TRY(forward(p, current, n, 28, false, s));
@@ -610,6 +666,25 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
     st3d_trace_pop();                                  // (gram_and_losses ends here; its guard pops "vgg_backward" below)
     st3d_trace_push("vgg_backward");
 
+    // ---- what the consumer of the image gradient needs (need.hip): with a mask, the bottom launches walk these lists.
+    // A launch may only be thinned out when every launch below it is -- each level is decided here, before the first launch,
+    // from the same predicates the loop below dispatches on
+    int need = 0;
+    if (need_mask) {
+        const int S = p->S;
+        const st3d_vgg *v = p->vgg;
+        need = p->need_levels;
+        if (!(v->fuse_tap0 && st3d_conv1_bwd_supported(S, S) && p->gbuf_floats >= (size_t)n * 27 * S * S)) need = 0;
+        if (need > 1 && !(v->pregate && dgrad_is_wino(p, 1) && dgrad_is_wino(p, 2) && use_wino43(v, 1, kConvCout[1], kConvCin[1], S, S)))
+            need = 1;
+        if (need > 2 && !use_wino43(v, 2, kConvCout[2], kConvCin[2], S / 2, S / 2)) need = 2;
+        if (need > 0) {
+            Scope sc(p, F_ELEM, s);
+            ST3D_TRY(st3d_need_build(need_mask, n, S, need, p->need_seg, p->need_flags, p->need_flags_bytes, p->need_list[0],
+                                     p->need_list[1], p->need_cnt, s));
+        }
+    }
+
     // ---- backward: gradient w.r.t. the post-ReLU output of each conv, top down
     float *g = p->gbuf[0], *gn = p->gbuf[1];
     bool have_g = false, g_is_pooled = false, g_gated = false, content_done = false;
@@ -625,7 +700,12 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
             p->gbuf_floats >= (size_t)n * 27 * H * W) {
             // relu1_1: style gradient + ReLU gate + conv1_1 input gradient in one pass over g and F (tap0.hip); the 27 tap
             // planes go through the idle gradient buffer
-            Scope sc(p, F_CONVX_DGRAD, s, m);
+            Scope sc(p, need >= 1 ? F_CONVX_DGRAD_NEED : F_CONVX_DGRAD, s, m);
+            if (need >= 1)
+                ST3D_TRY(st3d_conv1_bwd_masked(have_g ? g : nullptr, p->act[m], st >= 0 ? p->D[st] : nullptr,
+                                               st >= 0 ? style_coef[st] : 0.f, p->vgg->wd[0], gn, p->gbuf_floats * sizeof(float),
+                                               grad_current, n, H, W, p->need_seg, need_mask, s));
+            else
             ST3D_TRY(st3d_conv1_bwd(have_g ? g : nullptr, p->act[m], st >= 0 ? p->D[st] : nullptr, st >= 0 ? style_coef[st] : 0.f,
                                     p->vgg->wd[0], gn, p->gbuf_floats * sizeof(float), grad_current, n, H, W, s));
             break;
@@ -666,7 +746,9 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
             addt = p->content_target;
             content_done = true;
         }
-        ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, g_gated, og, addt, cc));
+        const int lvl = (cs == 1 || cs == 2) && need >= cs + 1 ? cs - 1 : -1;       // conv1_2 / conv2_1 over their need lists
+        ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, g_gated, og, addt, cc, lvl >= 0 ? p->need_list[lvl] : nullptr,
+                            lvl >= 0 ? p->need_cnt + lvl : nullptr));
         g_gated = og != nullptr;
         // dst is the gradient w.r.t. this conv's input: either the previous conv's post-ReLU
         // output or a pool output (then the next dgrad fuses the unpool)

@@ -32,11 +32,13 @@ __host__ __device__ constexpr int acc_row(int v, int h) { return 8 * (v >> 2) + 
 // One wave = 32 * J consecutive pixels per iteration as J MFMA n-tiles (pixel p0 + J * lane31 + j), so every global access is
 // a 4 * J-byte item per lane and a 128 * J-byte run per row per wave; the four waves of a workgroup take adjacent runs.
 // J = 2: 8-byte accesses at 2 waves per SIMD (256 VGPRs); J = 1: 4-byte accesses at 3 waves per SIMD.
-template <bool HAS_D, bool HAS_G, int J>
+// MASKED: seg (N, HW / 64) marks the 64-pixel segments whose tap planes somebody gathers (need.hip); a wave skips the
+// others whole -- no loads, no products, no stores.  The loop holds no workgroup barrier, so waves skip on their own.
+template <bool HAS_D, bool HAS_G, int J, bool MASKED = false>
 __global__ __launch_bounds__(256, J == 2 ? 3 : 4) void conv1_bwd_gemm_kernel(const float *__restrict__ g, const float *__restrict__ F,
                                                                          const float *__restrict__ D, float coef,
                                                                          const float *__restrict__ wd, float *__restrict__ Y,
-                                                                         int HW, int iters) {
+                                                                         int HW, int iters, const uint8_t *__restrict__ seg = nullptr) {
     __shared__ float A1s[HAS_D ? 2 * 32 * 64 : 64];   // [cout half][k step][lane]: coef * D[cout][k]
     __shared__ float A2s[32 * 64];                    // [k step][lane]: W'[(tap, i) = lane31][c]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -73,6 +75,11 @@ __global__ __launch_bounds__(256, J == 2 ? 3 : 4) void conv1_bwd_gemm_kernel(con
         }
     };
     for (int it = 0; it < iters; ++it) {
+        if (MASKED) {
+            const int p0 = ((blockIdx.x * iters + it) * 4 + wave) * (32 * J);            // the wave's first pixel: one segment holds all of them
+            if (p0 >= HW) continue;
+            if (!__builtin_amdgcn_readfirstlane((int)seg[(size_t)n * (HW >> 6) + (p0 >> 6)])) continue;
+        }
         const int px = ((blockIdx.x * iters + it) * 4 + wave) * (32 * J) + J * l31;     // J = 2: HW is even, px and px + 1 fall together
         const unsigned voff = px < HW ? (unsigned)px * 4u + (unsigned)lhi * 4u * rowb : kOob;
         float Fv[32][J];
@@ -151,6 +158,33 @@ __global__ __launch_bounds__(256) void conv1_bwd_gather_kernel(const float *__re
     o[0] = a0; o[HW] = a1; o[2 * HW] = a2;
 }
 
+// the same sums at the pixels of mask (N,H,W), exactly 0 elsewhere -- where the tap planes are not read (they need not exist)
+__global__ __launch_bounds__(256) void conv1_bwd_gather_masked_kernel(const float *__restrict__ Y, const uint8_t *__restrict__ mask,
+                                                                      float *__restrict__ gx, int H, int W) {
+    const size_t HW = (size_t)H * W;
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (p >= HW) return;
+    const int y = (int)(p / W), x = (int)(p - (size_t)y * W);
+    const float *Yn = Y + (size_t)blockIdx.y * kTaps * HW;
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    if (mask[(size_t)blockIdx.y * HW + p]) {
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kx = 0; kx < 3; ++kx) {
+                const int yy = y + ky - 1, xx = x + kx - 1;
+                if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+                const float *q = Yn + (size_t)((ky * 3 + kx) * 3) * HW + (size_t)yy * W + xx;
+                a0 += q[0]; a1 += q[HW]; a2 += q[2 * HW];
+            }
+    }
+    float *o = gx + (size_t)blockIdx.y * 3 * HW + p;
+    o[0] = a0; o[HW] = a1; o[2 * HW] = a2;
+}
+
+int conv1_bwd_run(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed, void *workspace,
+                  size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg, const uint8_t *mask, hipStream_t s);
+
 }  // namespace
 
 extern "C" int st3d_conv1_bwd_supported(int H, int W) {
@@ -164,29 +198,52 @@ extern "C" size_t st3d_conv1_bwd_workspace_bytes(int N, int H, int W) {
 
 extern "C" int st3d_conv1_bwd(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed,
                               void *workspace, size_t workspace_bytes, float *gx, int N, int H, int W, st3d_stream_t stream) {
+    return conv1_bwd_run(gy, act, D, coef, w_dgrad_packed, workspace, workspace_bytes, gx, N, H, W, nullptr, nullptr,
+                         st3d::as_stream(stream));
+}
+
+// st3d_conv1_bwd for a consumer that reads gx at the pixels of mask (N,H,W) only: gx is bitwise st3d_conv1_bwd's there and
+// exactly 0 elsewhere; gy is read only in the 64-pixel row segments marked in seg (N,H,W/64) = the segments that touch
+// dilate(mask, 1) (st3d_need_build).  W % 64 == 0.
+extern "C" int st3d_conv1_bwd_masked(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed,
+                                     void *workspace, size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg,
+                                     const uint8_t *mask, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(seg && mask && W > 0 && (W % 64) == 0);
+    return conv1_bwd_run(gy, act, D, coef, w_dgrad_packed, workspace, workspace_bytes, gx, N, H, W, seg, mask, st3d::as_stream(stream));
+}
+
+namespace {
+int conv1_bwd_run(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed, void *workspace,
+                  size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg, const uint8_t *mask, hipStream_t s) {
     ST3D_CHECK_ARG(act && w_dgrad_packed && workspace && gx);
     ST3D_CHECK_ARG(gy || D);
     ST3D_CHECK_ARG(N > 0 && st3d_conv1_bwd_supported(H, W));
     ST3D_CHECK_ARG(workspace_bytes >= st3d_conv1_bwd_workspace_bytes(N, H, W));
     ST3D_CHECK_ARG((((uintptr_t)gy | (uintptr_t)act | (uintptr_t)workspace) & 7) == 0);
-    hipStream_t s = st3d::as_stream(stream);
     const int HW = H * W;
     float *Y = reinterpret_cast<float *>(workspace);
     // ST3D_TAP0_J=1 / 2: pixels per lane (A/B runs)
     static const int J = [] { const char *e = getenv("ST3D_TAP0_J"); return e && e[0] == '1' ? 1 : 2; }();
     const int iters = HW >= 4096 ? 4 : 1;               // 128 * J * iters pixels per workgroup
     const dim3 grid(st3d::cdiv(HW, 128 * J * iters), N);
-#define ST3D_TAP0_LAUNCH(JJ)                                                                                                  \
+#define ST3D_TAP0_LAUNCH(JJ, MM)                                                                                              \
     do {                                                                                                                      \
-        if (D && gy) conv1_bwd_gemm_kernel<true, true, JJ><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters);   \
-        else if (D) conv1_bwd_gemm_kernel<true, false, JJ><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters);   \
-        else conv1_bwd_gemm_kernel<false, true, JJ><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters);          \
+        if (D && gy) conv1_bwd_gemm_kernel<true, true, JJ, MM><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters, seg);   \
+        else if (D) conv1_bwd_gemm_kernel<true, false, JJ, MM><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters, seg);   \
+        else conv1_bwd_gemm_kernel<false, true, JJ, MM><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters, seg);          \
     } while (0)
-    if (J == 1) ST3D_TAP0_LAUNCH(1);
-    else ST3D_TAP0_LAUNCH(2);
+    if (seg) {
+        if (J == 1) ST3D_TAP0_LAUNCH(1, true);
+        else ST3D_TAP0_LAUNCH(2, true);
+    } else {
+        if (J == 1) ST3D_TAP0_LAUNCH(1, false);
+        else ST3D_TAP0_LAUNCH(2, false);
+    }
 #undef ST3D_TAP0_LAUNCH
     ST3D_LAUNCH_CHECK();
-    conv1_bwd_gather_kernel<<<dim3(st3d::cdiv(HW, 256), N), 256, 0, s>>>(Y, gx, H, W);
+    if (mask) conv1_bwd_gather_masked_kernel<<<dim3(st3d::cdiv(HW, 256), N), 256, 0, s>>>(Y, mask, gx, H, W);
+    else conv1_bwd_gather_kernel<<<dim3(st3d::cdiv(HW, 256), N), 256, 0, s>>>(Y, gx, H, W);
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }
+}  // namespace

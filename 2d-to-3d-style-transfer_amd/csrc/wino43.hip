@@ -85,6 +85,8 @@ struct Wino43Args {
     float addc;
     int xpc;                        // XCDs per cout tile (slots are renumbered XCD-major, see wino43_body); 1 = as dealt
     unsigned magic_x, magic_y;      // floor(2^32 / tiles_x) + 1, likewise tiles_y: pix / tiles_x = umulhi(pix, magic_x) for pix * tiles_x < 2^32 (tiles_x >= 2)
+    const int *tile_list;           // LIST: the pixel tiles to compute, ascending (need.hip); the others are not written
+    const int *n_active;            // LIST: how many (device memory: the host never knows)
 };
 
 // T_a = sum_r B^T[a][r] d[r] for a = 0..5 (and, applied to t0..t5, the column half V_b = sum_c B^T[b][c] t[c])
@@ -112,7 +114,9 @@ __device__ __forceinline__ void bt6(T d0, T d1, T d2, T d3, T d4, T d5, T &t0, T
 // (BH = the wave's half of the domain's columns, a template parameter: the kernel branches ONCE per wave into the body of its
 //  half, so the column transform of every k-step and the b-direction of the epilogue are straight-line code in the same basic
 //  block as the k-step's MFMAs instead of two scalar branches behind them)
-template <int MODE, int EPI, int GATE, int BH, int TC>
+// LIST: the workgroup walks positions slot, slot + nslots, ... of a.tile_list instead of the pixel tiles themselves; the
+// walk, the ring and the epilogue are the same, a tile sees the inputs and the order of operations it sees unlisted.
+template <int MODE, int EPI, int GATE, int BH, int TC, bool LIST>
 __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     using G = Geo43<TC>;
     const int tid = threadIdx.x;
@@ -133,7 +137,7 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     const int ct = blockIdx.x % a.n_ct, nslots = gridDim.x / a.n_ct;
     int slot = blockIdx.x / a.n_ct;
     if (a.xpc > 1) slot = (slot % a.xpc) * (nslots / a.xpc) + slot / a.xpc;
-    const int npix = a.tiles_x * a.tiles_y * a.N;
+    const int npix = LIST ? __builtin_amdgcn_readfirstlane(a.n_active[0]) : a.tiles_x * a.tiles_y * a.N;
     const int co0 = ct * 64;
     int n = 0, x0 = 0, y0 = 0;                 // the tile whose patch columns are being STAGED (runs two stages ahead)
     auto decode = [&](int pix, int &tn, int &ty0, int &tx0) __attribute__((always_inline)) {
@@ -167,9 +171,14 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     const unsigned img_bytes = (unsigned)((size_t)a.Cin * in_plane * 4);
     __amdgpu_buffer_rsrc_t rx, ridx;
     // addresses of the staged tile `pix` (>= npix: past this workgroup's last tile -- everything out of range, loads return 0)
+    // LIST: stile = the tile at list position spix (the one being staged), ctile = the one being computed, nxt = the entry
+    // of position spix + nslots, requested a tile ahead so that nobody waits for it between two tiles' MFMAs
+    int stile = 0, ctile = 0;
+    unsigned nxt = 0;
+    auto list_at = [&](int pos) __attribute__((always_inline)) { return pos < npix ? (unsigned)a.tile_list[pos] : 0u; };
     auto stage_tile = [&](int pix) __attribute__((always_inline)) {
         const bool live = pix < npix;
-        decode(live ? pix : 0, n, y0, x0);
+        decode(live ? (LIST ? stile : pix) : 0, n, y0, x0);
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
             const int gy = y0 - 1 + 4 * s_tr + r, gx0 = x0 - 4 + s_col;
@@ -183,6 +192,10 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
             ridx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(a.idx + (size_t)n * a.Cin * in_plane), 0, img_bytes / 4, 0x00020000);
     };
     int spix = slot;                           // pixel tile being staged
+    if (LIST) {
+        stile = ctile = __builtin_amdgcn_readfirstlane((int)list_at(spix));
+        nxt = list_at(spix + nslots);
+    }
     stage_tile(spix);
 #if defined(ST3D_W43_DIAG) && ST3D_W43_DIAG == 10       // 10: staging loads out of range (issued, no memory traffic)
     if (a.N >= 0) spix = npix;
@@ -514,13 +527,17 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     for (int cpix = slot; cpix < npix; cpix += nslots) {
         for (int c = 0; c < nstages; ++c) {
             int sc = c + 2;
-            if (sc == nstages) { spix += nslots; stage_tile(spix); }      // the staging runs on into the next tile's patch
+            if (sc == nstages) {                                          // the staging runs on into the next tile's patch
+                spix += nslots;
+                if (LIST) stile = __builtin_amdgcn_readfirstlane((int)nxt);
+                stage_tile(spix);
+            }
             if (sc >= nstages) sc -= nstages;
             stage(c, sc, pb);
             pb = pb == 2 ? 0 : pb + 1;
         }
         int cn, cy0, cx0;
-        decode(cpix, cn, cy0, cx0);
+        decode(LIST ? ctile : cpix, cn, cy0, cx0);
 #if defined(ST3D_W43_DIAG) && ST3D_W43_DIAG == 2       // diagnostic build: no epilogue at all -- no results, timing only
         if (a.N < 0) { float sacc = 0.f; for (int b = 0; b < 3; ++b) for (int cb = 0; cb < 4; ++cb) for (int r = 0; r < 4; ++r) sacc += acc[b][cb][r]; ex[tid] = sacc; }
         uload(0, u4[0]); uload(1, u4[1]); uload(2, u4[2]);
@@ -529,6 +546,10 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
 #endif
         // (the staged tile's addresses are recomputed rather than carried through the epilogue's register peak)
         asm volatile("" : "+s"(spix));
+        if (LIST) {
+            ctile = stile;
+            nxt = list_at(spix + nslots);
+        }
         stage_tile(spix);
 #pragma unroll
         for (int b = 0; b < 3; ++b)
@@ -537,11 +558,11 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     }
 }
 
-template <int MODE, int EPI, int GATE, int TC>
+template <int MODE, int EPI, int GATE, int TC, bool LIST = false>
 __global__ __launch_bounds__(NT6, 3) void wino43_kernel(const Wino43Args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) wino43_body<MODE, EPI, GATE, 1, TC>(a, smem);
-    else wino43_body<MODE, EPI, GATE, 0, TC>(a, smem);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) wino43_body<MODE, EPI, GATE, 1, TC, LIST>(a, smem);
+    else wino43_body<MODE, EPI, GATE, 0, TC, LIST>(a, smem);
 }
 
 // w (Cout,Cin,3,3) -> U = G g G^T (6x6, fp64 -> fp32), forward and transposed (180-degree rotated filter, channel roles
@@ -625,6 +646,15 @@ int launch_wino43_tc(Wino43Args a, hipStream_t s) {
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     };
+    if (a.tile_list) {      // the listed walk: input-gradient launches only (no bias, no ReLU, no fused pool)
+        if (a.yp || a.bias || a.relu || !a.n_active) { st3d::set_error("wino43: a tile list belongs to the input-gradient chain"); return ST3D_E_INVALID; }
+        if (a.gate && a.addt) {
+            if (MODE != 0) { st3d::set_error("wino43: the content-target term rides on ungated input (MODE 0) only"); return ST3D_E_INVALID; }
+            return go(wino43_kernel<0, 0, 2, TC, true>);
+        }
+        if (a.gate) return go(wino43_kernel<MODE, 0, 1, TC, true>);
+        return go(wino43_kernel<MODE, 0, 0, TC, true>);
+    }
     if (a.yp) {
         if (MODE != 0 || a.gate) { st3d::set_error("wino43: the fused pool belongs to the plain forward"); return ST3D_E_INVALID; }
         return go(wino43_kernel<0, 1, 0, TC>);
@@ -645,6 +675,13 @@ int launch_wino43(Wino43Args a, hipStream_t s) {
 }  // namespace
 
 extern "C" int st3d_wino43_supported(int Cin, int Cout, int H, int W) { return shape_ok43(Cin, Cout, H, W) ? 1 : 0; }
+
+extern "C" int st3d_wino43_tile_geometry(int H, int W, int *rows, int *cols) {
+    const int tc = tc43(H, W);
+    if (rows) *rows = tc ? 4 * (16 / tc) : 0;
+    if (cols) *cols = 4 * tc;
+    return tc != 0;
+}
 
 extern "C" size_t st3d_wino43_packed_floats(int Cout, int Cin) { return (size_t)36 * Cout * Cin; }
 
@@ -675,6 +712,23 @@ extern "C" int st3d_wino43_dgrad_chain(const float *gy, const uint8_t *pool_idx,
     ST3D_CHECK_ARG(((uintptr_t)u_dgrad & 15) == 0 && ((uintptr_t)out_gate & 15) == 0 && ((uintptr_t)add_target & 15) == 0);
     ST3D_CHECK_ARG(!add_target || out_gate);
     Wino43Args a{gy, pool_idx, u_dgrad, nullptr, gx, nullptr, nullptr, N, Cout, Cin, H, W, 0, 0, 0, 0, out_gate, add_target, add_coef};
+    hipStream_t s = st3d::as_stream(stream);
+    return pool_idx ? launch_wino43<3>(a, s) : launch_wino43<0>(a, s);
+}
+
+// the same launch over the first *n_active entries of tile_list only (device memory; ascending tile indices (n * tiles_y +
+// ty) * tiles_x + tx of the launch's st3d_wino43_tile_geometry): listed tiles get bitwise what the call above gives them,
+// the rest of gx is left as it was
+extern "C" int st3d_wino43_dgrad_chain_tiles(const float *gy, const uint8_t *pool_idx, const float *u_dgrad, const float *out_gate,
+                                             const float *add_target, float add_coef, float *gx, int N, int Cin, int Cout, int H,
+                                             int W, const int *tile_list, const int *n_active, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(gy && u_dgrad && gx && tile_list && n_active);
+    ST3D_CHECK_ARG(N > 0 && shape_ok43(Cout, Cin, H, W));
+    ST3D_CHECK_ARG(((uintptr_t)u_dgrad & 15) == 0 && ((uintptr_t)out_gate & 15) == 0 && ((uintptr_t)add_target & 15) == 0);
+    ST3D_CHECK_ARG(!add_target || out_gate);
+    Wino43Args a{gy, pool_idx, u_dgrad, nullptr, gx, nullptr, nullptr, N, Cout, Cin, H, W, 0, 0, 0, 0, out_gate, add_target, add_coef};
+    a.tile_list = tile_list;
+    a.n_active = n_active;
     hipStream_t s = st3d::as_stream(stream);
     return pool_idx ? launch_wino43<3>(a, s) : launch_wino43<0>(a, s);
 }

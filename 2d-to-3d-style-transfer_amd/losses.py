@@ -10,6 +10,7 @@ cached on the tensors' identity/version, i.e. recomputed exactly when the caller
 modified content/style images.
 """
 import math
+import os
 
 import torch
 from torch.nn import functional as F  # noqa: F401  (star-import surface of the reference module)
@@ -27,9 +28,9 @@ device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
 class _PerceptualFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, current, plan, style_weight, content_weight, batch_denom):
+    def forward(ctx, current, plan, style_weight, content_weight, batch_denom, need_mask=None):
         loss, grad = plan.loss(current, style_weight, content_weight, batch_denom=batch_denom,
-                               want_grad=current.requires_grad)
+                               want_grad=current.requires_grad, need_mask=need_mask)
         ctx.grad = grad
         ctx.parts = loss.clone()
         return loss[0].clone()
@@ -37,7 +38,7 @@ class _PerceptualFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         g = ctx.grad * grad_out if ctx.grad is not None else None
-        return g, None, None, None, None
+        return g, None, None, None, None, None
 
 
 #method for the second approach
@@ -56,8 +57,14 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
     plan.set_content(content_imgs)          # conv4_2 of content      (reference :18)
     plan.set_style(style_imgs, B)           # Grams of style features (reference :19-25)
 
+    # A render tags its colour tensor with its coverage (st3d.render.tag_need): its backward reads the image gradient at
+    # covered pixels only, so the plan computes the gradient there (bit for bit) and writes 0 elsewhere, skipping the part
+    # of the VGG backward only the background would need.  Anything else -- pixels optimised directly, a tensor derived
+    # from the render, somebody watching the tensor's own gradient, ST3D_NEED_MASK=0 -- takes the full path.
+    need = None if os.environ.get("ST3D_NEED_MASK", "1") == "0" else _render.need_of(current_imgs)
+
     # batch_denom: the batch the means divide by -- the GLOBAL batch when views are sharded over ranks
-    return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom)
+    return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need)
 
 
 class _FusedLossFn(torch.autograd.Function):

@@ -100,6 +100,8 @@ SIGNATURES = {
     "st3d_conv1_bwd_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "st3d_conv1_bwd": (c_int, [c_f32p, c_f32p, c_f32p, c_float, c_f32p, ctypes.c_void_p, c_size, c_f32p, c_int, c_int, c_int,
                                c_stream]),
+    "st3d_conv1_bwd_masked": (c_int, [c_f32p, c_f32p, c_f32p, c_float, c_f32p, ctypes.c_void_p, c_size, c_f32p, c_int, c_int, c_int,
+                                      c_u8p, c_u8p, c_stream]),
     "st3d_wino_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "st3d_wino_packed_floats": (c_size, [c_int, c_int]),
     "st3d_wino_pack": (c_int, [c_f32p, c_int, c_int, c_f32p, c_f32p, c_stream]),
@@ -117,6 +119,12 @@ SIGNATURES = {
                                 c_stream]),
     "st3d_wino43_dgrad_chain": (c_int, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_float, c_f32p, c_int, c_int, c_int, c_int,
                                         c_int, c_stream]),
+    "st3d_wino43_tile_geometry": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "st3d_wino43_dgrad_chain_tiles": (c_int, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_float, c_f32p, c_int, c_int, c_int, c_int,
+                                              c_int, c_i32p, c_i32p, c_stream]),
+    "st3d_need_levels": (c_int, [c_int]),
+    "st3d_need_workspace_bytes": (c_size, [c_int, c_int]),
+    "st3d_need_build": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, ctypes.c_void_p, c_size, c_i32p, c_i32p, c_i32p, c_stream]),
     "st3d_maxpool2x2_fwd": (c_int, [c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_stream]),
     "st3d_gram_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "st3d_gram_fwd": (c_int, [c_f32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_f32p, c_stream]),
@@ -147,6 +155,7 @@ SIGNATURES = {
     "st3d_plan_set_content_features": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_stream]),
     "st3d_plan_set_style": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_stream]),
     "st3d_plan_loss": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_stream]),
+    "st3d_plan_loss_masked": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_u8p, c_stream]),
     "st3d_plan_graph": (c_int, [ctypes.c_void_p, c_int]),
     "st3d_plan_backward": (c_int, [ctypes.c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_void_p), c_f32p, c_stream]),
     "st3d_comm_unique_id": (c_int, [ctypes.c_char_p]),

@@ -590,6 +590,46 @@ def conv1_bwd(gy, act, D, coef, wd):
     return gx
 
 
+def conv1_bwd_masked(gy, act, D, coef, wd, seg, mask):
+    """conv1_bwd at the pixels of mask (N,H,W uint8), exactly 0 elsewhere; seg (N,H,W/64 uint8) from need_build."""
+    N, C, H, W = act.shape
+    nb = _lib.load().st3d_conv1_bwd_workspace_bytes(N, H, W)
+    ws = torch.empty((nb // 4,), dtype=F32, device=act.device)
+    gx = torch.empty((N, 3, H, W), dtype=F32, device=act.device)
+    call("st3d_conv1_bwd_masked", dptr(gy, F32), dptr(act, F32), dptr(D, F32), float(coef), dptr(wd, F32), dptr(ws), nb,
+         dptr(gx), N, H, W, dptr(seg, U8), dptr(mask, U8), stream_ptr())
+    return gx
+
+
+def need_levels(S):
+    return _lib.load().st3d_need_levels(int(S))
+
+
+def wino43_tile_geometry(H, W):
+    """(rows, cols) of the F(4x4,3x3) kernel's output tiles on an H x W map; None where it does not cover the map."""
+    r, c = ctypes.c_int(), ctypes.c_int()
+    ok = _lib.load().st3d_wino43_tile_geometry(int(H), int(W), ctypes.byref(r), ctypes.byref(c))
+    return (r.value, c.value) if ok else None
+
+
+def need_build(mask, levels=None):
+    """mask (N,S,S) uint8 -> (seg (N,S,S/64) uint8, [(list, count)] per tile level): st3d_need_build.  The lists are sized
+    for every tile; only the first `count` entries (a device int32 scalar) are meaningful."""
+    N, S, _ = mask.shape
+    levels = need_levels(S) if levels is None else levels
+    seg = torch.empty((N, S, S // 64), dtype=U8, device=mask.device)
+    counts = torch.zeros((2,), dtype=I32, device=mask.device)
+    lists = []
+    for l in range(levels - 1):
+        rows, cols = wino43_tile_geometry(S >> l, S >> l)
+        lists.append(torch.full((N * ((S >> l) // rows) * ((S >> l) // cols),), -1, dtype=I32, device=mask.device))
+    nb = _lib.load().st3d_need_workspace_bytes(N, S)
+    ws = torch.empty((max(nb, 1),), dtype=U8, device=mask.device)
+    call("st3d_need_build", dptr(mask, U8), N, S, levels, dptr(seg), dptr(ws), nb, dptr(lists[0]) if lists else None,
+         dptr(lists[1]) if len(lists) > 1 else None, dptr(counts), stream_ptr())
+    return seg, [(lst, counts[i]) for i, lst in enumerate(lists)]
+
+
 def conv3x3_dgrad_unpool(gy_pooled, pool_idx, pooled, wd, Cin):
     N, Cout, Hp, Wp = gy_pooled.shape
     H, W = 2 * Hp, 2 * Wp
@@ -676,6 +716,18 @@ def wino43_dgrad_chain(gy, ud, Cin, pool_idx=None, out_gate=None, add_target=Non
     call("st3d_wino43_dgrad_chain", dptr(gy.contiguous(), F32), dptr(pool_idx, U8), dptr(ud, F32), dptr(out_gate, F32),
          dptr(add_target, F32), float(add_coef), dptr(gx), N, Cin, Cout, H, W, stream_ptr())
     return gx
+
+
+def wino43_dgrad_chain_tiles(gy, ud, Cin, tile_list, n_active, out, pool_idx=None, out_gate=None, add_target=None, add_coef=0.0):
+    """wino43_dgrad_chain over the first n_active (device int32 scalar) tiles of tile_list (device int32), written into
+    `out` (N,Cin,H,W) in place: the other tiles of `out` are left alone (st3d_wino43_dgrad_chain_tiles)."""
+    N, Cout = gy.shape[:2]
+    H, W = (2 * gy.shape[2], 2 * gy.shape[3]) if pool_idx is not None else gy.shape[2:]
+    assert tuple(out.shape) == (N, Cin, H, W)
+    call("st3d_wino43_dgrad_chain_tiles", dptr(gy.contiguous(), F32), dptr(pool_idx, U8), dptr(ud, F32), dptr(out_gate, F32),
+         dptr(add_target, F32), float(add_coef), dptr(out, F32), N, Cin, Cout, H, W, dptr(tile_list, I32), dptr(n_active, I32),
+         stream_ptr())
+    return out
 
 
 def maxpool2x2(y, want_idx=True):

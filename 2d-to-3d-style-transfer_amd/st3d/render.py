@@ -756,6 +756,33 @@ class _SoftRenderFn(torch.autograd.Function):
         return (gverts, gtex) + (None,) * 16
 
 
+NEED_TAG = "_st3d_need"
+
+
+def tag_need(rgb, p2f):
+    """Tag the colour tensor a render returns with its coverage: (n,S,S) uint8, 1 where any layer of p2f (n,S,S[,K]) holds
+    a face.  The render backward reads the gradient of `rgb` at exactly those pixels (shade_bwd and its soft and lit
+    siblings walk the fragments; the background is a constant), so a loss that produces that gradient may skip whatever
+    only the other pixels would need (losses.compute_perceptual_loss -> PerceptualPlan.loss(need_mask=...)).  The tag
+    describes the tensor's PRODUCER: it stays true whatever else consumes the tensor.  Only tensors that will get a
+    gradient are tagged."""
+    if rgb.requires_grad:
+        hit = p2f >= 0
+        setattr(rgb, NEED_TAG, (hit.any(dim=-1) if hit.dim() == 4 else hit).view(torch.uint8))      # (bool is one 0/1 byte)
+    return rgb
+
+
+def need_of(t):
+    """The coverage tag of `t` if a gradient consumer may rely on it, else None: the tag must fit the tensor, and nobody
+    may be watching the tensor's own gradient (retain_grad, backward hooks) -- they would see the zeros."""
+    tag = getattr(t, NEED_TAG, None)
+    if tag is None or t.dim() != 4 or tuple(tag.shape) != (t.shape[0], t.shape[2], t.shape[3]) or tag.device != t.device:
+        return None
+    if t.is_leaf or t.retains_grad or getattr(t, "_backward_hooks", None):
+        return None
+    return tag
+
+
 def uses_hard_path(raster_settings, blend_params):
     """True for the reference's own configuration (K=1, blur 0, unclipped, default BlendParams): there
     softmax_rgb_blend reduces to texel-or-white and the specialised kernels apply."""
@@ -823,14 +850,19 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
         rs = RasterizationSettings(image_size=image_size, z_clip_value=RasterizationSettings.Z_CLIP_DEFAULT)
     if uses_hard_path(rs, bp):
         # K=1, blur 0: the blend weight cancels and the pixel is the sampled texel itself
-        return _RenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
-                               tex.faces_uvs_i32(), R, T, int(image_size), lighting)
+        rgb, mask = _RenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
+                                    tex.faces_uvs_i32(), R, T, int(image_size), lighting)
+        if rgb.requires_grad:
+            tag_need(rgb, rgb.grad_fn.frag[0])
+        return rgb, mask
     bp = bp if bp is not None else BlendParams()
     rs = rs if rs is not None else RasterizationSettings(image_size=image_size)
     rgb, alpha = _SoftRenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
                                      tex.faces_uvs_i32(), R, T, int(image_size), rs.faces_per_pixel,
                                      rs.blur_radius, rs.clip_barycentric_coords, bp.sigma, bp.gamma, bp.background_color,
                                      rs.cull_backfaces, rs.perspective_correct, rs.z_clip, lighting)
+    if rgb.requires_grad:
+        tag_need(rgb, rgb.grad_fn.frag[0])
     if hard_settings:
         # the caller asked for the hard configuration and is handed what the hard path hands out: the 0/1 coverage mask
         # (alpha of a K = 1 / blur 0 blend is in [0.5, 1) on covered pixels; the reference thresholds it, utils.py:72)

@@ -261,11 +261,20 @@ class PerceptualPlan:
             self.generation += 1
             self._style_key, self._style_ref = k, style
 
-    def loss(self, current, style_weight, content_weight, batch_denom=None, want_grad=True):
-        """-> (loss_buf view [total, content, style], grad (n,3,S,S) or None)."""
+    def loss(self, current, style_weight, content_weight, batch_denom=None, want_grad=True, need_mask=None):
+        """-> (loss_buf view [total, content, style], grad (n,3,S,S) or None).
+        need_mask (n,S,S) uint8: the only pixels at which the caller's consumer reads grad (st3d_plan_loss_masked) -- grad
+        is the same there, bit for bit, and 0 elsewhere; the bottom of the VGG backward computes only what they need."""
         cur = current.detach().to(torch.float32).contiguous()
         n = cur.shape[0]
         grad = torch.empty_like(cur) if want_grad else None
+        if need_mask is not None and want_grad:
+            if need_mask.dtype != torch.uint8 or tuple(need_mask.shape) != (n, self.S, self.S):
+                raise _lib.St3dError(f"need_mask must be uint8 ({n},{self.S},{self.S}), got {need_mask.dtype} {tuple(need_mask.shape)}")
+            call("st3d_plan_loss_masked", self._h, dptr(cur), n, int(batch_denom or n), float(style_weight),
+                 float(content_weight), dptr(self.loss_buf), dptr(grad), dptr(need_mask.contiguous()), stream_ptr())
+            self.generation += 1
+            return self.loss_buf, grad
         call("st3d_plan_loss", self._h, dptr(cur), n, int(batch_denom or n), float(style_weight), float(content_weight),
              dptr(self.loss_buf), dptr(grad), stream_ptr())
         self.generation += 1
@@ -275,15 +284,16 @@ class PerceptualPlan:
         call("st3d_plan_profile", self._h, 1 if enable else 0)
 
     def profile_read(self):
-        ms = (ctypes.c_float * 10)()
-        nl = (ctypes.c_int * 10)()
+        ms = (ctypes.c_float * len(self.FAMILIES))()
+        nl = (ctypes.c_int * len(self.FAMILIES))()
         call("st3d_plan_profile_read", self._h, ms, nl)
         return {k: {"ms": ms[i], "launches": nl[i]} for i, k in enumerate(self.FAMILIES)}
 
 
     # conv_*: Winograd F(2x2,3x3) launches; conv43_*: Winograd F(4x4,3x3); convx_*: direct / vector-ALU kernels
+    # *_need: launches that ran over a need list (loss(need_mask=...)): a fraction of the full launch's work
     FAMILIES = ("conv_fwd", "conv_dgrad", "pool", "gram_fwd", "gram_bwd", "elementwise", "convx_fwd", "convx_dgrad", "conv43_fwd",
-                "conv43_dgrad")
+                "conv43_dgrad", "conv43_dgrad_need", "convx_dgrad_need", "gram_bwd_need")
 
     def profile_launches(self):
         """[(family, VGG module index, ms)] for every launch bracket since the last read (profiling on)."""

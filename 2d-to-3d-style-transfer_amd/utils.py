@@ -40,15 +40,25 @@ class _Composite(torch.autograd.Function):
         return _ops.apply_background(grad_out.contiguous(), ctx.mask, None), None, None
 
 
+def _composite(tensors, masks, background):
+    out = _Composite.apply(tensors, masks, background)
+    # the composite hands its gradient to the render and to nobody else (the background is a constant): the render's
+    # coverage tag (st3d.render.tag_need) holds for the composite too
+    tag = _render.need_of(tensors)
+    if tag is not None and out.requires_grad:
+        setattr(out, _render.NEED_TAG, tag)
+    return out
+
+
 def apply_background(tensors, masks, background_type='noise', background=None):
     """reference :19-30 -- 'white' is the identity because the renderer's own background is white;
     'noise' draws a fresh U[0,1) image per call; any other type returns None like the reference."""
     if background_type == 'white':
         return tensors
     if background_type == 'style':
-        return _Composite.apply(tensors, masks, background)
+        return _composite(tensors, masks, background)
     if background_type == 'noise':
-        return _Composite.apply(tensors, masks, torch.rand(tensors.shape, device=tensors.device))
+        return _composite(tensors, masks, torch.rand(tensors.shape, device=tensors.device))
     return None
 
 

@@ -340,6 +340,13 @@ int st3d_conv1_bwd_supported(int H, int W);
 size_t st3d_conv1_bwd_workspace_bytes(int N, int H, int W);
 int st3d_conv1_bwd(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed,
                    void *workspace, size_t workspace_bytes, float *gx, int N, int H, int W, st3d_stream_t stream);
+/* st3d_conv1_bwd for a consumer that reads gx at the pixels of mask (N,H,W bytes, non-zero = read) only: gx is bitwise
+ * st3d_conv1_bwd's at those pixels and exactly 0 elsewhere.  seg (N,H,W/64 bytes) marks the 64-pixel row segments that
+ * touch dilate(mask, 1) (st3d_need_build): gy is read, and the tap planes are computed, in those segments only.
+ * W % 64 == 0. */
+int st3d_conv1_bwd_masked(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed,
+                          void *workspace, size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg,
+                          const uint8_t *mask, st3d_stream_t stream);
 /* As above, but gy is given at POOLED resolution (N,Cout,H/2,W/2) together with the pool's
  * argmax (uint8 0..3 = dy*2+dx) and pooled values: fuses max-unpool + ReLU gate into the load. */
 int st3d_conv3x3_dgrad_unpool(const float *gy_pooled, const uint8_t *pool_idx, const float *pooled,
@@ -387,6 +394,28 @@ int st3d_wino43_fwd(const float *x, const float *u_fwd, const float *bias, float
 int st3d_wino43_dgrad_chain(const float *gy, const uint8_t *pool_idx, const float *u_dgrad, const float *out_gate,
                             const float *add_target, float add_coef, float *gx, int N, int Cin, int Cout, int H, int W,
                             st3d_stream_t stream);
+/* The output tiles of a F(4x4,3x3) launch on an H x W map: rows x cols pixels (4 x 64 or 8 x 32), numbered
+ * (n * (H / rows) + ty) * (W / cols) + tx.  Returns 0 (and zeros) where the kernel does not cover the map. */
+int st3d_wino43_tile_geometry(int H, int W, int *rows, int *cols);
+/* st3d_wino43_dgrad_chain over the first *n_active entries of tile_list only (both in DEVICE memory, tile numbers
+ * ascending): a listed tile of gx is bitwise what the unlisted call writes, the other tiles are not written. */
+int st3d_wino43_dgrad_chain_tiles(const float *gy, const uint8_t *pool_idx, const float *u_dgrad, const float *out_gate,
+                                  const float *add_target, float add_coef, float *gx, int N, int Cin, int Cout, int H, int W,
+                                  const int *tile_list, const int *n_active, st3d_stream_t stream);
+/* Need propagation (csrc/need.hip): the only consumer of the perceptual loss's image gradient, the render backward, reads
+ * it at the pixels of mask (N,S,S bytes, non-zero = read; 16-byte aligned) only.  Bottom-up, what the last launches of the
+ * VGG backward then have to produce:
+ *   level 1  seg (N,S,S/64 bytes): 1 for the 64-pixel row segments that touch dilate(mask, 1) (st3d_conv1_bwd_masked)
+ *   level 2  list1 / counts[0]: the output tiles of the conv1_2 input gradient (geometry of an S x S map) that hold an
+ *            active segment
+ *   level 3  list2 / counts[1]: the output tiles of the conv2_1 input gradient (geometry of an S/2 x S/2 map) that hold a
+ *            pooled pixel of the 2x2 OR of dilate(union of the level-2 tiles, 1)
+ * Lists are ascending, images outermost, and sized for every tile; they and the counts stay in device memory.
+ * st3d_need_levels(S): how many levels exist at this size (0 when S % 64 != 0).  Ordered prefix-sum compaction, no atomics. */
+int st3d_need_levels(int S);
+size_t st3d_need_workspace_bytes(int N, int S);      /* one flag byte per tile of levels 2 and 3 */
+int st3d_need_build(const uint8_t *mask, int N, int S, int levels, uint8_t *seg, void *workspace, size_t workspace_bytes,
+                    int *list1, int *list2, int *counts, st3d_stream_t stream);
 /* MaxPool2d(2,2): y (N,C,H,W) -> p (N,C,H/2,W/2) (+ argmax idx, may be NULL) */
 int st3d_maxpool2x2_fwd(const float *y, float *p, uint8_t *idx, int N, int C, int H, int W,
                         st3d_stream_t stream);
@@ -521,6 +550,16 @@ int st3d_plan_set_style(st3d_plan *plan, const float *style, int style_batch, in
  * sharded over ranks).  loss_out: device float[3] = {total, content_loss, style_loss}. */
 int st3d_plan_loss(st3d_plan *plan, const float *current, int n, int batch_denom, float style_weight,
                    float content_weight, float *loss_out, float *grad_current, st3d_stream_t stream);
+/* st3d_plan_loss for a caller whose only consumer of grad_current reads it at the pixels of need_mask (n,S,S bytes,
+ * non-zero = read; 16-byte aligned; NULL = st3d_plan_loss): loss_out is bitwise st3d_plan_loss's; grad_current is bitwise
+ * st3d_plan_loss's at those pixels and exactly 0 elsewhere.  The bottom launches of the backward then compute only what
+ * those pixels need (st3d_need_build): the relu1_1 pass, the conv1_2 and the conv2_1 input gradient -- ST3D_NEED_DEPTH =
+ * 0..3 masks fewer of them, bottom-up (A/B runs; 0 and sizes with S % 64 != 0 run unmasked and return the full gradient).
+ * With graph replay the mask is staged into a plan-owned buffer like the other inputs and the lists are built inside
+ * the graph. */
+int st3d_plan_loss_masked(st3d_plan *plan, const float *current, int n, int batch_denom, float style_weight,
+                          float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask,
+                          st3d_stream_t stream);
 /* HIP-graph replay of st3d_plan_loss: its ~70 launches form a static sequence, so after one ordinary call it is captured
  * (per n / batch_denom / weights) and replayed with one hipGraphLaunch; inputs and outputs pass through plan-owned staging
  * buffers (three extra device copies per call).  Pays off where the step is launch-bound (small images). */
@@ -535,8 +574,10 @@ int st3d_plan_backward(st3d_plan *plan, int n, int upto_module, const float *con
 /* per-kernel-family timing of the next calls (HIP events on the call's stream): enable, then
  * read accumulated milliseconds + launch counts; families: 0 conv_fwd (Winograd launches) 1 conv_dgrad (Winograd)
  * 2 pool 3 gram_fwd 4 gram_bwd 5 loss/elementwise 6 convx_fwd (convs Winograd does not cover: conv1_1, odd shapes)
- * 7 convx_dgrad */
-#define ST3D_PROFILE_FAMILIES 10
+ * 7 convx_dgrad 8 conv43_fwd 9 conv43_dgrad (Winograd F(4x4,3x3)); launches that ran over a need list
+ * (st3d_plan_loss_masked) count under families of their own, their work being a fraction of the full launch's:
+ * 10 conv43_dgrad_need 11 convx_dgrad_need (the relu1_1 pass) 12 gram_bwd_need (none yet) */
+#define ST3D_PROFILE_FAMILIES 13
 int st3d_plan_profile(st3d_plan *plan, int enable);
 int st3d_plan_profile_read(st3d_plan *plan, float *ms_out /*host [ST3D_PROFILE_FAMILIES]*/,
                            int *launches_out /*host [ST3D_PROFILE_FAMILIES]*/);

@@ -90,7 +90,7 @@ def main(argv=None):
             run.log(f'Batch {vb.index}, Step {step}, Loss {shown}')
         run.maybe_checkpoint(vb.index + 1)
 
-    run.export(mesh)
+    run.export(run.current_mesh())      # rebuilt from the parameters as the last step left them
 
 
 if __name__ == "__main__":

@@ -59,6 +59,9 @@ SHARED_FLAGS = [
     Flag("silhouette_sigma", float, 1e-4, "sigma of the soft silhouette (SoftSilhouetteShader's BlendParams.sigma)"),
     Flag("silhouette_faces_per_pixel", int, None, "faces per pixel of the silhouette term, 1..64, on the silhouette rasteriser "
          "(PyTorch3D's silhouette tutorial uses 50); unset = the general rasteriser at 8"),
+    Flag("texture_pyramid_levels", int, 1, "optimise the texture as the sum of N maps of halving sides, so that texels no "
+         "rendered pixel touches move with their neighbours; 1 = the plain map, 0 = as many levels as the side allows "
+         "(down to a side of 4..7).  Every level moves by about lr a step, their sum by up to N x lr"),
 ]
 
 # regularisers the reference defines but never switches on (losses.py:48-65, notes.txt:36,39); weight 0 = off
@@ -79,6 +82,12 @@ def check_args(args):
     k = getattr(args, "silhouette_faces_per_pixel", None)
     if k is not None and not 1 <= k <= 64:
         return "--silhouette_faces_per_pixel must be in 1..64"
+    levels = getattr(args, "texture_pyramid_levels", 1)
+    if levels < 0:
+        return "--texture_pyramid_levels must be 0 (auto), 1 (off) or the number of levels"
+    if levels != 1 and getattr(args, "optimization_target", None) == 'mesh':
+        return ("--texture_pyramid_levels needs --optimization_target texture or both: with 'mesh' the texture is not "
+                "optimised")
     return None
 
 
@@ -233,10 +242,16 @@ class Run:
             torch.distributed.broadcast(self.cameras.T, 0)
 
         # one optimiser (one Adam state) for the whole run, over all view batches
-        self.opt = _u.setup_optimizations(args.optimization_target, self.content_mesh, lr)
+        levels = getattr(args, "texture_pyramid_levels", 1)
+        if levels == 1:
+            self.opt = _u.setup_optimizations(args.optimization_target, self.content_mesh, lr)
+        else:
+            self.opt = _u.setup_optimizations(args.optimization_target, self.content_mesh, lr, texture_pyramid_levels=levels)
+        self.pyramid = self.opt.get('texture_pyramid')      # None: the texture is the plain leaf opt['texture_map']
         if args.verts_lr is not None and args.optimization_target == 'both':
+            texture_leaf = self.pyramid.params if self.pyramid is not None else self.opt['texture_map']
             self.opt['optimizer'] = st3d_optim.Adam([{"params": [self.opt['verts']], "lr": args.verts_lr},
-                                                     {"params": [self.opt['texture_map']], "lr": lr}])
+                                                     {"params": [texture_leaf], "lr": lr}])
         self.optimizer = self.opt['optimizer']
         self.original_map = tex
         self.progress = 0               # epochs (second approach) / view batches (first approach) already done
@@ -270,7 +285,8 @@ class Run:
 
     def current_mesh(self):
         o = self.opt
-        return self._utils.build_mesh(o['verts_uvs'], o['faces_uvs'], o['texture_map'], o['verts'], o['faces'])
+        texture = self.pyramid.texture() if self.pyramid is not None else o['texture_map']      # synthesised every step
+        return self._utils.build_mesh(o['verts_uvs'], o['faces_uvs'], texture, o['verts'], o['faces'])
 
     def batches(self):
         """The reference's schedule (ceil(n_views / batch_size) consecutive slices) with this rank's share of each."""
@@ -310,9 +326,17 @@ class Run:
     def save_checkpoint(self, progress):
         if not self.main:
             return
+        if self.pyramid is None:
+            texture = self.opt['texture_map']
+        else:
+            with torch.no_grad():
+                texture = self.pyramid.texture()
         blob = {"progress": int(progress), "optimization_target": self.args.optimization_target,
-                "texture_map": self.opt['texture_map'].detach().cpu(), "verts": self.opt['verts'].detach().cpu(),
+                "texture_map": texture.detach().cpu(), "verts": self.opt['verts'].detach().cpu(),
                 "optimizer": self.optimizer.state_dict()}
+        if self.pyramid is not None:        # the flat parameters are the state of record; texture_map is what they sum to
+            blob["texture_pyramid"] = self.pyramid.params.detach().cpu()
+            blob["texture_pyramid_levels"] = self.pyramid.levels
         tmp = os.path.join(self.out_dir, "checkpoint.pt.tmp")
         torch.save(blob, tmp)
         os.replace(tmp, os.path.join(self.out_dir, "checkpoint.pt"))
@@ -321,8 +345,15 @@ class Run:
         blob = torch.load(path, map_location="cpu", weights_only=True)
         if blob["optimization_target"] != self.args.optimization_target:
             raise ValueError("checkpoint was written for optimization_target=%r" % blob["optimization_target"])
+        have = int(blob.get("texture_pyramid_levels", 1))
+        want = self.pyramid.levels if self.pyramid is not None else 1
+        if have != want:
+            raise ValueError("checkpoint was written with %d texture pyramid level(s), this run has %d" % (have, want))
         with torch.no_grad():
-            self.opt['texture_map'].copy_(blob["texture_map"])
+            if self.pyramid is not None:
+                self.pyramid.load_params(blob["texture_pyramid"].to(self.device))
+            else:
+                self.opt['texture_map'].copy_(blob["texture_map"])
             self.opt['verts'].copy_(blob["verts"])
         self.optimizer.load_state_dict(blob["optimizer"])
         self.progress = int(blob["progress"])

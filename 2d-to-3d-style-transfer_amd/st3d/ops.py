@@ -852,6 +852,63 @@ def range_loss(values, want_grad=True):
     return out, g
 
 
+# ------------------------------------------------------------------ texture pyramid (csrc/texpyr.hip)
+def texpyr_sides(T, levels):
+    """Sides [T, T/2, ...] of a pyramid of `levels` maps under a T x T texture.  levels = 0 is "auto": halve while the side
+    is even and the half is >= 4 (512 -> 8 levels down to 4, 768 -> 8 down to 6).  levels >= 2 needs T divisible by
+    2^(levels-1) and a coarsest side >= 2.  Pure host logic; anything else raises ValueError."""
+    T, levels = int(T), int(levels)
+    if T < 1:
+        raise ValueError(f"texture side must be positive, got {T}")
+    if levels < 0:
+        raise ValueError(f"texture pyramid levels must be >= 0 (0 = auto), got {levels}")
+    if levels == 0:
+        sides = [T]
+        while sides[-1] % 2 == 0 and sides[-1] // 2 >= 4:
+            sides.append(sides[-1] // 2)
+        return sides
+    if levels > 16:
+        raise ValueError(f"at most 16 texture pyramid levels, got {levels}")
+    if levels > 1 and (T % (1 << (levels - 1)) or T >> (levels - 1) < 2):
+        raise ValueError(f"{levels} pyramid levels need a texture side divisible by {1 << (levels - 1)} with a coarsest side "
+                         f">= 2, got {T}")
+    return [T >> l for l in range(levels)]
+
+
+def texpyr_numel(T, L):
+    """P = 3 * sum_l (T / 2^l)^2, the length of the flat parameter tensor of an L-level pyramid (L >= 1)."""
+    if int(L) < 1:
+        raise ValueError(f"texpyr_numel takes a resolved level count >= 1 (see texpyr_sides), got {L}")
+    texpyr_sides(T, L)
+    n = _lib.load().st3d_texpyr_numel(int(T), int(L))
+    if n == 0:
+        raise ValueError(f"no texture pyramid of {L} levels under a side of {T}")
+    return n
+
+
+def texpyr_synth(params, T, L, out=None):
+    """flat params (P,) -> texture (1,T,T,3) = level_0 + up2(level_1 + up2(...)); one launch whatever L is."""
+    P = texpyr_numel(T, L)
+    if params.numel() != P:
+        raise ValueError(f"a {L}-level pyramid under side {T} holds {P} values, got {params.numel()}")
+    if out is None:
+        out = torch.empty((1, T, T, 3), dtype=F32, device=params.device)
+    call("st3d_texpyr_synth", dptr(params, F32), int(T), int(L), dptr(out, F32), stream_ptr())
+    return out
+
+
+def texpyr_adjoint(grad_texture, T, L, out=None):
+    """grad_texture (T*T*3 values, HWC) -> the gradient of the flat params (P,): every coarse texel gathers its fine
+    footprint in a fixed order (no atomics); at most two launches."""
+    P = texpyr_numel(T, L)
+    if grad_texture.numel() != 3 * T * T:
+        raise ValueError(f"grad_texture must hold {T}x{T}x3 values, got {tuple(grad_texture.shape)}")
+    if out is None:
+        out = torch.empty((P,), dtype=F32, device=grad_texture.device)
+    call("st3d_texpyr_adjoint", dptr(grad_texture.contiguous(), F32), int(T), int(L), dptr(out, F32), stream_ptr())
+    return out
+
+
 def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8):
     call("st3d_adam_step", dptr(p, F32), dptr(g.contiguous(), F32), dptr(m, F32), dptr(v, F32), p.numel(), int(step),
          float(lr), float(b1), float(b2), float(eps), stream_ptr())

@@ -79,7 +79,7 @@ def main(argv=None):
             run.log(f'Round {rnd}, Batch {vb.index}, Loss {run.global_sum(loss).item()}')
         run.maybe_checkpoint(rnd + 1)
 
-    run.export(mesh)
+    run.export(run.current_mesh())      # rebuilt from the parameters as the last step left them
 
 
 if __name__ == "__main__":

@@ -148,9 +148,13 @@ def build_random_cameras(n_views, dist=2.10, generator=None):
 _LEAVES = {'texture': ('texture_map',), 'mesh': ('verts',), 'both': ('verts', 'texture_map')}
 
 
-def setup_optimizations(optimization_target, mesh, lr):
+def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1):
     """Clone the mesh, mark the tensors `optimization_target` names as leaves and put ONE Adam (single lr,
-    default betas/eps) over them (:173-204).  Keys of the returned dict are the reference's."""
+    default betas/eps) over them (:173-204).  Keys of the returned dict are the reference's.
+
+    texture_pyramid_levels != 1 (0 = auto, L >= 2; targets 'texture' / 'both'): the texture leaf is the flat parameter
+    tensor of an st3d.texpyr.TexturePyramid, returned under 'texture_pyramid' (for 'both' Adam sees the vertices first,
+    then the pyramid).  The dict then has NO 'texture_map' entry -- the map is pyramid.texture(), rebuilt every step."""
     work = mesh.clone()
     parts = {
         'texture_map': work.textures.maps_padded(),
@@ -162,5 +166,14 @@ def setup_optimizations(optimization_target, mesh, lr):
     if optimization_target not in _LEAVES:      # the reference falls through to an unbound `optimizer`
         raise UnboundLocalError("local variable 'optimizer' referenced before assignment "
                                 f"(optimization_target={optimization_target!r})")
+    if texture_pyramid_levels != 1:
+        if optimization_target == 'mesh':
+            raise ValueError("a texture pyramid needs optimization_target 'texture' or 'both': with 'mesh' the texture is "
+                             "not optimised")
+        from st3d.texpyr import TexturePyramid
+        parts['texture_pyramid'] = TexturePyramid(parts.pop('texture_map'), texture_pyramid_levels)
+        leaves = [parts['verts'].requires_grad_(True)] if optimization_target == 'both' else []
+        leaves.append(parts['texture_pyramid'].params)
+        return dict(parts, optimizable_mesh=work, optimizer=_st3d_optim.Adam(leaves, lr=lr))
     leaves = [parts[name].requires_grad_(True) for name in _LEAVES[optimization_target]]
     return dict(parts, optimizable_mesh=work, optimizer=_st3d_optim.Adam(leaves, lr=lr))

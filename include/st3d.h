@@ -509,6 +509,21 @@ int st3d_mesh_reg(const float *verts, const float *target_verts, int V, const in
                   const float *weights, float *scratch, float *partials, float *loss_out,
                   float *grad_verts, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ texture pyramid (csrc/texpyr.hip):
+ * the texture map (T,T,3) as the sum of L maps of sides T_l = T / 2^l, each upsampled to T x T.  `params` is one flat
+ * fp32 tensor of st3d_texpyr_numel(T, L) = 3 * sum_l T_l^2 elements; level l is the (T_l, T_l, 3) row-major block at
+ * offset 3 * sum_{k<l} T_k^2.  L >= 2 needs T divisible by 2^(L-1) and T_{L-1} >= 2; L = 1 is a copy; T <= 16384, L <= 16.
+ *   synth:   acc_{L-1} = level_{L-1}; acc_l = level_l + up2(acc_{l+1}); texture = acc_0, with up2 = F.interpolate(
+ *            scale_factor=2, mode='bilinear', align_corners=False): fine 2j = 0.25 c[j-1] + 0.75 c[j], fine 2j+1 =
+ *            0.75 c[j] + 0.25 c[j+1], indices clamped.  One launch whatever L is.
+ *   adjoint: g_0 = grad_texture; g_{l+1} = up2^T(g_l); block l of grad_params = g_l -- every coarse texel gathers its
+ *            <= 4 x 4 fine footprint in a fixed order (no atomics: bitwise reproducible).  At most two launches.
+ * NaN / Inf propagate as the expressions say (taps that do not exist are skipped, never multiplied by zero).  The two
+ * buffers of a call must not overlap.  Nothing is allocated.  st3d_texpyr_numel returns 0 for a shape the others refuse. */
+size_t st3d_texpyr_numel(int T, int L);
+int st3d_texpyr_synth(const float *params, int T, int L, float *texture, st3d_stream_t stream);
+int st3d_texpyr_adjoint(const float *grad_texture, int T, int L, float *grad_params, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ optimiser:
  * torch.optim.Adam defaults (utils.py:185-195, style_transfer.py:57) */
 int st3d_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,

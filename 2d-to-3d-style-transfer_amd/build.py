@@ -37,6 +37,7 @@ SOURCES = {
     "gram.hip": [],
     "tap0.hip": [],
     "need.hip": [],
+    "flat.hip": [],
     "loss.hip": ["-ffp-contract=off"],
     "mesh.hip": [],
     "texpyr.hip": ["-ffp-contract=off"],       # the roundings its tests count are the ones written in the source

@@ -179,12 +179,18 @@ struct st3d_plan {
     hipStream_t cap_stream;
     float *g_in, *g_grad, *g_loss;
     uint8_t *g_mask;
-    struct { int n, denom, want_grad, warm, masked; float sw, cw; } gkey;
+    struct { int n, denom, want_grad, warm, masked, flat; float sw, cw; } gkey;
     // need lists of st3d_plan_loss_masked (need.hip), rebuilt by every masked call; nullptr where the size has none
     int need_levels;           // levels that exist at this size, capped by ST3D_NEED_DEPTH
     uint8_t *need_seg, *need_flags;
     size_t need_flags_bytes;
     int *need_list[2], *need_cnt;
+    // flat-field lists of st3d_plan_loss_flat (flat.hip), rebuilt by every call that brings a colour
+    int flat_levels;           // how many of conv1_2, conv2_1, conv2_2 may run listed: st3d_flat_levels, capped by ST3D_FLAT_DEPTH
+    uint8_t *flat_ws;
+    size_t flat_ws_bytes;
+    int *flat_list[3], *flat_map[3], *flat_cnt;
+    float *g_color;
 };
 
 namespace {
@@ -228,8 +234,10 @@ struct Scope {   // HIP-event bracket around one kernel family (only when profil
 enum { F_CONV_FWD = 0, F_CONV_DGRAD = 1, F_POOL = 2, F_GRAM_FWD = 3, F_GRAM_BWD = 4, F_ELEM = 5, F_CONVX_FWD = 6, F_CONVX_DGRAD = 7,
        F_CONV43_FWD = 8, F_CONV43_DGRAD = 9,
        // launches that ran over a need list: a fraction of the full launch's work, so not priced as one
-       F_CONV43_DGRAD_NEED = 10, F_CONVX_DGRAD_NEED = 11, F_GRAM_BWD_NEED = 12 };
-static_assert(F_GRAM_BWD_NEED + 1 == ST3D_PROFILE_FAMILIES, "profile families");
+       F_CONV43_DGRAD_NEED = 10, F_CONVX_DGRAD_NEED = 11, F_GRAM_BWD_NEED = 12,
+       // forward launches over a flat-field list, and the copies that fill in the tiles they left out
+       F_CONV43_FWD_FLAT = 13, F_FLAT_FILL = 14 };
+static_assert(F_FLAT_FILL + 1 == ST3D_PROFILE_FAMILIES, "profile families");
 
 // F(4x4,3x3) for this GEMM?  K = channels reduced over (Cin forward, Cout for the input gradient), M = channels produced
 bool use_wino43(const st3d_vgg *v, int cs, int K, int M, int H, int W) {
@@ -238,9 +246,29 @@ bool use_wino43(const st3d_vgg *v, int cs, int K, int M, int H, int W) {
 
 // keep_full: also materialise the full-resolution output of convs whose 2x2 pool is fused into
 // their epilogue (needed only when a caller asks for that activation: st3d_plan_forward).
-int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hipStream_t s) {
+// flat_color (device, 3 floats; the loss call only): imgs hold this colour at many pixels -- conv slots 1 .. 3 (conv1_2,
+// conv2_1, conv2_2) compute the tiles of their flat-field lists and copy the rest (flat.hip); the buffers end up bitwise
+// what the full launches write
+int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hipStream_t s, const float *flat_color = nullptr) {
     const float *x = imgs;
     int Cin = 3, H = p->S, W = p->S;
+    int flat = 0;               // conv slots 1 .. flat run listed (each decided from the predicate the loop dispatches on)
+    if (flat_color) {
+        const st3d_vgg *v = p->vgg;
+        const int S = p->S;
+        const int HW[3] = {S, S / 2, S / 2};
+        for (int k = 0; k < p->flat_levels && kConvIdx[k + 1] <= upto; ++k) {
+            if (!(v->uf[k + 1] && st3d_wino_supported(kConvCin[k + 1], kConvCout[k + 1], HW[k], HW[k]) &&
+                  use_wino43(v, k + 1, kConvCin[k + 1], kConvCout[k + 1], HW[k], HW[k])))
+                break;
+            flat = k + 1;
+        }
+        if (flat > 0) {
+            Scope sc(p, F_ELEM, s);
+            ST3D_TRY(st3d_flat_build(imgs, flat_color, n, S, flat, p->flat_ws, p->flat_ws_bytes, p->flat_list[0], p->flat_map[0],
+                                     p->flat_list[1], p->flat_map[1], p->flat_list[2], p->flat_map[2], p->flat_cnt, s));
+        }
+    }
     for (int m = 0; m <= upto; ++m) {
         const int cs = conv_slot(m), ps = pool_slot(m);
         if (cs >= 0) {
@@ -250,6 +278,26 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
             }
             const bool wino = p->vgg->use_wino && p->vgg->uf[cs] && st3d_wino_supported(Cin, kConvCout[cs], H, W);
             const bool w43 = wino && use_wino43(p->vgg, cs, Cin, kConvCout[cs], H, W);
+            if (cs >= 1 && cs <= flat) {           // an F(4x4,3x3) launch over its flat-field list, then the copies
+                const int pool_m = m + 2;
+                const int pps = (pool_m <= upto) ? pool_slot(pool_m) : -1;
+                float *yfull = (pps < 0 || keep_full) ? p->act[m] : nullptr;
+                float *yp = pps >= 0 ? p->act[pool_m] : nullptr;
+                uint8_t *yi = pps >= 0 ? p->pidx[pps] : nullptr;
+                {
+                    Scope sc(p, F_CONV43_FWD_FLAT, s, m);
+                    ST3D_TRY(st3d_wino43_fwd_tiles(x, p->vgg->u6f[cs], p->vgg->bias[cs], yfull, yp, yi, n, Cin, kConvCout[cs], H, W, 1,
+                                                   p->flat_list[cs - 1], p->flat_cnt + (cs - 1), s));
+                }
+                {
+                    Scope sc(p, F_FLAT_FILL, s, m);
+                    ST3D_TRY(st3d_flat_fill(p->flat_map[cs - 1], yfull, yp, yi, n, kConvCout[cs], H, W, s));
+                }
+                Cin = kConvCout[cs];
+                x = pps >= 0 ? p->act[pool_m] : p->act[m];
+                if (pps >= 0) { H /= 2; W /= 2; m = pool_m; }
+                continue;
+            }
             Scope sc(p, w43 ? F_CONV43_FWD : (wino ? F_CONV_FWD : F_CONVX_FWD), s, m);
             if (wino) {
                 const int pool_m = m + 2;          // conv, relu, pool
@@ -382,6 +430,8 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     p->gbuf[0] = p->gbuf[1] = nullptr; p->content_target = nullptr; p->gram_ws = nullptr; p->partials = nullptr;
     p->have_content = p->have_style = false; p->style_batch = 0; p->last_n = 0; p->prof = false;
     p->use_graph = 0; p->gexec = nullptr; p->cap_stream = nullptr; p->g_in = p->g_grad = p->g_loss = nullptr; memset(&p->gkey, 0, sizeof(p->gkey));
+    p->flat_levels = 0; p->flat_ws = nullptr; p->flat_ws_bytes = 0; p->flat_cnt = nullptr; p->g_color = nullptr;
+    for (int k = 0; k < 3; ++k) p->flat_list[k] = p->flat_map[k] = nullptr;
     p->g_mask = nullptr; p->need_levels = 0; p->need_seg = p->need_flags = nullptr; p->need_flags_bytes = 0; p->need_list[0] = p->need_list[1] = nullptr; p->need_cnt = nullptr;
     memset(p->fam_ms, 0, sizeof(p->fam_ms)); memset(p->fam_n, 0, sizeof(p->fam_n));
     int rc = ST3D_OK;
@@ -443,6 +493,21 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
             rc = dev_alloc(p, &p->need_list[l], (size_t)B * ((S >> l) / rows) * ((S >> l) / cols));
         }
     }
+    // ST3D_FLAT_DEPTH=k: how many of the shallow forward launches may run over a flat-field list (0 none, 1 conv1_2, 2 +
+    // conv2_1, 3 + conv2_2 = the default)
+    const char *fd = getenv("ST3D_FLAT_DEPTH");
+    p->flat_levels = st3d_flat_levels(S);
+    if (fd && atoi(fd) >= 0 && atoi(fd) < p->flat_levels) p->flat_levels = atoi(fd);
+    if (p->flat_levels >= 1 && rc == ST3D_OK) {
+        p->flat_ws_bytes = st3d_flat_workspace_bytes(B, S);
+        rc = dev_alloc(p, &p->flat_ws, p->flat_ws_bytes);
+        if (rc == ST3D_OK) rc = dev_alloc(p, &p->flat_cnt, (size_t)4);
+        if (rc == ST3D_OK) rc = dev_alloc(p, &p->g_color, (size_t)4);
+        for (int k = 0; k < p->flat_levels && rc == ST3D_OK; ++k) {
+            rc = dev_alloc(p, &p->flat_list[k], (size_t)st3d_flat_tiles(B, S, k));
+            if (rc == ST3D_OK) rc = dev_alloc(p, &p->flat_map[k], (size_t)st3d_flat_tiles(B, S, k));
+        }
+    }
     if (rc != ST3D_OK) { st3d_plan_destroy(p); return rc; }
     *out = p;
     return ST3D_OK;
@@ -472,6 +537,13 @@ extern "C" int st3d_plan_destroy(st3d_plan *p) {
     if (p->need_cnt) (void)hipFree(p->need_cnt);
     for (int l = 0; l < 2; ++l)
         if (p->need_list[l]) (void)hipFree(p->need_list[l]);
+    if (p->flat_ws) (void)hipFree(p->flat_ws);
+    if (p->flat_cnt) (void)hipFree(p->flat_cnt);
+    if (p->g_color) (void)hipFree(p->g_color);
+    for (int k = 0; k < 3; ++k) {
+        if (p->flat_list[k]) (void)hipFree(p->flat_list[k]);
+        if (p->flat_map[k]) (void)hipFree(p->flat_map[k]);
+    }
     if (p->gexec) (void)hipGraphExecDestroy(p->gexec);
     if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
     for (auto &e : p->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -556,7 +628,7 @@ extern "C" int st3d_plan_set_style(st3d_plan *p, const float *style, int style_b
 }
 
 static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
-                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, hipStream_t s);
+                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, const float *flat_color, hipStream_t s);
 
 extern "C" int st3d_plan_graph(st3d_plan *p, int enable) {
     ST3D_CHECK_ARG(p);
@@ -574,9 +646,19 @@ extern "C" int st3d_plan_loss(st3d_plan *p, const float *current, int n, int bat
 extern "C" int st3d_plan_loss_masked(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
                                      float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask,
                                      st3d_stream_t stream) {
+    return st3d_plan_loss_flat(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, nullptr, stream);
+}
+
+extern "C" int st3d_plan_loss_flat(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
+                                   float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask,
+                                   const float *flat_color, st3d_stream_t stream) {
     ST3D_CHECK_ARG(p && current && loss_out);
     ST3D_CHECK_ARG(((uintptr_t)need_mask & 15) == 0);
     if (!grad_current || p->need_levels < 1) need_mask = nullptr;      // nothing to thin out: the ordinary call
+    if (flat_color) {           // ST3D_FLAT=0 (A/B runs, read per call), a size without lists, an unaligned image: the full forward
+        const char *fl = getenv("ST3D_FLAT");
+        if ((fl && fl[0] == '0') || p->flat_levels < 1 || ((uintptr_t)current & 15) != 0) flat_color = nullptr;
+    }
     ST3D_CHECK_ARG(n > 0 && n <= p->B && batch_denom >= n);
     if (!p->have_content || !p->have_style) {
         st3d::set_error("st3d_plan_loss: content/style targets not set");
@@ -585,29 +667,30 @@ extern "C" int st3d_plan_loss_masked(st3d_plan *p, const float *current, int n, 
     ST3D_CHECK_ARG(p->style_batch == 1 || p->style_batch == n);
     hipStream_t s = st3d::as_stream(stream);
     if (!p->use_graph || p->prof)
-        return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, s);
+        return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, flat_color, s);
 
     // ---- graph replay
     const size_t img = (size_t)n * 3 * p->S * p->S;
-    const int want_grad = grad_current ? 1 : 0, masked = need_mask ? 1 : 0;
+    const int want_grad = grad_current ? 1 : 0, masked = need_mask ? 1 : 0, flat = flat_color ? 1 : 0;
     const bool same = p->gexec && p->gkey.n == n && p->gkey.denom == batch_denom && p->gkey.want_grad == want_grad &&
-                      p->gkey.masked == masked && p->gkey.sw == style_weight && p->gkey.cw == content_weight;
+                      p->gkey.masked == masked && p->gkey.flat == flat && p->gkey.sw == style_weight && p->gkey.cw == content_weight;
     if (!same) {
         if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
         const bool warm = p->gkey.warm && p->gkey.n == n && p->gkey.denom == batch_denom && p->gkey.want_grad == want_grad &&
-                          p->gkey.masked == masked && p->gkey.sw == style_weight && p->gkey.cw == content_weight;
-        p->gkey.n = n; p->gkey.denom = batch_denom; p->gkey.want_grad = want_grad; p->gkey.masked = masked;
+                          p->gkey.masked == masked && p->gkey.flat == flat && p->gkey.sw == style_weight && p->gkey.cw == content_weight;
+        p->gkey.n = n; p->gkey.denom = batch_denom; p->gkey.want_grad = want_grad; p->gkey.masked = masked; p->gkey.flat = flat;
         p->gkey.sw = style_weight; p->gkey.cw = content_weight;
         if (!warm) {            // first call with these parameters: run it plainly (loads every code object, nothing to capture yet)
             p->gkey.warm = 1;
-            return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, s);
+            return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, flat_color, s);
         }
         hipGraph_t graph = nullptr;
         // captured on a stream of the plan's own: the caller's stream is usually the (uncapturable) default stream
         if (!p->cap_stream) ST3D_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
         ST3D_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
         const int rc = plan_loss_enqueue(p, p->g_in, n, batch_denom, style_weight, content_weight, p->g_loss,
-                                         want_grad ? p->g_grad : nullptr, masked ? p->g_mask : nullptr, p->cap_stream);
+                                         want_grad ? p->g_grad : nullptr, masked ? p->g_mask : nullptr, flat ? p->g_color : nullptr,
+                                         p->cap_stream);
         const hipError_t e = hipStreamEndCapture(p->cap_stream, &graph);
         if (rc != ST3D_OK || e != hipSuccess || !graph) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -620,6 +703,7 @@ extern "C" int st3d_plan_loss_masked(st3d_plan *p, const float *current, int n, 
     }
     ST3D_HIP(hipMemcpyAsync(p->g_in, current, img * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (masked) ST3D_HIP(hipMemcpyAsync(p->g_mask, need_mask, (size_t)n * p->S * p->S, hipMemcpyDeviceToDevice, s));
+    if (flat) ST3D_HIP(hipMemcpyAsync(p->g_color, flat_color, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     ST3D_HIP(hipGraphLaunch(p->gexec, s));
     ST3D_HIP(hipMemcpyAsync(loss_out, p->g_loss, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (grad_current) ST3D_HIP(hipMemcpyAsync(grad_current, p->g_grad, img * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -628,10 +712,10 @@ extern "C" int st3d_plan_loss_masked(st3d_plan *p, const float *current, int n, 
 }
 
 static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
-                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, hipStream_t s) {
+                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, const float *flat_color, hipStream_t s) {
     {
         st3d::TraceRange tr("vgg_forward");
-        ST3D_TRY(forward(p, current, n, 28, false, s));
+        ST3D_TRY(forward(p, current, n, 28, false, s, flat_color));
     }
     st3d::TraceRange tr_loss("gram_and_losses");
 

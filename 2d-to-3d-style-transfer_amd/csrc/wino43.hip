@@ -116,6 +116,7 @@ __device__ __forceinline__ void bt6(T d0, T d1, T d2, T d3, T d4, T d5, T &t0, T
 //  block as the k-step's MFMAs instead of two scalar branches behind them)
 // LIST: the workgroup walks positions slot, slot + nslots, ... of a.tile_list instead of the pixel tiles themselves; the
 // walk, the ring and the epilogue are the same, a tile sees the inputs and the order of operations it sees unlisted.
+// (the input-gradient chain over a need list, and the forward -- EPI 0 or 1, bias and ReLU -- over a flat-field list)
 template <int MODE, int EPI, int GATE, int BH, int TC, bool LIST>
 __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     using G = Geo43<TC>;
@@ -646,8 +647,10 @@ int launch_wino43_tc(Wino43Args a, hipStream_t s) {
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     };
-    if (a.tile_list) {      // the listed walk: input-gradient launches only (no bias, no ReLU, no fused pool)
-        if (a.yp || a.bias || a.relu || !a.n_active) { st3d::set_error("wino43: a tile list belongs to the input-gradient chain"); return ST3D_E_INVALID; }
+    if (a.tile_list) {      // the listed walk: the input-gradient chain (need.hip) and the plain forward (flat.hip)
+        if (!a.n_active) { st3d::set_error("wino43: a tile list without its count"); return ST3D_E_INVALID; }
+        if ((a.yp || a.bias || a.relu) && (MODE != 0 || a.gate)) { st3d::set_error("wino43: bias, ReLU and the fused pool belong to the plain forward"); return ST3D_E_INVALID; }
+        if (a.yp) return go(wino43_kernel<0, 1, 0, TC, true>);
         if (a.gate && a.addt) {
             if (MODE != 0) { st3d::set_error("wino43: the content-target term rides on ungated input (MODE 0) only"); return ST3D_E_INVALID; }
             return go(wino43_kernel<0, 0, 2, TC, true>);
@@ -699,6 +702,21 @@ extern "C" int st3d_wino43_fwd(const float *x, const float *u_fwd, const float *
     ST3D_CHECK_ARG(N > 0 && shape_ok43(Cin, Cout, H, W));
     ST3D_CHECK_ARG(((uintptr_t)u_fwd & 15) == 0);
     Wino43Args a{x, nullptr, u_fwd, bias, y, y_pooled, pool_idx, N, Cin, Cout, H, W, relu, 0, 0, 0, nullptr, nullptr, 0.f};
+    return launch_wino43<0>(a, st3d::as_stream(stream));
+}
+
+// the same launch over the first *n_active entries of tile_list only (device memory, ascending tile indices as for
+// st3d_wino43_dgrad_chain_tiles): listed tiles get bitwise what the call above gives them -- y, y_pooled and pool_idx alike --
+// and nothing else is written
+extern "C" int st3d_wino43_fwd_tiles(const float *x, const float *u_fwd, const float *bias, float *y, float *y_pooled,
+                                     uint8_t *pool_idx, int N, int Cin, int Cout, int H, int W, int relu, const int *tile_list,
+                                     const int *n_active, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(x && u_fwd && (y || y_pooled) && tile_list && n_active);
+    ST3D_CHECK_ARG(N > 0 && shape_ok43(Cin, Cout, H, W));
+    ST3D_CHECK_ARG(((uintptr_t)u_fwd & 15) == 0);
+    Wino43Args a{x, nullptr, u_fwd, bias, y, y_pooled, pool_idx, N, Cin, Cout, H, W, relu, 0, 0, 0, nullptr, nullptr, 0.f};
+    a.tile_list = tile_list;
+    a.n_active = n_active;
     return launch_wino43<0>(a, st3d::as_stream(stream));
 }
 

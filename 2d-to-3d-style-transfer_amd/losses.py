@@ -28,9 +28,9 @@ device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
 class _PerceptualFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, current, plan, style_weight, content_weight, batch_denom, need_mask=None):
+    def forward(ctx, current, plan, style_weight, content_weight, batch_denom, need_mask=None, flat_color=None):
         loss, grad = plan.loss(current, style_weight, content_weight, batch_denom=batch_denom,
-                               want_grad=current.requires_grad, need_mask=need_mask)
+                               want_grad=current.requires_grad, need_mask=need_mask, flat_color=flat_color)
         ctx.grad = grad
         ctx.parts = loss.clone()
         return loss[0].clone()
@@ -38,7 +38,7 @@ class _PerceptualFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         g = ctx.grad * grad_out if ctx.grad is not None else None
-        return g, None, None, None, None, None
+        return g, None, None, None, None, None, None
 
 
 #method for the second approach
@@ -63,8 +63,14 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
     # from the render, somebody watching the tensor's own gradient, ST3D_NEED_MASK=0 -- takes the full path.
     need = None if os.environ.get("ST3D_NEED_MASK", "1") == "0" else _render.need_of(current_imgs)
 
+    # A render also tags its colour tensor with its background colour (st3d.render.tag_flat): the shallow forward convs
+    # then compute the tiles that see anything but the flat field and copy the rest -- the same bits (the device compares the
+    # pixels, the tag only decides whether the lists are built; ST3D_FLAT=0 is read by the library).  Composites onto a
+    # style / noise background and pixels optimised directly carry no tag and take the full forward.
+    flat = _render.flat_of(current_imgs)
+
     # batch_denom: the batch the means divide by -- the GLOBAL batch when views are sharded over ranks
-    return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need)
+    return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need, flat)
 
 
 class _FusedLossFn(torch.autograd.Function):

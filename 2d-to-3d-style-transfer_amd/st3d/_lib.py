@@ -122,6 +122,14 @@ SIGNATURES = {
     "st3d_wino43_tile_geometry": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "st3d_wino43_dgrad_chain_tiles": (c_int, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_float, c_f32p, c_int, c_int, c_int, c_int,
                                               c_int, c_i32p, c_i32p, c_stream]),
+    "st3d_wino43_fwd_tiles": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                      c_i32p, c_i32p, c_stream]),
+    "st3d_flat_levels": (c_int, [c_int]),
+    "st3d_flat_tiles": (c_int, [c_int, c_int, c_int]),
+    "st3d_flat_workspace_bytes": (c_size, [c_int, c_int]),
+    "st3d_flat_build": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_i32p, c_i32p, c_i32p, c_i32p,
+                                c_i32p, c_i32p, c_i32p, c_stream]),
+    "st3d_flat_fill": (c_int, [c_i32p, c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_stream]),
     "st3d_need_levels": (c_int, [c_int]),
     "st3d_need_workspace_bytes": (c_size, [c_int, c_int]),
     "st3d_need_build": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, ctypes.c_void_p, c_size, c_i32p, c_i32p, c_i32p, c_stream]),
@@ -159,6 +167,8 @@ SIGNATURES = {
     "st3d_plan_set_style": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_stream]),
     "st3d_plan_loss": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_stream]),
     "st3d_plan_loss_masked": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_u8p, c_stream]),
+    "st3d_plan_loss_flat": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_u8p, c_f32p,
+                                    c_stream]),
     "st3d_plan_graph": (c_int, [ctypes.c_void_p, c_int]),
     "st3d_plan_backward": (c_int, [ctypes.c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_void_p), c_f32p, c_stream]),
     "st3d_comm_unique_id": (c_int, [ctypes.c_char_p]),

@@ -730,6 +730,44 @@ def wino43_dgrad_chain_tiles(gy, ud, Cin, tile_list, n_active, out, pool_idx=Non
     return out
 
 
+def wino43_fwd_tiles(x, uf, bias, Cout, tile_list, n_active, y=None, yp=None, idx=None, relu=True):
+    """wino43_fwd over the first n_active (device int32 scalar) tiles of tile_list (device int32), written in place into
+    whichever of y (N,Cout,H,W), yp and idx (N,Cout,H/2,W/2) are given; other tiles are left alone (st3d_wino43_fwd_tiles)."""
+    N, Cin, H, W = x.shape
+    call("st3d_wino43_fwd_tiles", dptr(x.contiguous(), F32), dptr(uf, F32), dptr(bias, F32), dptr(y, F32), dptr(yp, F32),
+         dptr(idx, U8), N, Cin, Cout, H, W, 1 if relu else 0, dptr(tile_list, I32), dptr(n_active, I32), stream_ptr())
+
+
+def flat_levels(S):
+    return _lib.load().st3d_flat_levels(int(S))
+
+
+def flat_build(imgs, color, levels=None):
+    """imgs (N,3,S,S), color (3,) device floats -> [(list, count, map)] for the forward launches of conv1_2, conv2_1 and
+    conv2_2 (st3d_flat_build).  Lists and maps are sized for every tile and start as -7; only the first `count` (device
+    int32 scalar) list entries are meaningful."""
+    N, _, S, _ = imgs.shape
+    lib = _lib.load()
+    levels = flat_levels(S) if levels is None else levels
+    nb = lib.st3d_flat_workspace_bytes(N, S)
+    ws = torch.empty((max(nb, 16),), dtype=U8, device=imgs.device)
+    counts = torch.full((3,), -7, dtype=I32, device=imgs.device)
+    lists = [torch.full((lib.st3d_flat_tiles(N, S, k),), -7, dtype=I32, device=imgs.device) for k in range(levels)]
+    maps = [torch.full_like(l, -7) for l in lists]
+    ptr = lambda seq, k: dptr(seq[k]) if k < len(seq) else None
+    call("st3d_flat_build", dptr(imgs, F32), dptr(color, F32), N, S, levels, dptr(ws), nb, ptr(lists, 0), ptr(maps, 0),
+         ptr(lists, 1), ptr(maps, 1), ptr(lists, 2), ptr(maps, 2), dptr(counts), stream_ptr())
+    return [(lists[k], counts[k], maps[k]) for k in range(levels)]
+
+
+def flat_fill(tile_map, y=None, yp=None, idx=None):
+    """Every tile with tile_map[t] >= 0 takes the block of tile tile_map[t], in place (st3d_flat_fill)."""
+    t = y if y is not None else yp
+    N, C = t.shape[:2]
+    H, W = (y.shape[2:] if y is not None else (2 * yp.shape[2], 2 * yp.shape[3]))
+    call("st3d_flat_fill", dptr(tile_map, I32), dptr(y, F32), dptr(yp, F32), dptr(idx, U8), N, C, H, W, stream_ptr())
+
+
 def maxpool2x2(y, want_idx=True):
     N, C, H, W = y.shape
     p = torch.empty((N, C, H // 2, W // 2), dtype=F32, device=y.device)

@@ -783,6 +783,27 @@ def need_of(t):
     return tag
 
 
+FLAT_TAG = "_st3d_flat"
+
+
+def tag_flat(rgb, background_color):
+    """Tag the colour tensor a render returns with the blend's background colour (3 floats): every pixel without a
+    fragment holds it, so a loss may compute the part of its forward that sees nothing else once and copy it
+    (losses.compute_perceptual_loss -> PerceptualPlan.loss(flat_color=...)).  A hint, never a premise: the device compares
+    the pixels themselves, a wrong tag costs the list build and changes no result.  Composites onto another background
+    (utils._composite) do not inherit it."""
+    setattr(rgb, FLAT_TAG, tuple(float(c) for c in background_color))
+    return rgb
+
+
+def flat_of(t):
+    """The background tag of `t` (3 floats) if it fits the tensor, else None."""
+    tag = getattr(t, FLAT_TAG, None)
+    if tag is None or t.dim() != 4 or t.shape[1] != 3 or len(tag) != 3:
+        return None
+    return tag
+
+
 def uses_hard_path(raster_settings, blend_params):
     """True for the reference's own configuration (K=1, blur 0, unclipped, default BlendParams): there
     softmax_rgb_blend reduces to texel-or-white and the specialised kernels apply."""
@@ -854,6 +875,7 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
                                     tex.faces_uvs_i32(), R, T, int(image_size), lighting)
         if rgb.requires_grad:
             tag_need(rgb, rgb.grad_fn.frag[0])
+        tag_flat(rgb, (1.0, 1.0, 1.0))           # (uses_hard_path: the default BlendParams, a white background)
         return rgb, mask
     bp = bp if bp is not None else BlendParams()
     rs = rs if rs is not None else RasterizationSettings(image_size=image_size)
@@ -863,6 +885,7 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
                                      rs.cull_backfaces, rs.perspective_correct, rs.z_clip, lighting)
     if rgb.requires_grad:
         tag_need(rgb, rgb.grad_fn.frag[0])
+    tag_flat(rgb, bp.background_color)
     if hard_settings:
         # the caller asked for the hard configuration and is handed what the hard path hands out: the 0/1 coverage mask
         # (alpha of a K = 1 / blur 0 blend is in [0.5, 1) on covered pixels; the reference thresholds it, utils.py:72)

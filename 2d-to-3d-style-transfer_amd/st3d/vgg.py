@@ -261,18 +261,38 @@ class PerceptualPlan:
             self.generation += 1
             self._style_key, self._style_ref = k, style
 
-    def loss(self, current, style_weight, content_weight, batch_denom=None, want_grad=True, need_mask=None):
+    def _color(self, rgb):
+        """The device copy of a background colour (one upload per colour and plan, not per step)."""
+        key = tuple(float(c) for c in rgb)
+        if len(key) != 3:
+            raise _lib.St3dError(f"flat_color must be 3 floats, got {rgb!r}")
+        cache = self.__dict__.setdefault("_colors", {})
+        if key not in cache:
+            if len(cache) > 64:
+                cache.clear()
+            cache[key] = torch.tensor(key, dtype=torch.float32, device=self.vgg.device)
+        return cache[key]
+
+    def loss(self, current, style_weight, content_weight, batch_denom=None, want_grad=True, need_mask=None, flat_color=None):
         """-> (loss_buf view [total, content, style], grad (n,3,S,S) or None).
         need_mask (n,S,S) uint8: the only pixels at which the caller's consumer reads grad (st3d_plan_loss_masked) -- grad
-        is the same there, bit for bit, and 0 elsewhere; the bottom of the VGG backward computes only what they need."""
+        is the same there, bit for bit, and 0 elsewhere; the bottom of the VGG backward computes only what they need.
+        flat_color (3 floats): `current` holds this colour at many pixels, as a render holds its background
+        (st3d_plan_loss_flat): the shallow forward convs compute the tiles that see anything else and copy the rest.  The
+        results are the same bits; the colour only decides whether the lists are built."""
         cur = current.detach().to(torch.float32).contiguous()
         n = cur.shape[0]
         grad = torch.empty_like(cur) if want_grad else None
         if need_mask is not None and want_grad:
             if need_mask.dtype != torch.uint8 or tuple(need_mask.shape) != (n, self.S, self.S):
                 raise _lib.St3dError(f"need_mask must be uint8 ({n},{self.S},{self.S}), got {need_mask.dtype} {tuple(need_mask.shape)}")
-            call("st3d_plan_loss_masked", self._h, dptr(cur), n, int(batch_denom or n), float(style_weight),
-                 float(content_weight), dptr(self.loss_buf), dptr(grad), dptr(need_mask.contiguous()), stream_ptr())
+            need_mask = need_mask.contiguous()
+        else:
+            need_mask = None
+        if need_mask is not None or flat_color is not None:
+            call("st3d_plan_loss_flat", self._h, dptr(cur), n, int(batch_denom or n), float(style_weight),
+                 float(content_weight), dptr(self.loss_buf), dptr(grad), dptr(need_mask),
+                 dptr(self._color(flat_color)) if flat_color is not None else None, stream_ptr())
             self.generation += 1
             return self.loss_buf, grad
         call("st3d_plan_loss", self._h, dptr(cur), n, int(batch_denom or n), float(style_weight), float(content_weight),
@@ -292,8 +312,9 @@ class PerceptualPlan:
 
     # conv_*: Winograd F(2x2,3x3) launches; conv43_*: Winograd F(4x4,3x3); convx_*: direct / vector-ALU kernels
     # *_need: launches that ran over a need list (loss(need_mask=...)): a fraction of the full launch's work
+    # conv43_fwd_flat / flat_fill: forward launches over a flat-field list (loss(flat_color=...)) and the copies behind them
     FAMILIES = ("conv_fwd", "conv_dgrad", "pool", "gram_fwd", "gram_bwd", "elementwise", "convx_fwd", "convx_dgrad", "conv43_fwd",
-                "conv43_dgrad", "conv43_dgrad_need", "convx_dgrad_need", "gram_bwd_need")
+                "conv43_dgrad", "conv43_dgrad_need", "convx_dgrad_need", "gram_bwd_need", "conv43_fwd_flat", "flat_fill")
 
     def profile_launches(self):
         """[(family, VGG module index, ms)] for every launch bracket since the last read (profiling on)."""

@@ -416,6 +416,31 @@ int st3d_need_levels(int S);
 size_t st3d_need_workspace_bytes(int N, int S);      /* one flag byte per tile of levels 2 and 3 */
 int st3d_need_build(const uint8_t *mask, int N, int S, int levels, uint8_t *seg, void *workspace, size_t workspace_bytes,
                     int *list1, int *list2, int *counts, st3d_stream_t stream);
+/* st3d_wino43_fwd over the first *n_active entries of tile_list only (as above): y, y_pooled and pool_idx of a listed tile
+ * are bitwise what st3d_wino43_fwd writes, nothing else is written. */
+int st3d_wino43_fwd_tiles(const float *x, const float *u_fwd, const float *bias, float *y, float *y_pooled, uint8_t *pool_idx,
+                          int N, int Cin, int Cout, int H, int W, int relu, const int *tile_list, const int *n_active,
+                          st3d_stream_t stream);
+/* Flat-field lists (csrc/flat.hip): a hard render holds its background colour bit for bit at most pixels, and a conv output
+ * tile whose input patch sees only the field that colour produces equals every other such tile of its border class.
+ * imgs (N,3,S,S; 16-byte aligned), color: 3 floats in DEVICE memory.  V0 = the pixel differs from color in any channel,
+ * compared as bits (NaN varies); conv1_1 maps V to dilate(V, 1), a Winograd conv to the aligned 4x4 output blocks that
+ * meet dilate(V, 1) (a block is rounded from its whole 6x6 patch), a 2x2 pool to the 2x2 OR; a tile is varying iff its input
+ * patch (tile +- 1, clipped) meets the V of its input.  Launches: 1 conv1_2 (S x S map), 2 conv2_1, 3 conv2_2 (S/2 x S/2),
+ * tiles numbered as st3d_wino43_tile_geometry.  list_k / counts[k-1]: the varying tiles plus, per class (min(ty,2),
+ * min(TY-1-ty,2), min(tx,2), min(TX-1-tx,2)) of non-varying tiles, its lowest-indexed member over the whole batch; ascending.
+ * map_k: per tile its class representative, -1 for listed tiles.  Lists and maps are sized st3d_flat_tiles(N, S, k - 1);
+ * everything stays in device memory.  levels = how many launches (1..st3d_flat_levels(S): 3, or 0 when S % 64 != 0).
+ * Ordered compaction, no atomics to global memory.
+ * st3d_flat_fill: every unlisted tile of y (N,C,H,W) / y_pooled / pool_idx (N,C,H/2,W/2; any may be NULL) takes its
+ * representative's block; listed tiles are not touched.  Runs behind the listed conv launch on the same stream. */
+int st3d_flat_levels(int S);
+int st3d_flat_tiles(int N, int S, int launch /*0..2*/);
+size_t st3d_flat_workspace_bytes(int N, int S);
+int st3d_flat_build(const float *imgs, const float *color, int N, int S, int levels, void *workspace, size_t workspace_bytes,
+                    int *list1, int *map1, int *list2, int *map2, int *list3, int *map3, int *counts, st3d_stream_t stream);
+int st3d_flat_fill(const int *tile_map, float *y, float *y_pooled, uint8_t *pool_idx, int N, int C, int H, int W,
+                   st3d_stream_t stream);
 /* MaxPool2d(2,2): y (N,C,H,W) -> p (N,C,H/2,W/2) (+ argmax idx, may be NULL) */
 int st3d_maxpool2x2_fwd(const float *y, float *p, uint8_t *idx, int N, int C, int H, int W,
                         st3d_stream_t stream);
@@ -575,6 +600,17 @@ int st3d_plan_loss(st3d_plan *plan, const float *current, int n, int batch_denom
 int st3d_plan_loss_masked(st3d_plan *plan, const float *current, int n, int batch_denom, float style_weight,
                           float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask,
                           st3d_stream_t stream);
+/* st3d_plan_loss_masked for a `current` that holds flat_color (3 floats in DEVICE memory; NULL = st3d_plan_loss_masked)
+ * at many pixels, as a render holds its background: the forward launches of conv1_2, conv2_1 and conv2_2 compute the tiles
+ * that see anything else plus one tile per border class of the rest, and the rest are copied (st3d_flat_build /
+ * st3d_wino43_fwd_tiles / st3d_flat_fill).  Every activation, the losses and the gradient are bitwise what the call without
+ * the colour gives: the device compares the pixels, the colour is a hint that costs the list build when it is wrong.
+ * ST3D_FLAT=0 (read by every call) ignores the colour; ST3D_FLAT_DEPTH = 0..3 (read by st3d_plan_create) lists only the
+ * first k of the three launches.  Sizes with S % 64 != 0 take the full path.  With graph replay the colour is staged and
+ * the lists are built inside the graph. */
+int st3d_plan_loss_flat(st3d_plan *plan, const float *current, int n, int batch_denom, float style_weight,
+                        float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask,
+                        const float *flat_color, st3d_stream_t stream);
 /* HIP-graph replay of st3d_plan_loss: its ~70 launches form a static sequence, so after one ordinary call it is captured
  * (per n / batch_denom / weights) and replayed with one hipGraphLaunch; inputs and outputs pass through plan-owned staging
  * buffers (three extra device copies per call).  Pays off where the step is launch-bound (small images). */
@@ -591,8 +627,9 @@ int st3d_plan_backward(st3d_plan *plan, int n, int upto_module, const float *con
  * 2 pool 3 gram_fwd 4 gram_bwd 5 loss/elementwise 6 convx_fwd (convs Winograd does not cover: conv1_1, odd shapes)
  * 7 convx_dgrad 8 conv43_fwd 9 conv43_dgrad (Winograd F(4x4,3x3)); launches that ran over a need list
  * (st3d_plan_loss_masked) count under families of their own, their work being a fraction of the full launch's:
- * 10 conv43_dgrad_need 11 convx_dgrad_need (the relu1_1 pass) 12 gram_bwd_need (none yet) */
-#define ST3D_PROFILE_FAMILIES 13
+ * 10 conv43_dgrad_need 11 convx_dgrad_need (the relu1_1 pass) 12 gram_bwd_need (none yet); likewise the forward launches
+ * over a flat-field list (st3d_plan_loss_flat) and the copies behind them: 13 conv43_fwd_flat 14 flat_fill */
+#define ST3D_PROFILE_FAMILIES 15
 int st3d_plan_profile(st3d_plan *plan, int enable);
 int st3d_plan_profile_read(st3d_plan *plan, float *ms_out /*host [ST3D_PROFILE_FAMILIES]*/,
                            int *launches_out /*host [ST3D_PROFILE_FAMILIES]*/);

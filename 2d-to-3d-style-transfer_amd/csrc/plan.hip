@@ -9,6 +9,7 @@
 #include <stdarg.h>
 #include <stdlib.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "common.h"
@@ -141,56 +142,87 @@ extern "C" int st3d_vgg_destroy(st3d_vgg *vgg) {
     return ST3D_OK;
 }
 
+// which kernel runs conv slot cs, per direction.  Every input is fixed when the plan is made -- the handle's switches, the
+// packs that exist, the layer's channels, the plan's H and W -- so st3d_plan_create fills the table once and every launch
+// site reads it; what a call adds is whether the arriving gradient is pooled or already gated
+enum : uint8_t { DIRECT, WINO, WINO43 };      // conv.hip, wino.hip F(2x2,3x3), wino43.hip F(4x4,3x3)
+struct Route {
+    uint8_t fwd = DIRECT;
+    bool dgrad_wino = false;    // the input gradient runs on wino.hip ...
+    bool dgrad_w43 = false;     // ... and on wino43.hip when its gradient arrives already gated (all F(4x4,3x3) takes)
+    // Producer-side ReLU gates (st3d_wino_dgrad_chain): whoever writes a gradient last zeroes it where its tensor's gate
+    // is closed, so the Winograd input gradient that consumes it streams one operand per stage
+    bool gate_taps = false;     // the style / content terms that join this conv's (unpooled) gradient gate it
+    bool gate_dst = false;      // this launch gates the gradient it writes: the launch below is a Winograd one too
+};
+
+struct GraphKey {               // what a captured loss step has baked in
+    int n = 0, denom = 0;
+    bool want_grad = false, masked = false, flat = false;
+    float sw = 0.f, cw = 0.f;
+    bool operator==(const GraphKey &o) const {
+        return n == o.n && denom == o.denom && want_grad == o.want_grad && masked == o.masked && flat == o.flat && sw == o.sw && cw == o.cw;
+    }
+};
+
 struct st3d_plan {
-    st3d_vgg *vgg;
-    int B, S;
+    st3d_vgg *vgg = nullptr;
+    int B = 0, S = 0;
+    std::vector<void *> owned;      // every device buffer of the plan (dev_alloc); the members below point into these
+    size_t bytes = 0;
     // per module: output activation (conv: post-ReLU; relu: alias of its conv; pool: pooled)
-    float *act[kModules];
-    int C[kModules], H[kModules], W[kModules];
-    uint8_t *pidx[5];
-    float *gbuf[2];
-    size_t gbuf_floats;
+    float *act[kModules] = {};
+    int C[kModules] = {}, H[kModules] = {}, W[kModules] = {};
+    uint8_t *pidx[5] = {};
+    float *gbuf[2] = {};
+    size_t gbuf_floats = 0;
+    Route route[16];
+    // relu1_1 style gradient + ReLU gate + conv1_1 input gradient in one pass (tap0.hip); its 27 tap planes go through the
+    // idle gradient buffer
+    bool fused_tap0 = false;
     // targets
-    float *content_target;   // (B, 512, S/8, S/8)
-    float *style_gram[5];     // (B or 1, C, C)
-    int style_batch;
-    bool have_content, have_style;
+    float *content_target = nullptr;   // (B, 512, S/8, S/8)
+    float *style_gram[5] = {};          // (B or 1, C, C)
+    int style_batch = 0;
+    bool have_content = false, have_style = false;
     // per-step scratch
-    float *gram[5], *D[5];
-    void *gram_ws;
-    size_t gram_ws_bytes;
-    float *partials;
-    size_t bytes;
-    int last_n;
+    float *gram[5] = {}, *D[5] = {};
+    float *gram_ws = nullptr;
+    size_t gram_ws_bytes = 0;
+    float *partials = nullptr;
+    int last_n = 0;
     // profiling
-    bool prof;
+    bool prof = false;
     struct Ev { int fam, module; hipEvent_t a, b; };
     std::vector<Ev> evs;
     std::vector<hipEvent_t> pool;
-    float fam_ms[ST3D_PROFILE_FAMILIES];
-    int fam_n[ST3D_PROFILE_FAMILIES];
+    float fam_ms[ST3D_PROFILE_FAMILIES] = {};
+    int fam_n[ST3D_PROFILE_FAMILIES] = {};
     std::vector<int> l_tag;        // per launch since the last read: family * 100 + VGG module index
     std::vector<float> l_ms;
-    // HIP-graph replay of the loss step (st3d_plan_graph): the launch sequence is static, so after one ordinary call it
-    // is captured once per (n, batch_denom, weights) and replayed; it works on plan-owned staging buffers because a
-    // captured kernel's pointers are baked in while the caller's tensors move
-    int use_graph;
-    hipGraphExec_t gexec;
-    hipStream_t cap_stream;
-    float *g_in, *g_grad, *g_loss;
-    uint8_t *g_mask;
-    struct { int n, denom, want_grad, warm, masked, flat; float sw, cw; } gkey;
-    // need lists of st3d_plan_loss_masked (need.hip), rebuilt by every masked call; nullptr where the size has none
-    int need_levels;           // levels that exist at this size, capped by ST3D_NEED_DEPTH
-    uint8_t *need_seg, *need_flags;
-    size_t need_flags_bytes;
-    int *need_list[2], *need_cnt;
-    // flat-field lists of st3d_plan_loss_flat (flat.hip), rebuilt by every call that brings a colour
-    int flat_levels;           // how many of conv1_2, conv2_1, conv2_2 may run listed: st3d_flat_levels, capped by ST3D_FLAT_DEPTH
-    uint8_t *flat_ws;
-    size_t flat_ws_bytes;
-    int *flat_list[3], *flat_map[3], *flat_cnt;
-    float *g_color;
+    // HIP-graph replay of the loss step (st3d_plan_graph): the launch sequence is static, so after one ordinary call
+    // (gwarm) it is captured once per key and replayed; it works on plan-owned staging buffers because a captured
+    // kernel's pointers are baked in while the caller's tensors move
+    int use_graph = 0;
+    hipGraphExec_t gexec = nullptr;
+    hipStream_t cap_stream = nullptr;
+    float *g_in = nullptr, *g_grad = nullptr, *g_loss = nullptr, *g_color = nullptr;
+    uint8_t *g_mask = nullptr;
+    GraphKey gkey;
+    bool gwarm = false;
+    // need lists of st3d_plan_loss_masked (need.hip), rebuilt by every masked call.  A launch may only be thinned out when
+    // every launch below it is, so the levels count from the bottom: 1 the relu1_1 pass, 2 + the conv1_2 input gradient,
+    // 3 + the conv2_1 input gradient -- as many as the size has, the routes allow and ST3D_NEED_DEPTH leaves
+    int need_levels = 0;
+    uint8_t *need_seg = nullptr, *need_flags = nullptr;
+    size_t need_flags_bytes = 0;
+    int *need_list[2] = {}, *need_cnt = nullptr;
+    // flat-field lists of st3d_plan_loss_flat (flat.hip), rebuilt by every call that brings a colour: how many of conv1_2,
+    // conv2_1, conv2_2 run listed -- as many as the size has, run F(4x4,3x3) and ST3D_FLAT_DEPTH leaves
+    int flat_levels = 0;
+    uint8_t *flat_ws = nullptr;
+    size_t flat_ws_bytes = 0;
+    int *flat_list[3] = {}, *flat_map[3] = {}, *flat_cnt = nullptr;
 };
 
 namespace {
@@ -202,6 +234,7 @@ int dev_alloc(st3d_plan *p, T **ptr, size_t count) {
         st3d::set_error("st3d_plan_create: hipMalloc(%zu bytes) failed", bytes);
         return ST3D_E_NOMEM;
     }
+    p->owned.push_back(*ptr);
     p->bytes += bytes;
     // ST3D_POISON_PLAN=1 (tests): the plan's buffers start as 0xFF.. (NaN / -1) instead of whatever hipMalloc returns, so a
     // launch that reads a buffer before the sequence has written it changes the result
@@ -239,94 +272,65 @@ enum { F_CONV_FWD = 0, F_CONV_DGRAD = 1, F_POOL = 2, F_GRAM_FWD = 3, F_GRAM_BWD 
        F_CONV43_FWD_FLAT = 13, F_FLAT_FILL = 14 };
 static_assert(F_FLAT_FILL + 1 == ST3D_PROFILE_FAMILIES, "profile families");
 
-// F(4x4,3x3) for this GEMM?  K = channels reduced over (Cin forward, Cout for the input gradient), M = channels produced
-bool use_wino43(const st3d_vgg *v, int cs, int K, int M, int H, int W) {
-    return v->use_wino && v->wino43_mink > 0 && v->u6f[cs] && K >= v->wino43_mink && st3d_wino43_supported(K, M, H, W);
-}
-
 // keep_full: also materialise the full-resolution output of convs whose 2x2 pool is fused into
 // their epilogue (needed only when a caller asks for that activation: st3d_plan_forward).
 // flat_color (device, 3 floats; the loss call only): imgs hold this colour at many pixels -- conv slots 1 .. 3 (conv1_2,
 // conv2_1, conv2_2) compute the tiles of their flat-field lists and copy the rest (flat.hip); the buffers end up bitwise
 // what the full launches write
 int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hipStream_t s, const float *flat_color = nullptr) {
-    const float *x = imgs;
-    int Cin = 3, H = p->S, W = p->S;
-    int flat = 0;               // conv slots 1 .. flat run listed (each decided from the predicate the loop dispatches on)
+    const st3d_vgg *v = p->vgg;
+    int flat = 0;               // conv slots 1 .. flat run listed
     if (flat_color) {
-        const st3d_vgg *v = p->vgg;
-        const int S = p->S;
-        const int HW[3] = {S, S / 2, S / 2};
-        for (int k = 0; k < p->flat_levels && kConvIdx[k + 1] <= upto; ++k) {
-            if (!(v->uf[k + 1] && st3d_wino_supported(kConvCin[k + 1], kConvCout[k + 1], HW[k], HW[k]) &&
-                  use_wino43(v, k + 1, kConvCin[k + 1], kConvCout[k + 1], HW[k], HW[k])))
-                break;
-            flat = k + 1;
-        }
+        while (flat < p->flat_levels && kConvIdx[flat + 1] <= upto) ++flat;
         if (flat > 0) {
             Scope sc(p, F_ELEM, s);
-            ST3D_TRY(st3d_flat_build(imgs, flat_color, n, S, flat, p->flat_ws, p->flat_ws_bytes, p->flat_list[0], p->flat_map[0],
+            ST3D_TRY(st3d_flat_build(imgs, flat_color, n, p->S, flat, p->flat_ws, p->flat_ws_bytes, p->flat_list[0], p->flat_map[0],
                                      p->flat_list[1], p->flat_map[1], p->flat_list[2], p->flat_map[2], p->flat_cnt, s));
         }
     }
+    const float *x = imgs;
     for (int m = 0; m <= upto; ++m) {
         const int cs = conv_slot(m), ps = pool_slot(m);
         if (cs >= 0) {
-            if (!p->vgg->set[cs]) {
+            if (!v->set[cs]) {
                 st3d::set_error("st3d_plan_forward: weights of module %d were never set", m);
                 return ST3D_E_STATE;
             }
-            const bool wino = p->vgg->use_wino && p->vgg->uf[cs] && st3d_wino_supported(Cin, kConvCout[cs], H, W);
-            const bool w43 = wino && use_wino43(p->vgg, cs, Cin, kConvCout[cs], H, W);
-            if (cs >= 1 && cs <= flat) {           // an F(4x4,3x3) launch over its flat-field list, then the copies
-                const int pool_m = m + 2;
-                const int pps = (pool_m <= upto) ? pool_slot(pool_m) : -1;
-                float *yfull = (pps < 0 || keep_full) ? p->act[m] : nullptr;
-                float *yp = pps >= 0 ? p->act[pool_m] : nullptr;
-                uint8_t *yi = pps >= 0 ? p->pidx[pps] : nullptr;
-                {
-                    Scope sc(p, F_CONV43_FWD_FLAT, s, m);
-                    ST3D_TRY(st3d_wino43_fwd_tiles(x, p->vgg->u6f[cs], p->vgg->bias[cs], yfull, yp, yi, n, Cin, kConvCout[cs], H, W, 1,
-                                                   p->flat_list[cs - 1], p->flat_cnt + (cs - 1), s));
-                }
-                {
-                    Scope sc(p, F_FLAT_FILL, s, m);
-                    ST3D_TRY(st3d_flat_fill(p->flat_map[cs - 1], yfull, yp, yi, n, kConvCout[cs], H, W, s));
-                }
-                Cin = kConvCout[cs];
-                x = pps >= 0 ? p->act[pool_m] : p->act[m];
-                if (pps >= 0) { H /= 2; W /= 2; m = pool_m; }
+            const int Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
+            const uint8_t route = p->route[cs].fwd;
+            if (route == DIRECT) {
+                Scope sc(p, F_CONVX_FWD, s, m);
+                ST3D_TRY(st3d_conv3x3_fwd(x, v->wf[cs], v->bias[cs], p->act[m], n, Cin, Cout, H, W, 1, s));
+                x = p->act[m];
                 continue;
             }
-            Scope sc(p, w43 ? F_CONV43_FWD : (wino ? F_CONV_FWD : F_CONVX_FWD), s, m);
-            if (wino) {
-                const int pool_m = m + 2;          // conv, relu, pool
-                const int pps = (pool_m <= upto) ? pool_slot(pool_m) : -1;
-                float *yfull = (pps < 0 || keep_full) ? p->act[m] : nullptr;
-                if (w43)
-                    ST3D_TRY(st3d_wino43_fwd(x, p->vgg->u6f[cs], p->vgg->bias[cs], yfull, pps >= 0 ? p->act[pool_m] : nullptr,
-                                             pps >= 0 ? p->pidx[pps] : nullptr, n, Cin, kConvCout[cs], H, W, 1, s));
-                else
-                ST3D_TRY(st3d_wino_fwd(x, p->vgg->uf[cs], p->vgg->bias[cs], yfull, pps >= 0 ? p->act[pool_m] : nullptr,
-                                       pps >= 0 ? p->pidx[pps] : nullptr, n, Cin, kConvCout[cs], H, W, 1, s));
-                Cin = kConvCout[cs];
-                if (pps >= 0) {                     // pool output produced by the conv epilogue: skip modules m+1, m+2
-                    x = p->act[pool_m];
-                    H /= 2; W /= 2;
-                    m = pool_m;
-                } else {
-                    x = p->act[m];
+            // the Winograd kernels pool in their epilogue: conv, relu and the pool behind them are one launch
+            const int pool_m = m + 2;
+            const int pps = (pool_m <= upto) ? pool_slot(pool_m) : -1;
+            float *yfull = (pps < 0 || keep_full) ? p->act[m] : nullptr;
+            float *yp = pps >= 0 ? p->act[pool_m] : nullptr;
+            uint8_t *yi = pps >= 0 ? p->pidx[pps] : nullptr;
+            if (cs >= 1 && cs <= flat) {           // an F(4x4,3x3) launch over its flat-field list, then the copies
+                {
+                    Scope sc(p, F_CONV43_FWD_FLAT, s, m);
+                    ST3D_TRY(st3d_wino43_fwd_tiles(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->flat_list[cs - 1],
+                                                   p->flat_cnt + (cs - 1), s));
                 }
+                Scope sc(p, F_FLAT_FILL, s, m);
+                ST3D_TRY(st3d_flat_fill(p->flat_map[cs - 1], yfull, yp, yi, n, Cout, H, W, s));
+            } else if (route == WINO43) {
+                Scope sc(p, F_CONV43_FWD, s, m);
+                ST3D_TRY(st3d_wino43_fwd(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
             } else {
-                ST3D_TRY(st3d_conv3x3_fwd(x, p->vgg->wf[cs], p->vgg->bias[cs], p->act[m], n, Cin, kConvCout[cs], H, W, 1, s));
-                x = p->act[m];
-                Cin = kConvCout[cs];
+                Scope sc(p, F_CONV_FWD, s, m);
+                ST3D_TRY(st3d_wino_fwd(x, v->uf[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
             }
-        } else if (ps >= 0) {
+            x = pps >= 0 ? yp : p->act[m];
+            if (pps >= 0) m = pool_m;               // modules m+1, m+2 are done
+        } else if (ps >= 0) {                       // (the ReLU before it kept its conv's C, H, W)
             Scope sc(p, F_POOL, s, m);
-            ST3D_TRY(st3d_maxpool2x2_fwd(x, p->act[m], p->pidx[ps], n, Cin, H, W, s));
+            ST3D_TRY(st3d_maxpool2x2_fwd(x, p->act[m], p->pidx[ps], n, p->C[m], p->H[m - 1], p->W[m - 1], s));
             x = p->act[m];
-            H /= 2; W /= 2;
         }   // ReLU modules are fused into their conv
     }
     p->last_n = n;
@@ -361,60 +365,49 @@ __global__ __launch_bounds__(256) void unpool_add_kernel(const float *__restrict
     }
 }
 
-bool dgrad_is_wino(const st3d_plan *p, int cs) {
-    const int m = kConvIdx[cs];
-    return p->vgg->use_wino && p->vgg->ud[cs] && st3d_wino_supported(kConvCout[cs], kConvCin[cs], p->H[m], p->W[m]);
-}
+// what the loss plan's chain adds to a plain input-gradient launch
+struct DgradOpts {
+    bool pregated = false;              // g is already zero where the gate this launch would apply is closed
+    const float *out_gate = nullptr;    // zero dst where this tensor is <= 0 (the next link's gate, Winograd only)
+    const float *add_target = nullptr;  // dst += add_coef * (out_gate - add_target): the content term, joining in the store
+    float add_coef = 0.f;
+    // compute the listed output tiles only (F(4x4,3x3) launches; anything else is an error, not a silent full launch: the
+    // caller has already skipped the work above on the strength of it)
+    const int *tile_list = nullptr, *n_active = nullptr;
+};
 
 // one input-gradient launch of conv slot cs: g (gradient w.r.t. the conv's post-ReLU output, or w.r.t. the output of
-// the pool behind it when pooled) -> dst (gradient w.r.t. the conv's input).  pregated: g is already zero where the gate
-// this launch would apply is closed; out_gate: zero dst where this tensor is <= 0 (the next link's gate, Winograd only)
-// tile_list / n_active: compute the listed output tiles only (F(4x4,3x3) launches; anything else is an error, not a
-// silent full launch: the caller has already skipped the work above on the strength of it)
+// the pool behind it when pooled) -> dst (gradient w.r.t. the conv's input)
 int dgrad_step(st3d_plan *p, int cs, const float *g, bool g_is_pooled, int pool_of_g, float *dst, int n, hipStream_t s,
-               bool pregated = false, const float *out_gate = nullptr, const float *add_target = nullptr, float add_coef = 0.f,
-               const int *tile_list = nullptr, const int *n_active = nullptr) {
+               const DgradOpts &o = {}) {
+    const st3d_vgg *v = p->vgg;
     const int m = kConvIdx[cs];
-    const int H = p->H[m], W = p->W[m];
-    const bool wino = dgrad_is_wino(p, cs);
-    // F(4x4,3x3) takes an already gated gradient only (what the producer-gated chain hands on)
-    const bool w43 = wino && pregated && use_wino43(p->vgg, cs, kConvCout[cs], kConvCin[cs], H, W);
-    if (tile_list && !w43) {
+    const int Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
+    const bool wino = p->route[cs].dgrad_wino;
+    const bool w43 = p->route[cs].dgrad_w43 && o.pregated;
+    if (o.tile_list && !w43) {
         st3d::set_error("st3d_plan_loss_masked: the input gradient of module %d is not an F(4x4,3x3) launch", m);
         return ST3D_E_STATE;
     }
-    Scope sc(p, tile_list ? F_CONV43_DGRAD_NEED : w43 ? F_CONV43_DGRAD : (wino ? F_CONV_DGRAD : F_CONVX_DGRAD), s, m);
-    if (tile_list) {
-        ST3D_TRY(st3d_wino43_dgrad_chain_tiles(g, g_is_pooled ? p->pidx[pool_of_g] : nullptr, p->vgg->u6d[cs], out_gate, add_target,
-                                               add_coef, dst, n, kConvCin[cs], kConvCout[cs], H, W, tile_list, n_active, s));
-        return ST3D_OK;
-    }
-    if (w43) {
-        ST3D_TRY(st3d_wino43_dgrad_chain(g, g_is_pooled ? p->pidx[pool_of_g] : nullptr, p->vgg->u6d[cs], out_gate, add_target,
-                                         add_coef, dst, n, kConvCin[cs], kConvCout[cs], H, W, s));
-        return ST3D_OK;
-    }
-    if (wino && (pregated || out_gate)) {
-        const uint8_t *pidx = g_is_pooled ? p->pidx[pool_of_g] : nullptr;
-        const float *pooled = (g_is_pooled && !pregated) ? p->act[kPoolIdx[pool_of_g]] : nullptr;
-        const float *act = (!g_is_pooled && !pregated) ? p->act[m] : nullptr;
-        ST3D_TRY(st3d_wino_dgrad_chain(g, act, pidx, pooled, p->vgg->ud[cs], out_gate, add_target, add_coef, dst, n,
-                                       kConvCin[cs], kConvCout[cs], H, W, s));
-        return ST3D_OK;
-    }
-    if (g_is_pooled) {
-        if (wino)
-            ST3D_TRY(st3d_wino_dgrad_unpool(g, p->pidx[pool_of_g], p->act[kPoolIdx[pool_of_g]], p->vgg->ud[cs], dst, n,
-                                            kConvCin[cs], kConvCout[cs], H, W, s));
-        else
-            ST3D_TRY(st3d_conv3x3_dgrad_unpool(g, p->pidx[pool_of_g], p->act[kPoolIdx[pool_of_g]], p->vgg->wd[cs], dst, n,
-                                               kConvCin[cs], kConvCout[cs], H, W, s));
-    } else {
-        if (wino)
-            ST3D_TRY(st3d_wino_dgrad(g, p->act[m], p->vgg->ud[cs], dst, n, kConvCin[cs], kConvCout[cs], H, W, s));
-        else
-            ST3D_TRY(st3d_conv3x3_dgrad(g, p->act[m], p->vgg->wd[cs], dst, n, kConvCin[cs], kConvCout[cs], H, W, s));
-    }
+    Scope sc(p, o.tile_list ? F_CONV43_DGRAD_NEED : w43 ? F_CONV43_DGRAD : (wino ? F_CONV_DGRAD : F_CONVX_DGRAD), s, m);
+    const uint8_t *pidx = g_is_pooled ? p->pidx[pool_of_g] : nullptr;
+    const float *pooled = g_is_pooled ? p->act[kPoolIdx[pool_of_g]] : nullptr;
+    if (o.tile_list)
+        ST3D_TRY(st3d_wino43_dgrad_chain_tiles(g, pidx, v->u6d[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W,
+                                               o.tile_list, o.n_active, s));
+    else if (w43)
+        ST3D_TRY(st3d_wino43_dgrad_chain(g, pidx, v->u6d[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W, s));
+    else if (wino && (o.pregated || o.out_gate))
+        ST3D_TRY(st3d_wino_dgrad_chain(g, (g_is_pooled || o.pregated) ? nullptr : p->act[m], pidx, o.pregated ? nullptr : pooled,
+                                       v->ud[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W, s));
+    else if (g_is_pooled && wino)
+        ST3D_TRY(st3d_wino_dgrad_unpool(g, pidx, pooled, v->ud[cs], dst, n, Cin, Cout, H, W, s));
+    else if (g_is_pooled)
+        ST3D_TRY(st3d_conv3x3_dgrad_unpool(g, pidx, pooled, v->wd[cs], dst, n, Cin, Cout, H, W, s));
+    else if (wino)
+        ST3D_TRY(st3d_wino_dgrad(g, p->act[m], v->ud[cs], dst, n, Cin, Cout, H, W, s));
+    else
+        ST3D_TRY(st3d_conv3x3_dgrad(g, p->act[m], v->wd[cs], dst, n, Cin, Cout, H, W, s));
     return ST3D_OK;
 }
 
@@ -424,88 +417,98 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     ST3D_CHECK_ARG(out && vgg);
     ST3D_CHECK_ARG(B > 0 && S >= 16);      // any size: shapes the Winograd kernels do not cover (odd H, W % 4) run on the direct ones, pools floor like MaxPool2d
     st3d_plan *p = new st3d_plan();
-    p->vgg = vgg; p->B = B; p->S = S; p->bytes = 0;
-    for (int m = 0; m < kModules; ++m) { p->act[m] = nullptr; p->C[m] = p->H[m] = p->W[m] = 0; }
-    for (int i = 0; i < 5; ++i) { p->pidx[i] = nullptr; p->style_gram[i] = p->gram[i] = p->D[i] = nullptr; }
-    p->gbuf[0] = p->gbuf[1] = nullptr; p->content_target = nullptr; p->gram_ws = nullptr; p->partials = nullptr;
-    p->have_content = p->have_style = false; p->style_batch = 0; p->last_n = 0; p->prof = false;
-    p->use_graph = 0; p->gexec = nullptr; p->cap_stream = nullptr; p->g_in = p->g_grad = p->g_loss = nullptr; memset(&p->gkey, 0, sizeof(p->gkey));
-    p->flat_levels = 0; p->flat_ws = nullptr; p->flat_ws_bytes = 0; p->flat_cnt = nullptr; p->g_color = nullptr;
-    for (int k = 0; k < 3; ++k) p->flat_list[k] = p->flat_map[k] = nullptr;
-    p->g_mask = nullptr; p->need_levels = 0; p->need_seg = p->need_flags = nullptr; p->need_flags_bytes = 0; p->need_list[0] = p->need_list[1] = nullptr; p->need_cnt = nullptr;
-    memset(p->fam_ms, 0, sizeof(p->fam_ms)); memset(p->fam_n, 0, sizeof(p->fam_n));
+    p->vgg = vgg; p->B = B; p->S = S;
     int rc = ST3D_OK;
-    int C = 3, H = S, W = S;
+    auto alloc = [&](auto **ptr, size_t count) { if (rc == ST3D_OK) rc = dev_alloc(p, ptr, count); };
     size_t gmax = 0, wsmax = 0;
-    for (int m = 0; m < kModules && rc == ST3D_OK; ++m) {
+    for (int m = 0, C = 3, H = S, W = S; m < kModules; ++m) {
         const int cs = conv_slot(m), ps = pool_slot(m);
         if (cs >= 0) {
             C = kConvCout[cs];
-            rc = dev_alloc(p, &p->act[m], (size_t)B * C * H * W);
+            alloc(&p->act[m], (size_t)B * C * H * W);
             if ((size_t)B * C * H * W > gmax) gmax = (size_t)B * C * H * W;
         } else if (ps >= 0) {
             H /= 2; W /= 2;
-            rc = dev_alloc(p, &p->act[m], (size_t)B * C * H * W);
-            if (rc == ST3D_OK) rc = dev_alloc(p, &p->pidx[ps], (size_t)B * C * H * W);
+            alloc(&p->act[m], (size_t)B * C * H * W);
+            alloc(&p->pidx[ps], (size_t)B * C * H * W);
         } else {
             p->act[m] = p->act[m - 1];   // in-place ReLU: the tap tensor IS the post-ReLU output
         }
         p->C[m] = C; p->H[m] = H; p->W[m] = W;
     }
     p->gbuf_floats = gmax;
-    for (int i = 0; i < 2 && rc == ST3D_OK; ++i) rc = dev_alloc(p, &p->gbuf[i], gmax);
-    if (rc == ST3D_OK) rc = dev_alloc(p, &p->content_target, (size_t)B * p->C[kContentTap] * p->H[kContentTap] * p->W[kContentTap]);
-    for (int i = 0; i < 5 && rc == ST3D_OK; ++i) {
+    // ---- the route table and what follows from it: the one place that reads the handle's switches and asks the kernels
+    // what they cover
+    const st3d_vgg *v = vgg;
+    for (int cs = 0; cs < 16 && v->use_wino; ++cs) {
+        const int m = kConvIdx[cs], Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
+        // F(4x4,3x3) for a GEMM that reduces over K channels (Cin forward, Cout for the input gradient) and produces M
+        auto w43 = [&](int K, int M) { return v->wino43_mink > 0 && v->u6f[cs] && K >= v->wino43_mink && st3d_wino43_supported(K, M, H, W); };
+        Route &r = p->route[cs];
+        if (v->uf[cs] && st3d_wino_supported(Cin, Cout, H, W)) r.fwd = w43(Cin, Cout) ? WINO43 : WINO;
+        r.dgrad_wino = v->ud[cs] && st3d_wino_supported(Cout, Cin, H, W);
+        r.dgrad_w43 = r.dgrad_wino && w43(Cout, Cin);
+        r.gate_taps = v->pregate && r.dgrad_wino && (Cout % 32) == 0;       // (what the gated tap kernels take)
+        r.gate_dst = v->pregate && cs > 0 && r.dgrad_wino && p->route[cs - 1].dgrad_wino;
+    }
+    p->fused_tap0 = v->fuse_tap0 && st3d_conv1_bwd_supported(S, S) && gmax >= (size_t)B * 27 * S * S;
+    // ST3D_NEED_DEPTH=k / ST3D_FLAT_DEPTH=k: at most k levels (A/B runs; the default is all of them: each measured to pay,
+    // DESIGN.md 6)
+    auto capped = [](int levels, const char *name) {
+        const char *e = getenv(name);
+        return (e && atoi(e) >= 0 && atoi(e) < levels) ? atoi(e) : levels;
+    };
+    // a listed conv1_2 / conv2_1 input gradient is an F(4x4,3x3) launch, so its gradient has to arrive gated
+    int need_ok = p->fused_tap0 ? 1 : 0;
+    if (need_ok == 1 && p->route[2].gate_dst && p->route[1].dgrad_w43) need_ok = 2;
+    if (need_ok == 2 && p->route[2].dgrad_w43) need_ok = 3;
+    p->need_levels = capped(std::min(need_ok, st3d_need_levels(S)), "ST3D_NEED_DEPTH");
+    int flat_ok = 0;
+    while (flat_ok < 3 && p->route[flat_ok + 1].fwd == WINO43) ++flat_ok;
+    p->flat_levels = capped(std::min(flat_ok, st3d_flat_levels(S)), "ST3D_FLAT_DEPTH");
+    for (int i = 0; i < 2; ++i) alloc(&p->gbuf[i], gmax);
+    alloc(&p->content_target, (size_t)B * p->C[kContentTap] * p->H[kContentTap] * p->W[kContentTap]);
+    for (int i = 0; i < 5; ++i) {
         const int m = kStyleTap[i];
         const size_t cc = (size_t)B * p->C[m] * p->C[m];
-        rc = dev_alloc(p, &p->style_gram[i], cc);
-        if (rc == ST3D_OK) rc = dev_alloc(p, &p->gram[i], cc);
-        if (rc == ST3D_OK) rc = dev_alloc(p, &p->D[i], cc);
+        alloc(&p->style_gram[i], cc);
+        alloc(&p->gram[i], cc);
+        alloc(&p->D[i], cc);
     }
     // every style layer has its own split-K slab region: the five Grams of a step run as ONE launch (st3d_gram_fwd_multi).
     // Sized for the worst batch 1..B (the split count is rounded per batch size, so n < B can need a little more than B).
-    for (int n = 1; n <= B && rc == ST3D_OK; ++n) {
+    for (int n = 1; n <= B; ++n) {
         st3d_gram_item items[5];
         for (int i = 0; i < 5; ++i) items[i] = st3d_gram_item{nullptr, nullptr, n, p->C[kStyleTap[i]], p->H[kStyleTap[i]] * p->W[kStyleTap[i]]};
         const size_t ws = st3d_gram_multi_workspace_bytes(items, 5);
         if (ws > wsmax) wsmax = ws;
     }
     p->gram_ws_bytes = wsmax;
-    if (rc == ST3D_OK) { float *t = nullptr; rc = dev_alloc(p, &t, wsmax / sizeof(float)); p->gram_ws = t; }
-    if (rc == ST3D_OK) rc = dev_alloc(p, &p->partials, (size_t)8 * st3d_reduce_partials());
-    if (rc == ST3D_OK) rc = dev_alloc(p, &p->g_in, (size_t)B * 3 * S * S);
-    if (rc == ST3D_OK) rc = dev_alloc(p, &p->g_grad, (size_t)B * 3 * S * S);
-    if (rc == ST3D_OK) rc = dev_alloc(p, &p->g_loss, (size_t)4);
-    // ST3D_NEED_DEPTH=k: how many of the bottom launches a need mask may thin out (0 none, 1 the relu1_1 pass, 2 + the
-    // conv1_2 input gradient, 3 + the conv2_1 input gradient = the default: each level measured to pay)
-    const char *nd = getenv("ST3D_NEED_DEPTH");
-    p->need_levels = st3d_need_levels(S);
-    if (nd && atoi(nd) >= 0 && atoi(nd) < p->need_levels) p->need_levels = atoi(nd);
-    if (p->need_levels >= 1 && rc == ST3D_OK) {
-        rc = dev_alloc(p, &p->g_mask, (size_t)B * S * S);
-        if (rc == ST3D_OK) rc = dev_alloc(p, &p->need_seg, (size_t)B * S * (S / 64));
-        if (rc == ST3D_OK) rc = dev_alloc(p, &p->need_cnt, (size_t)2);
+    alloc(&p->gram_ws, wsmax / sizeof(float));
+    alloc(&p->partials, (size_t)8 * st3d_reduce_partials());
+    alloc(&p->g_in, (size_t)B * 3 * S * S);
+    alloc(&p->g_grad, (size_t)B * 3 * S * S);
+    alloc(&p->g_loss, (size_t)4);
+    if (p->need_levels >= 1) {
+        alloc(&p->g_mask, (size_t)B * S * S);
+        alloc(&p->need_seg, (size_t)B * S * (S / 64));
+        alloc(&p->need_cnt, (size_t)2);
         p->need_flags_bytes = st3d_need_workspace_bytes(B, S);
-        if (rc == ST3D_OK && p->need_levels >= 2) rc = dev_alloc(p, &p->need_flags, p->need_flags_bytes);
-        for (int l = 0; l < 2 && l + 2 <= p->need_levels && rc == ST3D_OK; ++l) {
+        if (p->need_levels >= 2) alloc(&p->need_flags, p->need_flags_bytes);
+        for (int l = 0; l + 2 <= p->need_levels; ++l) {
             int rows = 0, cols = 0;
             st3d_wino43_tile_geometry(S >> l, S >> l, &rows, &cols);
-            rc = dev_alloc(p, &p->need_list[l], (size_t)B * ((S >> l) / rows) * ((S >> l) / cols));
+            alloc(&p->need_list[l], (size_t)B * ((S >> l) / rows) * ((S >> l) / cols));
         }
     }
-    // ST3D_FLAT_DEPTH=k: how many of the shallow forward launches may run over a flat-field list (0 none, 1 conv1_2, 2 +
-    // conv2_1, 3 + conv2_2 = the default)
-    const char *fd = getenv("ST3D_FLAT_DEPTH");
-    p->flat_levels = st3d_flat_levels(S);
-    if (fd && atoi(fd) >= 0 && atoi(fd) < p->flat_levels) p->flat_levels = atoi(fd);
-    if (p->flat_levels >= 1 && rc == ST3D_OK) {
+    if (p->flat_levels >= 1) {
         p->flat_ws_bytes = st3d_flat_workspace_bytes(B, S);
-        rc = dev_alloc(p, &p->flat_ws, p->flat_ws_bytes);
-        if (rc == ST3D_OK) rc = dev_alloc(p, &p->flat_cnt, (size_t)4);
-        if (rc == ST3D_OK) rc = dev_alloc(p, &p->g_color, (size_t)4);
-        for (int k = 0; k < p->flat_levels && rc == ST3D_OK; ++k) {
-            rc = dev_alloc(p, &p->flat_list[k], (size_t)st3d_flat_tiles(B, S, k));
-            if (rc == ST3D_OK) rc = dev_alloc(p, &p->flat_map[k], (size_t)st3d_flat_tiles(B, S, k));
+        alloc(&p->flat_ws, p->flat_ws_bytes);
+        alloc(&p->flat_cnt, (size_t)4);
+        alloc(&p->g_color, (size_t)4);
+        for (int k = 0; k < p->flat_levels; ++k) {
+            alloc(&p->flat_list[k], (size_t)st3d_flat_tiles(B, S, k));
+            alloc(&p->flat_map[k], (size_t)st3d_flat_tiles(B, S, k));
         }
     }
     if (rc != ST3D_OK) { st3d_plan_destroy(p); return rc; }
@@ -515,35 +518,7 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
 
 extern "C" int st3d_plan_destroy(st3d_plan *p) {
     if (!p) return ST3D_OK;
-    for (int m = 0; m < kModules; ++m)
-        if (p->act[m] && (m == 0 || p->act[m] != p->act[m - 1])) (void)hipFree(p->act[m]);
-    for (int i = 0; i < 5; ++i) {
-        if (p->pidx[i]) (void)hipFree(p->pidx[i]);
-        if (p->style_gram[i]) (void)hipFree(p->style_gram[i]);
-        if (p->gram[i]) (void)hipFree(p->gram[i]);
-        if (p->D[i]) (void)hipFree(p->D[i]);
-    }
-    for (int i = 0; i < 2; ++i)
-        if (p->gbuf[i]) (void)hipFree(p->gbuf[i]);
-    if (p->content_target) (void)hipFree(p->content_target);
-    if (p->gram_ws) (void)hipFree(p->gram_ws);
-    if (p->partials) (void)hipFree(p->partials);
-    if (p->g_in) (void)hipFree(p->g_in);
-    if (p->g_grad) (void)hipFree(p->g_grad);
-    if (p->g_loss) (void)hipFree(p->g_loss);
-    if (p->g_mask) (void)hipFree(p->g_mask);
-    if (p->need_seg) (void)hipFree(p->need_seg);
-    if (p->need_flags) (void)hipFree(p->need_flags);
-    if (p->need_cnt) (void)hipFree(p->need_cnt);
-    for (int l = 0; l < 2; ++l)
-        if (p->need_list[l]) (void)hipFree(p->need_list[l]);
-    if (p->flat_ws) (void)hipFree(p->flat_ws);
-    if (p->flat_cnt) (void)hipFree(p->flat_cnt);
-    if (p->g_color) (void)hipFree(p->g_color);
-    for (int k = 0; k < 3; ++k) {
-        if (p->flat_list[k]) (void)hipFree(p->flat_list[k]);
-        if (p->flat_map[k]) (void)hipFree(p->flat_map[k]);
-    }
+    for (void *b : p->owned) (void)hipFree(b);
     if (p->gexec) (void)hipGraphExecDestroy(p->gexec);
     if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
     for (auto &e : p->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
@@ -620,7 +595,7 @@ extern "C" int st3d_plan_set_style(st3d_plan *p, const float *style, int style_b
         ST3D_TRY(grams_of_taps(p, style_batch, p->style_gram, s));
     }
     if (p->style_batch != style_batch && p->gexec) {       // a captured loss step indexes the style Grams with the old batch stride
-        (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; p->gkey.warm = 0;
+        (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; p->gwarm = false;
     }
     p->style_batch = style_batch;
     p->have_style = true;
@@ -634,7 +609,7 @@ extern "C" int st3d_plan_graph(st3d_plan *p, int enable) {
     ST3D_CHECK_ARG(p);
     p->use_graph = enable ? 1 : 0;
     if (!enable && p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
-    p->gkey.warm = 0;
+    p->gwarm = false;
     return ST3D_OK;
 }
 
@@ -671,17 +646,13 @@ extern "C" int st3d_plan_loss_flat(st3d_plan *p, const float *current, int n, in
 
     // ---- graph replay
     const size_t img = (size_t)n * 3 * p->S * p->S;
-    const int want_grad = grad_current ? 1 : 0, masked = need_mask ? 1 : 0, flat = flat_color ? 1 : 0;
-    const bool same = p->gexec && p->gkey.n == n && p->gkey.denom == batch_denom && p->gkey.want_grad == want_grad &&
-                      p->gkey.masked == masked && p->gkey.flat == flat && p->gkey.sw == style_weight && p->gkey.cw == content_weight;
-    if (!same) {
+    const GraphKey key{n, batch_denom, grad_current != nullptr, need_mask != nullptr, flat_color != nullptr, style_weight, content_weight};
+    if (!(p->gexec && key == p->gkey)) {
         if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
-        const bool warm = p->gkey.warm && p->gkey.n == n && p->gkey.denom == batch_denom && p->gkey.want_grad == want_grad &&
-                          p->gkey.masked == masked && p->gkey.flat == flat && p->gkey.sw == style_weight && p->gkey.cw == content_weight;
-        p->gkey.n = n; p->gkey.denom = batch_denom; p->gkey.want_grad = want_grad; p->gkey.masked = masked; p->gkey.flat = flat;
-        p->gkey.sw = style_weight; p->gkey.cw = content_weight;
+        const bool warm = p->gwarm && key == p->gkey;
+        p->gkey = key;
         if (!warm) {            // first call with these parameters: run it plainly (loads every code object, nothing to capture yet)
-            p->gkey.warm = 1;
+            p->gwarm = true;
             return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, flat_color, s);
         }
         hipGraph_t graph = nullptr;
@@ -689,8 +660,8 @@ extern "C" int st3d_plan_loss_flat(st3d_plan *p, const float *current, int n, in
         if (!p->cap_stream) ST3D_HIP(hipStreamCreateWithFlags(&p->cap_stream, hipStreamNonBlocking));
         ST3D_HIP(hipStreamBeginCapture(p->cap_stream, hipStreamCaptureModeThreadLocal));
         const int rc = plan_loss_enqueue(p, p->g_in, n, batch_denom, style_weight, content_weight, p->g_loss,
-                                         want_grad ? p->g_grad : nullptr, masked ? p->g_mask : nullptr, flat ? p->g_color : nullptr,
-                                         p->cap_stream);
+                                         key.want_grad ? p->g_grad : nullptr, key.masked ? p->g_mask : nullptr,
+                                         key.flat ? p->g_color : nullptr, p->cap_stream);
         const hipError_t e = hipStreamEndCapture(p->cap_stream, &graph);
         if (rc != ST3D_OK || e != hipSuccess || !graph) {
             if (graph) (void)hipGraphDestroy(graph);
@@ -702,8 +673,8 @@ extern "C" int st3d_plan_loss_flat(st3d_plan *p, const float *current, int n, in
         if (ei != hipSuccess) { p->gexec = nullptr; st3d::set_error("st3d_plan_loss: hipGraphInstantiate: %s", hipGetErrorString(ei)); return ST3D_E_HIP; }
     }
     ST3D_HIP(hipMemcpyAsync(p->g_in, current, img * sizeof(float), hipMemcpyDeviceToDevice, s));
-    if (masked) ST3D_HIP(hipMemcpyAsync(p->g_mask, need_mask, (size_t)n * p->S * p->S, hipMemcpyDeviceToDevice, s));
-    if (flat) ST3D_HIP(hipMemcpyAsync(p->g_color, flat_color, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (key.masked) ST3D_HIP(hipMemcpyAsync(p->g_mask, need_mask, (size_t)n * p->S * p->S, hipMemcpyDeviceToDevice, s));
+    if (key.flat) ST3D_HIP(hipMemcpyAsync(p->g_color, flat_color, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     ST3D_HIP(hipGraphLaunch(p->gexec, s));
     ST3D_HIP(hipMemcpyAsync(loss_out, p->g_loss, 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (grad_current) ST3D_HIP(hipMemcpyAsync(grad_current, p->g_grad, img * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -750,23 +721,12 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
     st3d_trace_pop();                                  // (gram_and_losses ends here; its guard pops "vgg_backward" below)
     st3d_trace_push("vgg_backward");
 
-    // ---- what the consumer of the image gradient needs (need.hip): with a mask, the bottom launches walk these lists.
-    // A launch may only be thinned out when every launch below it is -- each level is decided here, before the first launch,
-    // from the same predicates the loop below dispatches on
-    int need = 0;
-    if (need_mask) {
-        const int S = p->S;
-        const st3d_vgg *v = p->vgg;
-        need = p->need_levels;
-        if (!(v->fuse_tap0 && st3d_conv1_bwd_supported(S, S) && p->gbuf_floats >= (size_t)n * 27 * S * S)) need = 0;
-        if (need > 1 && !(v->pregate && dgrad_is_wino(p, 1) && dgrad_is_wino(p, 2) && use_wino43(v, 1, kConvCout[1], kConvCin[1], S, S)))
-            need = 1;
-        if (need > 2 && !use_wino43(v, 2, kConvCout[2], kConvCin[2], S / 2, S / 2)) need = 2;
-        if (need > 0) {
-            Scope sc(p, F_ELEM, s);
-            ST3D_TRY(st3d_need_build(need_mask, n, S, need, p->need_seg, p->need_flags, p->need_flags_bytes, p->need_list[0],
-                                     p->need_list[1], p->need_cnt, s));
-        }
+    // ---- what the consumer of the image gradient needs (need.hip): with a mask, the bottom launches walk these lists
+    const int need = need_mask ? p->need_levels : 0;
+    if (need > 0) {
+        Scope sc(p, F_ELEM, s);
+        ST3D_TRY(st3d_need_build(need_mask, n, p->S, need, p->need_seg, p->need_flags, p->need_flags_bytes, p->need_list[0],
+                                 p->need_list[1], p->need_cnt, s));
     }
 
     // ---- backward: gradient w.r.t. the post-ReLU output of each conv, top down
@@ -780,10 +740,8 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
         int st = -1;
         for (int i = 0; i < 5; ++i)
             if (kStyleTap[i] == m) st = i;
-        if (cs == 0 && (st >= 0 || have_g) && p->vgg->fuse_tap0 && C == 64 && st3d_conv1_bwd_supported(H, W) &&
-            p->gbuf_floats >= (size_t)n * 27 * H * W) {
-            // relu1_1: style gradient + ReLU gate + conv1_1 input gradient in one pass over g and F (tap0.hip); the 27 tap
-            // planes go through the idle gradient buffer
+        const Route &r = p->route[cs];
+        if (cs == 0 && (st >= 0 || have_g) && p->fused_tap0) {       // relu1_1 and conv1_1 in one pass (tap0.hip)
             Scope sc(p, need >= 1 ? F_CONVX_DGRAD_NEED : F_CONVX_DGRAD, s, m);
             if (need >= 1)
                 ST3D_TRY(st3d_conv1_bwd_masked(have_g ? g : nullptr, p->act[m], st >= 0 ? p->D[st] : nullptr,
@@ -794,9 +752,7 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
                                     p->vgg->wd[0], gn, p->gbuf_floats * sizeof(float), grad_current, n, H, W, s));
             break;
         }
-        // Producer-side ReLU gates (st3d_wino_dgrad_chain): whoever writes a gradient last zeroes it where its tensor's gate
-        // is closed, so the Winograd input-gradient that consumes it streams one operand per stage
-        const bool chain = p->vgg->pregate && dgrad_is_wino(p, cs) && !g_is_pooled && (C % 32) == 0;
+        const bool chain = r.gate_taps && !g_is_pooled;
         if (st >= 0) {
             Scope sc(p, F_GRAM_BWD, s, m);
             if (chain) {
@@ -821,19 +777,21 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
         }
         if (!have_g) continue;
         float *dst = (cs == 0) ? grad_current : gn;
-        // the tensor dst is the gradient of = this conv's forward input (previous post-ReLU output, or the pool's output):
-        // gate it here when the launch that consumes it is a Winograd one
-        const float *og = nullptr, *addt = nullptr;
-        if (p->vgg->pregate && cs > 0 && dgrad_is_wino(p, cs) && dgrad_is_wino(p, cs - 1))
-            og = p->act[pool_slot(m - 1) >= 0 ? m - 1 : m - 2];
-        if (og && m - 2 == kContentTap) {       // dst is the gradient of the content tap: its own term joins in this launch's store
-            addt = p->content_target;
+        DgradOpts o;
+        o.pregated = g_gated;
+        // the tensor dst is the gradient of = this conv's forward input (previous post-ReLU output, or the pool's output)
+        if (r.gate_dst) o.out_gate = p->act[pool_slot(m - 1) >= 0 ? m - 1 : m - 2];
+        if (o.out_gate && m - 2 == kContentTap) {       // dst is the gradient of the content tap: its own term joins in this launch's store
+            o.add_target = p->content_target;
+            o.add_coef = cc;
             content_done = true;
         }
-        const int lvl = (cs == 1 || cs == 2) && need >= cs + 1 ? cs - 1 : -1;       // conv1_2 / conv2_1 over their need lists
-        ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, g_gated, og, addt, cc, lvl >= 0 ? p->need_list[lvl] : nullptr,
-                            lvl >= 0 ? p->need_cnt + lvl : nullptr));
-        g_gated = og != nullptr;
+        if ((cs == 1 || cs == 2) && need >= cs + 1) {   // conv1_2 / conv2_1 over their need lists
+            o.tile_list = p->need_list[cs - 1];
+            o.n_active = p->need_cnt + (cs - 1);
+        }
+        ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, o));
+        g_gated = o.out_gate != nullptr;
         // dst is the gradient w.r.t. this conv's input: either the previous conv's post-ReLU
         // output or a pool output (then the next dgrad fuses the unpool)
         g_is_pooled = (m > 0) && pool_slot(m - 1) >= 0;

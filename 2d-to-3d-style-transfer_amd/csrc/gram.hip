@@ -34,6 +34,20 @@ struct GemmArgs {
     int gate;               // backward only: zero the output where B (= F, the post-ReLU activation) is <= 0
 };
 
+// The weighted ("guided") variants: the same bodies under a compile-time switch W.  q (B, HW) holds the square roots of
+// the per-pixel weights of the guided Gram  G^ = sum_p w[p] F[:,p] F[:,p]^T = (q o F)(q o F)^T  (st3d_guidance_build).
+//   forward : both operand tiles are multiplied by q[p] on their way into LDS (p is the K index)
+//   backward: dF = coef * q o (D (q o F)) -- F is staged as it is (the ReLU gate is the sign of F itself) and multiplied by
+//             q[n] twice, fl(q fl(q F)), as the B operand leaves LDS (see gemm_body)
+// The arguments of the unweighted kernels keep their layout (the weighted ones take the derived struct), and every
+// weighted statement sits under `if constexpr (W)`: the unweighted instantiations keep their code.
+struct GemmArgsW : GemmArgs {
+    const float *q; size_t sQ;      // weights' square roots, batch stride (elements)
+};
+template <bool W> using GemmArgsT = std::conditional_t<W, GemmArgsW, GemmArgs>;
+
+__device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
+
 // load 4 consecutive elements p[0..3] along a contiguous axis, zero past `remain`
 __device__ __forceinline__ float4 load4(const float *p, int remain, bool aligned) {
     if (remain >= 4 && aligned) return *reinterpret_cast<const float4 *>(p);
@@ -60,8 +74,8 @@ struct GemmSmem {
     static constexpr int FLOATS = KCH * LA + KCH * LB;
 };
 
-template <int MT, int NT, int BMODE, int DIAG = 0, int KCH = 32, bool FAST = false>
-__device__ __forceinline__ void gemm_body(const GemmArgs &g, const int bx, const int by, const int bz, float *smem) {
+template <int MT, int NT, int BMODE, int DIAG = 0, int KCH = 32, bool FAST = false, bool W = false>
+__device__ __forceinline__ void gemm_body(const GemmArgsT<W> &g, const int bx, const int by, const int bz, float *smem) {
     constexpr int TM = 2 * MT * 32, TN = 2 * NT * 32;
     constexpr int LA = TM + 1;
     constexpr int LB = (BMODE == 0) ? TN + 1 : TN;
@@ -94,6 +108,28 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int bx, const
     const float *Bb = g.B + b * g.sB;
     const bool a_al = ((g.lda & 3) == 0) && ((((uintptr_t)Ab) & 15) == 0);
     const bool b_al = ((g.ldb & 3) == 0) && ((((uintptr_t)Bb) & 15) == 0);
+    // weighted forward: this thread's four q values, those of its four k (pixels) of the chunk -- every staging item of a
+    // thread has the same kq, A and B alike (256 threads are a multiple of the KCH / 4 float4 of a row) -- reloaded per chunk
+    const float *Qb = nullptr;
+    bool q_al = false;
+    float4 qv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (W) {
+        Qb = g.q + b * g.sQ;
+        q_al = (((uintptr_t)Qb) & 15) == 0;
+    }
+    // weighted backward: q of this lane's NT result columns.  Both q[n] of q o (D (q o F)) multiply the B operand as it
+    // leaves LDS (a column of the product is a column of B): nothing is scaled in the epilogue, so the accumulators start
+    // from the destination as in the unweighted kernel and q == 1 gives its bits whether it accumulates or not; and LDS
+    // holds F itself, so the gate bits are the sign of F -- a gradient arriving from the layers above passes wherever the
+    // ReLU was open, also under q = 0 (and no underflow of q F can close a gate).
+    [[maybe_unused]] float qcol[NT];
+    if constexpr (W && BMODE == 1) {
+#pragma unroll
+        for (int q = 0; q < NT; ++q) {
+            const int gn = n0 + wn * (NT * 32) + q * 32 + l31;
+            qcol[q] = gn < g.N ? Qb[gn] : 0.f;
+        }
+    }
 
     // C = coef * A B (+ C): the accumulators START from the destination tile when accumulating (its loads are in flight
     // under the first operand tiles instead of a dependent load -> add -> store chain behind the last MFMA) and coef is
@@ -122,6 +158,11 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int bx, const
         for (int q = 0; q < NT; ++q) gmask[m][q] = 0xffffu;
     float4 av[A4], bv[B4];
     auto load_tiles = [&](int k0) {
+        if constexpr (W && BMODE == 0) {
+            const int gk = k0 + (tid % (KCH / 4)) * 4;
+            if (FAST) qv = *reinterpret_cast<const float4 *>(Qb + gk);
+            else qv = load4(Qb + gk, kend - gk, q_al && ((gk & 3) == 0));
+        }
 #pragma unroll
         for (int i = 0; i < A4; ++i) {       // A tile: TM rows x 32 k, 8 float4 per row
             const int e = tid + i * 256, row = e / (KCH / 4), kq = (e % (KCH / 4)) * 4;
@@ -154,6 +195,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int bx, const
         for (int i = 0; i < A4; ++i) {
             const int e = tid + i * 256, row = e / (KCH / 4), kq = (e % (KCH / 4)) * 4;
             const float cf = BMODE == 1 ? g.coef : 1.f;        // the forward has no coefficient: no multiply
+            if constexpr (W && BMODE == 0) av[i] = mul4(av[i], qv);       // q[p] F[m][p] (NaN and Inf as the product says)
             As[(kq + 0) * LA + row] = cf * av[i].x; As[(kq + 1) * LA + row] = cf * av[i].y;
             As[(kq + 2) * LA + row] = cf * av[i].z; As[(kq + 3) * LA + row] = cf * av[i].w;
         }
@@ -161,6 +203,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int bx, const
 #pragma unroll
         for (int i = 0; i < B4; ++i) {
             const int e = tid + i * 256;
+            if constexpr (W && BMODE == 0) bv[i] = mul4(bv[i], qv);
             if (BMODE == 0) {
                 const int row = e / (KCH / 4), kq = (e % (KCH / 4)) * 4;
                 Bs[(kq + 0) * LB + row] = bv[i].x; Bs[(kq + 1) * LB + row] = bv[i].y;
@@ -206,6 +249,10 @@ __device__ __forceinline__ void gemm_body(const GemmArgs &g, const int bx, const
             for (int m = 0; m < MT; ++m) a[m] = pa[(kk * 2) * LA + m * 32];
 #pragma unroll
             for (int q = 0; q < NT; ++q) bb[q] = pb[(kk * 2) * LB + q * 32];
+            if constexpr (W && BMODE == 1) {
+#pragma unroll
+                for (int q = 0; q < NT; ++q) bb[q] = (bb[q] * qcol[q]) * qcol[q];
+            }
 #pragma unroll
             for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -248,6 +295,12 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
     gemm_body<MT, NT, BMODE, DIAG, KCH, FAST>(g, blockIdx.x, blockIdx.y, blockIdx.z, smem);
 }
 
+template <int MT, int NT, int BMODE, int DIAG = 0, int KCH = 32, bool FAST = false>
+__global__ __launch_bounds__(256, 2) void gemm_w_kernel(const GemmArgsW g) {
+    __shared__ __attribute__((aligned(16))) float smem[(GemmSmem<MT, NT, BMODE, DIAG, KCH, FAST>::FLOATS + 3) & ~3];
+    gemm_body<MT, NT, BMODE, DIAG, KCH, FAST, true>(g, blockIdx.x, blockIdx.y, blockIdx.z, smem);
+}
+
 // Gram backward of the loss plan (st3d_gram_bwd_gated: D = G - S is SYMMETRIC, whole 128 x 64 tiles, aligned).  Same tile
 // shape and arithmetic as gemm_kernel<2, 1, 1> -- 128 channels x 64 pixels per workgroup, each wave 64 x 32, accumulators
 // started from the destination tile, coef folded into A, gate bits from the F chunk in LDS -- but written like the Winograd
@@ -255,7 +308,10 @@ __global__ __launch_bounds__(256, 2) void gemm_kernel(const GemmArgs g) {
 // 64-bit address arithmetic, no bounds code), the A tile is read ALONG m from row k of D (= column k, by symmetry), so it
 // lands k-major in LDS with 16-byte stores instead of 16 transposing 4-byte ones, and the chunk loop is one basic block
 // with an explicit MFMA / LDS-read interleave and the next chunk's loads first.
-__global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgs g) {
+// (a template of the kernel itself, not a body shared by two kernels: inlined into a wrapper the unweighted code came
+// out with its instructions in another order; this way it is the parent's, instruction for instruction)
+template <bool W>
+__global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgsT<W> g) {
     constexpr int TM = 128, TN = 64, KCH = 32, LA = TM + 4, LB = TN;
     constexpr unsigned kOob = 0x80000000u;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -289,6 +345,9 @@ __global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgs g) 
     }
     // this lane's rows of the result: m0 + 64 wm + 32 m + (r & 3) + 8 (r >> 2) + 4 lhi, column n0 + 32 wn + lane31
     const unsigned voC = (unsigned)(m0 + wm * 64 + 4 * lhi) * rowF + (unsigned)(n0 + wn * 32 + l31) * 4u;
+    // weighted: q of this lane's result column, applied twice to the B operand as it leaves LDS (see gemm_body)
+    [[maybe_unused]] float qn = 0.f;
+    if constexpr (W) qn = g.q[b * g.sQ + n0 + wn * 32 + l31];
     f32x16 acc[2];
 #pragma unroll
     for (int m = 0; m < 2; ++m)
@@ -330,7 +389,9 @@ __global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgs g) 
         }
 #pragma unroll
         for (int kk = 0; kk < KCH / 2; ++kk) {
-            const float a0 = pa[(kk * 2) * LA], a1 = pa[(kk * 2) * LA + 32], bb = pb[(kk * 2) * LB];
+            const float a0 = pa[(kk * 2) * LA], a1 = pa[(kk * 2) * LA + 32];
+            float bb = pb[(kk * 2) * LB];
+            if constexpr (W) bb = (bb * qn) * qn;
             acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, bb, acc[0], 0, 0, 0);
             acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, bb, acc[1], 0, 0, 0);
         }
@@ -345,6 +406,7 @@ __global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgs g) 
         }
 }
 
+
 // Gram forward of the single-tile layers (C = 64: NB = 2, C = 128: NB = 4 blocks of 32 channels), whole aligned shapes only.
 // The 4 waves of gemm_kernel<.., DIAG> tile the full C x C output, so a quarter (C = 64) to three eighths (C = 128) of
 // their MFMAs compute the mirror image of another wave's block.  Here only the NB (NB + 1) / 2 blocks on or above the
@@ -352,8 +414,8 @@ __global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgs g) 
 // chunk's k-steps; C = 128 -- two block groups of 5 x two k-groups.  Each k-group writes its own slab (the ordered
 // reduce sums KG x nsplit of them and mirrors at block granularity), so nothing is exchanged between waves.  One LDS
 // value serves as row operand and as column operand (the tile is its own transpose partner).
-template <int NB>
-__device__ __forceinline__ void gram_diag_body(const GemmArgs &g, const int by, const int bz, float *As) {
+template <int NB, bool W = false>
+__device__ __forceinline__ void gram_diag_body(const GemmArgsT<W> &g, const int by, const int bz, float *As) {
     constexpr int TM = 32 * NB, LA = TM + 1, KCH = 32;
     constexpr int KG = NB == 2 ? 4 : 2;                 // k-groups
     constexpr int NBLK = NB == 2 ? 3 : 5;               // blocks per wave
@@ -376,7 +438,9 @@ __device__ __forceinline__ void gram_diag_body(const GemmArgs &g, const int by, 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
     float4 av[A4];
+    float4 qv = make_float4(0.f, 0.f, 0.f, 0.f);      // weighted: q of this thread's four pixels of the chunk (one kq per thread)
     auto load_tile = [&](int k0) {
+        if constexpr (W) qv = *reinterpret_cast<const float4 *>(g.q + b * g.sQ + k0 + (tid % (KCH / 4)) * 4);
 #pragma unroll
         for (int i = 0; i < A4; ++i) {
             const int e = tid + i * 256, row = e / (KCH / 4), kq = (e % (KCH / 4)) * 4;
@@ -389,6 +453,7 @@ __device__ __forceinline__ void gram_diag_body(const GemmArgs &g, const int by, 
 #pragma unroll
         for (int i = 0; i < A4; ++i) {
             const int e = tid + i * 256, row = e / (KCH / 4), kq = (e % (KCH / 4)) * 4;
+            if constexpr (W) av[i] = mul4(av[i], qv);
             As[(kq + 0) * LA + row] = av[i].x; As[(kq + 1) * LA + row] = av[i].y;
             As[(kq + 2) * LA + row] = av[i].z; As[(kq + 3) * LA + row] = av[i].w;
         }
@@ -438,6 +503,12 @@ __global__ __launch_bounds__(256, 2) void gram_diag_kernel(const GemmArgs g) {
     gram_diag_body<NB>(g, blockIdx.y, blockIdx.z, As);
 }
 
+template <int NB>
+__global__ __launch_bounds__(256, 2) void gram_diag_w_kernel(const GemmArgsW g) {
+    __shared__ __attribute__((aligned(16))) float As[32 * (32 * NB + 1)];
+    gram_diag_body<NB, true>(g, blockIdx.y, blockIdx.z, As);
+}
+
 // ---- all style layers of a step in ONE launch (round 3).  Five launches of 500-1300 workgroups each ran one after the
 // other, every one with its own ramp and tail, the HBM-bound relu1_1 layer (64 row streams of 1 MB per image) with the
 // matrix pipe idle and the deep layers with HBM idle.  Here one grid holds the workgroups of every layer: a block finds
@@ -445,16 +516,20 @@ __global__ __launch_bounds__(256, 2) void gram_diag_kernel(const GemmArgs g) {
 // code, the same per-split slabs, so the sums are bitwise what the separate launches produce.  The relu1_1 blocks are
 // dealt between the others (every `stride`-th block) so that streams and MFMA work overlap in time.
 constexpr int kMaxGramItems = 8;
-struct GramMulti {
-    GemmArgs g[kMaxGramItems];
+template <typename Args>
+struct GramMultiFields {
+    Args g[kMaxGramItems];
     int kind[kMaxGramItems];            // 0: gram_diag<2>, 1: gram_diag<4>, 2: gemm<2,2> multi-tile FAST, 3: generic (not FAST)
     int gx[kMaxGramItems], gy[kMaxGramItems];
     int first[kMaxGramItems + 1];       // block ranges of items 1.. in the "rest" numbering; item 0 is the dealt-in one
     int n_items, n0, stride;            // n0 blocks of item 0, one every `stride` blocks (stride 0: item 0 is part of the rest)
 };
+struct GramMulti : GramMultiFields<GemmArgs> {};
+struct GramMultiW : GramMultiFields<GemmArgsW> {};
+template <bool W> using GramMultiT = std::conditional_t<W, GramMultiW, GramMulti>;
 
-__global__ __launch_bounds__(256, 2) void gram_multi_kernel(const GramMulti m) {
-    __shared__ __attribute__((aligned(16))) float smem[(GemmSmem<2, 2, 0, 0, 32, true>::FLOATS + 3) & ~3];
+template <bool W>
+__device__ __forceinline__ void gram_multi_body(const GramMultiT<W> &m, float *smem) {
     int b = blockIdx.x, it;
     if (m.stride > 0) {
         const int q = b / m.stride, dealt = b - q * m.stride == 0 && q < m.n0;
@@ -469,15 +544,25 @@ __global__ __launch_bounds__(256, 2) void gram_multi_kernel(const GramMulti m) {
         while (it + 1 < m.n_items && b >= m.first[it + 1]) ++it;
         b -= m.first[it];
     }
-    const GemmArgs &g = m.g[it];
+    const GemmArgsT<W> &g = m.g[it];
     const int gx = m.gx[it], gy = m.gy[it];
     const int bx = b % gx, by = (b / gx) % gy, bz = b / (gx * gy);
     switch (m.kind[it]) {
-        case 0: gram_diag_body<2>(g, by, bz, smem); break;
-        case 1: gram_diag_body<4>(g, by, bz, smem); break;
-        case 2: gemm_body<2, 2, 0, 0, 32, true>(g, bx, by, bz, smem); break;
+        case 0: gram_diag_body<2, W>(g, by, bz, smem); break;
+        case 1: gram_diag_body<4, W>(g, by, bz, smem); break;
+        case 2: gemm_body<2, 2, 0, 0, 32, true, W>(g, bx, by, bz, smem); break;
         default: break;
     }
+}
+
+__global__ __launch_bounds__(256, 2) void gram_multi_kernel(const GramMulti m) {
+    __shared__ __attribute__((aligned(16))) float smem[(GemmSmem<2, 2, 0, 0, 32, true>::FLOATS + 3) & ~3];
+    gram_multi_body<false>(m, smem);
+}
+
+__global__ __launch_bounds__(256, 2) void gram_multi_w_kernel(const GramMultiW m) {
+    __shared__ __attribute__((aligned(16))) float smem[(GemmSmem<2, 2, 0, 0, 32, true>::FLOATS + 3) & ~3];
+    gram_multi_body<true>(m, smem);
 }
 
 struct ReduceItem { const float *slab; float *gram; int nsplit, C, TM, blocks_per_image; size_t sSplit, sB; };
@@ -605,7 +690,7 @@ extern "C" size_t st3d_gram_workspace_bytes(int B, int C, int HW) {
 // arguments and grid, and the reduce that follows (slabs to sum, mirror granularity).
 struct GramFwdPlan { GemmArgs g; int kind, gx, gy, TM; bool fast; int red_nsplit, red_tm; };
 
-static GramFwdPlan gram_fwd_plan(const float *feat, int B, int C, int HW, void *workspace, int scale = 1) {
+static GramFwdPlan gram_fwd_plan(const float *feat, int B, int C, int HW, void *workspace, int scale = 1, bool may_fast = true) {
     GramFwdPlan q;
     GemmArgs &g = q.g;
     memset(&g, 0, sizeof(g));
@@ -620,7 +705,7 @@ static GramFwdPlan gram_fwd_plan(const float *feat, int B, int C, int HW, void *
     q.gx = g.tiles_n * (g.tiles_n + 1) / 2; q.gy = g.nsplit;
     // whole tiles, whole 32-pixel chunks in every split, 16-byte aligned rows: the branch-free instantiation
     static const bool allow_fast = [] { const char *e = getenv("ST3D_GRAM_FAST"); return !(e && e[0] == '0'); }();
-    q.fast = allow_fast && C % TM == 0 && HW % 32 == 0 && g.kper % 32 == 0 && (((uintptr_t)feat) & 15) == 0;
+    q.fast = allow_fast && may_fast && C % TM == 0 && HW % 32 == 0 && g.kper % 32 == 0 && (((uintptr_t)feat) & 15) == 0;
     static const bool tri = [] { const char *e = getenv("ST3D_GRAM_DIAG_TRI"); return !(e && e[0] == '0'); }();
     q.kind = 3; q.red_nsplit = g.nsplit;
     if (q.fast && tri && (C == 64 || C == 128)) {     // upper blocks only, waves split the K chunk (gram_diag_kernel)
@@ -635,20 +720,38 @@ static GramFwdPlan gram_fwd_plan(const float *feat, int B, int C, int HW, void *
     return q;
 }
 
-extern "C" int st3d_gram_fwd(const float *feat, int B, int C, int HW, void *workspace, size_t workspace_bytes, float *gram,
-                             st3d_stream_t stream) {
-    ST3D_CHECK_ARG(feat && workspace && gram);
-    ST3D_CHECK_ARG(B > 0 && C > 0 && HW > 0);
-    ST3D_CHECK_ARG(workspace_bytes >= st3d_gram_workspace_bytes(B, C, HW));
-    hipStream_t s = st3d::as_stream(stream);
-    const GramFwdPlan q = gram_fwd_plan(feat, B, C, HW, workspace);
-    const GemmArgs &g = q.g;
+// kernel arguments of a launch: the plain ones, or (weighted) the same with the q planes behind them
+template <bool W>
+static GemmArgsT<W> gram_args(const GemmArgs &g, const float *qw, int HW) {
+    if constexpr (W) {
+        GemmArgsW w;
+        static_cast<GemmArgs &>(w) = g;
+        w.q = qw; w.sQ = (size_t)HW;
+        return w;
+    } else {
+        return g;
+    }
+}
+
+// the weighted kernels' branch-free paths read q in 16-byte pieces as they read feat
+static bool gram_q_aligned(const float *qw) { return (((uintptr_t)qw) & 15) == 0; }
+
+template <bool W>
+static int gram_fwd_run(const float *feat, const float *qw, int B, int C, int HW, void *workspace, float *gram, hipStream_t s) {
+    GramFwdPlan q = gram_fwd_plan(feat, B, C, HW, workspace);
+    if (W && q.fast && !gram_q_aligned(qw)) q = gram_fwd_plan(feat, B, C, HW, workspace, 1, false);
+    const GemmArgsT<W> g = gram_args<W>(q.g, qw, HW);
     const int TM = q.TM;
     const bool fast = q.fast;
     dim3 grid(q.gx, q.gy, B);
     if (q.kind <= 1) {
-        if (C == 64) gram_diag_kernel<2><<<dim3(1, g.nsplit, B), 256, 0, s>>>(g);
-        else gram_diag_kernel<4><<<dim3(1, g.nsplit, B), 256, 0, s>>>(g);
+        if constexpr (W) {
+            if (C == 64) gram_diag_w_kernel<2><<<dim3(1, g.nsplit, B), 256, 0, s>>>(g);
+            else gram_diag_w_kernel<4><<<dim3(1, g.nsplit, B), 256, 0, s>>>(g);
+        } else {
+            if (C == 64) gram_diag_kernel<2><<<dim3(1, g.nsplit, B), 256, 0, s>>>(g);
+            else gram_diag_kernel<4><<<dim3(1, g.nsplit, B), 256, 0, s>>>(g);
+        }
         ST3D_LAUNCH_CHECK();
         if (gram_reduce_vw(C, q.red_tm, g.sSplit, g.sC) == 4)
             gram_reduce_kernel<4><<<dim3(st3d::cdiv((long)C * C, 256), B), 256, 0, s>>>(g.C, q.red_nsplit, C, q.red_tm, g.sSplit, g.sC, gram);
@@ -657,11 +760,19 @@ extern "C" int st3d_gram_fwd(const float *feat, int B, int C, int HW, void *work
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     }
+    if constexpr (W) {
+        if (g.tiles_n == 1) {
+            if (TM == 128) { if (fast) gemm_w_kernel<2, 2, 0, 1, 32, true><<<grid, 256, 0, s>>>(g); else gemm_w_kernel<2, 2, 0, 1><<<grid, 256, 0, s>>>(g); }
+            else { if (fast) gemm_w_kernel<1, 1, 0, 1, 32, true><<<grid, 256, 0, s>>>(g); else gemm_w_kernel<1, 1, 0, 1><<<grid, 256, 0, s>>>(g); }
+        } else if (TM == 128) { if (fast) gemm_w_kernel<2, 2, 0, 0, 32, true><<<grid, 256, 0, s>>>(g); else gemm_w_kernel<2, 2, 0><<<grid, 256, 0, s>>>(g); }
+        else gemm_w_kernel<1, 1, 0><<<grid, 256, 0, s>>>(g);
+    } else {
     if (g.tiles_n == 1) {           // one (diagonal) tile: A and B tiles coincide
         if (TM == 128) { if (fast) gemm_kernel<2, 2, 0, 1, 32, true><<<grid, 256, 0, s>>>(g); else gemm_kernel<2, 2, 0, 1><<<grid, 256, 0, s>>>(g); }
         else { if (fast) gemm_kernel<1, 1, 0, 1, 32, true><<<grid, 256, 0, s>>>(g); else gemm_kernel<1, 1, 0, 1><<<grid, 256, 0, s>>>(g); }
     } else if (TM == 128) { if (fast) gemm_kernel<2, 2, 0, 0, 32, true><<<grid, 256, 0, s>>>(g); else gemm_kernel<2, 2, 0><<<grid, 256, 0, s>>>(g); }
     else gemm_kernel<1, 1, 0><<<grid, 256, 0, s>>>(g);
+    }
     ST3D_LAUNCH_CHECK();
     if (gram_reduce_vw(C, q.red_tm, g.sSplit, g.sC) == 4)
             gram_reduce_kernel<4><<<dim3(st3d::cdiv((long)C * C, 256), B), 256, 0, s>>>(g.C, q.red_nsplit, C, q.red_tm, g.sSplit, g.sC, gram);
@@ -669,6 +780,24 @@ extern "C" int st3d_gram_fwd(const float *feat, int B, int C, int HW, void *work
             gram_reduce_kernel<1><<<dim3(st3d::cdiv((long)C * C, 64), B), 256, 0, s>>>(g.C, q.red_nsplit, C, q.red_tm, g.sSplit, g.sC, gram);
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
+}
+
+extern "C" int st3d_gram_fwd(const float *feat, int B, int C, int HW, void *workspace, size_t workspace_bytes, float *gram,
+                             st3d_stream_t stream) {
+    ST3D_CHECK_ARG(feat && workspace && gram);
+    ST3D_CHECK_ARG(B > 0 && C > 0 && HW > 0);
+    ST3D_CHECK_ARG(workspace_bytes >= st3d_gram_workspace_bytes(B, C, HW));
+    return gram_fwd_run<false>(feat, nullptr, B, C, HW, workspace, gram, st3d::as_stream(stream));
+}
+
+// The guided Gram: G^ = (q o F)(q o F)^T, q (B, HW) from st3d_guidance_build.  Same splits, same kernels' bodies, same
+// reduce as st3d_gram_fwd, so q == 1 gives its bits.
+extern "C" int st3d_gram_fwd_weighted(const float *feat, const float *q, int B, int C, int HW, void *workspace,
+                                      size_t workspace_bytes, float *gram, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(feat && q && workspace && gram);
+    ST3D_CHECK_ARG(B > 0 && C > 0 && HW > 0);
+    ST3D_CHECK_ARG(workspace_bytes >= st3d_gram_workspace_bytes(B, C, HW));
+    return gram_fwd_run<true>(feat, q, B, C, HW, workspace, gram, st3d::as_stream(stream));
 }
 
 // Every style layer's Gram in one launch pair (gram_multi_kernel + gram_reduce_multi_kernel).  items: host array; every
@@ -682,9 +811,11 @@ extern "C" size_t st3d_gram_multi_workspace_bytes(const st3d_gram_item *items, i
     return tot;
 }
 
-extern "C" int st3d_gram_fwd_multi(const st3d_gram_item *items, int count, void *workspace, size_t workspace_bytes,
-                                   st3d_stream_t stream) {
+template <bool W>
+static int gram_fwd_multi_run(const st3d_gram_item *items, const float *const *qs, int count, void *workspace,
+                              size_t workspace_bytes, st3d_stream_t stream) {
     ST3D_CHECK_ARG(items && count > 0 && count <= kMaxGramItems && workspace);
+    ST3D_CHECK_ARG(!W || qs);
     ST3D_CHECK_ARG(workspace_bytes >= st3d_gram_multi_workspace_bytes(items, count) && ((uintptr_t)workspace & 255) == 0);
     hipStream_t s = st3d::as_stream(stream);
     static const bool fuse = [] { const char *e = getenv("ST3D_GRAM_MULTI"); return !(e && e[0] == '0'); }();
@@ -692,7 +823,7 @@ extern "C" int st3d_gram_fwd_multi(const st3d_gram_item *items, int count, void 
     static const int deal = [] { const char *e = getenv("ST3D_GRAM_MULTI_DEAL"); return e ? atoi(e) : 0; }();
     // (read per call, not cached: tests compare scale 1 with st3d_gram_fwd bit for bit)
     const int scale = [] { const char *e = getenv("ST3D_GRAM_MULTI_SCALE"); const int v = e ? atoi(e) : 2; return v >= 1 && v <= 16 ? v : 2; }();
-    GramMulti gm;
+    GramMultiT<W> gm;
     ReduceMulti rm;
     memset(&gm, 0, sizeof(gm));
     memset(&rm, 0, sizeof(rm));
@@ -704,6 +835,7 @@ extern "C" int st3d_gram_fwd_multi(const st3d_gram_item *items, int count, void 
     for (int i = 0; i < count; ++i) {
         const st3d_gram_item &it = items[i];
         ST3D_CHECK_ARG(it.feat && it.gram && it.B > 0 && it.C > 0 && it.HW > 0);
+        ST3D_CHECK_ARG(!W || qs[i]);
         woff[i] = off;
         int sc = scale;
         if (const char *e = getenv("ST3D_GRAM_MULTI_SCALES")) {        // tuning knob (tools/gram_multi_sweep.py): "c64,c128,c256,c512"
@@ -714,6 +846,7 @@ extern "C" int st3d_gram_fwd_multi(const st3d_gram_item *items, int count, void 
         }
         plans[i] = gram_fwd_plan(it.feat, it.B, it.C, it.HW, ws + off, fuse ? sc : 1);
         if (plans[i].kind > 2) plans[i] = gram_fwd_plan(it.feat, it.B, it.C, it.HW, ws + off, 1);      // (runs through st3d_gram_fwd below)
+        if (W && !gram_q_aligned(qs[i])) plans[i].kind = 3;       // a plane the 16-byte reads cannot take: likewise (gram_fwd_run re-plans)
         off += (st3d_gram_workspace_bytes(it.B, it.C, it.HW) + 255) & ~(size_t)255;
     }
     // fused items: the dealt-in one (first kind-0 item) goes to slot 0, the rest by descending work per block
@@ -733,7 +866,7 @@ extern "C" int st3d_gram_fwd_multi(const st3d_gram_item *items, int count, void 
         int restblocks = 0;
         for (int k = 0; k < nf; ++k) {
             const GramFwdPlan &q = plans[order[k]];
-            gm.g[k] = q.g; gm.kind[k] = q.kind; gm.gx[k] = q.gx; gm.gy[k] = q.gy;
+            gm.g[k] = gram_args<W>(q.g, W ? qs[order[k]] : nullptr, items[order[k]].HW); gm.kind[k] = q.kind; gm.gx[k] = q.gx; gm.gy[k] = q.gy;
             const int blocks = q.gx * q.gy * items[order[k]].B;
             if (k == 0 && dealt >= 0) { gm.n0 = blocks; gm.first[0] = 0; continue; }
             gm.first[k] = restblocks;
@@ -744,7 +877,8 @@ extern "C" int st3d_gram_fwd_multi(const st3d_gram_item *items, int count, void 
         const int total = gm.n0 + restblocks;
         gm.stride = (dealt >= 0 && gm.n0 > 0) ? (total / gm.n0 > 0 ? total / gm.n0 : 1) : 0;
         if (restblocks == 0) gm.stride = gm.n0 > 0 ? 1 : 0;
-        gram_multi_kernel<<<total, 256, 0, s>>>(gm);
+        if constexpr (W) gram_multi_w_kernel<<<total, 256, 0, s>>>(gm);
+        else gram_multi_kernel<<<total, 256, 0, s>>>(gm);
         ST3D_LAUNCH_CHECK();
         int rblocks = 0, vw = 4;
         for (int k = 0; k < nf; ++k) {
@@ -767,31 +901,63 @@ extern "C" int st3d_gram_fwd_multi(const st3d_gram_item *items, int count, void 
     for (int i = 0; i < count; ++i)
         if (!(fuse && plans[i].kind <= 2)) {
             const st3d_gram_item &it = items[i];
-            ST3D_TRY(st3d_gram_fwd(it.feat, it.B, it.C, it.HW, ws + woff[i], st3d_gram_workspace_bytes(it.B, it.C, it.HW), it.gram, stream));
+            ST3D_TRY(gram_fwd_run<W>(it.feat, W ? qs[i] : nullptr, it.B, it.C, it.HW, ws + woff[i], it.gram, s));
         }
     return ST3D_OK;
 }
 
-static int gram_bwd_launch(const float *D, const float *feat, int B, int C, int HW, float coef, int accumulate, int gate,
-                           float *gfeat, st3d_stream_t stream);
+extern "C" int st3d_gram_fwd_multi(const st3d_gram_item *items, int count, void *workspace, size_t workspace_bytes,
+                                   st3d_stream_t stream) {
+    return gram_fwd_multi_run<false>(items, nullptr, count, workspace, workspace_bytes, stream);
+}
+
+// the guided Grams of all style layers in one launch pair: q[i] (B, HW) belongs to items[i] (a parallel host array;
+// st3d_gram_item is unchanged).  Bitwise the results of st3d_gram_fwd_weighted per item.
+extern "C" int st3d_gram_fwd_multi_weighted(const st3d_gram_item *items, const float *const *q, int count, void *workspace,
+                                            size_t workspace_bytes, st3d_stream_t stream) {
+    return gram_fwd_multi_run<true>(items, q, count, workspace, workspace_bytes, stream);
+}
+
+template <bool W>
+static int gram_bwd_launch(const float *D, const float *feat, const float *qw, int B, int C, int HW, float coef, int accumulate,
+                           int gate, float *gfeat, st3d_stream_t stream);
 
 extern "C" int st3d_gram_bwd(const float *D, const float *feat, int B, int C, int HW, float coef, int accumulate,
                              float *gfeat, st3d_stream_t stream) {
-    return gram_bwd_launch(D, feat, B, C, HW, coef, accumulate, 0, gfeat, stream);
+    return gram_bwd_launch<false>(D, feat, nullptr, B, C, HW, coef, accumulate, 0, gfeat, stream);
 }
 
 extern "C" int st3d_gram_bwd_gated(const float *D, const float *feat, int B, int C, int HW, float coef, int accumulate,
                                    float *gfeat, st3d_stream_t stream) {
     ST3D_CHECK_ARG(C % 32 == 0);        // the gate bits are picked up per 32-row block of the activation
-    return gram_bwd_launch(D, feat, B, C, HW, coef, accumulate, 1, gfeat, stream);
+    return gram_bwd_launch<false>(D, feat, nullptr, B, C, HW, coef, accumulate, 1, gfeat, stream);
 }
 
-static int gram_bwd_launch(const float *D, const float *feat, int B, int C, int HW, float coef, int accumulate, int gate,
-                           float *gfeat, st3d_stream_t stream) {
+// gfeat (+)= coef * D (q o (q o feat)) = coef * q o (D (q o feat)), the gradient of the guided style term; gated != 0: then 0
+// where feat <= 0
+extern "C" int st3d_gram_bwd_weighted(const float *D, const float *feat, const float *q, int B, int C, int HW, float coef,
+                                      int accumulate, int gated, float *gfeat, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(q);
+    ST3D_CHECK_ARG(!gated || C % 32 == 0);
+    return gram_bwd_launch<true>(D, feat, q, B, C, HW, coef, accumulate, gated ? 1 : 0, gfeat, stream);
+}
+
+// one of the general backward instantiations (BMODE 1), plain or weighted
+template <bool W, int MT, int NT, int BMODE, int DIAG = 0, int KCH = 32>
+static void gram_bwd_gemm(const GemmArgsT<W> &g, dim3 grid, hipStream_t s) {
+    static_assert(BMODE == 1 && DIAG == 0, "backward launches only");
+    if constexpr (W) gemm_w_kernel<MT, NT, BMODE, DIAG, KCH><<<grid, 256, 0, s>>>(g);
+    else gemm_kernel<MT, NT, BMODE, DIAG, KCH><<<grid, 256, 0, s>>>(g);
+}
+
+template <bool W>
+static int gram_bwd_launch(const float *D, const float *feat, const float *qw, int B, int C, int HW, float coef, int accumulate,
+                           int gate, float *gfeat, st3d_stream_t stream) {
     ST3D_CHECK_ARG(D && feat && gfeat);
     ST3D_CHECK_ARG(B > 0 && C > 0 && HW > 0);
-    GemmArgs g;
+    GemmArgsT<W> g;
     memset(&g, 0, sizeof(g));
+    if constexpr (W) { g.q = qw; g.sQ = (size_t)HW; }
     g.gate = gate;
     g.A = D; g.B = feat; g.C = gfeat;
     g.M = C; g.N = HW; g.K = C; g.lda = C; g.ldb = HW; g.ldc = HW;
@@ -814,7 +980,7 @@ static int gram_bwd_launch(const float *D, const float *feat, int B, int C, int 
     static const bool k64 = [] { const char *e = getenv("ST3D_GRAM_BWD_K64"); return e && e[0] == '1'; }();
     if (force && force[0] == '4') {             // 64 rows x 256 pixels (1 KB row segments)
         g.tiles_m = st3d::cdiv(C, 64); g.tiles_n = st3d::cdiv(HW, 256);
-        gemm_kernel<1, 4, 1><<<dim3(g.tiles_m * g.tiles_n, 1, B), 256, 0, s>>>(g);
+        gram_bwd_gemm<W, 1, 4, 1>(g, dim3(g.tiles_m * g.tiles_n, 1, B), s);
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     }
@@ -825,25 +991,25 @@ static int gram_bwd_launch(const float *D, const float *feat, int B, int C, int 
         (((uintptr_t)D | (uintptr_t)feat | (uintptr_t)gfeat) & 15) == 0) {
         // the plan's call (symmetric D, whole tiles): the lean kernel
         g.tiles_m = C / 128; g.tiles_n = HW / 64;
-        gram_bwd_sym_kernel<<<dim3(g.tiles_m * g.tiles_n, 1, B), 256, 0, s>>>(g);
+        gram_bwd_sym_kernel<W><<<dim3(g.tiles_m * g.tiles_n, 1, B), 256, 0, s>>>(g);
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     }
     if (wide) {
         g.tiles_m = C / 128; g.tiles_n = st3d::cdiv(HW, 64);
-        if (k64) gemm_kernel<2, 1, 1, 0, 64><<<dim3(g.tiles_m * g.tiles_n, 1, B), 256, 0, s>>>(g);
-        else gemm_kernel<2, 1, 1><<<dim3(g.tiles_m * g.tiles_n, 1, B), 256, 0, s>>>(g);
+        if (k64) gram_bwd_gemm<W, 2, 1, 1, 0, 64>(g, dim3(g.tiles_m * g.tiles_n, 1, B), s);
+        else gram_bwd_gemm<W, 2, 1, 1>(g, dim3(g.tiles_m * g.tiles_n, 1, B), s);
     } else if (C <= 128 && !tall && k64) {
         // short K (= C): the whole reduction (C = 64) or half of it is staged at once, so a workgroup has its operand tile and
         // the accumulate tile in flight together instead of one 32-row chunk after the other
         g.tiles_m = st3d::cdiv(C, 64); g.tiles_n = st3d::cdiv(HW, 128);
-        gemm_kernel<1, 2, 1, 0, 64><<<dim3(g.tiles_m * g.tiles_n, 1, B), 256, 0, s>>>(g);
+        gram_bwd_gemm<W, 1, 2, 1, 0, 64>(g, dim3(g.tiles_m * g.tiles_n, 1, B), s);
     } else if (tall) {
         g.tiles_m = C / 128; g.tiles_n = st3d::cdiv(HW, 128);
-        gemm_kernel<2, 2, 1><<<dim3(g.tiles_m * g.tiles_n, 1, B), 256, 0, s>>>(g);
+        gram_bwd_gemm<W, 2, 2, 1>(g, dim3(g.tiles_m * g.tiles_n, 1, B), s);
     } else {
         g.tiles_m = st3d::cdiv(C, 64); g.tiles_n = st3d::cdiv(HW, 128);
-        gemm_kernel<1, 2, 1><<<dim3(g.tiles_m * g.tiles_n, 1, B), 256, 0, s>>>(g);
+        gram_bwd_gemm<W, 1, 2, 1>(g, dim3(g.tiles_m * g.tiles_n, 1, B), s);
     }
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;

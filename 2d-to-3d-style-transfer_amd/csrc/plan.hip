@@ -160,8 +160,10 @@ struct GraphKey {               // what a captured loss step has baked in
     int n = 0, denom = 0;
     bool want_grad = false, masked = false, flat = false;
     float sw = 0.f, cw = 0.f;
+    bool guided = false;
     bool operator==(const GraphKey &o) const {
-        return n == o.n && denom == o.denom && want_grad == o.want_grad && masked == o.masked && flat == o.flat && sw == o.sw && cw == o.cw;
+        return n == o.n && denom == o.denom && want_grad == o.want_grad && masked == o.masked && flat == o.flat && sw == o.sw && cw == o.cw &&
+               guided == o.guided;
     }
 };
 
@@ -223,6 +225,16 @@ struct st3d_plan {
     uint8_t *flat_ws = nullptr;
     size_t flat_ws_bytes = 0;
     int *flat_list[3] = {}, *flat_map[3] = {}, *flat_cnt = nullptr;
+    // guidance of the style term (st3d_plan_set_style_guidance; guide.hip): the q planes of the five taps for guide_n
+    // images (0 = off), and w_0 = q_0^2 for the fused bottom pass.  Allocated by the first call that sets a guidance (for B
+    // images: the pointers never move, so a captured loss step keeps reading them), rebuilt by every such call.
+    int guide_n = 0;
+    float *guide_q = nullptr, *guide_w0 = nullptr, *guide_sums = nullptr, *guide_parts = nullptr;
+    const float *guide_plane(int level) const {
+        size_t off = 0;
+        for (int l = 0; l < level; ++l) off += (size_t)guide_n * (S >> l) * (S >> l);
+        return guide_q + off;
+    }
 };
 
 namespace {
@@ -335,6 +347,12 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
     }
     p->last_n = n;
     return ST3D_OK;
+}
+
+// w = q * q (the weight plane of the fused bottom pass from the q plane of level 0)
+__global__ __launch_bounds__(256) void square_kernel(const float *__restrict__ q, size_t n, float *__restrict__ w) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) w[i] = q[i] * q[i];
 }
 
 // g = (accumulate ? g : 0) + x
@@ -577,13 +595,39 @@ extern "C" int st3d_plan_set_content_features(st3d_plan *p, const float *feat, i
 }
 
 // the five style taps' Grams (of the n images of the last forward) in one launch pair
-static int grams_of_taps(st3d_plan *p, int n, float *const *out, hipStream_t s) {
+// (guided: the guided Grams, under the plan's guidance planes)
+static int grams_of_taps(st3d_plan *p, int n, float *const *out, hipStream_t s, bool guided = false) {
     st3d_gram_item items[5];
+    const float *q[5];
     for (int i = 0; i < 5; ++i) {
         const int m = kStyleTap[i];
         items[i] = st3d_gram_item{p->act[m], out[i], n, p->C[m], p->H[m] * p->W[m]};
+        q[i] = guided ? p->guide_plane(i) : nullptr;
     }
+    if (guided) return st3d_gram_fwd_multi_weighted(items, q, 5, p->gram_ws, p->gram_ws_bytes, s);
     return st3d_gram_fwd_multi(items, 5, p->gram_ws, p->gram_ws_bytes, s);
+}
+
+// Guidance of the style term: mask (n,1,S,S) in [0,1] -> the plan's q planes (st3d_guidance_build); every later
+// st3d_plan_loss* call with the same n takes the Gram of each tap over the guided region (the style targets stay the plain
+// Grams, the content term is unchanged, the guidance carries no gradient).  mask NULL clears (n is ignored).
+extern "C" int st3d_plan_set_style_guidance(st3d_plan *p, const float *mask, int n, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(p);
+    if (!mask) { p->guide_n = 0; return ST3D_OK; }
+    ST3D_CHECK_ARG(n > 0 && n <= p->B);
+    hipStream_t s = st3d::as_stream(stream);
+    p->guide_n = 0;
+    // each buffer once: a call that follows a failed allocation asks only for what is still missing
+    if (!p->guide_q) ST3D_TRY(dev_alloc(p, &p->guide_q, st3d_guidance_floats(p->B, p->S)));
+    if (!p->guide_w0) ST3D_TRY(dev_alloc(p, &p->guide_w0, (size_t)p->B * p->S * p->S));
+    if (!p->guide_sums) ST3D_TRY(dev_alloc(p, &p->guide_sums, (size_t)5 * p->B));
+    if (!p->guide_parts) ST3D_TRY(dev_alloc(p, &p->guide_parts, st3d_guidance_partials(p->B, p->S)));
+    ST3D_TRY(st3d_guidance_build(mask, n, p->S, p->guide_q, p->guide_sums, p->guide_parts, s));
+    const size_t cnt = (size_t)n * p->S * p->S;
+    square_kernel<<<(unsigned)std::min<size_t>((cnt + 255) / 256, 65535), 256, 0, s>>>(p->guide_q, cnt, p->guide_w0);
+    ST3D_LAUNCH_CHECK();
+    p->guide_n = n;
+    return ST3D_OK;
 }
 
 extern "C" int st3d_plan_set_style(st3d_plan *p, const float *style, int style_batch, int n, st3d_stream_t stream) {
@@ -640,13 +684,18 @@ extern "C" int st3d_plan_loss_flat(st3d_plan *p, const float *current, int n, in
         return ST3D_E_STATE;
     }
     ST3D_CHECK_ARG(p->style_batch == 1 || p->style_batch == n);
+    if (p->guide_n != 0 && p->guide_n != n) {
+        st3d::set_error("st3d_plan_loss: the style guidance was set for %d images, this call brings %d", p->guide_n, n);
+        return ST3D_E_STATE;
+    }
     hipStream_t s = st3d::as_stream(stream);
     if (!p->use_graph || p->prof)
         return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, flat_color, s);
 
     // ---- graph replay
     const size_t img = (size_t)n * 3 * p->S * p->S;
-    const GraphKey key{n, batch_denom, grad_current != nullptr, need_mask != nullptr, flat_color != nullptr, style_weight, content_weight};
+    const GraphKey key{n, batch_denom, grad_current != nullptr, need_mask != nullptr, flat_color != nullptr, style_weight, content_weight,
+                       p->guide_n != 0};
     if (!(p->gexec && key == p->gkey)) {
         if (p->gexec) { (void)hipGraphExecDestroy(p->gexec); p->gexec = nullptr; }
         const bool warm = p->gwarm && key == p->gkey;
@@ -689,6 +738,7 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
         ST3D_TRY(forward(p, current, n, 28, false, s, flat_color));
     }
     st3d::TraceRange tr_loss("gram_and_losses");
+    const bool guided = p->guide_n != 0;        // (== n: checked by the caller)
 
     const double bd = (double)batch_denom;
     // content loss: mean over (B,C,H,W) of (F - Ft)^2            (losses.py:31)
@@ -702,7 +752,7 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
     float style_coef[5];
     {
         Scope sc(p, F_GRAM_FWD, s);
-        ST3D_TRY(grams_of_taps(p, n, p->gram, s));
+        ST3D_TRY(grams_of_taps(p, n, p->gram, s, guided));
     }
     for (int i = 0; i < 5; ++i) {
         const int m = kStyleTap[i];
@@ -743,7 +793,11 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
         const Route &r = p->route[cs];
         if (cs == 0 && (st >= 0 || have_g) && p->fused_tap0) {       // relu1_1 and conv1_1 in one pass (tap0.hip)
             Scope sc(p, need >= 1 ? F_CONVX_DGRAD_NEED : F_CONVX_DGRAD, s, m);
-            if (need >= 1)
+            if (guided && st >= 0)
+                ST3D_TRY(st3d_conv1_bwd_weighted(have_g ? g : nullptr, p->act[m], p->D[st], style_coef[st], p->vgg->wd[0], gn,
+                                                 p->gbuf_floats * sizeof(float), grad_current, n, H, W, p->guide_w0,
+                                                 need >= 1 ? p->need_seg : nullptr, need >= 1 ? need_mask : nullptr, s));
+            else if (need >= 1)
                 ST3D_TRY(st3d_conv1_bwd_masked(have_g ? g : nullptr, p->act[m], st >= 0 ? p->D[st] : nullptr,
                                                st >= 0 ? style_coef[st] : 0.f, p->vgg->wd[0], gn, p->gbuf_floats * sizeof(float),
                                                grad_current, n, H, W, p->need_seg, need_mask, s));
@@ -755,7 +809,11 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
         const bool chain = r.gate_taps && !g_is_pooled;
         if (st >= 0) {
             Scope sc(p, F_GRAM_BWD, s, m);
-            if (chain) {
+            if (guided) {
+                ST3D_TRY(st3d_gram_bwd_weighted(p->D[st], p->act[m], p->guide_plane(st), n, C, H * W, style_coef[st], have_g ? 1 : 0,
+                                                chain ? 1 : 0, g, s));
+                g_gated = chain;
+            } else if (chain) {
                 ST3D_TRY(st3d_gram_bwd_gated(p->D[st], p->act[m], n, C, H * W, style_coef[st], have_g ? 1 : 0, g, s));
                 g_gated = true;
             } else {

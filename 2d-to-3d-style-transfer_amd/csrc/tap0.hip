@@ -15,6 +15,8 @@
 //   gather    gx[i][y][x] = sum over the 9 taps of Y[(tap, i)][y + ky - 1][x + kx - 1]   (second, tiny kernel)
 // Y (27 planes) costs 27/64 of one gradient write + read; the pass is 1-D over pixels (no halo, no spatial tiling), and
 // every sum has a fixed order (bitwise reproducible).  fp32 MFMA (v_mfma_f32_32x32x2_f32) throughout, like gram.hip.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -34,11 +36,22 @@ __host__ __device__ constexpr int acc_row(int v, int h) { return 8 * (v >> 2) + 
 // J = 2: 8-byte accesses at 2 waves per SIMD (256 VGPRs); J = 1: 4-byte accesses at 3 waves per SIMD.
 // MASKED: seg (N, HW / 64) marks the 64-pixel segments whose tap planes somebody gathers (need.hip); a wave skips the
 // others whole -- no loads, no products, no stores.  The loop holds no workgroup barrier, so waves skip on their own.
-template <bool HAS_D, bool HAS_G, int J, bool MASKED = false>
-__global__ __launch_bounds__(256, J == 2 ? 3 : 4) void conv1_bwd_gemm_kernel(const float *__restrict__ g, const float *__restrict__ F,
+// WT (the guided style loss): w0 (N, HW) holds one weight per pixel and GEMM 1's B operand is w0[p] * F[:, p], so that
+// t = g + coef * D (w0[p] F[:, p]) -- the gradient of the guided Gram's term; the gate is still the sign of F itself.
+// A compile-time switch of the kernel itself (a body shared by two kernels came out with its instructions in another
+// order): the unweighted instantiations keep their code, and their last argument is an empty struct.
+struct NoWeights {};
+__device__ __forceinline__ const float *weights_of(const float *w, const float *) { return w; }
+__device__ __forceinline__ const float *weights_of(NoWeights, const float *other) { return other; }
+template <bool WT> using Tap0Weights = std::conditional_t<WT, const float *, NoWeights>;
+
+// (the weighted J = 1 variant needs a few registers more than 4 waves per SIMD leave it: 3, like J = 2, and nothing spills)
+template <bool HAS_D, bool HAS_G, int J, bool MASKED = false, bool WT = false>
+__global__ __launch_bounds__(256, (J == 2 || WT) ? 3 : 4) void conv1_bwd_gemm_kernel(const float *__restrict__ g, const float *__restrict__ F,
                                                                          const float *__restrict__ D, float coef,
                                                                          const float *__restrict__ wd, float *__restrict__ Y,
-                                                                         int HW, int iters, const uint8_t *__restrict__ seg = nullptr) {
+                                                                         int HW, int iters, const uint8_t *__restrict__ seg = nullptr,
+                                                                         Tap0Weights<WT> w0 = {}) {
     __shared__ float A1s[HAS_D ? 2 * 32 * 64 : 64];   // [cout half][k step][lane]: coef * D[cout][k]
     __shared__ float A2s[32 * 64];                    // [k step][lane]: W'[(tap, i) = lane31][c]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -66,6 +79,8 @@ __global__ __launch_bounds__(256, J == 2 ? 3 : 4) void conv1_bwd_gemm_kernel(con
         const_cast<float *>(HAS_G ? g + (size_t)n * 64 * HW : F), 0, 64u * rowb, 0x00020000);
     const __amdgpu_buffer_rsrc_t rY = __builtin_amdgcn_make_buffer_rsrc(Y + (size_t)n * kTaps * HW, 0, (unsigned)kTaps * rowb,
                                                                        0x00020000);
+    const __amdgpu_buffer_rsrc_t rW = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(weights_of(w0, F) + (WT ? (size_t)n * HW : 0)), 0, rowb,
+                                                                       0x00020000);
     auto ld = [&](const __amdgpu_buffer_rsrc_t &r, unsigned vo, unsigned so, float (&dst)[J]) __attribute__((always_inline)) {
         if (J == 2) {
             const f32x2 t = __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(r, vo, so, 0));
@@ -86,6 +101,10 @@ __global__ __launch_bounds__(256, J == 2 ? 3 : 4) void conv1_bwd_gemm_kernel(con
         f32x16 acc1[J][2];          // [pixel j][channel half]
 #pragma unroll
         for (int s = 0; s < 32; ++s) ld(rF, voff, (unsigned)(32 * (s >> 4) + acc_row(s & 15, 0)) * rowb, Fv[s]);
+        float wv[J];
+#pragma unroll
+        for (int j = 0; j < J; ++j) wv[j] = 0.f;
+        if constexpr (WT) ld(rW, px < HW ? (unsigned)px * 4u : kOob, 0u, wv);
 #pragma unroll
         for (int s = 0; s < 32; ++s) {
             float t[J];
@@ -102,8 +121,10 @@ __global__ __launch_bounds__(256, J == 2 ? 3 : 4) void conv1_bwd_gemm_kernel(con
                 const float a0 = A1s[s * 64 + lane], a1 = A1s[2048 + s * 64 + lane];
 #pragma unroll
                 for (int j = 0; j < J; ++j) {
-                    acc1[j][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, Fv[s][j], acc1[j][0], 0, 0, 0);
-                    acc1[j][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, Fv[s][j], acc1[j][1], 0, 0, 0);
+                    float b1 = Fv[s][j];
+                    if constexpr (WT) b1 *= wv[j];          // (NaN / Inf as the product says: NaN under weight 0 stays NaN)
+                    acc1[j][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc1[j][0], 0, 0, 0);
+                    acc1[j][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc1[j][1], 0, 0, 0);
                 }
             }
         }
@@ -183,7 +204,8 @@ __global__ __launch_bounds__(256) void conv1_bwd_gather_masked_kernel(const floa
 }
 
 int conv1_bwd_run(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed, void *workspace,
-                  size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg, const uint8_t *mask, hipStream_t s);
+                  size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg, const uint8_t *mask, hipStream_t s,
+                  const float *w0 = nullptr);
 
 }  // namespace
 
@@ -212,9 +234,24 @@ extern "C" int st3d_conv1_bwd_masked(const float *gy, const float *act, const fl
     return conv1_bwd_run(gy, act, D, coef, w_dgrad_packed, workspace, workspace_bytes, gx, N, H, W, seg, mask, st3d::as_stream(stream));
 }
 
+// The bottom of the guided style loss: t = gy + coef * D (w0[p] act[:, p]) with w0 (N,H,W) one weight per pixel, applied
+// to the activation before GEMM 1; the gate is the sign of the unweighted activation.  seg and mask both NULL: the
+// unmasked form; both given: st3d_conv1_bwd_masked's.  Without D there is nothing to weight: st3d_conv1_bwd[_masked] itself.
+extern "C" int st3d_conv1_bwd_weighted(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed,
+                                       void *workspace, size_t workspace_bytes, float *gx, int N, int H, int W, const float *w0,
+                                       const uint8_t *seg, const uint8_t *mask, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(w0);
+    ST3D_CHECK_ARG((seg == nullptr) == (mask == nullptr));
+    ST3D_CHECK_ARG(!seg || (W > 0 && (W % 64) == 0));
+    ST3D_CHECK_ARG(((uintptr_t)w0 & 7) == 0);
+    return conv1_bwd_run(gy, act, D, coef, w_dgrad_packed, workspace, workspace_bytes, gx, N, H, W, seg, mask, st3d::as_stream(stream),
+                         w0);
+}
+
 namespace {
 int conv1_bwd_run(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed, void *workspace,
-                  size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg, const uint8_t *mask, hipStream_t s) {
+                  size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg, const uint8_t *mask, hipStream_t s,
+                  const float *w0) {
     ST3D_CHECK_ARG(act && w_dgrad_packed && workspace && gx);
     ST3D_CHECK_ARG(gy || D);
     ST3D_CHECK_ARG(N > 0 && st3d_conv1_bwd_supported(H, W));
@@ -232,7 +269,20 @@ int conv1_bwd_run(const float *gy, const float *act, const float *D, float coef,
         else if (D) conv1_bwd_gemm_kernel<true, false, JJ, MM><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters, seg);   \
         else conv1_bwd_gemm_kernel<false, true, JJ, MM><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters, seg);          \
     } while (0)
-    if (seg) {
+#define ST3D_TAP0_LAUNCH_W(JJ, MM)                                                                                            \
+    do {                                                                                                                      \
+        if (gy) conv1_bwd_gemm_kernel<true, true, JJ, MM, true><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters, seg, w0);  \
+        else conv1_bwd_gemm_kernel<true, false, JJ, MM, true><<<grid, 256, 0, s>>>(gy, act, D, coef, w_dgrad_packed, Y, HW, iters, seg, w0);    \
+    } while (0)
+    if (w0 && D) {
+        if (seg) {
+            if (J == 1) ST3D_TAP0_LAUNCH_W(1, true);
+            else ST3D_TAP0_LAUNCH_W(2, true);
+        } else {
+            if (J == 1) ST3D_TAP0_LAUNCH_W(1, false);
+            else ST3D_TAP0_LAUNCH_W(2, false);
+        }
+    } else if (seg) {
         if (J == 1) ST3D_TAP0_LAUNCH(1, true);
         else ST3D_TAP0_LAUNCH(2, true);
     } else {
@@ -240,6 +290,7 @@ int conv1_bwd_run(const float *gy, const float *act, const float *D, float coef,
         else ST3D_TAP0_LAUNCH(2, false);
     }
 #undef ST3D_TAP0_LAUNCH
+#undef ST3D_TAP0_LAUNCH_W
     ST3D_LAUNCH_CHECK();
     if (mask) conv1_bwd_gather_masked_kernel<<<dim3(st3d::cdiv(HW, 256), N), 256, 0, s>>>(Y, mask, gx, H, W);
     else conv1_bwd_gather_kernel<<<dim3(st3d::cdiv(HW, 256), N), 256, 0, s>>>(Y, gx, H, W);

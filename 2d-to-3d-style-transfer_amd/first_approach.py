@@ -32,14 +32,15 @@ def build_parser():
     return make_parser(FLAGS)
 
 
-def _phase_a_start(run, args, content, cams, style):
-    """Initial pixels of the 2-D style transfer (reference :167-175)."""
+def _phase_a_start(run, args, content, outline, cams, style):
+    """Initial pixels of the 2-D style transfer (reference :167-175) and the coverage of the render they come from
+    (--style_mask object; for 'noise' the object is where the content render has it)."""
     if args.style_transfer_init == 'content':
-        return content
+        return content, outline
     if args.style_transfer_init == 'noise':
-        return torch.rand(content.shape, device=run.device)
+        return torch.rand(content.shape, device=run.device), outline
     img, cov = render_meshes(run.renderer, run.current_mesh(), cams)          # 'current'
-    return apply_background(img, cov, background_type=args.current_background, background=style)
+    return apply_background(img, cov, background_type=args.current_background, background=style), cov
 
 
 def main(argv=None):
@@ -60,11 +61,12 @@ def main(argv=None):
             with torch.no_grad():
                 img, outline = render_meshes(run.renderer, run.content_mesh, cams)    # outline: --silhouette_weight's target
                 content = apply_background(img, outline, background_type=args.content_background, background=style)
-                start = _phase_a_start(run, args, content, cams, style)
+                start, region = _phase_a_start(run, args, content, outline, cams, style)
             # phase A: the whole batch is stylised at once; the result may leave [0,1], hence the clamp
             targets = finalize_tensor(style_transfer(start, content, style, run.vgg, steps=args.n_style_transfer_steps,
                                                      style_weight=args.style_weight, content_weight=args.content_weight,
-                                                     lr=args.style_transfer_lr))
+                                                     lr=args.style_transfer_lr,
+                                                     style_masks=region if args.style_mask == 'object' else None))
             run.save_views(targets, vb.lo)
 
         # phase B: masked MSE between the renders and the stylised views

@@ -28,9 +28,10 @@ device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
 class _PerceptualFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, current, plan, style_weight, content_weight, batch_denom, need_mask=None, flat_color=None):
+    def forward(ctx, current, plan, style_weight, content_weight, batch_denom, need_mask=None, flat_color=None, style_mask=None):
         loss, grad = plan.loss(current, style_weight, content_weight, batch_denom=batch_denom,
-                               want_grad=current.requires_grad, need_mask=need_mask, flat_color=flat_color)
+                               want_grad=current.requires_grad, need_mask=need_mask, flat_color=flat_color,
+                               style_mask=style_mask)
         ctx.grad = grad
         ctx.parts = loss.clone()
         return loss[0].clone()
@@ -38,12 +39,26 @@ class _PerceptualFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         g = ctx.grad * grad_out if ctx.grad is not None else None
-        return g, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None
 
 
 #method for the second approach
+def check_style_masks(style_masks, n, S):
+    """None, or the guidance of the style term: (n,1,S,S) or (n,S,S) on the GPU, values in [0,1] (a render's coverage)"""
+    if style_masks is None:
+        return None
+    if not torch.is_tensor(style_masks):
+        raise TypeError("style_masks must be a tensor (n,1,S,S) or (n,S,S)")
+    if not style_masks.is_cuda:
+        raise RuntimeError("st3d runs on the GPU (libst3d); got CPU style_masks -- there is no CPU fallback")
+    shp = tuple(style_masks.shape)
+    if shp not in ((n, 1, S, S), (n, S, S)):
+        raise ValueError(f"style_masks must be ({n},1,{S},{S}) or ({n},{S},{S}), got {shp}")
+    return style_masks.detach().to(torch.float32)
+
+
 def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style_weight=1e6, content_weight=1, *,
-                            batch_denom=None):
+                            batch_denom=None, style_masks=None):
 
     # Ensure content_imgs and style_imgs are batched tensors
     assert current_imgs.shape[0] == content_imgs.shape[0] == style_imgs.shape[0]
@@ -53,6 +68,10 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
         raise RuntimeError("st3d runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
 
     B, S = current_imgs.shape[0], current_imgs.shape[2]
+    # style_masks: the guided style loss (Gatys et al. 2017) -- each style tap's Gram of the current images is taken over
+    # the masked region (the object's coverage), so the background neither takes part in the style term nor draws its
+    # gradient; the style targets stay the plain Grams, the content term is unchanged, the masks carry no gradient
+    style_masks = check_style_masks(style_masks, B, S)
     plan = model.plan(B, S)
     plan.set_content(content_imgs)          # conv4_2 of content      (reference :18)
     plan.set_style(style_imgs, B)           # Grams of style features (reference :19-25)
@@ -70,7 +89,7 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
     flat = _render.flat_of(current_imgs)
 
     # batch_denom: the batch the means divide by -- the GLOBAL batch when views are sharded over ranks
-    return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need, flat)
+    return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need, flat, style_masks)
 
 
 class _FusedLossFn(torch.autograd.Function):
@@ -278,10 +297,10 @@ def compute_first_approach_loss(rendered, masks, target_rendered, verts, target_
 
 
 def compute_second_approach_loss(current, content, style, model, style_weight, content_weight, verts, target_verts, mesh,
-                                 weights, opt_type, *, batch_denom=None):
+                                 weights, opt_type, *, batch_denom=None, style_masks=None):
     if opt_type in ('texture', 'mesh', 'both'):
         perceptual = compute_perceptual_loss(current, content, style, model, style_weight=style_weight,
-                                             content_weight=content_weight, batch_denom=batch_denom)
+                                             content_weight=content_weight, batch_denom=batch_denom, style_masks=style_masks)
     if opt_type == 'texture':
         loss = perceptual                                   # no main_loss_weight here (reference :103-104)
     elif opt_type in ('mesh', 'both'):

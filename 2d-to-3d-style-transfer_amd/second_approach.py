@@ -70,7 +70,8 @@ def main(argv=None):
             loss = compute_second_approach_loss(
                 current=current, content=content, style=style, model=run.vgg, style_weight=args.style_weight,
                 content_weight=args.content_weight, verts=run.opt['verts'], target_verts=run.original_verts, mesh=mesh,
-                weights=run.loss_weights, opt_type=args.optimization_target, batch_denom=vb.size)
+                weights=run.loss_weights, opt_type=args.optimization_target, batch_denom=vb.size,
+                style_masks=cov if args.style_mask == 'object' else None)      # this rank's views, their own coverage
             extra = run.regularisers(current, cov, mesh, vb.hi - vb.lo, vb.size)
             if torch.is_tensor(extra):              # every weight is 0 by default: nothing is added, as in the reference
                 loss = loss + extra

@@ -102,6 +102,8 @@ SIGNATURES = {
                                c_stream]),
     "st3d_conv1_bwd_masked": (c_int, [c_f32p, c_f32p, c_f32p, c_float, c_f32p, ctypes.c_void_p, c_size, c_f32p, c_int, c_int, c_int,
                                       c_u8p, c_u8p, c_stream]),
+    "st3d_conv1_bwd_weighted": (c_int, [c_f32p, c_f32p, c_f32p, c_float, c_f32p, ctypes.c_void_p, c_size, c_f32p, c_int, c_int, c_int,
+                                        c_f32p, c_u8p, c_u8p, c_stream]),
     "st3d_wino_supported": (c_int, [c_int, c_int, c_int, c_int]),
     "st3d_wino_packed_floats": (c_size, [c_int, c_int]),
     "st3d_wino_pack": (c_int, [c_f32p, c_int, c_int, c_f32p, c_f32p, c_stream]),
@@ -140,6 +142,12 @@ SIGNATURES = {
     "st3d_gram_fwd_multi": (c_int, [ctypes.c_void_p, c_int, ctypes.c_void_p, c_size, c_stream]),
     "st3d_gram_bwd": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_float, c_int, c_f32p, c_stream]),
     "st3d_gram_bwd_gated": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_float, c_int, c_f32p, c_stream]),
+    "st3d_guidance_floats": (c_size, [c_int, c_int]),
+    "st3d_guidance_partials": (c_size, [c_int, c_int]),
+    "st3d_guidance_build": (c_int, [c_f32p, c_int, c_int, c_f32p, c_f32p, c_f32p, c_stream]),
+    "st3d_gram_fwd_weighted": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_f32p, c_stream]),
+    "st3d_gram_fwd_multi_weighted": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, c_size, c_stream]),
+    "st3d_gram_bwd_weighted": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_float, c_int, c_int, c_f32p, c_stream]),
     "st3d_reduce_partials": (c_int, []),
     "st3d_sqdiff_sum": (c_int, [c_f32p, c_f32p, c_size, c_size, c_float, c_f32p, c_f32p, c_f32p, c_stream]),
     "st3d_sqdiff_sum_multi": (c_int, [ctypes.c_void_p, c_int, c_f32p, c_f32p, c_int, c_int, c_float, c_float, c_stream]),
@@ -165,6 +173,7 @@ SIGNATURES = {
     "st3d_plan_get_content_features": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_stream]),
     "st3d_plan_set_content_features": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_stream]),
     "st3d_plan_set_style": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_stream]),
+    "st3d_plan_set_style_guidance": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_stream]),
     "st3d_plan_loss": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_stream]),
     "st3d_plan_loss_masked": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_u8p, c_stream]),
     "st3d_plan_loss_flat": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_u8p, c_f32p,

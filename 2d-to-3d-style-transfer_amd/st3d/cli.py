@@ -23,6 +23,7 @@ Flag = namedtuple("Flag", "name type default help choices nargs", defaults=(None
 _BACKGROUNDS = ['noise', 'style', 'white']
 _TARGETS = ['texture', 'mesh', 'both']
 _LIGHTS = ['ambient', 'point', 'directional', 'headlight']
+_STYLE_MASKS = ['none', 'object']
 
 # name, type, default and choices are the reference's (first_approach.py:23-45, second_approach.py:23-42); note
 # `type=bool` flags keep argparse's "any non-empty string is True" behaviour of the reference.
@@ -59,6 +60,9 @@ SHARED_FLAGS = [
     Flag("silhouette_sigma", float, 1e-4, "sigma of the soft silhouette (SoftSilhouetteShader's BlendParams.sigma)"),
     Flag("silhouette_faces_per_pixel", int, None, "faces per pixel of the silhouette term, 1..64, on the silhouette rasteriser "
          "(PyTorch3D's silhouette tutorial uses 50); unset = the general rasteriser at 8"),
+    Flag("style_mask", str, 'none', "region the style term's Gram matrices are taken over: 'none' = the whole image (the "
+         "reference's loss), 'object' = the coverage of each render being optimised (guided Gram matrices, Gatys et al. 2017), "
+         "so that the background neither takes part in the style term nor draws its gradient", _STYLE_MASKS),
     Flag("texture_pyramid_levels", int, 1, "optimise the texture as the sum of N maps of halving sides, so that texels no "
          "rendered pixel touches move with their neighbours; 1 = the plain map, 0 = as many levels as the side allows "
          "(down to a side of 4..7).  Every level moves by about lr a step, their sum by up to N x lr"),

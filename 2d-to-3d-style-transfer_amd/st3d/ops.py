@@ -601,6 +601,20 @@ def conv1_bwd_masked(gy, act, D, coef, wd, seg, mask):
     return gx
 
 
+def conv1_bwd_weighted(gy, act, D, coef, wd, w0, seg=None, mask=None):
+    """gx = conv1_1^T(gate(gy + coef * D (w0 act))), w0 (N,H,W) one weight per pixel (st3d_conv1_bwd_weighted); with seg and
+    mask: at the pixels of mask only, as conv1_bwd_masked."""
+    N, C, H, W = act.shape
+    nb = _lib.load().st3d_conv1_bwd_workspace_bytes(N, H, W)
+    ws = torch.empty((nb // 4,), dtype=F32, device=act.device)
+    gx = torch.empty((N, 3, H, W), dtype=F32, device=act.device)
+    if w0.numel() != N * H * W:
+        raise _lib.St3dError(f"w0 has {w0.numel()} values for {N} x {H} x {W} pixels")
+    call("st3d_conv1_bwd_weighted", dptr(gy, F32), dptr(act, F32), dptr(D, F32), float(coef), dptr(wd, F32), dptr(ws), nb,
+         dptr(gx), N, H, W, dptr(w0.contiguous(), F32), dptr(seg, U8), dptr(mask, U8), stream_ptr())
+    return gx
+
+
 def need_levels(S):
     return _lib.load().st3d_need_levels(int(S))
 
@@ -777,14 +791,65 @@ def maxpool2x2(y, want_idx=True):
 
 
 # ------------------------------------------------------------------ gram / losses
-def gram_fwd(feat):
-    """(B,C,H,W) or (B,C,HW) -> (B,C,C) unnormalised Gram (style_transfer.py:31-35)."""
+GUIDANCE_LEVELS = 5
+
+
+def guidance_sides(S):
+    """sides of the five guidance planes: the style taps' (each pool floors)"""
+    return [S >> l for l in range(GUIDANCE_LEVELS)]
+
+
+def _guidance_mask(mask):
+    """(n,1,S,S) or (n,S,S) fp32 device tensor -> contiguous (n,S,S)"""
+    if not torch.is_tensor(mask):
+        raise _lib.St3dError("the guidance mask is a tensor (n,1,S,S) or (n,S,S)")
+    if mask.dim() == 4 and mask.shape[1] == 1:
+        mask = mask[:, 0]
+    if mask.dim() != 3 or mask.shape[1] != mask.shape[2] or mask.shape[0] < 1 or mask.shape[1] < 16:
+        raise _lib.St3dError(f"the guidance mask is (n,1,S,S) or (n,S,S) with S >= 16; got {tuple(mask.shape)}")
+    if not mask.is_cuda:
+        raise _lib.St3dError("libst3d takes device tensors; got a CPU mask (no CPU fallback)")
+    if mask.dtype != F32:
+        raise _lib.St3dError(f"expected {F32}, got {mask.dtype}")
+    return mask.detach().contiguous()
+
+
+def guidance_build(mask):
+    """mask (n,1,S,S) | (n,S,S) in [0,1] -> (planes, sums): planes[l] (n,H_l,H_l) = q_l = sqrt(a_l H_l^2 / Sigma_l) with a_l
+    the 2x2 average pyramid of the mask (views of one buffer), sums (5,n) = Sigma_l (st3d_guidance_build)."""
+    m = _guidance_mask(mask)
+    n, S = m.shape[0], m.shape[1]
+    lib = _lib.load()
+    q = torch.empty((lib.st3d_guidance_floats(n, S),), dtype=F32, device=m.device)
+    sums = torch.empty((GUIDANCE_LEVELS, n), dtype=F32, device=m.device)
+    parts = torch.empty((lib.st3d_guidance_partials(n, S),), dtype=F32, device=m.device)
+    call("st3d_guidance_build", dptr(m, F32), n, S, dptr(q), dptr(sums), dptr(parts), stream_ptr())
+    planes, off = [], 0
+    for H in guidance_sides(S):
+        planes.append(q[off:off + n * H * H].view(n, H, H))
+        off += n * H * H
+    return planes, sums
+
+
+def _check_q(q, B, HW):
+    if q.numel() != B * HW:
+        raise _lib.St3dError(f"the weight plane has {q.numel()} values, the features {B} x {HW} pixels")
+    return dptr(q.contiguous(), F32)
+
+
+def gram_fwd(feat, q=None):
+    """(B,C,H,W) or (B,C,HW) -> (B,C,C) unnormalised Gram (style_transfer.py:31-35).  q (B,H,W) | (B,HW): the guided Gram
+    sum_p q[p]^2 F[:,p] F[:,p]^T (st3d_gram_fwd_weighted; q from guidance_build)."""
     B, C = feat.shape[:2]
     HW = feat[0, 0].numel()
     ws_bytes = _lib.load().st3d_gram_workspace_bytes(B, C, HW)
     ws = torch.empty((max(ws_bytes // 4, 1),), dtype=F32, device=feat.device)
     g = torch.empty((B, C, C), dtype=F32, device=feat.device)
-    call("st3d_gram_fwd", dptr(feat.contiguous(), F32), B, C, HW, dptr(ws), ws_bytes, dptr(g), stream_ptr())
+    if q is None:
+        call("st3d_gram_fwd", dptr(feat.contiguous(), F32), B, C, HW, dptr(ws), ws_bytes, dptr(g), stream_ptr())
+    else:
+        call("st3d_gram_fwd_weighted", dptr(feat.contiguous(), F32), _check_q(q, B, HW), B, C, HW, dptr(ws), ws_bytes, dptr(g),
+             stream_ptr())
     return g
 
 
@@ -792,8 +857,9 @@ class _GramItem(ctypes.Structure):
     _fields_ = [("feat", ctypes.c_void_p), ("gram", ctypes.c_void_p), ("B", ctypes.c_int), ("C", ctypes.c_int), ("HW", ctypes.c_int)]
 
 
-def gram_fwd_multi(feats):
-    """[(B,C,H,W) ...] -> [(B,C,C) ...]: the Grams of several layers in one launch pair (st3d_gram_fwd_multi)."""
+def gram_fwd_multi(feats, qs=None):
+    """[(B,C,H,W) ...] -> [(B,C,C) ...]: the Grams of several layers in one launch pair (st3d_gram_fwd_multi); qs: one
+    weight plane per layer (st3d_gram_fwd_multi_weighted)."""
     feats = [f.contiguous() for f in feats]
     grams = [torch.empty((f.shape[0], f.shape[1], f.shape[1]), dtype=F32, device=f.device) for f in feats]
     items = (_GramItem * len(feats))()
@@ -802,18 +868,30 @@ def gram_fwd_multi(feats):
     nb = _lib.load().st3d_gram_multi_workspace_bytes(items, len(feats))
     ws = torch.empty((max(nb // 4, 64),), dtype=F32, device=feats[0].device)
     assert ws.data_ptr() % 256 == 0
-    call("st3d_gram_fwd_multi", items, len(feats), dptr(ws), nb, stream_ptr())
+    if qs is None:
+        call("st3d_gram_fwd_multi", items, len(feats), dptr(ws), nb, stream_ptr())
+    else:
+        if len(qs) != len(feats):
+            raise _lib.St3dError("one weight plane per layer")
+        qs = [q.contiguous() for q in qs]
+        qp = (ctypes.c_void_p * len(feats))(*[_check_q(q, f.shape[0], f[0, 0].numel()) for q, f in zip(qs, feats)])
+        call("st3d_gram_fwd_multi_weighted", items, qp, len(feats), dptr(ws), nb, stream_ptr())
     return grams
 
 
-def gram_bwd(D, feat, coef, out=None, gated=False):
-    """out (+)= coef * D feat; gated: then zeroed where feat <= 0 (st3d_gram_bwd_gated)."""
+def gram_bwd(D, feat, coef, out=None, gated=False, q=None):
+    """out (+)= coef * D feat; gated: then zeroed where feat <= 0 (st3d_gram_bwd_gated).  q: the guided term's gradient
+    out (+)= coef * q (D (q feat)) (st3d_gram_bwd_weighted)."""
     B, C = feat.shape[:2]
     HW = feat[0, 0].numel()
     acc = 1
     if out is None:
         out = torch.empty_like(feat)
         acc = 0
+    if q is not None:
+        call("st3d_gram_bwd_weighted", dptr(D.contiguous(), F32), dptr(feat.contiguous(), F32), _check_q(q, B, HW), B, C, HW,
+             float(coef), acc, 1 if gated else 0, dptr(out), stream_ptr())
+        return out
     call("st3d_gram_bwd_gated" if gated else "st3d_gram_bwd", dptr(D.contiguous(), F32), dptr(feat.contiguous(), F32), B, C, HW, float(coef), acc, dptr(out),
          stream_ptr())
     return out

@@ -273,15 +273,38 @@ class PerceptualPlan:
             cache[key] = torch.tensor(key, dtype=torch.float32, device=self.vgg.device)
         return cache[key]
 
-    def loss(self, current, style_weight, content_weight, batch_denom=None, want_grad=True, need_mask=None, flat_color=None):
+    def set_style_guidance(self, mask, n=None):
+        """mask (n,1,S,S) | (n,S,S) fp32 in [0,1]: the style term of every later loss call over n images takes each tap's Gram
+        over the guided region (st3d_plan_set_style_guidance); None clears."""
+        if mask is None:
+            if self.__dict__.get("_guided"):
+                call("st3d_plan_set_style_guidance", self._h, None, 0, stream_ptr())
+                self._guided = False
+            return
+        m = mask.detach()
+        if m.dim() == 4 and m.shape[1] == 1:
+            m = m[:, 0]
+        if m.dim() != 3 or tuple(m.shape[1:]) != (self.S, self.S) or (n is not None and m.shape[0] != n):
+            raise _lib.St3dError(f"style_mask must be ({n if n is not None else 'n'},1,{self.S},{self.S}) or (n,{self.S},{self.S}), "
+                                 f"got {tuple(mask.shape)}")
+        if not m.is_cuda:
+            raise _lib.St3dError("libst3d takes device tensors; got a CPU style_mask (no CPU fallback)")
+        m = m.to(torch.float32).contiguous()
+        call("st3d_plan_set_style_guidance", self._h, dptr(m, torch.float32), m.shape[0], stream_ptr())
+        self._guided = True
+
+    def loss(self, current, style_weight, content_weight, batch_denom=None, want_grad=True, need_mask=None, flat_color=None,
+             style_mask=None):
         """-> (loss_buf view [total, content, style], grad (n,3,S,S) or None).
         need_mask (n,S,S) uint8: the only pixels at which the caller's consumer reads grad (st3d_plan_loss_masked) -- grad
         is the same there, bit for bit, and 0 elsewhere; the bottom of the VGG backward computes only what they need.
         flat_color (3 floats): `current` holds this colour at many pixels, as a render holds its background
         (st3d_plan_loss_flat): the shallow forward convs compute the tiles that see anything else and copy the rest.  The
-        results are the same bits; the colour only decides whether the lists are built."""
+        results are the same bits; the colour only decides whether the lists are built.
+        style_mask (n,1,S,S) | (n,S,S) in [0,1]: the guided style loss -- set before the call, cleared when absent."""
         cur = current.detach().to(torch.float32).contiguous()
         n = cur.shape[0]
+        self.set_style_guidance(style_mask, n)
         grad = torch.empty_like(cur) if want_grad else None
         if need_mask is not None and want_grad:
             if need_mask.dtype != torch.uint8 or tuple(need_mask.shape) != (n, self.S, self.S):

@@ -112,7 +112,39 @@ def gram_matrix(tensor):
     return _GramFn.apply(tensor)
 
 
-def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, steps=2000, style_weight=1e6, content_weight=1, lr=0.003):
+class _GuidedGramFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tensor, q):
+        t = tensor.detach().to(torch.float32).contiguous()
+        ctx.save_for_backward(t, q)
+        return _ops.gram_fwd(t, q=q)
+
+    @staticmethod
+    def backward(ctx, grad_gram):
+        t, q = ctx.saved_tensors
+        D = (grad_gram + grad_gram.transpose(1, 2)).contiguous()       # dF = q o ((dG + dG^T) (q o F))
+        return _ops.gram_bwd(D, t, 1.0, q=q), None
+
+
+def guided_gram_matrix(tensor, mask):
+    """The Gram of ``tensor`` (B,C,H,W) taken over the guided region (Gatys et al. 2017): ``mask`` (B,1,S,S) or (B,S,S) in
+    [0,1] is brought to H x H by 2x2 averages (S / H one of 1, 2, 4, 8, 16) and normalised to mean 1 over the image, and
+    G^ = sum_p w[p] F[:,p] F[:,p]^T.  Gradient to ``tensor``; the mask is a constant."""
+    batch_size, d, h, w = tensor.size()
+    if not tensor.is_cuda:
+        raise RuntimeError("st3d guided_gram_matrix runs on the GPU (libst3d); got a CPU tensor -- there is no CPU fallback")
+    planes, _ = _ops.guidance_build(mask)
+    for q in planes:
+        if q.shape[0] == batch_size and q.shape[1] == h and q.shape[2] == w:
+            return _GuidedGramFn.apply(tensor, q)
+    raise ValueError(f"features of {h} x {w} are no style-tap resolution of a mask of side {planes[0].shape[1]} "
+                     f"(sides {[int(p.shape[1]) for p in planes]})")
+
+
+def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, steps=2000, style_weight=1e6, content_weight=1, lr=0.003,
+                   style_masks=None):
+    # style_masks (B,1,S,S) | (B,S,S) in [0,1], e.g. the coverage of the renders being stylised: the guided style loss --
+    # each tap's Gram of the optimised images is taken over the masked region only (default None: the reference's loss)
 
     # Ensure content_imgs and style_imgs are batched tensors
     assert initial_optimized_imgs.shape[0] == content_imgs.shape[0] == style_imgs.shape[0]
@@ -121,6 +153,10 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
 
     B, S = initial_optimized_imgs.shape[0], initial_optimized_imgs.shape[2]
     plan = model.plan(B, S)
+    if style_masks is not None:
+        if not torch.is_tensor(style_masks) or tuple(style_masks.shape) not in ((B, 1, S, S), (B, S, S)):
+            raise ValueError(f"style_masks must be ({B},1,{S},{S}) or ({B},{S},{S})")
+        style_masks = style_masks.detach().to(device=device, dtype=torch.float32)
 
     # content conv4_2 features and style Grams: computed once (reference :44-51)
     plan.set_content(content_imgs.to(device), force=True)
@@ -133,7 +169,7 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
     optimizer = _st3d_optim.Adam([optimized_imgs], lr=lr, reduce_grads=False)
 
     for step in tqdm(range(steps), desc="2D Style Transfer"):
-        _, grad = plan.loss(optimized_imgs, style_weight, content_weight)
+        _, grad = plan.loss(optimized_imgs, style_weight, content_weight, style_mask=style_masks)
         optimized_imgs.grad = grad
         optimizer.step()
 

@@ -347,6 +347,12 @@ int st3d_conv1_bwd(const float *gy, const float *act, const float *D, float coef
 int st3d_conv1_bwd_masked(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed,
                           void *workspace, size_t workspace_bytes, float *gx, int N, int H, int W, const uint8_t *seg,
                           const uint8_t *mask, st3d_stream_t stream);
+/* The bottom pass of the guided style loss: t = gy + coef * D (w0[p] act[:,p]), w0 (N,H,W) one weight per pixel applied to
+ * the activation before the first product; the ReLU gate is the sign of the unweighted activation.  With D NULL there is nothing to weight (st3d_conv1_bwd's result).
+ * seg and mask both NULL: st3d_conv1_bwd's form; both given: st3d_conv1_bwd_masked's (W % 64 == 0). */
+int st3d_conv1_bwd_weighted(const float *gy, const float *act, const float *D, float coef, const float *w_dgrad_packed,
+                            void *workspace, size_t workspace_bytes, float *gx, int N, int H, int W, const float *w0,
+                            const uint8_t *seg, const uint8_t *mask, st3d_stream_t stream);
 /* As above, but gy is given at POOLED resolution (N,Cout,H/2,W/2) together with the pool's
  * argmax (uint8 0..3 = dy*2+dx) and pooled values: fuses max-unpool + ReLU gate into the load. */
 int st3d_conv3x3_dgrad_unpool(const float *gy_pooled, const uint8_t *pool_idx, const float *pooled,
@@ -474,6 +480,37 @@ int st3d_gram_bwd(const float *D, const float *feat, int B, int C, int HW, float
  * LDS), so the gradient leaves already gated (see st3d_wino_dgrad_chain).  C % 32 == 0. */
 int st3d_gram_bwd_gated(const float *D, const float *feat, int B, int C, int HW, float coef,
                         int accumulate, float *gfeat, st3d_stream_t stream);
+/* ---- guided style loss (default off): the Gram of a tap taken over a guided region (Gatys et al. 2017, spatial control).
+ * Guidance planes of a mask (n,1,S,S), fp32 in [0,1] (a render's 0/1 coverage), one per style tap l = 0..4:
+ *   H_0 = S, H_{l+1} = H_l / 2 (floor);  a_0 = mask;
+ *   a_{l+1}[y][x] = 0.25f * ((a_l[2y][2x] + a_l[2y][2x+1]) + (a_l[2y+1][2x] + a_l[2y+1][2x+1]));
+ *   Sigma_l = sum_p a_l[p] per image (ordered two-stage reduction: bitwise reproducible; exact for 0/1 masks up to S = 4096);
+ *   r_l = (float)(H_l^2) / Sigma_l, or 0 when Sigma_l is not > 0;   w_l = a_l r_l;   q_l = sqrtf(w_l)
+ * (correctly rounded division and square root).  A value outside [0,1] is the caller's business: a negative one gives NaN.
+ * st3d_guidance_build writes the q_l planes one after the other into q_out (st3d_guidance_floats(n, S) floats: level l is
+ * (n, H_l, H_l) and starts n * (H_0^2 + .. + H_{l-1}^2) floats in) and Sigma into sums_out (5 x n floats, [l * n + image]);
+ * partials: st3d_guidance_partials(n, S) floats of scratch.  S >= 16.  Two launches, no atomics, nothing allocated. */
+size_t st3d_guidance_floats(int n, int S);
+size_t st3d_guidance_partials(int n, int S);
+int st3d_guidance_build(const float *mask, int n, int S, float *q_out, float *sums_out, float *partials,
+                        st3d_stream_t stream);
+/* The guided Gram  gram[b] = sum_p w[b][p] F[:,p] F[:,p]^T  computed as the Gram of q o F, q (B,HW) one plane of
+ * st3d_guidance_build: both operand tiles are multiplied by q[p] on their way into LDS (no scaled copy of the activation
+ * exists anywhere).  Workspace, splits, kernels' bodies and reduce are those of st3d_gram_fwd: symmetric bit for bit, and
+ * q == 1 gives st3d_gram_fwd's bits.  NaN / Inf propagate as the products say (NaN under q = 0 stays NaN). */
+int st3d_gram_fwd_weighted(const float *feat, const float *q, int B, int C, int HW, void *workspace,
+                           size_t workspace_bytes, float *gram, st3d_stream_t stream);
+/* All guided Grams of a step in one launch pair: q[i] (a HOST array of device pointers, parallel to items) is the plane
+ * of items[i].  Workspace as st3d_gram_fwd_multi.  Bitwise the results of st3d_gram_fwd_weighted per item. */
+int st3d_gram_fwd_multi_weighted(const st3d_gram_item *items, const float *const *q, int count, void *workspace,
+                                 size_t workspace_bytes, st3d_stream_t stream);
+/* Gradient of the guided style term: gfeat (B,C,HW) (+)= coef * q o (D (q o feat)), D (B,C,C) = G^ - S symmetric.  feat is
+ * staged as it is and multiplied by q[n] twice, fl(q fl(q feat)), as the operand leaves LDS (a column of the product is a
+ * column of that operand): the accumulators start from gfeat as in st3d_gram_bwd, and q == 1 gives its bits in every mode.
+ * gated != 0 (C % 32 == 0): gfeat = 0 where feat <= 0 -- the gate is the sign of feat itself, so with accumulate the
+ * gradient that arrived from the layers above passes wherever the ReLU was open, also under q = 0. */
+int st3d_gram_bwd_weighted(const float *D, const float *feat, const float *q, int B, int C, int HW, float coef,
+                           int accumulate, int gated, float *gfeat, st3d_stream_t stream);
 /* loss_out[0] += scale * sum((a-b)^2) over n elements (b broadcast with period nb, nb | n);
  * if D != NULL also D = a - b.  Deterministic two-stage reduction through `partials`
  * (>= st3d_reduce_partials() floats). */
@@ -585,6 +622,16 @@ int st3d_plan_set_content(st3d_plan *plan, const float *content, int n, st3d_str
 int st3d_plan_get_content_features(st3d_plan *plan, float *out, int n, st3d_stream_t stream);
 int st3d_plan_set_content_features(st3d_plan *plan, const float *features, int n, st3d_stream_t stream);
 int st3d_plan_set_style(st3d_plan *plan, const float *style, int style_batch, int n, st3d_stream_t stream);
+/* Guidance of the style term (default off): mask (n,1,S,S) fp32 in [0,1], NULL clears.  Builds the guidance planes
+ * (st3d_guidance_build) into buffers the plan owns -- allocated by the first call that sets a guidance, st3d_plan_bytes
+ * grows by st3d_guidance_floats(B, S) + B S^2 (w_0 = q_0^2 for the fused bottom pass) + 5 B + st3d_guidance_partials(B, S)
+ * floats -- and every later st3d_plan_loss* call with the same n takes the Gram of each style tap over the guided region:
+ * G^_l = sum_p w_l[p] F[:,p] F[:,p]^T in place of G_l, the gradient coef_l q o (D_l (q o F)).  The style targets stay the
+ * plain Grams of the style image, the content term is unchanged, the guidance carries no gradient.  A loss call with
+ * another n: ST3D_E_STATE.  Need masks, flat colours and graph replay work as without guidance (the planes' addresses
+ * never change; a captured step is keyed on whether a guidance is set).  st3d_plan_forward / _backward are unaffected.
+ * An image whose Sigma_l is 0 has G^_l = 0: its term is the constant ||S_l||^2 norm, with no gradient. */
+int st3d_plan_set_style_guidance(st3d_plan *plan, const float *mask, int n, st3d_stream_t stream);
 /* loss (losses.py:28-42) of current (n,3,S,S) and, if grad_current != NULL, d loss/d current.
  * batch_denom = the batch size the means divide by (n, or the GLOBAL batch when views are
  * sharded over ranks).  loss_out: device float[3] = {total, content_loss, style_loss}. */

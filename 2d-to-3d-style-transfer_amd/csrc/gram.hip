@@ -45,6 +45,12 @@ struct GemmArgsW : GemmArgs {
     const float *q; size_t sQ;      // weights' square roots, batch stride (elements)
 };
 template <bool W> using GemmArgsT = std::conditional_t<W, GemmArgsW, GemmArgs>;
+// The listed Gram backward (need.hip): workgroup i computes the 64-pixel run seg_list[i] = image * tiles_n + run, for i below
+// *seg_count (both in device memory); again a derived struct, so the unlisted kernels keep their arguments.
+template <typename A> struct Listed : A {
+    const int *seg_list; const int *seg_count;
+};
+template <bool W, bool LIST> using GemmArgsL = std::conditional_t<LIST, Listed<GemmArgsT<W>>, GemmArgsT<W>>;
 
 __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 
@@ -310,8 +316,10 @@ __global__ __launch_bounds__(256, 2) void gemm_w_kernel(const GemmArgsW g) {
 // with an explicit MFMA / LDS-read interleave and the next chunk's loads first.
 // (a template of the kernel itself, not a body shared by two kernels: inlined into a wrapper the unweighted code came
 // out with its instructions in another order; this way it is the parent's, instruction for instruction)
-template <bool W>
-__global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgsT<W> g) {
+// LIST (C = 128: one workgroup per 64-pixel run): the grid covers every run, workgroup i takes run seg_list[i] and ends at
+// once when i is at or past *seg_count; the runs nobody lists are not touched.  Under `if constexpr` like W.
+template <bool W, bool LIST = false>
+__global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgsL<W, LIST> g) {
     constexpr int TM = 128, TN = 64, KCH = 32, LA = TM + 4, LB = TN;
     constexpr unsigned kOob = 0x80000000u;
     typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -320,7 +328,15 @@ __global__ __launch_bounds__(256, 4) void gram_bwd_sym_kernel(const GemmArgsT<W>
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, lhi = lane >> 5;
     const int wm = wave >> 1, wn = wave & 1;
-    const int ti = blockIdx.x / g.tiles_n, tj = blockIdx.x % g.tiles_n, b = blockIdx.z;
+    unsigned bx = blockIdx.x;
+    int b = blockIdx.z;
+    if constexpr (LIST) {
+        if ((int)bx >= g.seg_count[0]) return;
+        const int e = g.seg_list[bx];
+        b = e / g.tiles_n;
+        bx = (unsigned)(e - b * g.tiles_n);
+    }
+    const int ti = bx / g.tiles_n, tj = bx % g.tiles_n;
     const int m0 = ti * TM, n0 = tj * TN;
     const unsigned rowD = (unsigned)g.lda * 4u, rowF = (unsigned)g.ldb * 4u;      // bytes per row of D / of F and the result
     const __amdgpu_buffer_rsrc_t rD = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(g.A + b * g.sA), 0,
@@ -942,6 +958,44 @@ extern "C" int st3d_gram_bwd_weighted(const float *D, const float *feat, const f
     return gram_bwd_launch<true>(D, feat, q, B, C, HW, coef, accumulate, gated ? 1 : 0, gfeat, stream);
 }
 
+// what the lean symmetric kernel takes (besides 16-byte aligned pointers)
+static bool gram_bwd_sym_shape(int C, int HW) { return C > 0 && HW > 0 && C % 128 == 0 && HW % 64 == 0 && (size_t)C * HW * 4 < (1ull << 31); }
+
+extern "C" int st3d_gram_bwd_segs_supported(int C, int HW) { return C == 128 && gram_bwd_sym_shape(C, HW) ? 1 : 0; }
+
+template <bool W>
+static int gram_bwd_segs_launch(const float *D, const float *feat, const float *qw, int B, int C, int HW, float coef, int accumulate,
+                                const int *seg_list, const int *seg_count, float *gfeat, st3d_stream_t stream) {
+    Listed<GemmArgsT<W>> g;
+    memset(&g, 0, sizeof(g));
+    if constexpr (W) { g.q = qw; g.sQ = (size_t)HW; }
+    g.gate = 1;
+    g.A = D; g.B = feat; g.C = gfeat;
+    g.M = C; g.N = HW; g.K = C; g.lda = C; g.ldb = HW; g.ldc = HW;
+    g.sA = (size_t)C * C; g.sB = g.sC = (size_t)C * HW;
+    g.nsplit = 1; g.kper = (C + 63) / 64 * 64; g.sSplit = 0;
+    g.tri = 0; g.coef = coef; g.accumulate = accumulate;
+    g.tiles_m = 1; g.tiles_n = HW / 64;
+    g.seg_list = seg_list; g.seg_count = seg_count;
+    gram_bwd_sym_kernel<W, true><<<dim3(B * g.tiles_n, 1, 1), 256, 0, st3d::as_stream(stream)>>>(g);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+// st3d_gram_bwd_gated (q == NULL) or st3d_gram_bwd_weighted, gated (q given), for the listed 64-pixel runs only: entry i of
+// seg_list (device, i < *seg_count) = image * (HW / 64) + run.  C = 128.  Listed runs of gfeat are bitwise what the full
+// launch writes, the others are not touched.
+extern "C" int st3d_gram_bwd_gated_segs(const float *D, const float *feat, const float *q, int B, int C, int HW, float coef,
+                                        int accumulate, const int *seg_list, const int *seg_count, float *gfeat,
+                                        st3d_stream_t stream) {
+    ST3D_CHECK_ARG(D && feat && gfeat && seg_list && seg_count);
+    ST3D_CHECK_ARG(B > 0 && st3d_gram_bwd_segs_supported(C, HW));
+    ST3D_CHECK_ARG((long)B * (HW / 64) < (1L << 31));
+    ST3D_CHECK_ARG((((uintptr_t)D | (uintptr_t)feat | (uintptr_t)gfeat) & 15) == 0);
+    return q ? gram_bwd_segs_launch<true>(D, feat, q, B, C, HW, coef, accumulate, seg_list, seg_count, gfeat, stream)
+             : gram_bwd_segs_launch<false>(D, feat, nullptr, B, C, HW, coef, accumulate, seg_list, seg_count, gfeat, stream);
+}
+
 // one of the general backward instantiations (BMODE 1), plain or weighted
 template <bool W, int MT, int NT, int BMODE, int DIAG = 0, int KCH = 32>
 static void gram_bwd_gemm(const GemmArgsT<W> &g, dim3 grid, hipStream_t s) {
@@ -987,7 +1041,7 @@ static int gram_bwd_launch(const float *D, const float *feat, const float *qw, i
     // (the branch-free FAST instantiation is forward-only: measured 3-8 % SLOWER on the backward shapes, with the explicit
     // schedule -- one or two LDS reads per MFMA -- and without it)
     static const bool sym = [] { const char *e = getenv("ST3D_GRAM_BWD_SYM"); return !(e && e[0] == '0'); }();
-    if (gate && sym && !force && !k64 && C % 128 == 0 && HW % 64 == 0 && (size_t)C * HW * 4 < (1ull << 31) &&
+    if (gate && sym && !force && !k64 && gram_bwd_sym_shape(C, HW) &&
         (((uintptr_t)D | (uintptr_t)feat | (uintptr_t)gfeat) & 15) == 0) {
         // the plan's call (symmetric D, whole tiles): the lean kernel
         g.tiles_m = C / 128; g.tiles_n = HW / 64;

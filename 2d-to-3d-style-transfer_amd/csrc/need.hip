@@ -14,16 +14,27 @@
 // map (one thread per segment), one flag per tile of either level (one thread per tile, straight from the segment map)
 // and one 1024-thread workgroup per list (ordered prefix-sum compaction of the flags: no atomics, the same list every
 // time).  At 8 x 512^2: 32768 segments, 8192 + 2048 tiles.
+//
+// PER BLOCK (st3d_need_blocks_build).  The rule above hands a whole listed tile, dilated, to the level above, so every level
+// grows by a tile.  An F(4x4,3x3) launch computes each aligned 4x4 output block from that block's own 6x6 input patch and
+// from nothing else, so need travels per block instead: with need_k the pixels at which the output of list k's launch is
+// needed (need_0 = dilate(mask, 1): the relu1_1 pass),
+//     B_k = block4(need_k)                          the blocks that have to be right
+//     list k = the tiles of the launch's geometry (4 x 64 or 8 x 32 pixels: 1 x 16 or 2 x 8 blocks) that hold one of B_k
+//     need_k+1 = dilate(B_k, 1), clipped to the map; through the 2x2 OR where launch k un-pools its input
+// An unneeded block of a listed tile may read input nobody wrote and write garbage; no needed block reads that garbage.
+// On block bitmaps: B_k+1 = the 3x3 block neighbourhood OR of B_k (same resolution) or, through the un-pool, the OR over
+// block rows / columns 2b - 1 .. 2b + 2.  Lists 0 .. 5 = the input gradients of conv1_2, conv2_1, conv2_2, conv3_1, conv3_2,
+// conv3_3; conv1_2 and conv2_2 un-pool.  Three launches: the front one writes the segment map and B_0 (one thread per
+// block, straight from the mask); one workgroup per image then walks the levels with the bitmaps in LDS (two buffers, (S/4)^2
+// + (S/8)^2 bytes) and writes one flag per tile; the compaction is the one above, one workgroup per list.
 #include "common.h"
 
 namespace {
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-__global__ __launch_bounds__(256) void need_segments_kernel(const uint8_t *__restrict__ mask, int S, int total,
-                                                            uint8_t *__restrict__ seg) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= total) return;
+__device__ __forceinline__ void need_segment(const uint8_t *__restrict__ mask, int S, int i, uint8_t *__restrict__ seg) {
     const int segs = S >> 6;
     const int sx = i % segs, y = (i / segs) % S, n = i / (segs * S);
     const uint8_t *m = mask + (size_t)n * S * S;
@@ -42,6 +53,12 @@ __global__ __launch_bounds__(256) void need_segments_kernel(const uint8_t *__res
         if (sx + 1 < segs) any |= row[64];
     }
     seg[i] = any ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void need_segments_kernel(const uint8_t *__restrict__ mask, int S, int total,
+                                                            uint8_t *__restrict__ seg) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < total) need_segment(mask, S, i, seg);
 }
 
 struct NeedGeo {
@@ -114,6 +131,128 @@ __global__ __launch_bounds__(1024) void need_lists_kernel(const uint8_t *__restr
     if (tid == 1023) counts[level] = scan[1023];
 }
 
+constexpr int kLists = ST3D_NEED_MAX_LISTS;
+constexpr int kListShift[kLists] = {0, 1, 1, 2, 2, 2};       // the map of list k is (S >> shift)^2
+constexpr int kListUnpools[kLists] = {1, 0, 1, 0, 0, 0};     // launch k reads its input through a 2x2 un-pool
+
+struct BlockLevels {
+    int nlists;
+    int bw[kLists];                  // blocks per row (and per column) of the map
+    int trows[kLists], tcols[kLists];        // a tile in blocks: 1 x 16 or 2 x 8
+    int unpools[kLists];
+    int off[kLists + 1];             // first flag of list k (all images); off[nlists] = the total
+    int *list[kLists];
+    // the Gram backward at relu2_1 (gram.hip): the 64-pixel runs of the (S/2)^2 map that meet need_2 = dilate(B_1, 1), numbered
+    // image * runs + run; their flags follow the tiles' (gram_runs per image, 0 = not asked for), compacted by one more workgroup
+    int gram_runs, gram_total;       // per image, all images
+    int *gram_list, *gram_count;
+};
+
+// The front launch: the first seg_wgs workgroups write the segment map (one thread per segment), the others B_0, one thread
+// per block: the block is needed when its 6x6 patch (rows / columns 4 b - 1 .. 4 b + 4) holds a mask pixel.  Rows and columns
+// past the edge are clamped back INTO the patch, so the 18 loads are unconditional and go out together.
+__global__ __launch_bounds__(256) void need_front_kernel(const uint8_t *__restrict__ mask, int S, int seg_total, int seg_wgs,
+                                                         uint8_t *__restrict__ seg, int b0_total, uint8_t *__restrict__ b0) {
+    if ((int)blockIdx.x < seg_wgs) {
+        const int i = blockIdx.x * 256 + threadIdx.x;
+        if (i < seg_total) need_segment(mask, S, i, seg);
+        return;
+    }
+    const int i = (blockIdx.x - seg_wgs) * 256 + threadIdx.x;
+    if (i >= b0_total) return;
+    const int bw = S >> 2;
+    const int bx = i % bw, by = (i / bw) % bw, n = i / (bw * bw);
+    const uint8_t *m = mask + (size_t)n * S * S + 4 * bx;            // 4-byte aligned: S % 64 == 0, the mask 16-byte aligned
+    const int left = bx > 0 ? -1 : 0, right = bx + 1 < bw ? 4 : 3;
+    unsigned any = 0;
+#pragma unroll
+    for (int r = -1; r <= 4; ++r) {
+        const uint8_t *row = m + (size_t)min(max(4 * by + r, 0), S - 1) * S;
+        any |= *reinterpret_cast<const unsigned *>(row) | row[left] | row[right];
+    }
+    b0[i] = any ? 1 : 0;
+}
+
+// workgroup n: the block bitmaps of image n, level by level from B_0, and the flags of the tiles that hold a needed block
+__global__ __launch_bounds__(1024) void need_blocks_kernel(const uint8_t *__restrict__ b0, BlockLevels L, uint8_t *__restrict__ flags) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t need_lds[];
+    const int tid = threadIdx.x, n = blockIdx.x;
+    uint8_t *cur = need_lds, *nxt = need_lds + L.bw[0] * L.bw[0];
+    {
+        const int words = L.bw[0] * L.bw[0] / 16;          // (bw % 16 == 0: S % 64 == 0)
+        const u32x4 *src = reinterpret_cast<const u32x4 *>(b0) + (size_t)n * words;
+        for (int i = tid; i < words; i += 1024) reinterpret_cast<u32x4 *>(cur)[i] = src[i];
+    }
+    __syncthreads();
+    for (int k = 0; k < L.nlists; ++k) {
+        const int bw = L.bw[k], tr = L.trows[k], tc = L.tcols[k];
+        const int tiles_x = bw / tc, per_img = tiles_x * (bw / tr);
+        for (int t = tid; t < per_img; t += 1024) {
+            const int ty = t / tiles_x, tx = t - ty * tiles_x;
+            unsigned any = 0;
+            for (int i = 0; i < tr; ++i)
+                for (int j = 0; j < tc; ++j) any |= cur[(ty * tr + i) * bw + tx * tc + j];
+            flags[L.off[k] + n * per_img + t] = any ? 1 : 0;
+        }
+        if (k == 1 && L.gram_runs > 0) {     // cur = B_1; a run is a row segment: rows y - 1 .. y + 1, columns 64 sx - 1 .. 64 sx + 64
+            const int per_row = bw / 16;
+            for (int j = tid; j < L.gram_runs; j += 1024) {
+                const int y = j / per_row, sx = j - y * per_row;
+                const int ya = max(0, y - 1) >> 2, yb = min(4 * bw - 1, y + 1) >> 2;
+                const int xa = max(0, 16 * sx - 1), xb = min(bw - 1, 16 * sx + 16);
+                unsigned any = 0;
+                for (int by = ya; by <= yb; ++by)
+                    for (int x = xa; x <= xb; ++x) any |= cur[by * bw + x];
+                flags[L.off[L.nlists] + n * L.gram_runs + j] = any ? 1 : 0;
+            }
+        }
+        if (k + 1 == L.nlists) break;
+        const int up = L.unpools[k];                     // B_k+1: rows / columns b - 1 .. b + 1, or 2 b - 1 .. 2 b + 2 through the un-pool
+        const int bw2 = up ? bw / 2 : bw;
+        for (int b = tid; b < bw2 * bw2; b += 1024) {
+            const int by = b / bw2, bx = b - by * bw2;
+            const int ya = max(0, (up ? 2 * by : by) - 1), yb = min(bw - 1, up ? 2 * by + 2 : by + 1);
+            const int xa = max(0, (up ? 2 * bx : bx) - 1), xb = min(bw - 1, up ? 2 * bx + 2 : bx + 1);
+            unsigned any = 0;
+            for (int y = ya; y <= yb; ++y)
+                for (int x = xa; x <= xb; ++x) any |= cur[y * bw + x];
+            nxt[b] = any ? 1 : 0;
+        }
+        __syncthreads();
+        uint8_t *t = cur; cur = nxt; nxt = t;
+    }
+}
+
+// need_lists_kernel for up to kLists lists: workgroup k compacts flags[off[k] .. off[k + 1]) into list k
+__global__ __launch_bounds__(1024) void need_block_lists_kernel(const uint8_t *__restrict__ flags, BlockLevels L,
+                                                                int *__restrict__ counts) {
+    __shared__ int scan[1024];
+    const int k = blockIdx.x, tid = threadIdx.x;
+    const bool gram = k == L.nlists;                 // the workgroup behind the lists' own: the Gram runs
+    const uint8_t *__restrict__ f = flags + L.off[k];
+    int *__restrict__ list = gram ? L.gram_list : L.list[k];
+    const int total = gram ? L.gram_total : L.off[k + 1] - L.off[k];
+    const int per = (total + 1023) / 1024;
+    const int lo = min(total, tid * per), hi = min(total, lo + per);
+    int cnt = 0;
+    for (int t = lo; t < hi; ++t) cnt += f[t];
+    scan[tid] = cnt;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+        const int v = tid >= d ? scan[tid - d] : 0;
+        __syncthreads();
+        scan[tid] += v;
+        __syncthreads();
+    }
+    int o = scan[tid] - cnt;
+    for (int t = lo; t < hi; ++t)
+        if (f[t]) list[o++] = t;
+    if (tid == 1023) (gram ? L.gram_count : counts + k)[0] = scan[1023];
+}
+
+// the two bitmap buffers of need_blocks_kernel have to fit the 64 KB of LDS a launch gets without asking
+bool blocks_fit(int S) { return S > 0 && (S % 64) == 0 && (size_t)5 * (S / 4) * (S / 4) / 4 <= 65536; }
+
 int geo_of(int H, int W, NeedGeo *g) {
     int rows = 0, cols = 0;
     if (!st3d_wino43_tile_geometry(H, W, &rows, &cols)) return 0;
@@ -165,5 +304,80 @@ extern "C" int st3d_need_build(const uint8_t *mask, int N, int S, int levels, ui
         need_lists_kernel<<<levels - 1, 1024, 0, s>>>(flags, total1, total2, list1, list2, counts);
         ST3D_LAUNCH_CHECK();
     }
+    return ST3D_OK;
+}
+
+extern "C" int st3d_need_blocks_lists(int S) {
+    if (!blocks_fit(S)) return 0;
+    int k = 0;
+    while (k < kLists && st3d_wino43_tile_geometry(S >> kListShift[k], S >> kListShift[k], nullptr, nullptr)) ++k;
+    return k;
+}
+
+extern "C" size_t st3d_need_blocks_tiles(int N, int S, int k) {
+    if (N <= 0 || k < 0 || k >= st3d_need_blocks_lists(S)) return 0;
+    const size_t bw = (size_t)(S >> kListShift[k]) / 4;
+    return (size_t)N * bw * bw / 16;         // 16 blocks per tile in either geometry
+}
+
+extern "C" size_t st3d_need_blocks_gram_runs(int N, int S) {
+    const int R = S / 2;
+    if (N <= 0 || st3d_need_blocks_lists(S) < 2 || (R % 64) != 0) return 0;
+    return (size_t)N * R * (R / 64);
+}
+
+// workspace: B_0 (one byte per block of the S x S map; first, so it stays 16-byte aligned), then the flags
+static size_t b0_bytes(int N, int S) { return (size_t)N * (S / 4) * (S / 4); }
+
+extern "C" size_t st3d_need_blocks_workspace_bytes(int N, int S) {
+    if (N <= 0 || st3d_need_blocks_lists(S) == 0) return 0;
+    size_t b = b0_bytes(N, S) + st3d_need_blocks_gram_runs(N, S);
+    for (int k = 0; k < st3d_need_blocks_lists(S); ++k) b += st3d_need_blocks_tiles(N, S, k);
+    return b;
+}
+
+extern "C" int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nlists, const int *tile_cols, uint8_t *seg,
+                                      void *workspace, size_t workspace_bytes, int *const *lists, int *counts, int *gram_list,
+                                      int *gram_count, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(mask && seg && N > 0);
+    ST3D_CHECK_ARG(!gram_list || (gram_count && nlists >= 2 && st3d_need_blocks_gram_runs(N, S) > 0));
+    ST3D_CHECK_ARG(nlists >= 1 && nlists <= st3d_need_blocks_lists(S));
+    ST3D_CHECK_ARG(((uintptr_t)mask & 15) == 0);
+    ST3D_CHECK_ARG((long)N * S * S < (1L << 31));
+    ST3D_CHECK_ARG(lists && counts && workspace && workspace_bytes >= st3d_need_blocks_workspace_bytes(N, S));
+    ST3D_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
+    BlockLevels L;
+    memset(&L, 0, sizeof(L));
+    L.nlists = nlists;
+    for (int k = 0; k < nlists; ++k) {
+        const int R = S >> kListShift[k];
+        int rows = 0, cols = 0;
+        st3d_wino43_tile_geometry(R, R, &rows, &cols);
+        if (tile_cols && tile_cols[k]) cols = tile_cols[k];
+        ST3D_CHECK_ARG(lists[k]);
+        ST3D_CHECK_ARG((cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0));      // (R % 8 == 0 with it: S % 64 == 0)
+        L.bw[k] = R / 4;
+        L.trows[k] = cols == 64 ? 1 : 2;
+        L.tcols[k] = cols / 4;
+        L.unpools[k] = kListUnpools[k];
+        L.off[k + 1] = L.off[k] + (int)st3d_need_blocks_tiles(N, S, k);
+        L.list[k] = lists[k];
+    }
+    if (gram_list) {
+        L.gram_runs = (int)(st3d_need_blocks_gram_runs(N, S) / N);
+        L.gram_total = N * L.gram_runs;
+        L.gram_list = gram_list;
+        L.gram_count = gram_count;
+    }
+    hipStream_t s = st3d::as_stream(stream);
+    const int total = N * S * (S / 64), seg_wgs = st3d::cdiv(total, 256), b0_total = (int)b0_bytes(N, S);
+    uint8_t *b0 = reinterpret_cast<uint8_t *>(workspace), *flags = b0 + b0_total;
+    need_front_kernel<<<seg_wgs + st3d::cdiv(b0_total, 256), 256, 0, s>>>(mask, S, total, seg_wgs, seg, b0_total, b0);
+    ST3D_LAUNCH_CHECK();
+    const size_t lds = (size_t)5 * (S / 4) * (S / 4) / 4;
+    need_blocks_kernel<<<N, 1024, lds, s>>>(b0, L, flags);
+    ST3D_LAUNCH_CHECK();
+    need_block_lists_kernel<<<nlists + (gram_list ? 1 : 0), 1024, 0, s>>>(flags, L, counts);
+    ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }

@@ -214,11 +214,19 @@ struct st3d_plan {
     bool gwarm = false;
     // need lists of st3d_plan_loss_masked (need.hip), rebuilt by every masked call.  A launch may only be thinned out when
     // every launch below it is, so the levels count from the bottom: 1 the relu1_1 pass, 2 + the conv1_2 input gradient,
-    // 3 + the conv2_1 input gradient -- as many as the size has, the routes allow and ST3D_NEED_DEPTH leaves
+    // 3 + the conv2_1 input gradient -- as many as the size has, the routes allow and ST3D_NEED_DEPTH leaves.
+    // need_blocks: the lists are the per-block ones (st3d_need_blocks_build; ST3D_NEED_BLOCKS=0: the tile-granular ones of
+    // st3d_need_build).  They stay thin further up, so the levels go on: 4 + conv2_2, 5 + conv3_1, 6 + conv3_2, 7 + conv3_3,
+    // each in the geometry need_cols says (64 / 32 pixels across; 0 = the kernel's own choice for the map).
     int need_levels = 0;
+    bool need_blocks = false;
     uint8_t *need_seg = nullptr, *need_flags = nullptr;
     size_t need_flags_bytes = 0;
-    int *need_list[2] = {}, *need_cnt = nullptr;
+    int *need_list[ST3D_NEED_MAX_LISTS] = {}, *need_cnt = nullptr;
+    int need_cols[ST3D_NEED_MAX_LISTS] = {};
+    // the Gram backward at relu2_1 over the 64-pixel runs the conv2_1 input gradient reads (level 3 and up; gram.hip)
+    bool need_gram = false;
+    int *need_gram_list = nullptr, *need_gram_cnt = nullptr;
     // flat-field lists of st3d_plan_loss_flat (flat.hip), rebuilt by every call that brings a colour: how many of conv1_2,
     // conv2_1, conv2_2 run listed -- as many as the size has, run F(4x4,3x3) and ST3D_FLAT_DEPTH leaves
     int flat_levels = 0;
@@ -392,6 +400,7 @@ struct DgradOpts {
     // compute the listed output tiles only (F(4x4,3x3) launches; anything else is an error, not a silent full launch: the
     // caller has already skipped the work above on the strength of it)
     const int *tile_list = nullptr, *n_active = nullptr;
+    int tile_cols = 0;                  // the geometry the list numbers (0 = st3d_wino43_tile_geometry's)
 };
 
 // one input-gradient launch of conv slot cs: g (gradient w.r.t. the conv's post-ReLU output, or w.r.t. the output of
@@ -411,8 +420,8 @@ int dgrad_step(st3d_plan *p, int cs, const float *g, bool g_is_pooled, int pool_
     const uint8_t *pidx = g_is_pooled ? p->pidx[pool_of_g] : nullptr;
     const float *pooled = g_is_pooled ? p->act[kPoolIdx[pool_of_g]] : nullptr;
     if (o.tile_list)
-        ST3D_TRY(st3d_wino43_dgrad_chain_tiles(g, pidx, v->u6d[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W,
-                                               o.tile_list, o.n_active, s));
+        ST3D_TRY(st3d_wino43_dgrad_chain_tiles_geo(g, pidx, v->u6d[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W,
+                                                   o.tile_cols, o.tile_list, o.n_active, s));
     else if (w43)
         ST3D_TRY(st3d_wino43_dgrad_chain(g, pidx, v->u6d[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W, s));
     else if (wino && (o.pregated || o.out_gate))
@@ -480,7 +489,51 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     int need_ok = p->fused_tap0 ? 1 : 0;
     if (need_ok == 1 && p->route[2].gate_dst && p->route[1].dgrad_w43) need_ok = 2;
     if (need_ok == 2 && p->route[2].dgrad_w43) need_ok = 3;
-    p->need_levels = capped(std::min(need_ok, st3d_need_levels(S)), "ST3D_NEED_DEPTH");
+    int need_max = st3d_need_levels(S);
+    auto flag = [](const char *name, bool dflt) { const char *e = getenv(name); return e && e[0] ? e[0] != '0' : dflt; };
+    p->need_blocks = need_ok >= 2 && st3d_need_blocks_lists(S) >= 2 && flag("ST3D_NEED_BLOCKS", true);
+    if (p->need_blocks) {
+        // The per-block lists (need.hip).  Level cs + 1 lists the input gradient of conv slot cs = list cs - 1.  A level above
+        // conv2_1, or a geometry other than the kernel's own, engages only where the full launch walks at least two tiles per
+        // persistent workgroup, N tiles_x tiles_y >= 2 (CUs / n_ct): below that every workgroup has one tile at the most and a
+        // list saves nothing (ST3D_NEED_FORCE=1 lifts the rule: tests reach every level at small sizes).
+        // ST3D_NEED_TILE=64|32 (or one value per list, comma-separated): that geometry on every listed level it fits.
+        need_max = 1 + st3d_need_blocks_lists(S);
+        const bool force = flag("ST3D_NEED_FORCE", false);
+        int cus = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        auto two_rounds = [&](int cs) {
+            const int R = p->H[kConvIdx[cs]];
+            return force || (long)B * (R / 4) * (R / 4) / 16 >= 2L * (cus / std::max(1, kConvCin[cs] / 64));
+        };
+        // conv2_2 and conv3_1 .. conv3_3: F(4x4,3x3) launches whose gradient arrives gated (from the launch above, or the taps)
+        for (int cs = 3; cs <= ST3D_NEED_MAX_LISTS && need_ok == cs; ++cs)
+            if (p->route[cs].dgrad_w43 && (cs == 4 ? p->route[cs].gate_taps : p->route[cs + 1].gate_dst) && two_rounds(cs)) need_ok = cs + 1;
+        // measured defaults: 8 x 32 tiles from conv2_2 up
+        static const int kDefaultCols[ST3D_NEED_MAX_LISTS] = {0, 0, 32, 32, 32, 32};
+        const char *tile = getenv("ST3D_NEED_TILE");
+        for (int k = 0; k < ST3D_NEED_MAX_LISTS; ++k) {
+            const int R = p->H[kConvIdx[k + 1]];
+            int cols = kDefaultCols[k];
+            if (tile && tile[0]) {
+                cols = atoi(tile);
+                if (const char *c = strchr(tile, ',')) { tile = c + 1; }
+            }
+            int rows0 = 0, cols0 = 0;
+            st3d_wino43_tile_geometry(R, R, &rows0, &cols0);
+            const bool fits = (cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0 && R % 8 == 0);
+            p->need_cols[k] = (fits && cols != cols0 && two_rounds(k + 1)) ? cols : 0;
+        }
+    }
+    p->need_levels = capped(std::min(need_ok, need_max), "ST3D_NEED_DEPTH");
+    if (p->need_blocks && p->need_levels >= 3) {
+        // the relu2_1 Gram backward listed: one workgroup per 64-pixel run, four to a CU -- the same two-rounds rule
+        const int m = kConvIdx[2], HW = p->H[m] * p->W[m];
+        int cus = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        p->need_gram = flag("ST3D_NEED_GRAM", true) && p->route[2].gate_taps && st3d_gram_bwd_segs_supported(p->C[m], HW) &&
+                       st3d_need_blocks_gram_runs(B, S) > 0 && (flag("ST3D_NEED_FORCE", false) || (long)B * (HW / 64) >= 2L * 4 * cus);
+    }
     int flat_ok = 0;
     while (flat_ok < 3 && p->route[flat_ok + 1].fwd == WINO43) ++flat_ok;
     p->flat_levels = capped(std::min(flat_ok, st3d_flat_levels(S)), "ST3D_FLAT_DEPTH");
@@ -510,10 +563,18 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     if (p->need_levels >= 1) {
         alloc(&p->g_mask, (size_t)B * S * S);
         alloc(&p->need_seg, (size_t)B * S * (S / 64));
-        alloc(&p->need_cnt, (size_t)2);
-        p->need_flags_bytes = st3d_need_workspace_bytes(B, S);
+        alloc(&p->need_cnt, (size_t)ST3D_NEED_MAX_LISTS);
+        p->need_flags_bytes = p->need_blocks ? st3d_need_blocks_workspace_bytes(B, S) : st3d_need_workspace_bytes(B, S);
         if (p->need_levels >= 2) alloc(&p->need_flags, p->need_flags_bytes);
+        if (p->need_gram) {
+            alloc(&p->need_gram_list, st3d_need_blocks_gram_runs(B, S));
+            alloc(&p->need_gram_cnt, (size_t)1);
+        }
         for (int l = 0; l + 2 <= p->need_levels; ++l) {
+            if (p->need_blocks) {
+                alloc(&p->need_list[l], st3d_need_blocks_tiles(B, S, l));
+                continue;
+            }
             int rows = 0, cols = 0;
             st3d_wino43_tile_geometry(S >> l, S >> l, &rows, &cols);
             alloc(&p->need_list[l], (size_t)B * ((S >> l) / rows) * ((S >> l) / cols));
@@ -775,8 +836,13 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
     const int need = need_mask ? p->need_levels : 0;
     if (need > 0) {
         Scope sc(p, F_ELEM, s);
-        ST3D_TRY(st3d_need_build(need_mask, n, p->S, need, p->need_seg, p->need_flags, p->need_flags_bytes, p->need_list[0],
-                                 p->need_list[1], p->need_cnt, s));
+        if (p->need_blocks && need >= 2)
+            ST3D_TRY(st3d_need_blocks_build(need_mask, n, p->S, need - 1, p->need_cols, p->need_seg, p->need_flags, p->need_flags_bytes,
+                                            p->need_list, p->need_cnt, need >= 3 && p->need_gram ? p->need_gram_list : nullptr,
+                                            p->need_gram_cnt, s));
+        else
+            ST3D_TRY(st3d_need_build(need_mask, n, p->S, need, p->need_seg, p->need_flags, p->need_flags_bytes, p->need_list[0],
+                                     p->need_list[1], p->need_cnt, s));
     }
 
     // ---- backward: gradient w.r.t. the post-ReLU output of each conv, top down
@@ -807,7 +873,13 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
             break;
         }
         const bool chain = r.gate_taps && !g_is_pooled;
-        if (st >= 0) {
+        if (st >= 0 && cs == 2 && need >= 3 && p->need_gram && chain) {        // relu2_1 over the runs conv2_1's input gradient reads
+            Scope sc(p, F_GRAM_BWD_NEED, s, m);
+            ST3D_TRY(st3d_gram_bwd_gated_segs(p->D[st], p->act[m], guided ? p->guide_plane(st) : nullptr, n, C, H * W, style_coef[st],
+                                              have_g ? 1 : 0, p->need_gram_list, p->need_gram_cnt, g, s));
+            g_gated = true;
+            have_g = true;
+        } else if (st >= 0) {
             Scope sc(p, F_GRAM_BWD, s, m);
             if (guided) {
                 ST3D_TRY(st3d_gram_bwd_weighted(p->D[st], p->act[m], p->guide_plane(st), n, C, H * W, style_coef[st], have_g ? 1 : 0,
@@ -844,9 +916,10 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
             o.add_coef = cc;
             content_done = true;
         }
-        if ((cs == 1 || cs == 2) && need >= cs + 1) {   // conv1_2 / conv2_1 over their need lists
+        if (cs >= 1 && cs <= ST3D_NEED_MAX_LISTS && need >= cs + 1) {   // conv1_2 .. conv3_3 over their need lists
             o.tile_list = p->need_list[cs - 1];
             o.n_active = p->need_cnt + (cs - 1);
+            o.tile_cols = p->need_cols[cs - 1];
         }
         ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, o));
         g_gated = o.out_gate != nullptr;

@@ -670,9 +670,17 @@ int launch_wino43_tc(Wino43Args a, hipStream_t s) {
     return go(wino43_kernel<MODE, 0, 0, TC>);
 }
 
+// cols: the caller's choice of geometry (listed launches: the lists number the tiles of one geometry) -- 64 or 32 pixels
+// across where the map allows it, 0 = tc43's
 template <int MODE>
-int launch_wino43(Wino43Args a, hipStream_t s) {
-    return tc43(a.H, a.W) == 16 ? launch_wino43_tc<MODE, 16>(a, s) : launch_wino43_tc<MODE, 8>(a, s);
+int launch_wino43(Wino43Args a, hipStream_t s, int cols = 0) {
+    const int native = tc43(a.H, a.W);
+    if (cols != 0 && !((cols == 64 && native == 16) || (cols == 32 && a.H > 0 && a.W > 0 && (a.H % 8) == 0 && (a.W % 32) == 0))) {
+        st3d::set_error("wino43: %d-pixel tile columns do not fit a %d x %d map", cols, a.H, a.W);
+        return ST3D_E_INVALID;
+    }
+    const int tc = cols ? cols / 4 : native;
+    return tc == 16 ? launch_wino43_tc<MODE, 16>(a, s) : launch_wino43_tc<MODE, 8>(a, s);
 }
 
 }  // namespace
@@ -720,6 +728,18 @@ extern "C" int st3d_wino43_fwd_tiles(const float *x, const float *u_fwd, const f
     return launch_wino43<0>(a, st3d::as_stream(stream));
 }
 
+extern "C" int st3d_wino43_fwd_tiles_geo(const float *x, const float *u_fwd, const float *bias, float *y, float *y_pooled,
+                                         uint8_t *pool_idx, int N, int Cin, int Cout, int H, int W, int relu, int tile_cols,
+                                         const int *tile_list, const int *n_active, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(x && u_fwd && (y || y_pooled) && tile_list && n_active);
+    ST3D_CHECK_ARG(N > 0 && shape_ok43(Cin, Cout, H, W));
+    ST3D_CHECK_ARG(((uintptr_t)u_fwd & 15) == 0);
+    Wino43Args a{x, nullptr, u_fwd, bias, y, y_pooled, pool_idx, N, Cin, Cout, H, W, relu, 0, 0, 0, nullptr, nullptr, 0.f};
+    a.tile_list = tile_list;
+    a.n_active = n_active;
+    return launch_wino43<0>(a, st3d::as_stream(stream), tile_cols);
+}
+
 // gy: gradient w.r.t. the conv's output, ALREADY gated by its producer (or, with pool_idx, the pooled-resolution gradient
 // of the pool behind the conv, gated at pooled resolution); out_gate / add_target / add_coef as st3d_wino_dgrad_chain.
 extern "C" int st3d_wino43_dgrad_chain(const float *gy, const uint8_t *pool_idx, const float *u_dgrad, const float *out_gate,
@@ -749,4 +769,20 @@ extern "C" int st3d_wino43_dgrad_chain_tiles(const float *gy, const uint8_t *poo
     a.n_active = n_active;
     hipStream_t s = st3d::as_stream(stream);
     return pool_idx ? launch_wino43<3>(a, s) : launch_wino43<0>(a, s);
+}
+
+// the same with the geometry chosen by the caller (need.hip's per-block lists: 8 x 32 tiles follow the picture more closely)
+extern "C" int st3d_wino43_dgrad_chain_tiles_geo(const float *gy, const uint8_t *pool_idx, const float *u_dgrad, const float *out_gate,
+                                                 const float *add_target, float add_coef, float *gx, int N, int Cin, int Cout,
+                                                 int H, int W, int tile_cols, const int *tile_list, const int *n_active,
+                                                 st3d_stream_t stream) {
+    ST3D_CHECK_ARG(gy && u_dgrad && gx && tile_list && n_active);
+    ST3D_CHECK_ARG(N > 0 && shape_ok43(Cout, Cin, H, W));
+    ST3D_CHECK_ARG(((uintptr_t)u_dgrad & 15) == 0 && ((uintptr_t)out_gate & 15) == 0 && ((uintptr_t)add_target & 15) == 0);
+    ST3D_CHECK_ARG(!add_target || out_gate);
+    Wino43Args a{gy, pool_idx, u_dgrad, nullptr, gx, nullptr, nullptr, N, Cout, Cin, H, W, 0, 0, 0, 0, out_gate, add_target, add_coef};
+    a.tile_list = tile_list;
+    a.n_active = n_active;
+    hipStream_t s = st3d::as_stream(stream);
+    return pool_idx ? launch_wino43<3>(a, s, tile_cols) : launch_wino43<0>(a, s, tile_cols);
 }

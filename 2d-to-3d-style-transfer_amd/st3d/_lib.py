@@ -135,6 +135,19 @@ SIGNATURES = {
     "st3d_need_levels": (c_int, [c_int]),
     "st3d_need_workspace_bytes": (c_size, [c_int, c_int]),
     "st3d_need_build": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, ctypes.c_void_p, c_size, c_i32p, c_i32p, c_i32p, c_stream]),
+    "st3d_need_blocks_lists": (c_int, [c_int]),
+    "st3d_need_blocks_tiles": (c_size, [c_int, c_int, c_int]),
+    "st3d_need_blocks_workspace_bytes": (c_size, [c_int, c_int]),
+    "st3d_need_blocks_build": (c_int, [c_u8p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_u8p, ctypes.c_void_p, c_size,
+                                       ctypes.POINTER(ctypes.c_void_p), c_i32p, c_i32p, c_i32p, c_stream]),
+    "st3d_need_blocks_gram_runs": (c_size, [c_int, c_int]),
+    "st3d_gram_bwd_segs_supported": (c_int, [c_int, c_int]),
+    "st3d_gram_bwd_gated_segs": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_float, c_int, c_i32p, c_i32p, c_f32p,
+                                         c_stream]),
+    "st3d_wino43_dgrad_chain_tiles_geo": (c_int, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_float, c_f32p, c_int, c_int, c_int,
+                                                  c_int, c_int, c_int, c_i32p, c_i32p, c_stream]),
+    "st3d_wino43_fwd_tiles_geo": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_int, c_i32p, c_i32p, c_stream]),
     "st3d_maxpool2x2_fwd": (c_int, [c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_stream]),
     "st3d_gram_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "st3d_gram_fwd": (c_int, [c_f32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_f32p, c_stream]),

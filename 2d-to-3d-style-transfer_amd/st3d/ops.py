@@ -644,6 +644,44 @@ def need_build(mask, levels=None):
     return seg, [(lst, counts[i]) for i, lst in enumerate(lists)]
 
 
+def need_blocks_lists(S):
+    return _lib.load().st3d_need_blocks_lists(int(S))
+
+
+def need_blocks_build(mask, nlists=None, tile_cols=None, gram=False):
+    """mask (N,S,S) uint8 -> (seg (N,S,S/64) uint8, [(list, count)] per list): the per-block need lists of the input
+    gradients of conv1_2, conv2_1, conv2_2, conv3_1, conv3_2, conv3_3 (st3d_need_blocks_build).  tile_cols: 64 / 32 / 0 per
+    list (0 or None = the kernel's own geometry for the map).  Lists are sized for every tile and start as -1.
+    gram=True: a third value, (list, count) of the 64-pixel runs of the relu2_1 Gram backward (gram_bwd_gated_segs)."""
+    lib = _lib.load()
+    N, S, _ = mask.shape
+    nlists = need_blocks_lists(S) if nlists is None else nlists
+    seg = torch.empty((N, S, S // 64), dtype=U8, device=mask.device)
+    counts = torch.zeros((max(nlists, 1),), dtype=I32, device=mask.device)
+    lists = [torch.full((lib.st3d_need_blocks_tiles(N, S, k),), -1, dtype=I32, device=mask.device) for k in range(nlists)]
+    nb = lib.st3d_need_blocks_workspace_bytes(N, S)
+    ws = torch.empty((max(nb, 1),), dtype=U8, device=mask.device)
+    cols = (ctypes.c_int * max(nlists, 1))(*[int(c or 0) for c in (tile_cols or [0] * nlists)])
+    ptrs = (ctypes.c_void_p * max(nlists, 1))(*[l.data_ptr() for l in lists])
+    glist = torch.full((lib.st3d_need_blocks_gram_runs(N, S),), -1, dtype=I32, device=mask.device) if gram else None
+    gcount = torch.zeros((1,), dtype=I32, device=mask.device) if gram else None
+    call("st3d_need_blocks_build", dptr(mask, U8), N, S, nlists, cols, dptr(seg), dptr(ws), nb, ptrs, dptr(counts), dptr(glist),
+         dptr(gcount), stream_ptr())
+    out = [(lst, counts[i]) for i, lst in enumerate(lists)]
+    return (seg, out, (glist, gcount[0])) if gram else (seg, out)
+
+
+def gram_bwd_gated_segs(D, feat, coef, seg_list, seg_count, out, accumulate=False, q=None):
+    """The gated Gram backward over the first seg_count (device int32 scalar) entries of seg_list (device int32: image * (HW /
+    64) + 64-pixel run), written into `out` (B,128,H,W) in place; the other runs are left alone (st3d_gram_bwd_gated_segs)."""
+    B, C = feat.shape[:2]
+    HW = feat.shape[2] * feat.shape[3]
+    assert out.shape == feat.shape
+    call("st3d_gram_bwd_gated_segs", dptr(D, F32), dptr(feat, F32), dptr(q, F32), B, C, HW, float(coef), 1 if accumulate else 0,
+         dptr(seg_list, I32), dptr(seg_count, I32), dptr(out, F32), stream_ptr())
+    return out
+
+
 def conv3x3_dgrad_unpool(gy_pooled, pool_idx, pooled, wd, Cin):
     N, Cout, Hp, Wp = gy_pooled.shape
     H, W = 2 * Hp, 2 * Wp
@@ -732,22 +770,34 @@ def wino43_dgrad_chain(gy, ud, Cin, pool_idx=None, out_gate=None, add_target=Non
     return gx
 
 
-def wino43_dgrad_chain_tiles(gy, ud, Cin, tile_list, n_active, out, pool_idx=None, out_gate=None, add_target=None, add_coef=0.0):
+def wino43_dgrad_chain_tiles(gy, ud, Cin, tile_list, n_active, out, pool_idx=None, out_gate=None, add_target=None, add_coef=0.0,
+                             tile_cols=None):
     """wino43_dgrad_chain over the first n_active (device int32 scalar) tiles of tile_list (device int32), written into
-    `out` (N,Cin,H,W) in place: the other tiles of `out` are left alone (st3d_wino43_dgrad_chain_tiles)."""
+    `out` (N,Cin,H,W) in place: the other tiles of `out` are left alone (st3d_wino43_dgrad_chain_tiles).  tile_cols = 64 /
+    32: the list numbers the 4 x 64 / 8 x 32 tiles (st3d_wino43_dgrad_chain_tiles_geo)."""
     N, Cout = gy.shape[:2]
     H, W = (2 * gy.shape[2], 2 * gy.shape[3]) if pool_idx is not None else gy.shape[2:]
     assert tuple(out.shape) == (N, Cin, H, W)
+    if tile_cols is not None:
+        call("st3d_wino43_dgrad_chain_tiles_geo", dptr(gy.contiguous(), F32), dptr(pool_idx, U8), dptr(ud, F32), dptr(out_gate, F32),
+             dptr(add_target, F32), float(add_coef), dptr(out, F32), N, Cin, Cout, H, W, int(tile_cols), dptr(tile_list, I32),
+             dptr(n_active, I32), stream_ptr())
+        return out
     call("st3d_wino43_dgrad_chain_tiles", dptr(gy.contiguous(), F32), dptr(pool_idx, U8), dptr(ud, F32), dptr(out_gate, F32),
          dptr(add_target, F32), float(add_coef), dptr(out, F32), N, Cin, Cout, H, W, dptr(tile_list, I32), dptr(n_active, I32),
          stream_ptr())
     return out
 
 
-def wino43_fwd_tiles(x, uf, bias, Cout, tile_list, n_active, y=None, yp=None, idx=None, relu=True):
+def wino43_fwd_tiles(x, uf, bias, Cout, tile_list, n_active, y=None, yp=None, idx=None, relu=True, tile_cols=None):
     """wino43_fwd over the first n_active (device int32 scalar) tiles of tile_list (device int32), written in place into
     whichever of y (N,Cout,H,W), yp and idx (N,Cout,H/2,W/2) are given; other tiles are left alone (st3d_wino43_fwd_tiles)."""
     N, Cin, H, W = x.shape
+    if tile_cols is not None:
+        call("st3d_wino43_fwd_tiles_geo", dptr(x.contiguous(), F32), dptr(uf, F32), dptr(bias, F32), dptr(y, F32), dptr(yp, F32),
+             dptr(idx, U8), N, Cin, Cout, H, W, 1 if relu else 0, int(tile_cols), dptr(tile_list, I32), dptr(n_active, I32),
+             stream_ptr())
+        return
     call("st3d_wino43_fwd_tiles", dptr(x.contiguous(), F32), dptr(uf, F32), dptr(bias, F32), dptr(y, F32), dptr(yp, F32),
          dptr(idx, U8), N, Cin, Cout, H, W, 1 if relu else 0, dptr(tile_list, I32), dptr(n_active, I32), stream_ptr())
 

@@ -422,6 +422,40 @@ int st3d_need_levels(int S);
 size_t st3d_need_workspace_bytes(int N, int S);      /* one flag byte per tile of levels 2 and 3 */
 int st3d_need_build(const uint8_t *mask, int N, int S, int levels, uint8_t *seg, void *workspace, size_t workspace_bytes,
                     int *list1, int *list2, int *counts, st3d_stream_t stream);
+/* Need propagation per 4x4 block (csrc/need.hip): an F(4x4,3x3) launch computes each aligned 4x4 output block from that
+ * block's own 6x6 patch alone, so what list k's launch has to get right is B_k = block4(need_k), and what it reads is
+ * need_k+1 = dilate(B_k, 1) clipped to the map (through the 2x2 OR where the launch un-pools its input); need_0 =
+ * dilate(mask, 1).  Lists 0 .. 5: the input gradients of conv1_2 (S x S), conv2_1, conv2_2 (S/2), conv3_1, conv3_2, conv3_3
+ * (S/4).  list k holds the tiles that hold a block of B_k, in the geometry tile_cols[k] (host array; 64 = 4 x 64 pixels, 32 =
+ * 8 x 32, 0 or tile_cols == NULL = st3d_wino43_tile_geometry's), ascending, st3d_need_blocks_tiles(N, S, k) entries long;
+ * counts[k] the number listed.  lists: HOST array of nlists device pointers.  seg as st3d_need_build.  Device memory
+ * throughout, no atomics.  st3d_need_blocks_lists(S): how many lists exist at this size (0: not covered). */
+#define ST3D_NEED_MAX_LISTS 6
+int st3d_need_blocks_lists(int S);
+size_t st3d_need_blocks_tiles(int N, int S, int k);
+size_t st3d_need_blocks_workspace_bytes(int N, int S);
+/* gram_list / gram_count (device; NULL = not wanted): the 64-pixel runs of the (S/2)^2 map that meet need_2, the pixels at
+ * which the conv2_1 input gradient reads the gradient of relu2_1 -- what st3d_gram_bwd_gated_segs takes; numbered image *
+ * runs per image + run, st3d_need_blocks_gram_runs(N, S) entries (0: S/2 is no multiple of 64, no such list); nlists >= 2. */
+size_t st3d_need_blocks_gram_runs(int N, int S);
+int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nlists, const int *tile_cols, uint8_t *seg, void *workspace,
+                           size_t workspace_bytes, int *const *lists, int *counts, int *gram_list, int *gram_count,
+                           st3d_stream_t stream);
+/* The gated Gram backward (st3d_gram_bwd_gated; with q: st3d_gram_bwd_weighted, gated) over the first *seg_count entries of
+ * seg_list only (device memory; entry = image * (HW / 64) + 64-pixel run).  C = 128 (st3d_gram_bwd_segs_supported).  A listed
+ * run of gfeat is bitwise what the full launch writes; the other runs are not touched. */
+int st3d_gram_bwd_segs_supported(int C, int HW);
+int st3d_gram_bwd_gated_segs(const float *D, const float *feat, const float *q, int B, int C, int HW, float coef, int accumulate,
+                             const int *seg_list, const int *seg_count, float *gfeat, st3d_stream_t stream);
+/* st3d_wino43_dgrad_chain_tiles / st3d_wino43_fwd_tiles with the tile geometry as an argument: tile_cols = 64 (4 x 64 pixels,
+ * W % 64 == 0) or 32 (8 x 32 pixels, H % 8 == 0 and W % 32 == 0); tile_list numbers the tiles of THAT geometry.  0 = the
+ * geometry of st3d_wino43_tile_geometry. */
+int st3d_wino43_dgrad_chain_tiles_geo(const float *gy, const uint8_t *pool_idx, const float *u_dgrad, const float *out_gate,
+                                      const float *add_target, float add_coef, float *gx, int N, int Cin, int Cout, int H, int W,
+                                      int tile_cols, const int *tile_list, const int *n_active, st3d_stream_t stream);
+int st3d_wino43_fwd_tiles_geo(const float *x, const float *u_fwd, const float *bias, float *y, float *y_pooled, uint8_t *pool_idx,
+                              int N, int Cin, int Cout, int H, int W, int relu, int tile_cols, const int *tile_list,
+                              const int *n_active, st3d_stream_t stream);
 /* st3d_wino43_fwd over the first *n_active entries of tile_list only (as above): y, y_pooled and pool_idx of a listed tile
  * are bitwise what st3d_wino43_fwd writes, nothing else is written. */
 int st3d_wino43_fwd_tiles(const float *x, const float *u_fwd, const float *bias, float *y, float *y_pooled, uint8_t *pool_idx,
@@ -640,8 +674,10 @@ int st3d_plan_loss(st3d_plan *plan, const float *current, int n, int batch_denom
 /* st3d_plan_loss for a caller whose only consumer of grad_current reads it at the pixels of need_mask (n,S,S bytes,
  * non-zero = read; 16-byte aligned; NULL = st3d_plan_loss): loss_out is bitwise st3d_plan_loss's; grad_current is bitwise
  * st3d_plan_loss's at those pixels and exactly 0 elsewhere.  The bottom launches of the backward then compute only what
- * those pixels need (st3d_need_build): the relu1_1 pass, the conv1_2 and the conv2_1 input gradient -- ST3D_NEED_DEPTH =
- * 0..3 masks fewer of them, bottom-up (A/B runs; 0 and sizes with S % 64 != 0 run unmasked and return the full gradient).
+ * those pixels need (st3d_need_blocks_build; ST3D_NEED_BLOCKS=0: st3d_need_build): the relu1_1 pass, the conv1_2 and the
+ * conv2_1 input gradient and, where the full launch walks two tiles or more per workgroup, the relu2_1 Gram backward and the
+ * conv2_2 .. conv3_3 input gradients -- ST3D_NEED_DEPTH = 0..7 masks fewer of them, bottom-up (A/B runs; 0 and sizes with
+ * S % 64 != 0 run unmasked and return the full gradient).
  * With graph replay the mask is staged into a plan-owned buffer like the other inputs and the lists are built inside
  * the graph. */
 int st3d_plan_loss_masked(st3d_plan *plan, const float *current, int n, int batch_denom, float style_weight,

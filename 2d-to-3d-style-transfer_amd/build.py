@@ -25,7 +25,9 @@ COMMON = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-
 # geometry kernels are compared bit-for-bit with the gcc oracle: no FMA contraction there
 SOURCES = {
     "raster.hip": ["-ffp-contract=off"],
-    "shade.hip": ["-ffp-contract=off"],
+    # the supersampled kernels and the box filter are compared bit for bit with each other and with ordered torch adds: the
+    # correctly rounded division is hipcc's default (the plain kernels' code is the same with and without the flag)
+    "shade.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "soft.hip": ["-ffp-contract=off"],
     "lighting.hip": ["-ffp-contract=off"],
     "silhouette.hip": ["-ffp-contract=off"],   # its alpha is compared bit for bit with soft.hip's

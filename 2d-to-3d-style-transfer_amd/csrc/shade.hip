@@ -9,6 +9,8 @@
 // HBM-bound: algorithmic bytes per pixel = 24 B fragments + 16 B written (fwd),
 // 24 + 12 B read (bwd) + <= 12 float atomics per covered pixel into the 3*T*T*4-byte map.
 // Built with -ffp-contract=off (same operation sequence as oracle/raster_ref.c).
+// Supersampling (st3d_shade_ss_*, st3d_box_down_*): the same kernels over fragments at side a*S with the a x a box filter
+// fused in -- 24 a^2 B of fragments + 16 B written per output pixel; neither the a*S image nor an a*S gradient exists.
 #include <type_traits>
 
 #include "common.h"
@@ -101,6 +103,78 @@ __global__ __launch_bounds__(256) void shade_fwd_kernel(const int32_t *__restric
     mask[i] = ((1.0f - (1.0f - bl.prob)) > 0.f) ? 1.f : 0.f;
 }
 
+// shade_fwd_kernel's pixel as a function: colour (3) and 0/1 mask of fragment i (view b), white and 0 where there is no
+// face.  The same expressions in the same order (the plain kernel keeps its own copy: calling this from it moves its
+// registers and branches, and its code is pinned instruction for instruction).
+template <int LIT>
+__device__ __forceinline__ float shade_px(const int32_t *__restrict__ p2f, const float *__restrict__ bary,
+                                          const float *__restrict__ zbuf, const float *__restrict__ dists,
+                                          const float *__restrict__ uvs, const int32_t *__restrict__ fuv,
+                                          const float *__restrict__ tex, int T, size_t i, int b,
+                                          const st3d_phong::LitArgs &la, float col[3]) {
+    const int f = p2f[i];
+    if (f < 0) {
+        col[0] = 1.f; col[1] = 1.f; col[2] = 1.f;
+        return 0.f;
+    }
+    const float b0 = bary[3 * i], b1 = bary[3 * i + 1], b2 = bary[3 * i + 2];
+    const int u0 = fuv[3 * f], u1 = fuv[3 * f + 1], u2 = fuv[3 * f + 2];
+    const float u = b0 * uvs[2 * u0] + b1 * uvs[2 * u1] + b2 * uvs[2 * u2];
+    const float v = b0 * uvs[2 * u0 + 1] + b1 * uvs[2 * u1 + 1] + b2 * uvs[2 * u2 + 1];
+    const Footprint q = uv_footprint(u, v, T);
+    const Blend bl = blend_k1(dists[i], zbuf[i]);
+    const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
+    const float *t00 = tex + ((size_t)q.r0 * T + q.x0) * 3, *t01 = tex + ((size_t)q.r0 * T + q.x1) * 3;
+    const float *t10 = tex + ((size_t)q.r1 * T + q.x0) * 3, *t11 = tex + ((size_t)q.r1 * T + q.x1) * 3;
+    float ad[3] = {1.f, 1.f, 1.f}, sp[3] = {0.f, 0.f, 0.f};
+    if (LIT) st3d_phong::phong_fwd(la, b, f, b0, b1, b2, ad, sp);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float t = 0.f;
+        if (q.vy0 && q.vx0) t += t00[c] * w00;
+        if (q.vy0 && q.vx1) t += t01[c] * w01;
+        if (q.vy1 && q.vx0) t += t10[c] * w10;
+        if (q.vy1 && q.vx1) t += t11[c] * w11;
+        if (LIT) t = ad[c] * t + sp[c];
+        col[c] = (bl.wnum * t + bl.delta * 1.0f) / bl.denom;
+    }
+    return ((1.0f - (1.0f - bl.prob)) > 0.f) ? 1.f : 0.f;
+}
+
+// Supersampled forward: the fragments are at side A*S, one thread per OUTPUT pixel shades its A x A sub-pixels (the A of a
+// row are contiguous: lanes stay coalesced) and writes their ordered sum / A^2 -- the A*S image never exists.  Sum order
+// and division are those of box_down_fwd_kernel, so the result is bitwise shade_fwd_kernel at A*S followed by that filter.
+// coverage = the same expression over the 0/1 mask (exact: a count over A^2).
+template <int A, int LIT>
+__global__ __launch_bounds__(256) void shade_ss_fwd_kernel(const int32_t *__restrict__ p2f, const float *__restrict__ bary,
+                                                           const float *__restrict__ zbuf, const float *__restrict__ dists,
+                                                           const float *__restrict__ uvs, const int32_t *__restrict__ fuv,
+                                                           const float *__restrict__ tex, int B, int S, int T,
+                                                           float *__restrict__ rgb, float *__restrict__ coverage,
+                                                           const st3d_phong::LitArgs la = {}) {
+    const size_t HW = (size_t)S * S;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * HW) return;
+    const size_t b = i / HW, p = i - b * HW;
+    const int y = (int)(p / S), x = (int)(p - (size_t)y * S);
+    const size_t SS = (size_t)A * S;
+    const size_t base = b * SS * SS + (size_t)(A * y) * SS + (size_t)A * x;
+    float s[3], sm;
+#pragma unroll
+    for (int j = 0; j < A; ++j) {
+#pragma unroll
+        for (int k = 0; k < A; ++k) {
+            float col[3];
+            const float m = shade_px<LIT>(p2f, bary, zbuf, dists, uvs, fuv, tex, T, base + (size_t)j * SS + k, (int)b, la, col);
+            if (j == 0 && k == 0) { s[0] = col[0]; s[1] = col[1]; s[2] = col[2]; sm = m; }
+            else { s[0] = s[0] + col[0]; s[1] = s[1] + col[1]; s[2] = s[2] + col[2]; sm = sm + m; }
+        }
+    }
+    float *o = rgb + b * 3 * HW + p;
+    o[0] = s[0] / (float)(A * A); o[HW] = s[1] / (float)(A * A); o[2 * HW] = s[2] / (float)(A * A);
+    coverage[i] = sm / (float)(A * A);
+}
+
 // Texture-sampling backward.  One workgroup per 16x16-pixel tile of one view.  The <= 12 bilinear contributions of a
 // pixel are not sent to HBM one float atomic each (neighbouring pixels hit the same texels: ~6 M contended L2 atomics
 // per step at config 2): they are first summed per texel in an LDS table (open addressing on the texel index,
@@ -113,7 +187,10 @@ constexpr int kTexSlots = 2048;          // >= 4 x 256 footprint corners: the pr
 // reproducible whatever the order (det.h).
 // LIT 1: colour = ad * texel + sp (phong.h) -- the texture / uv factor of a channel becomes g k ad_c, and with la.grad_np the
 // lighting's own d/dN, d/dP go to grad_np (per pixel) and, through N = sum b_i n_i and P = sum b_i v_i, into gbary.
-template <int DET, int LIT = 0>
+// A > 1 (supersampling): S and every per-pixel array are at the SUB-PIXEL side; grad_rgb is (B,3,S/A,S/A) and sub-pixel
+// (yi, xi) takes grad_rgb(yi / A, xi / A) / A^2 -- the backward of the ordered box sum of shade_ss_fwd_kernel.  The tile is
+// still 16 x 16 sub-pixels = 256 footprints, so kTexSlots stays.  A = 1 is the plain kernel, instruction for instruction.
+template <int DET, int LIT = 0, int A = 1>
 __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict__ grad_rgb, const int32_t *__restrict__ p2f,
                                                         const float *__restrict__ bary, const float *__restrict__ zbuf,
                                                         const float *__restrict__ dists, const float *__restrict__ uvs,
@@ -154,8 +231,11 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
         const float k = bl.wnum / bl.denom;
         const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
         const int e00 = q.r0 * T + q.x0, e01 = q.r0 * T + q.x1, e10 = q.r1 * T + q.x0, e11 = q.r1 * T + q.x1;
-        const float *g = grad_rgb + (size_t)b * 3 * HW + p;
-        const float gk0[3] = {g[0] * k, g[HW] * k, g[2 * HW] * k};
+        const size_t gHW = A == 1 ? HW : (size_t)(S / A) * (S / A);
+        const float *g = grad_rgb + (size_t)b * 3 * gHW + (A == 1 ? p : (size_t)(yi / A) * (S / A) + xi / A);
+        const float gs[3] = {A == 1 ? g[0] : g[0] / (float)(A * A), A == 1 ? g[gHW] : g[gHW] / (float)(A * A),
+                             A == 1 ? g[2 * gHW] : g[2 * gHW] / (float)(A * A)};
+        const float gk0[3] = {gs[0] * k, gs[1] * k, gs[2] * k};
         float ad[3] = {1.f, 1.f, 1.f}, sp[3] = {0.f, 0.f, 0.f};
         if (LIT) st3d_phong::phong_fwd(la, b, f, b0, b1, b2, ad, sp);
         const float gk[3] = {LIT ? gk0[0] * ad[0] : gk0[0], LIT ? gk0[1] * ad[1] : gk0[1], LIT ? gk0[2] * ad[2] : gk0[2]};
@@ -257,6 +337,130 @@ __global__ __launch_bounds__(256) void background_kernel(const float *__restrict
     out[i] = v;
 }
 
+// a x a box filter (B*C planes of side A*S -> side S): out = (ordered row-major sum of the block) / A^2, the sum order and
+// the division of shade_ss_fwd_kernel.  VEC: four outputs per thread, A float4 loads per block row and one float4 store
+// (S % 4 == 0 and 16-byte aligned pointers); else one output per thread.
+template <int A, int VEC>
+__global__ __launch_bounds__(256) void box_down_fwd_kernel(const float *__restrict__ in, size_t N, int S, float *__restrict__ out) {
+    constexpr int V = VEC ? 4 : 1;
+    const size_t W = (size_t)(S / V), per = W * S;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= N * per) return;
+    const size_t n = t / per, r = t - n * per;
+    const int y = (int)(r / W), x = (int)(r - (size_t)y * W) * V;
+    const size_t SS = (size_t)A * S;
+    const float *src = in + n * SS * SS + (size_t)(A * y) * SS + (size_t)A * x;
+    float s[V];
+#pragma unroll
+    for (int j = 0; j < A; ++j) {
+        float row[A * V];
+        if constexpr (VEC != 0) {
+#pragma unroll
+            for (int q = 0; q < A; ++q) {
+                const float4 v4 = *reinterpret_cast<const float4 *>(src + (size_t)j * SS + 4 * q);
+                row[4 * q] = v4.x; row[4 * q + 1] = v4.y; row[4 * q + 2] = v4.z; row[4 * q + 3] = v4.w;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < A; ++q) row[q] = src[(size_t)j * SS + q];
+        }
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+#pragma unroll
+            for (int k = 0; k < A; ++k) {
+                if (j == 0 && k == 0) s[v] = row[A * v];
+                else s[v] = s[v] + row[A * v + k];
+            }
+        }
+    }
+    float *dst = out + n * (size_t)S * S + (size_t)y * S + x;
+#pragma unroll
+    for (int v = 0; v < V; ++v) s[v] = s[v] / (float)(A * A);
+    if constexpr (VEC != 0) *reinterpret_cast<float4 *>(dst) = make_float4(s[0], s[1], s[2], s[3]);
+    else dst[0] = s[0];
+}
+
+// its transpose: every sub-pixel of a block gets grad_out / A^2 (one division per output value)
+template <int A, int VEC>
+__global__ __launch_bounds__(256) void box_down_bwd_kernel(const float *__restrict__ gout, size_t N, int S, float *__restrict__ gin) {
+    constexpr int V = VEC ? 4 : 1;
+    const size_t W = (size_t)(S / V), per = W * S;
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= N * per) return;
+    const size_t n = t / per, r = t - n * per;
+    const int y = (int)(r / W), x = (int)(r - (size_t)y * W) * V;
+    const size_t SS = (size_t)A * S;
+    const float *src = gout + n * (size_t)S * S + (size_t)y * S + x;
+    float g[V];
+    if constexpr (VEC != 0) {
+        const float4 v4 = *reinterpret_cast<const float4 *>(src);
+        g[0] = v4.x; g[1] = v4.y; g[2] = v4.z; g[3] = v4.w;
+    } else {
+        g[0] = src[0];
+    }
+    float row[A * V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        const float gs = g[v] / (float)(A * A);
+#pragma unroll
+        for (int k = 0; k < A; ++k) row[A * v + k] = gs;
+    }
+    float *dst = gin + n * SS * SS + (size_t)(A * y) * SS + (size_t)A * x;
+#pragma unroll
+    for (int j = 0; j < A; ++j) {
+        if constexpr (VEC != 0) {
+#pragma unroll
+            for (int q = 0; q < A; ++q)
+                *reinterpret_cast<float4 *>(dst + (size_t)j * SS + 4 * q) = make_float4(row[4 * q], row[4 * q + 1], row[4 * q + 2], row[4 * q + 3]);
+        } else {
+#pragma unroll
+            for (int q = 0; q < A; ++q) dst[(size_t)j * SS + q] = row[q];
+        }
+    }
+}
+
+// The fixed-point bound of the supersampled texture scatter: partials[block] = scale * sum |grad_rgb| over the block's
+// grid-stride share of the B*3*S^2 values (fixed order, like st3d_det::det_abs_sum_kernel).  A pixel none of whose A x A
+// sub-pixels holds a face deposits nothing, so its values enter with weight 0: finite ones leave the bound -- and with it
+// the power-of-two scale -- independent of what a loss wrote on the background (a loss that skips the background's
+// gradient gets the bits of one that does not), a NaN or an infinity there still poisons it (x * 0 = NaN).
+template <int A>
+__global__ __launch_bounds__(256) void ss_abs_sum_kernel(const float *__restrict__ g, const int32_t *__restrict__ p2f, int B, int S,
+                                                         float scale, float *__restrict__ partials) {
+    __shared__ float s4[4];
+    float acc = 0.f;
+    const size_t HW = (size_t)S * S, n = (size_t)B * HW, SS = (size_t)A * S;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const size_t b = i / HW, p = i - b * HW;
+        const int y = (int)(p / S), x = (int)(p - (size_t)y * S);
+        const int32_t *f = p2f + b * SS * SS + (size_t)(A * y) * SS + (size_t)A * x;
+        bool covered = false;
+#pragma unroll
+        for (int j = 0; j < A; ++j)
+#pragma unroll
+            for (int k = 0; k < A; ++k) covered = covered || f[(size_t)j * SS + k] >= 0;
+        const float *gp = g + b * 3 * HW + p;
+        const float w = covered ? 1.f : 0.f;
+        acc += fabsf(gp[0]) * w;
+        acc += fabsf(gp[HW]) * w;
+        acc += fabsf(gp[2 * HW]) * w;
+    }
+    const float t = st3d_det::det_block_sum(acc, s4);
+    if (threadIdx.x == 0) partials[blockIdx.x] = t * scale;
+}
+
+constexpr int kMaxSide = 4096;      // the rasteriser's limit: fragments exist up to this side
+
+// a = 1..4 -> the template argument
+#define ST3D_SS_DISPATCH(a, CALL) \
+    switch (a) {                  \
+    case 1: { constexpr int A_ = 1; CALL; } break; \
+    case 2: { constexpr int A_ = 2; CALL; } break; \
+    case 3: { constexpr int A_ = 3; CALL; } break; \
+    default: { constexpr int A_ = 4; CALL; } break; \
+    }
+
 }  // namespace
 
 extern "C" int st3d_shade_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
@@ -271,18 +475,74 @@ extern "C" int st3d_shade_fwd(const int32_t *pix_to_face, const float *bary, con
     return ST3D_OK;
 }
 
+extern "C" int st3d_shade_ss_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                                 const float *verts_uvs, const int32_t *faces_uvs, const float *texture, int B, int S, int a,
+                                 int T, int F, int VT, float *rgb, float *coverage, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(a >= 1 && a <= 4 && S > 0 && S <= kMaxSide / a);
+    if (a == 1) return st3d_shade_fwd(pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, F, VT, rgb, coverage, stream);
+    ST3D_CHECK_ARG(pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture && rgb && coverage);
+    ST3D_CHECK_ARG(B > 0 && T > 1 && F > 0 && VT > 0);
+    const size_t n = (size_t)B * S * S;
+    ST3D_SS_DISPATCH(a, (shade_ss_fwd_kernel<A_, 0><<<st3d::cdiv((long)n, 256), 256, 0, st3d::as_stream(stream)>>>(
+                            pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, rgb, coverage)));
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+namespace {
+int box_args_ok(const void *in, const void *out, int B, int C, int S, int a) {
+    return in && out && B > 0 && C > 0 && a >= 1 && a <= 4 && S > 0 && S <= kMaxSide / a;
+}
+bool box_vec(const void *p, const void *q, int S) { return S % 4 == 0 && (((uintptr_t)p | (uintptr_t)q) & 15) == 0; }
+}  // namespace
+
+extern "C" int st3d_box_down_fwd(const float *in, int B, int C, int S, int a, float *out, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(box_args_ok(in, out, B, C, S, a));
+    const size_t N = (size_t)B * C;
+    hipStream_t s = st3d::as_stream(stream);
+    if (box_vec(in, out, S)) {
+        ST3D_SS_DISPATCH(a, (box_down_fwd_kernel<A_, 1><<<st3d::cdiv((long)(N * S * (S / 4)), 256), 256, 0, s>>>(in, N, S, out)));
+    } else {
+        ST3D_SS_DISPATCH(a, (box_down_fwd_kernel<A_, 0><<<st3d::cdiv((long)(N * S * S), 256), 256, 0, s>>>(in, N, S, out)));
+    }
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+extern "C" int st3d_box_down_bwd(const float *grad_out, int B, int C, int S, int a, float *grad_in, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(box_args_ok(grad_out, grad_in, B, C, S, a));
+    const size_t N = (size_t)B * C;
+    hipStream_t s = st3d::as_stream(stream);
+    if (box_vec(grad_out, grad_in, S)) {
+        ST3D_SS_DISPATCH(a, (box_down_bwd_kernel<A_, 1><<<st3d::cdiv((long)(N * S * (S / 4)), 256), 256, 0, s>>>(grad_out, N, S, grad_in)));
+    } else {
+        ST3D_SS_DISPATCH(a, (box_down_bwd_kernel<A_, 0><<<st3d::cdiv((long)(N * S * S), 256), 256, 0, s>>>(grad_out, N, S, grad_in)));
+    }
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
 extern "C" int st3d_shade_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
                               const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
                               int B, int S, int T, int F, int VT, float *grad_texture, float *grad_uv,
                               float *grad_bary, st3d_stream_t stream) {
+    return st3d_shade_ss_bwd(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, 1, T, F, VT,
+                             grad_texture, grad_uv, grad_bary, stream);
+}
+
+// (S: the side of grad_rgb; fragments and the per-pixel outputs are at a * S)
+extern "C" int st3d_shade_ss_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                                 const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                                 int B, int S, int a, int T, int F, int VT, float *grad_texture, float *grad_uv,
+                                 float *grad_bary, st3d_stream_t stream) {
     ST3D_CHECK_ARG(grad_rgb && pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture);
     ST3D_CHECK_ARG(grad_texture || grad_uv || grad_bary);
     ST3D_CHECK_ARG(B > 0 && S > 0 && T > 1 && F > 0 && VT > 0);
-    const size_t n = (size_t)B * S * S;
-    const int tiles = (S + 15) / 16;
-    shade_bwd_kernel<0><<<dim3(tiles * tiles, B), 256, 0, st3d::as_stream(stream)>>>(
-        grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, tiles, grad_texture, grad_uv, grad_bary,
-        nullptr);
+    ST3D_CHECK_ARG(a >= 1 && a <= 4 && S <= kMaxSide / a);
+    const int SS = a * S, tiles = (SS + 15) / 16;
+    ST3D_SS_DISPATCH(a, (shade_bwd_kernel<0, 0, A_><<<dim3(tiles * tiles, B), 256, 0, st3d::as_stream(stream)>>>(
+                            grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, SS, T, tiles, grad_texture,
+                            grad_uv, grad_bary, nullptr)));
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }
@@ -302,24 +562,39 @@ extern "C" int st3d_shade_bwd_det(const float *grad_rgb, const int32_t *pix_to_f
                                   const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
                                   int B, int S, int T, int F, int VT, float *grad_texture, float *grad_uv, float *grad_bary,
                                   void *workspace, size_t workspace_bytes, st3d_stream_t stream) {
+    return st3d_shade_ss_bwd_det(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, 1, T, F, VT,
+                                 grad_texture, grad_uv, grad_bary, workspace, workspace_bytes, stream);
+}
+
+// a > 1: the bound pass runs over grad_rgb itself (B*3*S^2 values, ss_abs_sum_kernel): a block deposits a^2 contributions
+// of at most |g| / a^2 each, so sum |g| over the pixels that deposit anything bounds every texel sum
+extern "C" int st3d_shade_ss_bwd_det(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                                     const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                                     int B, int S, int a, int T, int F, int VT, float *grad_texture, float *grad_uv,
+                                     float *grad_bary, void *workspace, size_t workspace_bytes, st3d_stream_t stream) {
     ST3D_CHECK_ARG(grad_rgb && pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture && workspace);
     ST3D_CHECK_ARG(grad_texture);
     ST3D_CHECK_ARG(B > 0 && S > 0 && T > 1 && F > 0 && VT > 0);
+    ST3D_CHECK_ARG(a >= 1 && a <= 4 && S <= kMaxSide / a);
     ST3D_CHECK_ARG(workspace_bytes >= st3d_shade_bwd_det_workspace_bytes(T) && ((uintptr_t)workspace & 15) == 0);
     hipStream_t s = st3d::as_stream(stream);
     auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
     float *partials = st3d_det::partials_of(workspace);
     long long *acc = st3d_det::accum_of(workspace, kDetPartials);
     const size_t npx = (size_t)B * 3 * S * S, nacc = (size_t)T * T * 3;
-    st3d_det::det_abs_sum_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, npx, partials);
+    if (a == 1) {
+        st3d_det::det_abs_sum_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, npx, partials);
+    } else {
+        ST3D_SS_DISPATCH(a, (ss_abs_sum_kernel<A_><<<kDetPartials, 256, 0, s>>>(grad_rgb, pix_to_face, B, S, 1.f, partials)));
+    }
     ST3D_LAUNCH_CHECK();
     st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kDetPartials, hdr);
     ST3D_LAUNCH_CHECK();
     ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
-    const int tiles = (S + 15) / 16;
-    shade_bwd_kernel<1><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs,
-                                                                texture, B, S, T, tiles, reinterpret_cast<float *>(acc), grad_uv,
-                                                                grad_bary, hdr);
+    const int SS = a * S, tiles = (SS + 15) / 16;
+    ST3D_SS_DISPATCH(a, (shade_bwd_kernel<1, 0, A_><<<dim3(tiles * tiles, B), 256, 0, s>>>(
+                            grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, SS, T, tiles,
+                            reinterpret_cast<float *>(acc), grad_uv, grad_bary, hdr)));
     ST3D_LAUNCH_CHECK();
     st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_texture);
     ST3D_LAUNCH_CHECK();
@@ -353,15 +628,30 @@ extern "C" int st3d_shade_lit_fwd(const int32_t *pix_to_face, const float *bary,
                                   int F, int VT, const float *verts, const float *normals, const int32_t *faces, const float *R,
                                   const float *trans, const float *light, int n_lights, int kind, float *rgb, float *mask,
                                   st3d_stream_t stream) {
-    ST3D_CHECK_ARG(pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture && rgb && mask);
+    return st3d_shade_ss_lit_fwd(pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, 1, T, F, VT, verts, normals,
+                                 faces, R, trans, light, n_lights, kind, rgb, mask, stream);
+}
+
+extern "C" int st3d_shade_ss_lit_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                                     const float *verts_uvs, const int32_t *faces_uvs, const float *texture, int B, int S, int a,
+                                     int T, int F, int VT, const float *verts, const float *normals, const int32_t *faces,
+                                     const float *R, const float *trans, const float *light, int n_lights, int kind, float *rgb,
+                                     float *coverage, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture && rgb && coverage);
     ST3D_CHECK_ARG(faces && R && trans && light && (n_lights == 1 || n_lights == B));
     ST3D_CHECK_ARG(kind >= st3d_phong::kAmbient && kind <= st3d_phong::kHeadlight);
     ST3D_CHECK_ARG(kind == st3d_phong::kAmbient || (verts && normals));
     ST3D_CHECK_ARG(B > 0 && S > 0 && T > 1 && F > 0 && VT > 0);
+    ST3D_CHECK_ARG(a >= 1 && a <= 4 && S <= kMaxSide / a);
     const size_t n = (size_t)B * S * S;
-    shade_fwd_kernel<1><<<st3d::cdiv((long)n, 256), 256, 0, st3d::as_stream(stream)>>>(
-        pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, rgb, mask,
-        lit_args(verts, normals, faces, R, trans, light, n_lights, kind, nullptr));
+    const st3d_phong::LitArgs la = lit_args(verts, normals, faces, R, trans, light, n_lights, kind, nullptr);
+    if (a == 1) {
+        shade_fwd_kernel<1><<<st3d::cdiv((long)n, 256), 256, 0, st3d::as_stream(stream)>>>(
+            pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, rgb, coverage, la);
+    } else {
+        ST3D_SS_DISPATCH(a, (shade_ss_fwd_kernel<A_, 1><<<st3d::cdiv((long)n, 256), 256, 0, st3d::as_stream(stream)>>>(
+                                pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, rgb, coverage, la)));
+    }
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }
@@ -372,6 +662,17 @@ extern "C" int st3d_shade_lit_bwd(const float *grad_rgb, const int32_t *pix_to_f
                                   const int32_t *faces, const float *R, const float *trans, const float *light, int n_lights,
                                   int kind, float weight_bound, float *grad_texture, float *grad_bary, float *grad_np,
                                   void *workspace, size_t workspace_bytes, st3d_stream_t stream) {
+    return st3d_shade_ss_lit_bwd(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, 1, T, F, VT, verts,
+                                 normals, faces, R, trans, light, n_lights, kind, weight_bound, grad_texture, grad_bary, grad_np,
+                                 workspace, workspace_bytes, stream);
+}
+
+extern "C" int st3d_shade_ss_lit_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                                     const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                                     int B, int S, int a, int T, int F, int VT, const float *verts, const float *normals,
+                                     const int32_t *faces, const float *R, const float *trans, const float *light, int n_lights,
+                                     int kind, float weight_bound, float *grad_texture, float *grad_bary, float *grad_np,
+                                     void *workspace, size_t workspace_bytes, st3d_stream_t stream) {
     ST3D_CHECK_ARG(grad_rgb && pix_to_face && bary && zbuf && dists && verts_uvs && faces_uvs && texture);
     ST3D_CHECK_ARG(faces && R && trans && light && (n_lights == 1 || n_lights == B));
     ST3D_CHECK_ARG(kind >= st3d_phong::kAmbient && kind <= st3d_phong::kHeadlight);
@@ -379,13 +680,14 @@ extern "C" int st3d_shade_lit_bwd(const float *grad_rgb, const int32_t *pix_to_f
     ST3D_CHECK_ARG(grad_texture || grad_bary);
     ST3D_CHECK_ARG(!grad_bary == !grad_np);
     ST3D_CHECK_ARG(B > 0 && S > 0 && T > 1 && F > 0 && VT > 0 && weight_bound >= 0.f);
+    ST3D_CHECK_ARG(a >= 1 && a <= 4 && S <= kMaxSide / a);
     hipStream_t s = st3d::as_stream(stream);
-    const int tiles = (S + 15) / 16;
+    const int SS = a * S, tiles = (SS + 15) / 16;
     const st3d_phong::LitArgs la = lit_args(verts, normals, faces, R, trans, light, n_lights, kind, grad_np);
     if (!workspace) {
-        shade_bwd_kernel<0, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs,
-                                                                       faces_uvs, texture, B, S, T, tiles, grad_texture, nullptr,
-                                                                       grad_bary, nullptr, la);
+        ST3D_SS_DISPATCH(a, (shade_bwd_kernel<0, 1, A_><<<dim3(tiles * tiles, B), 256, 0, s>>>(
+                                grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, SS, T, tiles, grad_texture,
+                                nullptr, grad_bary, nullptr, la)));
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     }
@@ -396,14 +698,18 @@ extern "C" int st3d_shade_lit_bwd(const float *grad_rgb, const int32_t *pix_to_f
     float *partials = st3d_det::partials_of(workspace);
     long long *acc = st3d_det::accum_of(workspace, kDetPartials);
     const size_t npx = (size_t)B * 3 * S * S, nacc = (size_t)T * T * 3;
-    st3d_det::det_abs_sum_scaled_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, npx, weight_bound, partials);
+    if (a == 1) {
+        st3d_det::det_abs_sum_scaled_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, npx, weight_bound, partials);
+    } else {
+        ST3D_SS_DISPATCH(a, (ss_abs_sum_kernel<A_><<<kDetPartials, 256, 0, s>>>(grad_rgb, pix_to_face, B, S, weight_bound, partials)));
+    }
     ST3D_LAUNCH_CHECK();
     st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kDetPartials, hdr);
     ST3D_LAUNCH_CHECK();
     ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
-    shade_bwd_kernel<1, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs,
-                                                                   texture, B, S, T, tiles, reinterpret_cast<float *>(acc), nullptr,
-                                                                   grad_bary, hdr, la);
+    ST3D_SS_DISPATCH(a, (shade_bwd_kernel<1, 1, A_><<<dim3(tiles * tiles, B), 256, 0, s>>>(
+                            grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, SS, T, tiles,
+                            reinterpret_cast<float *>(acc), nullptr, grad_bary, hdr, la)));
     ST3D_LAUNCH_CHECK();
     st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_texture);
     ST3D_LAUNCH_CHECK();

@@ -89,6 +89,20 @@ SIGNATURES = {
     "st3d_phong_scatter_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "st3d_phong_scatter": (c_int, [c_f32p, c_i32p, c_f32p, c_i32p, c_int, c_int, c_int, c_int, c_int, c_f32p, ctypes.c_void_p,
                                    c_size, c_stream]),
+    "st3d_shade_ss_fwd": (c_int, [c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_f32p, c_f32p, c_stream]),
+    "st3d_shade_ss_bwd": (c_int, [c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int,
+                                  c_int, c_int, c_f32p, c_f32p, c_f32p, c_stream]),
+    "st3d_shade_ss_bwd_det": (c_int, [c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_size, c_stream]),
+    "st3d_shade_ss_lit_fwd": (c_int, [c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_int,
+                                      c_int, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_f32p, c_f32p,
+                                      c_stream]),
+    "st3d_shade_ss_lit_bwd": (c_int, [c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int,
+                                      c_int, c_int, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_float, c_f32p,
+                                      c_f32p, c_f32p, ctypes.c_void_p, c_size, c_stream]),
+    "st3d_box_down_fwd": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_stream]),
+    "st3d_box_down_bwd": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_stream]),
     "st3d_apply_background": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_f32p, c_stream]),
     "st3d_conv3x3_packed_floats": (c_size, [c_int, c_int]),
     "st3d_conv3x3_pack": (c_int, [c_f32p, c_int, c_int, c_f32p, c_f32p, c_stream]),

@@ -66,6 +66,9 @@ SHARED_FLAGS = [
     Flag("texture_pyramid_levels", int, 1, "optimise the texture as the sum of N maps of halving sides, so that texels no "
          "rendered pixel touches move with their neighbours; 1 = the plain map, 0 = as many levels as the side allows "
          "(down to a side of 4..7).  Every level moves by about lr a step, their sum by up to N x lr"),
+    Flag("supersample", int, 1, "rasterise and shade every render of the run (current, content, final) at N x size and hand the "
+         "loss the N x N box-filtered image at size: each pixel then carries gradient to N^2 texture footprints and "
+         "silhouette pixels get a fractional coverage; 1..4, N x size <= 4096, 1 = off"),
 ]
 
 # regularisers the reference defines but never switches on (losses.py:48-65, notes.txt:36,39); weight 0 = off
@@ -92,6 +95,14 @@ def check_args(args):
     if levels != 1 and getattr(args, "optimization_target", None) == 'mesh':
         return ("--texture_pyramid_levels needs --optimization_target texture or both: with 'mesh' the texture is not "
                 "optimised")
+    n = getattr(args, "supersample", 1)
+    if not 1 <= n <= 4:
+        return "--supersample must be in 1..4"
+    if n * getattr(args, "size", 0) > 4096:
+        return f"--supersample {n} x --size {args.size} exceeds the rasteriser's 4096 pixels a side"
+    if n > 1 and getattr(args, "silhouette_weight", 0.0):
+        return ("--supersample > 1 cannot be combined with --silhouette_weight: alpha-only (silhouette) renders are not "
+                "supersampled")
     return None
 
 
@@ -229,7 +240,11 @@ class Run:
         self.content_mesh = _u.build_mesh(verts_uvs, faces_uvs, tex, verts, faces)
 
         cams = FoVPerspectiveCameras(device=self.device)
-        settings = RasterizationSettings(image_size=args.size, blur_radius=0.0, faces_per_pixel=1)
+        supersample = getattr(args, "supersample", 1)
+        if supersample == 1:
+            settings = RasterizationSettings(image_size=args.size, blur_radius=0.0, faces_per_pixel=1)
+        else:
+            settings = RasterizationSettings(image_size=args.size, blur_radius=0.0, faces_per_pixel=1, supersample=supersample)
         lights, materials = make_lights(args, self.device)
         self.renderer = MeshRenderer(rasterizer=MeshRasterizer(cameras=cams, raster_settings=settings),
                                      shader=SoftPhongShader(device=self.device, cameras=cams, lights=lights,

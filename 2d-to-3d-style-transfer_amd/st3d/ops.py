@@ -170,6 +170,94 @@ def shade_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, grad_texture=No
     return out if len(out) > 1 else out[0]
 
 
+# ---- supersampling (csrc/shade.hip): fragments at side a * S, images and their gradients at side S
+MAX_RASTER_SIDE = 4096
+SUPERSAMPLE_MAX = 4
+
+
+def check_supersample(a, S=None):
+    """a must be an int in 1..4 (ValueError) and a * S within the rasteriser's 4096."""
+    if isinstance(a, bool) or not isinstance(a, int) or not 1 <= a <= SUPERSAMPLE_MAX:
+        raise ValueError(f"supersample must be an int in 1..{SUPERSAMPLE_MAX}, got {a!r}")
+    if S is not None and a * int(S) > MAX_RASTER_SIDE:
+        raise ValueError(f"supersample * image_size = {a} * {S} exceeds the rasteriser's {MAX_RASTER_SIDE}")
+    return a
+
+
+def _ss_side(p2f, a):
+    B, SS, _ = p2f.shape
+    check_supersample(a)
+    if SS % a:
+        raise ValueError(f"fragments of side {SS} are no multiple of supersample = {a}")
+    return B, SS // a
+
+
+def box_down_fwd(x, a):
+    """(B,C,a*S,a*S) -> (B,C,S,S): ordered row-major sum of every a x a block / a^2"""
+    check_supersample(a)
+    B, C, SS, W = x.shape
+    if SS != W or SS % a:
+        raise ValueError(f"box_down_fwd takes square images whose side is a multiple of {a}, got {tuple(x.shape)}")
+    out = torch.empty((B, C, SS // a, SS // a), dtype=F32, device=x.device)
+    call("st3d_box_down_fwd", dptr(x.contiguous(), F32), B, C, SS // a, a, dptr(out), stream_ptr())
+    return out
+
+
+def box_down_bwd(grad_out, a):
+    """(B,C,S,S) -> (B,C,a*S,a*S): grad_out / a^2 at every sub-pixel"""
+    check_supersample(a)
+    B, C, S, W = grad_out.shape
+    if S != W:
+        raise ValueError(f"box_down_bwd takes square images, got {tuple(grad_out.shape)}")
+    check_supersample(a, S)
+    out = torch.empty((B, C, a * S, a * S), dtype=F32, device=grad_out.device)
+    call("st3d_box_down_bwd", dptr(grad_out.contiguous(), F32), B, C, S, a, dptr(out), stream_ptr())
+    return out
+
+
+def shade_ss_fwd(frag, verts_uvs, faces_uvs_i32, texture, a):
+    """frag at side a*S -> rgb (B,3,S,S), coverage (B,1,S,S) in {0, 1/a^2, ..., 1}"""
+    p2f, zbuf, bary, dists = frag
+    B, S = _ss_side(p2f, a)
+    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
+    cov = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
+    call("st3d_shade_ss_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
+         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, a, texture.shape[0], faces_uvs_i32.shape[0], verts_uvs.shape[0],
+         dptr(rgb), dptr(cov), stream_ptr())
+    return rgb, cov
+
+
+def shade_ss_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, a, grad_texture=None, want_uv=False, want_bary=False,
+                 want_texture=True):
+    """grad_rgb (B,3,S,S), frag at side a*S -> grad_texture (T,T,3) [, grad_uv (B,aS,aS,2)] [, grad_bary (B,aS,aS,3)]"""
+    p2f, zbuf, bary, dists = frag
+    B, S = _ss_side(p2f, a)
+    SS = a * S
+    T = texture.shape[0]
+    if tuple(grad_rgb.shape) != (B, 3, S, S):
+        raise ValueError(f"grad_rgb must be {(B, 3, S, S)}, got {tuple(grad_rgb.shape)}")
+    if grad_texture is None and want_texture:
+        grad_texture = torch.zeros((T, T, 3), dtype=F32, device=p2f.device)
+    guv = torch.empty((B, SS, SS, 2), dtype=F32, device=p2f.device) if want_uv else None
+    gbary = torch.empty((B, SS, SS, 3), dtype=F32, device=p2f.device) if want_bary else None
+    grad_rgb = grad_rgb.contiguous()
+    head = (dptr(grad_rgb, F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
+            dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, a, T, faces_uvs_i32.shape[0], verts_uvs.shape[0],
+            dptr(grad_texture, F32) if grad_texture is not None else None, dptr(guv), dptr(gbary))
+    if _DETERMINISTIC and grad_texture is not None:
+        nb = _lib.load().st3d_shade_bwd_det_workspace_bytes(T)
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=p2f.device)
+        call("st3d_shade_ss_bwd_det", *head, dptr(ws), nb, stream_ptr())
+    else:
+        call("st3d_shade_ss_bwd", *head, stream_ptr())
+    out = (grad_texture,)
+    if want_uv:
+        out += (guv,)
+    if want_bary:
+        out += (gbary,)
+    return out if len(out) > 1 else out[0]
+
+
 def raster_bwd(grad_bary, p2f, verts_ndc, faces_i32):
     """grad_bary (B,S,S,3) -> grad_verts_ndc (B,V,3)"""
     B, V, _ = verts_ndc.shape
@@ -490,6 +578,40 @@ def shade_lit_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, lit, want_t
          dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, faces_uvs_i32.shape[0],
          verts_uvs.shape[0], *_lit_ptrs(lit), float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gnp), dptr(ws), nb,
          stream_ptr())
+    return gt, gb, gnp
+
+
+def shade_ss_lit_fwd(frag, verts_uvs, faces_uvs_i32, texture, lit, a):
+    p2f, zbuf, bary, dists = frag
+    B, S = _ss_side(p2f, a)
+    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
+    cov = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
+    call("st3d_shade_ss_lit_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
+         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, a, texture.shape[0], faces_uvs_i32.shape[0], verts_uvs.shape[0],
+         *_lit_ptrs(lit), dptr(rgb), dptr(cov), stream_ptr())
+    return rgb, cov
+
+
+def shade_ss_lit_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, lit, a, want_texture=True, want_geometry=False):
+    """-> (grad_texture (T,T,3) | None, grad_bary (B,aS,aS,3) | None, grad_np (B,aS,aS,6) | None)"""
+    p2f, zbuf, bary, dists = frag
+    B, S = _ss_side(p2f, a)
+    SS = a * S
+    T = texture.shape[0]
+    dev = p2f.device
+    if tuple(grad_rgb.shape) != (B, 3, S, S):
+        raise ValueError(f"grad_rgb must be {(B, 3, S, S)}, got {tuple(grad_rgb.shape)}")
+    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
+    gb = torch.empty((B, SS, SS, 3), dtype=F32, device=dev) if want_geometry else None
+    gnp = torch.empty((B, SS, SS, 6), dtype=F32, device=dev) if want_geometry else None
+    ws, nb = None, 0
+    if _DETERMINISTIC and gt is not None:
+        nb = _lib.load().st3d_shade_bwd_det_workspace_bytes(T)
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
+    call("st3d_shade_ss_lit_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
+         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, a, T,
+         faces_uvs_i32.shape[0], verts_uvs.shape[0], *_lit_ptrs(lit), float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gnp),
+         dptr(ws), nb, stream_ptr())
     return gt, gb, gnp
 
 

@@ -27,6 +27,7 @@ alone, without a texture, and alpha -- its own and SoftPhongShader's under soft 
 vertices through the signed edge distance (csrc/silhouette.hip); losses.compute_silhouette_loss is the fused loss on it.
 """
 import math
+import os
 
 import torch
 
@@ -233,14 +234,17 @@ class RasterizationSettings:
     """PyTorch3D RasterizationSettings: image_size, blur_radius, faces_per_pixel, clip_barycentric_coords
     (None = clip iff blur_radius > 0, the PyTorch3D default), perspective_correct (None = True: every camera here is a
     perspective camera), cull_backfaces.  bin_size / max_faces_per_bin only pick PyTorch3D's binning strategy and are
-    accepted and ignored.  Anything but the reference's own values (first_approach.py:107) runs on the general kernels."""
+    accepted and ignored.  Anything but the reference's own values (first_approach.py:107) runs on the general kernels.
+    supersample = a in 1..4 (not PyTorch3D's; 1 = off): rasterise and shade at a * image_size, hand out the a x a
+    box-filtered image at image_size (PyTorch3D's documented anti-aliasing, render larger then avg_pool2d, without the
+    larger image: csrc/shade.hip).  Coverage then is the covered share of the pixel's a^2 sub-pixels."""
     MAX_FACES_PER_PIXEL = 8
 
     Z_CLIP_DEFAULT = 0.5        # PyTorch3D MeshRasterizer: z_clip_value None -> znear / 2 for perspective cameras (znear = 1)
 
     def __init__(self, image_size=256, blur_radius=0.0, faces_per_pixel=1, bin_size=None, max_faces_per_bin=None,
                  perspective_correct=None, clip_barycentric_coords=None, cull_backfaces=False, z_clip_value=None,
-                 cull_to_frustum=False, **kw):
+                 cull_to_frustum=False, supersample=1, **kw):
         if isinstance(image_size, (tuple, list)):
             if len(image_size) != 2 or image_size[0] != image_size[1]:
                 raise NotImplementedError("square images only")
@@ -261,6 +265,7 @@ class RasterizationSettings:
         # None: PyTorch3D's default plane.  The general kernels clip at it; the specialised K = 1 kernels only WATCH it
         # (st3d.ops.check_near_plane) -- an explicit value sends the render to the general kernels
         self.z_clip_value = None if z_clip_value is None else float(z_clip_value)
+        self.supersample = ops.check_supersample(supersample, self.image_size)
 
     @property
     def z_clip(self):
@@ -278,6 +283,11 @@ class SilhouetteRasterizationSettings(RasterizationSettings):
     MeshRenderer with a SoftSilhouetteShader accepts them; every other shader needs each fragment's depth and colour and
     stays at RasterizationSettings' 8."""
     MAX_FACES_PER_PIXEL = 64
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        if self.supersample > 1:
+            raise NotImplementedError("supersample > 1 is not implemented for alpha-only (silhouette) renders")
 
 
 class BlendParams:
@@ -550,6 +560,12 @@ class SoftSilhouetteShader:
         self.blend_params = blend_params if blend_params is not None else BlendParams()
 
 
+def _refuse_supersampled_silhouette(raster_settings):
+    if getattr(raster_settings, "supersample", 1) > 1:
+        raise NotImplementedError("supersample > 1 is not implemented for alpha-only (silhouette) renders: a "
+                                  "SoftSilhouetteShader takes RasterizationSettings(supersample=1)")
+
+
 class _SilhouetteFn(torch.autograd.Function):
     """verts -> alpha (B,1,S,S): project, general raster, silhouette_fwd; backward silhouette_bwd -> raster_soft_bwd with
     d/d(dists) alone -> project_verts_bwd."""
@@ -611,6 +627,7 @@ def render_silhouette(meshes, R, T, image_size, raster_settings=None, blend_para
     select the silhouette rasteriser (no fragments, faces_per_pixel up to 64)."""
     dev = meshes.device
     rs = raster_settings if raster_settings is not None else RasterizationSettings(image_size=image_size)
+    _refuse_supersampled_silhouette(rs)
     bp = blend_params if blend_params is not None else BlendParams()
     with ops.trace("render"):
         if isinstance(rs, SilhouetteRasterizationSettings):
@@ -679,6 +696,78 @@ class _RenderFn(torch.autograd.Function):
                 gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
                 gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
         return gverts, gtex, None, None, None, None, None, None, None
+
+
+class _SSRenderFn(torch.autograd.Function):
+    """_RenderFn supersampled: fragments at side a * S on the same rasteriser, (rgb (B,3,S,S), coverage (B,1,S,S)) from the
+    fused kernels (st3d.ops.shade_ss_*); the backward hands the S-sized gradient to them and the a * S barycentric
+    gradients to the unchanged raster / projection backward."""
+
+    @staticmethod
+    def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, a, lighting=None):
+        v = verts.detach().to(torch.float32).contiguous()
+        tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
+        if tex.shape[0] != tex.shape[1]:
+            raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
+        uvs = verts_uvs.detach().to(torch.float32).reshape(-1, 2).contiguous()
+        ndc = ops.project_verts(v, R, T)
+        frag = ops.raster_fwd(ndc, faces_i32, a * S)
+        ctx.lit = _lit_setup(lighting, verts, v, faces_i32, R, T)
+        if ctx.lit is None:
+            rgb, cov = ops.shade_ss_fwd(frag, uvs, faces_uvs_i32, tex, a)
+        else:
+            rgb, cov = ops.shade_ss_lit_fwd(frag, uvs, faces_uvs_i32, tex, ctx.lit, a)
+        ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.a = frag, uvs, faces_uvs_i32, tex, a
+        ctx.tex_shape = tex_map.shape
+        ctx.geom = (v, ndc, faces_i32, R, T)
+        ctx.verts_shape = verts.shape
+        ctx.mark_non_differentiable(cov)
+        return rgb, cov
+
+    @staticmethod
+    def backward(ctx, grad_rgb, _grad_cov):
+        with ops.trace("render_backward"):
+            return _SSRenderFn._backward(ctx, grad_rgb)
+
+    @staticmethod
+    def _backward(ctx, grad_rgb):
+        need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gtex = gverts = None
+        if need_v or need_t:
+            g = grad_rgb.to(torch.float32)
+            gnp = None
+            if ctx.lit is not None:
+                gt, gbary, gnp = ops.shade_ss_lit_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit, ctx.a,
+                                                      want_texture=need_t, want_geometry=need_v)
+            else:
+                res = ops.shade_ss_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.a, want_bary=need_v, want_texture=need_t)
+                gt, gbary = (res if need_v else (res, None))
+            if need_t:
+                gtex = gt.reshape(ctx.tex_shape)
+            if need_v:
+                v, ndc, faces_i32, R, T = ctx.geom
+                gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
+                gverts = ops.project_verts_bwd(v, R, T, gndc)
+                if ctx.lit is not None:
+                    gverts = _lit_vertex_grad(ctx.lit, gverts, gnp, ctx.frag[0], ctx.frag[2])
+                gverts = gverts.reshape(ctx.verts_shape)
+        return (gverts, gtex) + (None,) * 8
+
+
+class _BoxDownFn(torch.autograd.Function):
+    """(B,C,a*S,a*S) -> (B,C,S,S) box filter (st3d.ops.box_down_fwd) and its transpose"""
+
+    @staticmethod
+    def forward(ctx, x, a):
+        ctx.a = a
+        ctx.set_materialize_grads(False)
+        return ops.box_down_fwd(x.detach().to(torch.float32), a)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if grad_out is None:
+            return None, None
+        return ops.box_down_bwd(grad_out.to(torch.float32), ctx.a), None
 
 
 class _SoftRenderFn(torch.autograd.Function):
@@ -772,6 +861,13 @@ def tag_need(rgb, p2f):
     return rgb
 
 
+def tag_need_mask(rgb, need):
+    """tag_need for a producer that knows its coverage as a boolean (n,S,S) rather than as fragments"""
+    if rgb.requires_grad:
+        setattr(rgb, NEED_TAG, need.view(torch.uint8))
+    return rgb
+
+
 def need_of(t):
     """The coverage tag of `t` if a gradient consumer may rely on it, else None: the tag must fit the tensor, and nobody
     may be watching the tensor's own gradient (retain_grad, backward hooks) -- they would see the zeros."""
@@ -859,6 +955,8 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
                                   "only: they need a SoftSilhouetteShader")
     R, T = R.to(dev), T.to(dev)
     lighting = lighting_of(lights, materials, dev)
+    if getattr(rs, "supersample", 1) > 1:
+        return _render_views_ss(meshes, R, T, int(image_size), rs, bp, lighting)
     hard_settings = uses_hard_path(rs, bp)
     if hard_settings and (ops.near_plane_triggered() or
                           reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT)):
@@ -893,6 +991,52 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
     return rgb, alpha
 
 
+def ss_fused():
+    """ST3D_SS_FUSED=0: the hard path of a supersampled render runs the plain kernels at a * S and the box filter (the
+    composition the fused kernels are compared with) instead of the fused kernels.  Read at every render."""
+    return os.environ.get("ST3D_SS_FUSED", "1") not in ("", "0")
+
+
+def _render_views_ss(meshes, R, T, S, rs, bp, lighting):
+    """_render_views at supersample = a > 1 -> (rgb (B,3,S,S), coverage (B,1,S,S)): everything is rasterised and shaded at
+    a * S and box-filtered.  Hard settings: the fused kernels on the specialised rasteriser.  Everything else (K > 1,
+    blur, another blend, the near-plane reroute): _SoftRenderFn at a * S, then the box filter over rgb and alpha, whose
+    gradients go back through its transpose.  Coverage is fractional either way; ``coverage > 0`` == some sub-pixel
+    covered."""
+    a = ops.check_supersample(rs.supersample, S)
+    tex = meshes.textures
+    hard_settings = uses_hard_path(rs, bp)
+    rs_hi = rs
+    if hard_settings and (ops.near_plane_triggered() or
+                          reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT)):
+        if ops.NEAR_PLANE_POLICY == "raise":         # (the decision is about vertices, not pixels: as at a = 1)
+            raise RuntimeError(ops.NEAR_PLANE_MESSAGE)
+        ops.note_near_plane()
+        rs_hi = RasterizationSettings(image_size=S, z_clip_value=RasterizationSettings.Z_CLIP_DEFAULT)
+    args = (meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(), tex.faces_uvs_i32(), R, T)
+    if uses_hard_path(rs_hi, bp):
+        if ss_fused():
+            rgb, cov = _SSRenderFn.apply(*args, S, a, lighting)
+        else:
+            rgb_hi, mask_hi = _RenderFn.apply(*args, a * S, lighting)
+            rgb, cov = _BoxDownFn.apply(rgb_hi, a), ops.box_down_fwd(mask_hi, a)
+        tag_need_mask(rgb, cov[:, 0] > 0)
+        tag_flat(rgb, (1.0, 1.0, 1.0))
+        return rgb, cov
+    bp = bp if bp is not None else BlendParams()
+    rgb_hi, alpha_hi = _SoftRenderFn.apply(*args, a * S, rs_hi.faces_per_pixel, rs_hi.blur_radius,
+                                           rs_hi.clip_barycentric_coords, bp.sigma, bp.gamma, bp.background_color,
+                                           rs_hi.cull_backfaces, rs_hi.perspective_correct, rs_hi.z_clip, lighting)
+    if hard_settings:       # thresholded at a * S first, as at a = 1; the filter then hands out the same fractional coverage
+        alpha_hi = (alpha_hi.detach() > 0).to(torch.float32)
+    rgb, alpha = _BoxDownFn.apply(rgb_hi, a), _BoxDownFn.apply(alpha_hi, a)
+    if rgb.requires_grad:
+        hit = (rgb_hi.grad_fn.frag[0] >= 0).any(dim=-1)           # (B,aS,aS): the RGB backward reads its gradient there
+        tag_need_mask(rgb, hit.view(hit.shape[0], S, a, S, a).any(dim=4).any(dim=2))
+    tag_flat(rgb, bp.background_color)
+    return rgb, alpha
+
+
 class MeshRenderer:
     """``renderer(meshes_world=mesh, cameras=camera)`` -> (n,S,S,4) RGBA like PyTorch3D's
     MeshRenderer (utils.py:69); ``render_meshes`` in the drop-in utils.py calls
@@ -903,11 +1047,17 @@ class MeshRenderer:
                 and not isinstance(shader, SoftSilhouetteShader):
             raise NotImplementedError("SilhouetteRasterizationSettings render on the silhouette rasteriser, which produces "
                                       "alpha only: they need a SoftSilhouetteShader, got " + type(shader).__name__)
+        if isinstance(shader, SoftSilhouetteShader):
+            _refuse_supersampled_silhouette(getattr(rasterizer, "raster_settings", None))
         self.rasterizer, self.shader = rasterizer, shader
 
     @property
     def image_size(self):
         return self.rasterizer.raster_settings.image_size
+
+    @property
+    def supersample(self):
+        return getattr(self.rasterizer.raster_settings, "supersample", 1)
 
     @property
     def is_hard(self):

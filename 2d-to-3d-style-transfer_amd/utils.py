@@ -88,7 +88,8 @@ def get_vgg(weights=None, seed=0):
 def render_meshes(renderer, meshes, cameras):
     """-> colour (n,3,H,W), mask (n,1,H,W) with mask = (alpha > 0) as float (:65-77)."""
     colour, coverage = renderer.render(meshes, cameras)
-    if not renderer.is_hard:                 # soft settings hand back alpha itself
+    if not renderer.is_hard or getattr(renderer, "supersample", 1) > 1:
+        # soft settings hand back alpha itself, a supersampled render the covered share of each pixel
         coverage = (coverage.detach() > 0).float()
     return colour, coverage
 

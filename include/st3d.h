@@ -307,6 +307,45 @@ int st3d_phong_scatter(const float *grad_np, const int32_t *pix_to_face, const f
                        int B, int V, int F, int S, int K, float *out, void *workspace, size_t workspace_bytes,
                        st3d_stream_t stream);
 
+/* ---- supersampled rendering: the fragments are rasterised at side a * S (a = 1..4, a * S <= 4096) and the loss sees the
+ * a x a box-filtered image at side S.  For output pixel (y, x): s = c[ay][ax], then s = s + c[ay+j][ax+i] for the other
+ * sub-pixels in row-major order, out = s / (float)(a * a) -- fp32, uncontracted, correctly rounded division; c is the colour
+ * st3d_shade_fwd computes at the sub-pixel (white where there is no face).  coverage (B,1,S,S) is the same expression over
+ * the 0/1 mask: a count over a^2, > 0 exactly where some sub-pixel is covered.  Backward: every sub-pixel of a block runs
+ * st3d_shade_bwd's expressions with grad_rgb(y, x) / (float)(a * a) as its gradient.  S is the side of rgb / grad_rgb;
+ * pix_to_face, bary, zbuf, dists and the per-pixel outputs grad_uv, grad_bary, grad_np are at side a * S.  Neither the
+ * a * S image nor an a * S gradient is ever written.  a = 1 is the plain entry point. */
+int st3d_shade_ss_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                      const float *verts_uvs, const int32_t *faces_uvs, const float *texture, int B, int S, int a,
+                      int T, int F, int VT, float *rgb, float *coverage, st3d_stream_t stream);
+int st3d_shade_ss_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                      const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                      int B, int S, int a, int T, int F, int VT, float *grad_texture, float *grad_uv,
+                      float *grad_bary, st3d_stream_t stream);
+/* fixed point (workspace >= st3d_shade_bwd_det_workspace_bytes(T)): the bound pass runs over grad_rgb itself; for a > 1 the
+ * values of a pixel none of whose sub-pixels holds a face (it deposits nothing) enter it with weight 0, so the result does
+ * not depend on finite values there and a NaN or an infinity anywhere still comes out as NaN */
+int st3d_shade_ss_bwd_det(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                          const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                          int B, int S, int a, int T, int F, int VT, float *grad_texture /* accumulated into */,
+                          float *grad_uv, float *grad_bary, void *workspace, size_t workspace_bytes,
+                          st3d_stream_t stream);
+int st3d_shade_ss_lit_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                          const float *verts_uvs, const int32_t *faces_uvs, const float *texture, int B, int S, int a,
+                          int T, int F, int VT, const float *verts, const float *normals, const int32_t *faces,
+                          const float *R, const float *trans, const float *light, int n_lights, int kind, float *rgb,
+                          float *coverage, st3d_stream_t stream);
+int st3d_shade_ss_lit_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                          const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
+                          int B, int S, int a, int T, int F, int VT, const float *verts, const float *normals,
+                          const int32_t *faces, const float *R, const float *trans, const float *light, int n_lights,
+                          int kind, float weight_bound, float *grad_texture, float *grad_bary, float *grad_np,
+                          void *workspace, size_t workspace_bytes, st3d_stream_t stream);
+/* the box filter alone, in (B,C,a*S,a*S) -> out (B,C,S,S) with the sum order and division above, and its transpose
+ * grad_out (B,C,S,S) -> grad_in (B,C,a*S,a*S) = grad_out / (float)(a * a) at every sub-pixel (overwritten) */
+int st3d_box_down_fwd(const float *in, int B, int C, int S, int a, float *out, st3d_stream_t stream);
+int st3d_box_down_bwd(const float *grad_out, int B, int C, int S, int a, float *grad_in, st3d_stream_t stream);
+
 /* apply_background, utils.py:19-30: out = img*mask + bg*(1-mask); bg (B,3,S,S) or, with
  * bg_batch == 1, one (3,S,S) image broadcast over the batch.  Optional grad path is the
  * same kernel applied to the gradient with bg = NULL (out = g*mask). */

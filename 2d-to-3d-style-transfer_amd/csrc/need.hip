@@ -25,9 +25,10 @@
 // An unneeded block of a listed tile may read input nobody wrote and write garbage; no needed block reads that garbage.
 // On block bitmaps: B_k+1 = the 3x3 block neighbourhood OR of B_k (same resolution) or, through the un-pool, the OR over
 // block rows / columns 2b - 1 .. 2b + 2.  Lists 0 .. 5 = the input gradients of conv1_2, conv2_1, conv2_2, conv3_1, conv3_2,
-// conv3_3; conv1_2 and conv2_2 un-pool.  Three launches: the front one writes the segment map and B_0 (one thread per
-// block, straight from the mask); one workgroup per image then walks the levels with the bitmaps in LDS (two buffers, (S/4)^2
-// + (S/8)^2 bytes) and writes one flag per tile; the compaction is the one above, one workgroup per list.
+// conv3_3; conv1_2 and conv2_2 un-pool.  The maps are bit rows, one 64-bit word per 64 blocks of a row, so the ORs are shifts.  Two
+// launches: the front one writes the segment map and B_0 (one lane per block, straight from the mask, the wave's ballot is
+// the word); then one workgroup per list walks the levels up to its own in LDS, one thread per word, takes each tile's flag
+// from the words and compacts as above.
 #include "common.h"
 
 namespace {
@@ -140,118 +141,210 @@ struct BlockLevels {
     int bw[kLists];                  // blocks per row (and per column) of the map
     int trows[kLists], tcols[kLists];        // a tile in blocks: 1 x 16 or 2 x 8
     int unpools[kLists];
-    int off[kLists + 1];             // first flag of list k (all images); off[nlists] = the total
+    int N;                           // images
+    int total[kLists + 1];           // tiles of list k (all images), then the Gram runs
     int *list[kLists];
     // the Gram backward at relu2_1 (gram.hip): the 64-pixel runs of the (S/2)^2 map that meet need_2 = dilate(B_1, 1), numbered
-    // image * runs + run; their flags follow the tiles' (gram_runs per image, 0 = not asked for), compacted by one more workgroup
-    int gram_runs, gram_total;       // per image, all images
+    // image * runs + run (gram_runs per image, 0 = not asked for), compacted by one more workgroup
+    int gram_runs;
     int *gram_list, *gram_count;
 };
 
-// The front launch: the first seg_wgs workgroups write the segment map (one thread per segment), the others B_0, one thread
-// per block: the block is needed when its 6x6 patch (rows / columns 4 b - 1 .. 4 b + 4) holds a mask pixel.  Rows and columns
-// past the edge are clamped back INTO the patch, so the 18 loads are unconditional and go out together.
+typedef unsigned long long u64;
+
+// A block map is kept as bit rows: row r = words [r * W, (r + 1) * W), W = ceil(bw / 64), bit i of word j = block column
+// 64 j + i; the bits past column bw - 1 are 0.
+__device__ __forceinline__ int row_words(int bw) { return (bw + 63) >> 6; }
+__device__ __forceinline__ u64 row_tail_mask(int bw, int j) {      // the columns of word j that are inside the map
+    const int left = bw - 64 * j;
+    return left >= 64 ? ~0ull : (1ull << left) - 1ull;
+}
+
+// The front launch: the first seg_wgs workgroups write the segment map (one thread per segment), the others B_0, one lane
+// per block and one wave per word: the block is needed when its 6x6 patch (rows / columns 4 b - 1 .. 4 b + 4) holds a mask
+// pixel.  Rows and columns past the edge are clamped back INTO the patch, so the 18 loads are unconditional and go out
+// together; the wave's ballot is the word.
 __global__ __launch_bounds__(256) void need_front_kernel(const uint8_t *__restrict__ mask, int S, int seg_total, int seg_wgs,
-                                                         uint8_t *__restrict__ seg, int b0_total, uint8_t *__restrict__ b0) {
+                                                         uint8_t *__restrict__ seg, int b0_words, u64 *__restrict__ b0) {
     if ((int)blockIdx.x < seg_wgs) {
         const int i = blockIdx.x * 256 + threadIdx.x;
         if (i < seg_total) need_segment(mask, S, i, seg);
         return;
     }
-    const int i = (blockIdx.x - seg_wgs) * 256 + threadIdx.x;
-    if (i >= b0_total) return;
-    const int bw = S >> 2;
-    const int bx = i % bw, by = (i / bw) % bw, n = i / (bw * bw);
-    const uint8_t *m = mask + (size_t)n * S * S + 4 * bx;            // 4-byte aligned: S % 64 == 0, the mask 16-byte aligned
-    const int left = bx > 0 ? -1 : 0, right = bx + 1 < bw ? 4 : 3;
+    const int word = (blockIdx.x - seg_wgs) * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (word >= b0_words) return;                    // (the whole wave)
+    const int bw = S >> 2, W = row_words(bw);
+    const int j = word % W, by = (word / W) % bw, n = word / (W * bw);
+    const int bx = 64 * j + lane;
     unsigned any = 0;
+    if (bx < bw) {
+        const uint8_t *m = mask + (size_t)n * S * S + 4 * bx;            // 4-byte aligned: S % 64 == 0, the mask 16-byte aligned
+        const int left = bx > 0 ? -1 : 0, right = bx + 1 < bw ? 4 : 3;
 #pragma unroll
-    for (int r = -1; r <= 4; ++r) {
-        const uint8_t *row = m + (size_t)min(max(4 * by + r, 0), S - 1) * S;
-        any |= *reinterpret_cast<const unsigned *>(row) | row[left] | row[right];
+        for (int r = -1; r <= 4; ++r) {
+            const uint8_t *row = m + (size_t)min(max(4 * by + r, 0), S - 1) * S;
+            any |= *reinterpret_cast<const unsigned *>(row) | row[left] | row[right];
+        }
     }
-    b0[i] = any ? 1 : 0;
+    const u64 bits = __ballot(any != 0);
+    if (lane == 0) b0[word] = bits;
 }
 
-// workgroup n: the block bitmaps of image n, level by level from B_0, and the flags of the tiles that hold a needed block
-__global__ __launch_bounds__(1024) void need_blocks_kernel(const uint8_t *__restrict__ b0, BlockLevels L, uint8_t *__restrict__ flags) {
-    extern __shared__ __attribute__((aligned(16))) uint8_t need_lds[];
-    const int tid = threadIdx.x, n = blockIdx.x;
-    uint8_t *cur = need_lds, *nxt = need_lds + L.bw[0] * L.bw[0];
-    {
-        const int words = L.bw[0] * L.bw[0] / 16;          // (bw % 16 == 0: S % 64 == 0)
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(b0) + (size_t)n * words;
-        for (int i = tid; i < words; i += 1024) reinterpret_cast<u32x4 *>(cur)[i] = src[i];
+// every second bit of x (bits 0, 2, .. 62) packed into the low half
+__device__ __forceinline__ u64 even_bits(u64 x) {
+    x &= 0x5555555555555555ull;
+    x = (x | (x >> 1)) & 0x3333333333333333ull;
+    x = (x | (x >> 2)) & 0x0f0f0f0f0f0f0f0full;
+    x = (x | (x >> 4)) & 0x00ff00ff00ff00ffull;
+    x = (x | (x >> 8)) & 0x0000ffff0000ffffull;
+    x = (x | (x >> 16)) & 0x00000000ffffffffull;
+    return x;
+}
+
+// OR of word j of the ROWS rows from ra on (those inside 0 .. bw - 1); 0 for a word outside the row.  Row and word are
+// clamped into the map and the value dropped afterwards, so the loads do not wait for each other.
+template <int ROWS>
+__device__ __forceinline__ u64 rows_or(const u64 *__restrict__ m, int bw, int W, int ra, int j) {
+    const int jc = min(max(j, 0), W - 1);
+    u64 v = 0;
+#pragma unroll
+    for (int d = 0; d < ROWS; ++d) {
+        const int r = ra + d;
+        const u64 x = m[min(max(r, 0), bw - 1) * W + jc];
+        v |= (r >= 0 && r < bw) ? x : 0ull;
     }
-    __syncthreads();
-    for (int k = 0; k < L.nlists; ++k) {
-        const int bw = L.bw[k], tr = L.trows[k], tc = L.tcols[k];
-        const int tiles_x = bw / tc, per_img = tiles_x * (bw / tr);
-        for (int t = tid; t < per_img; t += 1024) {
-            const int ty = t / tiles_x, tx = t - ty * tiles_x;
-            unsigned any = 0;
-            for (int i = 0; i < tr; ++i)
-                for (int j = 0; j < tc; ++j) any |= cur[(ty * tr + i) * bw + tx * tc + j];
-            flags[L.off[k] + n * per_img + t] = any ? 1 : 0;
+    return (j >= 0 && j < W) ? v : 0ull;
+}
+
+// does row `row` hold a block in columns xa .. xb (inside the map, xb - xa < 64)
+__device__ __forceinline__ bool cols_any(const u64 *__restrict__ row, int xa, int xb) {
+    const int j = xa >> 6, sh = xa & 63, n = xb - xa + 1;
+    u64 v = row[j] >> sh;
+    if (sh + n > 64) v |= row[j + 1] << (64 - sh);           // (xb is inside the map, so word j + 1 exists)
+    return (v & (n >= 64 ? ~0ull : (1ull << n) - 1ull)) != 0;
+}
+
+// word j2 of row by of B_k+1 from B_k (cur: bw rows of W words): the 3x3 OR is the OR of three rows, then of the word with
+// itself shifted by one either way, the neighbouring words lending the bit that crosses; through the un-pool (up), four
+// rows, shifts -1, +1, +2 and every second bit
+__device__ __forceinline__ u64 next_level_word(const u64 *__restrict__ cur, int bw, int W, int up, int bw2, int by, int j2) {
+    u64 out;
+    if (up) {
+        u64 g[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int j = 2 * j2 + h;
+            const u64 lo = rows_or<4>(cur, bw, W, 2 * by - 1, j - 1), v = rows_or<4>(cur, bw, W, 2 * by - 1, j);
+            const u64 hi = rows_or<4>(cur, bw, W, 2 * by - 1, j + 1);
+            g[h] = v | (v << 1) | (lo >> 63) | (v >> 1) | (hi << 63) | (v >> 2) | (hi << 62);
         }
-        if (k == 1 && L.gram_runs > 0) {     // cur = B_1; a run is a row segment: rows y - 1 .. y + 1, columns 64 sx - 1 .. 64 sx + 64
-            const int per_row = bw / 16;
-            for (int j = tid; j < L.gram_runs; j += 1024) {
-                const int y = j / per_row, sx = j - y * per_row;
-                const int ya = max(0, y - 1) >> 2, yb = min(4 * bw - 1, y + 1) >> 2;
-                const int xa = max(0, 16 * sx - 1), xb = min(bw - 1, 16 * sx + 16);
-                unsigned any = 0;
-                for (int by = ya; by <= yb; ++by)
-                    for (int x = xa; x <= xb; ++x) any |= cur[by * bw + x];
-                flags[L.off[L.nlists] + n * L.gram_runs + j] = any ? 1 : 0;
+        out = even_bits(g[0]) | (even_bits(g[1]) << 32);
+    } else {
+        const u64 lo = rows_or<3>(cur, bw, W, by - 1, j2 - 1), v = rows_or<3>(cur, bw, W, by - 1, j2);
+        const u64 hi = rows_or<3>(cur, bw, W, by - 1, j2 + 1);
+        out = v | (v << 1) | (lo >> 63) | (v >> 1) | (hi << 63);
+    }
+    return out & row_tail_mask(bw2, j2);
+}
+
+// does tile (ty, tx) of image n (of the chunk) hold a block of B_k (maps: bw rows of W words per image; a tile is tr x tc blocks)
+__device__ __forceinline__ bool tile_flag(const u64 *__restrict__ maps, int bw, int W, int tr, int tc, int n, int ty, int tx) {
+    const u64 *rows = maps + (n * bw + ty * tr) * W;
+    bool any = cols_any(rows, tx * tc, tx * tc + tc - 1);
+    if (tr == 2) any = cols_any(rows + W, tx * tc, tx * tc + tc - 1) || any;
+    return any;
+}
+
+// does run (y, sx) of image n meet dilate(B_k, 1): a run is a row segment, rows y - 1 .. y + 1, columns 64 sx - 1 .. 64 sx + 64
+// of the map, in blocks 16 sx - 1 .. 16 sx + 16 of at most two block rows
+__device__ __forceinline__ bool run_flag(const u64 *__restrict__ maps, int bw, int W, int n, int y, int sx) {
+    const int ya = max(0, y - 1) >> 2, yb = min(4 * bw - 1, y + 1) >> 2;
+    const int xa = max(0, 16 * sx - 1), xb = min(bw - 1, 16 * sx + 16);
+    const u64 *rows = maps + n * bw * W;
+    return cols_any(rows + ya * W, xa, xb) || cols_any(rows + yb * W, xa, xb);
+}
+
+constexpr int kMapWords = 4096;      // LDS: B_even of a chunk of images; B_odd has at most half the words (kMapWords / 2)
+constexpr int kMaxMapWords = 896;    // one image's B_0 at the largest side blocks_fit admits (896: 224 rows x 4 words)
+
+// Workgroup k makes list k, the workgroup behind the lists' own the Gram runs (from B_1), each from B_0 on its own: for a chunk of
+// images at a time (as many as kMapWords holds) it walks the levels up to its own in LDS, one thread per word, then thread t
+// owns the items [t * per, (t + 1) * per) of the chunk, takes their flags from the bit rows, counts, an ordered scan over the
+// 1024 counts (shuffles inside a wave, the 16 wave sums through LDS) gives its offset behind what the chunks before listed,
+// and it writes its items in order: no atomics, the same list every time.  (The levels below its own are computed by every
+// workgroup that needs them: a few hundred words each, against a launch and a round trip through memory.)
+__global__ __launch_bounds__(1024) void need_block_lists_kernel(const u64 *__restrict__ b0, BlockLevels L, int *__restrict__ counts) {
+    __shared__ u64 map_even[kMapWords], map_odd[kMapWords / 2];
+    __shared__ int wave_sum[16];
+    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool gram = k == L.nlists;
+    int *__restrict__ list = gram ? L.gram_list : L.list[k];
+    const int level = gram ? 1 : k;
+    const int words0 = L.bw[0] * row_words(L.bw[0]), chunk = kMapWords / words0;
+    // the items of an image: rows x cols tiles, or runs
+    const int bwk = L.bw[level], Wk = row_words(bwk), tr = gram ? 0 : L.trows[k], tc = gram ? 0 : L.tcols[k];
+    const int ncol = gram ? bwk / 16 : bwk / tc, nrow = gram ? 4 * bwk : bwk / tr, per_img = nrow * ncol;
+    int listed = 0;
+    for (int n0 = 0; n0 < L.N; n0 += chunk) {
+        const int nc = min(chunk, L.N - n0);
+        for (int i = tid; i < nc * words0; i += 1024) map_even[i] = b0[(size_t)n0 * words0 + i];
+        __syncthreads();
+        u64 *cur = map_even, *nxt = map_odd;
+        for (int lv = 0; lv < level; ++lv) {
+            const int bw = L.bw[lv], W = row_words(bw), up = L.unpools[lv];
+            const int bw2 = up ? bw / 2 : bw, W2 = row_words(bw2), words2 = bw2 * W2;
+            for (int w = tid; w < nc * words2; w += 1024) {
+                const int n = w / words2, r = w - n * words2, by = r / W2, j2 = r - by * W2;
+                nxt[w] = next_level_word(cur + n * bw * W, bw, W, up, bw2, by, j2);
+            }
+            __syncthreads();
+            u64 *t = cur; cur = nxt; nxt = t;
+        }
+        const int total = nc * per_img, per = (total + 1023) / 1024;
+        const int lo = min(total, tid * per), hi = min(total, lo + per);
+        // (a chunk has at most 4 items per word of B_0, 16 per thread: the flags of a thread's items fit a mask, and the
+        // items are walked by carrying (image, row, column) along instead of dividing each time)
+        int n = lo / per_img, row = (lo - n * per_img) / ncol, col = lo - n * per_img - row * ncol;
+        unsigned mask = 0;
+        for (int i = 0; lo + i < hi; ++i) {
+            const bool f = gram ? run_flag(cur, bwk, Wk, n, row, col) : tile_flag(cur, bwk, Wk, tr, tc, n, row, col);
+            mask |= (f ? 1u : 0u) << i;
+            if (++col == ncol) {
+                col = 0;
+                if (++row == nrow) { row = 0; ++n; }
             }
         }
-        if (k + 1 == L.nlists) break;
-        const int up = L.unpools[k];                     // B_k+1: rows / columns b - 1 .. b + 1, or 2 b - 1 .. 2 b + 2 through the un-pool
-        const int bw2 = up ? bw / 2 : bw;
-        for (int b = tid; b < bw2 * bw2; b += 1024) {
-            const int by = b / bw2, bx = b - by * bw2;
-            const int ya = max(0, (up ? 2 * by : by) - 1), yb = min(bw - 1, up ? 2 * by + 2 : by + 1);
-            const int xa = max(0, (up ? 2 * bx : bx) - 1), xb = min(bw - 1, up ? 2 * bx + 2 : bx + 1);
-            unsigned any = 0;
-            for (int y = ya; y <= yb; ++y)
-                for (int x = xa; x <= xb; ++x) any |= cur[y * bw + x];
-            nxt[b] = any ? 1 : 0;
+        const int cnt = __popc(mask);
+        int incl = cnt;
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const int v = __shfl_up(incl, d);
+            if (lane >= d) incl += v;
         }
+        if (lane == 63) wave_sum[wave] = incl;
         __syncthreads();
-        uint8_t *t = cur; cur = nxt; nxt = t;
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const int v = wave_sum[w];
+            before += w < wave ? v : 0;
+            all += v;
+        }
+        int o = listed + before + incl - cnt;
+        for (int i = 0; lo + i < hi; ++i)
+            if (mask >> i & 1u) list[o++] = n0 * per_img + lo + i;
+        listed += all;
+        __syncthreads();                             // (the maps and wave_sum are the next chunk's)
     }
+    if (tid == 0) (gram ? L.gram_count : counts + k)[0] = listed;
 }
 
-// need_lists_kernel for up to kLists lists: workgroup k compacts flags[off[k] .. off[k + 1]) into list k
-__global__ __launch_bounds__(1024) void need_block_lists_kernel(const uint8_t *__restrict__ flags, BlockLevels L,
-                                                                int *__restrict__ counts) {
-    __shared__ int scan[1024];
-    const int k = blockIdx.x, tid = threadIdx.x;
-    const bool gram = k == L.nlists;                 // the workgroup behind the lists' own: the Gram runs
-    const uint8_t *__restrict__ f = flags + L.off[k];
-    int *__restrict__ list = gram ? L.gram_list : L.list[k];
-    const int total = gram ? L.gram_total : L.off[k + 1] - L.off[k];
-    const int per = (total + 1023) / 1024;
-    const int lo = min(total, tid * per), hi = min(total, lo + per);
-    int cnt = 0;
-    for (int t = lo; t < hi; ++t) cnt += f[t];
-    scan[tid] = cnt;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = tid >= d ? scan[tid - d] : 0;
-        __syncthreads();
-        scan[tid] += v;
-        __syncthreads();
-    }
-    int o = scan[tid] - cnt;
-    for (int t = lo; t < hi; ++t)
-        if (f[t]) list[o++] = t;
-    if (tid == 1023) (gram ? L.gram_count : counts + k)[0] = scan[1023];
+// the sizes the per-block lists cover: one image's B_0 has to fit kMaxMapWords (b0_words(1, S), below; S <= 896)
+bool blocks_fit(int S) {
+    if (S <= 0 || (S % 64) != 0) return false;
+    const size_t bw = (size_t)S / 4;
+    return bw * ((bw + 63) / 64) <= (size_t)kMaxMapWords;
 }
-
-// the two bitmap buffers of need_blocks_kernel have to fit the 64 KB of LDS a launch gets without asking
-bool blocks_fit(int S) { return S > 0 && (S % 64) == 0 && (size_t)5 * (S / 4) * (S / 4) / 4 <= 65536; }
 
 int geo_of(int H, int W, NeedGeo *g) {
     int rows = 0, cols = 0;
@@ -326,14 +419,15 @@ extern "C" size_t st3d_need_blocks_gram_runs(int N, int S) {
     return (size_t)N * R * (R / 64);
 }
 
-// workspace: B_0 (one byte per block of the S x S map; first, so it stays 16-byte aligned), then the flags
-static size_t b0_bytes(int N, int S) { return (size_t)N * (S / 4) * (S / 4); }
+// workspace: the bit rows of B_0, all images
+static size_t b0_words(int N, int S) {
+    const size_t bw = (size_t)S / 4;
+    return (size_t)N * bw * ((bw + 63) / 64);
+}
 
 extern "C" size_t st3d_need_blocks_workspace_bytes(int N, int S) {
     if (N <= 0 || st3d_need_blocks_lists(S) == 0) return 0;
-    size_t b = b0_bytes(N, S) + st3d_need_blocks_gram_runs(N, S);
-    for (int k = 0; k < st3d_need_blocks_lists(S); ++k) b += st3d_need_blocks_tiles(N, S, k);
-    return b;
+    return b0_words(N, S) * sizeof(u64);
 }
 
 extern "C" int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nlists, const int *tile_cols, uint8_t *seg,
@@ -349,6 +443,7 @@ extern "C" int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nli
     BlockLevels L;
     memset(&L, 0, sizeof(L));
     L.nlists = nlists;
+    L.N = N;
     for (int k = 0; k < nlists; ++k) {
         const int R = S >> kListShift[k];
         int rows = 0, cols = 0;
@@ -360,24 +455,22 @@ extern "C" int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nli
         L.trows[k] = cols == 64 ? 1 : 2;
         L.tcols[k] = cols / 4;
         L.unpools[k] = kListUnpools[k];
-        L.off[k + 1] = L.off[k] + (int)st3d_need_blocks_tiles(N, S, k);
+        L.total[k] = (int)st3d_need_blocks_tiles(N, S, k);
         L.list[k] = lists[k];
     }
     if (gram_list) {
         L.gram_runs = (int)(st3d_need_blocks_gram_runs(N, S) / N);
-        L.gram_total = N * L.gram_runs;
         L.gram_list = gram_list;
         L.gram_count = gram_count;
     }
+    L.total[nlists] = N * L.gram_runs;
     hipStream_t s = st3d::as_stream(stream);
-    const int total = N * S * (S / 64), seg_wgs = st3d::cdiv(total, 256), b0_total = (int)b0_bytes(N, S);
-    uint8_t *b0 = reinterpret_cast<uint8_t *>(workspace), *flags = b0 + b0_total;
-    need_front_kernel<<<seg_wgs + st3d::cdiv(b0_total, 256), 256, 0, s>>>(mask, S, total, seg_wgs, seg, b0_total, b0);
+    const int words = (int)b0_words(N, S);
+    const int total = N * S * (S / 64), seg_wgs = st3d::cdiv(total, 256);
+    u64 *bits = reinterpret_cast<u64 *>(workspace);
+    need_front_kernel<<<seg_wgs + st3d::cdiv(words, 4), 256, 0, s>>>(mask, S, total, seg_wgs, seg, words, bits);
     ST3D_LAUNCH_CHECK();
-    const size_t lds = (size_t)5 * (S / 4) * (S / 4) / 4;
-    need_blocks_kernel<<<N, 1024, lds, s>>>(b0, L, flags);
-    ST3D_LAUNCH_CHECK();
-    need_block_lists_kernel<<<nlists + (gram_list ? 1 : 0), 1024, 0, s>>>(flags, L, counts);
+    need_block_lists_kernel<<<nlists + (gram_list ? 1 : 0), 1024, 0, s>>>(bits, L, counts);
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }

@@ -177,10 +177,19 @@ __global__ __launch_bounds__(256) void shade_ss_fwd_kernel(const int32_t *__rest
 
 // Texture-sampling backward.  One workgroup per 16x16-pixel tile of one view.  The <= 12 bilinear contributions of a
 // pixel are not sent to HBM one float atomic each (neighbouring pixels hit the same texels: ~6 M contended L2 atomics
-// per step at config 2): they are first summed per texel in an LDS table (open addressing on the texel index,
-// ds_add_f32) and each distinct texel of the tile then costs three global atomics.  d/d(u,v) and d/d(bary) (vertex
-// path) are per-pixel outputs written directly.
-constexpr int kTexSlots = 2048;          // >= 4 x 256 footprint corners: the probe always terminates
+// per step at config 2): they are first summed per texel in LDS and each distinct texel of the tile then costs three
+// global atomics.  d/d(u,v) and d/d(bary) (vertex path) are per-pixel outputs written directly.
+// A tile in which no pixel has a face writes its zero rows and leaves (one workgroup-wide OR): three quarters of the tiles
+// of a typical view.  The others sum in two pieces, so that only the keys are cleared and only what the tile used is
+// zeroed and flushed:
+//   s_key    open addressing on the texel index, kTexSlots >= 2 x the 4 x 256 footprint corners a tile can deposit: the
+//            probe always terminates.  The lane whose CAS claimed a slot owns the texel.
+//   s_texel, s_acc   one compact entry per distinct texel, kTexMax = 4 x 256 of them: after a barrier every owner takes the
+//            next entry (one LDS atomic per wave and corner), zeroes its three sums, notes the texel and replaces the key by
+//            the entry's number; after the next barrier every lane reads the entry of its slots and deposits.
+// 36 KB + 4 B of LDS in fixed point, 24 KB + 4 B in float: four and six workgroups per CU (the one 56 KB table allowed two).
+constexpr int kTexSlots = 2048;
+constexpr int kTexMax = 1024;
 
 // DET 0: float LDS table + float global atomics (fast default).  DET 1: the same binning in 64-bit fixed point (LDS and
 // global integer atomics; `gtex` is then the int64 accumulator array and `det` holds the power-of-two scale): bitwise
@@ -189,7 +198,7 @@ constexpr int kTexSlots = 2048;          // >= 4 x 256 footprint corners: the pr
 // lighting's own d/dN, d/dP go to grad_np (per pixel) and, through N = sum b_i n_i and P = sum b_i v_i, into gbary.
 // A > 1 (supersampling): S and every per-pixel array are at the SUB-PIXEL side; grad_rgb is (B,3,S/A,S/A) and sub-pixel
 // (yi, xi) takes grad_rgb(yi / A, xi / A) / A^2 -- the backward of the ordered box sum of shade_ss_fwd_kernel.  The tile is
-// still 16 x 16 sub-pixels = 256 footprints, so kTexSlots stays.  A = 1 is the plain kernel, instruction for instruction.
+// still 16 x 16 sub-pixels = 256 footprints, so kTexSlots and kTexMax stay.
 template <int DET, int LIT = 0, int A = 1>
 __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict__ grad_rgb, const int32_t *__restrict__ p2f,
                                                         const float *__restrict__ bary, const float *__restrict__ zbuf,
@@ -201,14 +210,11 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
                                                         const st3d_phong::LitArgs la = {}) {
     typedef typename std::conditional<DET != 0, unsigned long long, float>::type acc_t;
     __shared__ int s_key[kTexSlots];
-    __shared__ acc_t s_acc[kTexSlots][3];
+    __shared__ int s_texel[kTexMax];
+    __shared__ acc_t s_acc[kTexMax][3];
+    __shared__ int s_count;
     const int tid = threadIdx.x;
     const double dscale = DET ? det->scale : 1.0;
-    if (gtex) {
-        for (int e = tid; e < kTexSlots; e += 256) s_key[e] = -1;
-        for (int e = tid; e < kTexSlots * 3; e += 256) (&s_acc[0][0])[e] = (acc_t)0;
-        __syncthreads();
-    }
     const size_t HW = (size_t)S * S;
     const int b = blockIdx.y;
     const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
@@ -220,6 +226,15 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
         if (guv) { guv[2 * i] = 0.f; guv[2 * i + 1] = 0.f; }
         if (gbary) { gbary[3 * i] = 0.f; gbary[3 * i + 1] = 0.f; gbary[3 * i + 2] = 0.f; }
     }
+    if (gtex) {
+        if (!__syncthreads_or(f >= 0)) return;           // the same answer in every lane: the whole workgroup leaves
+        for (int e = tid; e < kTexSlots; e += 256) s_key[e] = -1;
+        if (tid == 0) s_count = 0;
+        __syncthreads();
+    }
+    int dep_texel[4];            // this pixel's footprint corners: texel, weight; dep_valid: bit c = corner c deposits
+    float dep_w[4], dep_g[3] = {0.f, 0.f, 0.f};
+    unsigned dep_valid = 0;
     if (f >= 0) {
         const bool want_uv = guv || gbary;
         const float b0 = bary[3 * i], b1 = bary[3 * i + 1], b2 = bary[3 * i + 2];
@@ -285,39 +300,70 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
                 }
             }
         }
-        if (gtex) {
-            auto deposit = [&](int texel, float w) __attribute__((always_inline)) {
-                int slot = (int)(((unsigned)texel * 2654435761u) >> 21) & (kTexSlots - 1);
-                for (;;) {
-                    const int prev = atomicCAS(&s_key[slot], -1, texel);
-                    if (prev == -1 || prev == texel) break;
-                    slot = (slot + 1) & (kTexSlots - 1);
-                }
-                if (DET) {
-#pragma unroll
-                    for (int c = 0; c < 3; ++c)
-                        atomicAdd(reinterpret_cast<unsigned long long *>(&s_acc[slot][c]),
-                                  (unsigned long long)st3d_det::det_quantise(gk[c] * w, dscale));
-                } else {
-                    atomicAdd(reinterpret_cast<float *>(&s_acc[slot][0]), gk[0] * w);
-                    atomicAdd(reinterpret_cast<float *>(&s_acc[slot][1]), gk[1] * w);
-                    atomicAdd(reinterpret_cast<float *>(&s_acc[slot][2]), gk[2] * w);
-                }
-            };
-            if (q.vy0 && q.vx0) deposit(e00, w00);
-            if (q.vy0 && q.vx1) deposit(e01, w01);
-            if (q.vy1 && q.vx0) deposit(e10, w10);
-            if (q.vy1 && q.vx1) deposit(e11, w11);
-        }
+        dep_texel[0] = e00; dep_texel[1] = e01; dep_texel[2] = e10; dep_texel[3] = e11;
+        dep_w[0] = w00; dep_w[1] = w01; dep_w[2] = w10; dep_w[3] = w11;
+        dep_g[0] = gk[0]; dep_g[1] = gk[1]; dep_g[2] = gk[2];
+        dep_valid = (q.vy0 && q.vx0 ? 1u : 0u) | (q.vy0 && q.vx1 ? 2u : 0u) | (q.vy1 && q.vx0 ? 4u : 0u) | (q.vy1 && q.vx1 ? 8u : 0u);
     }
     if (gtex) {
+        int slot[4];
+        unsigned mine = 0;               // bit c: this lane's CAS claimed the slot of corner c
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            slot[c] = 0;
+            if (dep_valid >> c & 1) {
+                const int texel = dep_texel[c];
+                int s = (int)(((unsigned)texel * 2654435761u) >> 21) & (kTexSlots - 1);
+                for (;;) {
+                    const int prev = atomicCAS(&s_key[s], -1, texel);
+                    if (prev == -1) mine |= 1u << c;
+                    if (prev == -1 || prev == texel) break;
+                    s = (s + 1) & (kTexSlots - 1);
+                }
+                slot[c] = s;
+            }
+        }
+        __syncthreads();                 // every key is in: nobody probes any more
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const bool own = mine >> c & 1;
+            const unsigned long long owners = __ballot(own);
+            if (owners == 0) continue;
+            const int lane = tid & 63, leader = __ffsll((long long)owners) - 1;
+            int base = 0;
+            if (lane == leader) base = atomicAdd(&s_count, __popcll(owners));
+            base = __shfl(base, leader);
+            if (own) {
+                const int e = base + __popcll(owners & ((1ull << lane) - 1ull));
+                s_texel[e] = dep_texel[c];
+                s_acc[e][0] = (acc_t)0; s_acc[e][1] = (acc_t)0; s_acc[e][2] = (acc_t)0;
+                s_key[slot[c]] = e;
+            }
+        }
         __syncthreads();
-        for (int e = tid; e < kTexSlots * 3; e += 256) {
-            const int slot = e / 3, c = e - slot * 3;
-            const int texel = s_key[slot];
-            if (texel < 0) continue;
-            const acc_t v = s_acc[slot][c];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            if (!(dep_valid >> c & 1)) continue;
+            const int e = s_key[slot[c]];
+            const float w = dep_w[c];
+            if (DET) {
+#pragma unroll
+                for (int ch = 0; ch < 3; ++ch)
+                    atomicAdd(reinterpret_cast<unsigned long long *>(&s_acc[e][ch]),
+                              (unsigned long long)st3d_det::det_quantise(dep_g[ch] * w, dscale));
+            } else {
+                atomicAdd(reinterpret_cast<float *>(&s_acc[e][0]), dep_g[0] * w);
+                atomicAdd(reinterpret_cast<float *>(&s_acc[e][1]), dep_g[1] * w);
+                atomicAdd(reinterpret_cast<float *>(&s_acc[e][2]), dep_g[2] * w);
+            }
+        }
+        __syncthreads();
+        const int used = s_count * 3;
+        for (int e = tid; e < used; e += 256) {
+            const int entry = e / 3, c = e - entry * 3;
+            const acc_t v = s_acc[entry][c];
             if (v == (acc_t)0) continue;
+            const int texel = s_texel[entry];
             if (DET) atomicAdd(reinterpret_cast<unsigned long long *>(gtex) + (size_t)texel * 3 + c, (unsigned long long)v);
             else atomicAdd(gtex + (size_t)texel * 3 + c, (float)v);
         }

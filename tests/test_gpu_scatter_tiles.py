@@ -1,0 +1,137 @@
+"""The texture scatter's tiles (csrc/shade.hip: shade_bwd_kernel): empty tiles leave early, the others sum per texel in a
+key table plus compact entries.  The scene (tests/_scatter_scene.py) has an empty view, a view with one covered pixel in a
+tile corner and a fully covered view, at S = 40 (ragged last tile); texture sides 4 (every deposit on a handful of
+texels), 64 and 1024 (all 4 x 256 corners of a tile distinct: the table's worst case).
+
+Fixed point (the default): integer sums are order-free, so the texture gradient is the same twice and equal bit for bit to
+tests/golden/scatter_tiles_parent.npz -- the non-zero texels (and d/d bary entries) recorded on the GPU from the build
+before the table was split.  Float atomics: against the fp64 CPU oracle at 1e-5 of its max, the bound of
+test_gpu_kernels.py::test_shade_fwd_bwd_match_oracle.  Per-pixel outputs of uncovered pixels are exactly zero, with
+torch.empty handing out NaN-filled memory."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import _scatter_scene as sc
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def ops():
+    from st3d import ops as o
+    return o
+
+
+@pytest.fixture(scope="module")
+def scene(dev):
+    frag_np = sc.fragments()
+    return {"frag_np": frag_np, "frag": tuple(torch.from_numpy(a).to(dev) for a in frag_np), "g_np": sc.grad_rgb(),
+            "g": torch.from_numpy(sc.grad_rgb()).to(dev), "uvs": torch.from_numpy(sc.VERTS_UVS).to(dev),
+            "fuv": torch.from_numpy(sc.FACES_UVS).to(dev),
+            "tex": {T: torch.from_numpy(sc.texture(T)).to(dev) for T in sc.TEX_SIDES}}
+
+
+@pytest.fixture(scope="module")
+def parent(golden_dir):
+    d = np.load(os.path.join(golden_dir, "scatter_tiles_parent.npz"))
+    return {k: d[k] for k in d.files}
+
+
+@pytest.fixture(scope="module")
+def oracle_gtex(scene):
+    """fp64 texture gradient of the CPU oracle per texture side, computed once"""
+    from oracle import render_ref as rr
+    out = {}
+    for T in sc.TEX_SIDES:
+        acc = np.zeros((T, T, 3), np.float64)
+        for b in range(sc.B):
+            rr.shade_bwd(scene["g_np"][b], tuple(a[b] for a in scene["frag_np"]), sc.VERTS_UVS, sc.FACES_UVS, sc.texture(T), acc)
+        out[T] = acc
+    return out
+
+
+def _run(ops, scene, T, want_bary):
+    res = ops.shade_bwd(scene["g"], scene["frag"], scene["uvs"], scene["fuv"], scene["tex"][T], want_bary=want_bary)
+    torch.cuda.synchronize()
+    return (res[0], res[1]) if want_bary else (res, None)
+
+
+def _bits(t):
+    return t.detach().cpu().numpy().view(np.uint32)
+
+
+def test_scene_is_what_the_docstring_says():
+    p2f = sc.fragments()[0]
+    assert (p2f[0] < 0).all() and (p2f[1] >= 0).sum() == 1 and p2f[sc.LONE] >= 0 and (p2f[2] >= 0).all()
+    assert sc.LONE[1] % 16 == 0 and sc.LONE[2] % 16 == 15
+
+
+@pytest.mark.parametrize("want_bary", [False, True])
+@pytest.mark.parametrize("T", sc.TEX_SIDES)
+def test_fixed_point_is_reproducible_and_the_parents_bits(dev, ops, scene, parent, T, want_bary):
+    was = ops._DETERMINISTIC
+    ops.set_deterministic(True)
+    try:
+        gt1, gb1 = _run(ops, scene, T, want_bary)
+        gt2, gb2 = _run(ops, scene, T, want_bary)
+    finally:
+        ops.set_deterministic(was)
+    np.testing.assert_array_equal(_bits(gt1), _bits(gt2))
+    want = sc.from_sparse(parent[f"gtex_idx_{T}"], parent[f"gtex_bits_{T}"], (T, T, 3))
+    assert np.count_nonzero(want) > 0
+    np.testing.assert_array_equal(_bits(gt1), want.view(np.uint32))
+    if want_bary:
+        np.testing.assert_array_equal(_bits(gb1), _bits(gb2))
+        wb = sc.from_sparse(parent[f"gbary_idx_{T}"], parent[f"gbary_bits_{T}"], (sc.B, sc.S, sc.S, 3))
+        np.testing.assert_array_equal(_bits(gb1), wb.view(np.uint32))
+
+
+@pytest.mark.parametrize("want_bary", [False, True])
+@pytest.mark.parametrize("T", sc.TEX_SIDES)
+def test_float_atomics_match_the_oracle(dev, ops, scene, oracle_gtex, T, want_bary):
+    was = ops._DETERMINISTIC
+    ops.set_deterministic(False)
+    try:
+        gt, _ = _run(ops, scene, T, want_bary)
+    finally:
+        ops.set_deterministic(was)
+    ref = oracle_gtex[T]
+    scale = np.abs(ref).max()
+    err = np.abs(gt.cpu().numpy().astype(np.float64) - ref).max()
+    print(f"T={T} want_bary={want_bary}: max err {err:.3e}, scale {scale:.3e}")
+    assert scale > 0 and err <= 1e-5 * scale
+
+
+@pytest.mark.parametrize("det", [True, False])
+def test_uncovered_pixels_get_exact_zeros_over_poison(dev, ops, scene, det):
+    """torch.empty filled with NaN (what ST3D_POISON_EMPTY=1 turns on for a whole session): the rows of uncovered pixels --
+    whole empty tiles included -- are written, +0.0 each, and nothing non-finite is left anywhere"""
+    was_det, was_alg = ops._DETERMINISTIC, torch.are_deterministic_algorithms_enabled()
+    was_warn = torch.is_deterministic_algorithms_warn_only_enabled()
+    was_fill = torch.utils.deterministic.fill_uninitialized_memory
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    torch.utils.deterministic.fill_uninitialized_memory = True
+    ops.set_deterministic(det)
+    try:
+        assert torch.isnan(torch.empty(64, device=dev)).all()
+        gt, guv, gbary = ops.shade_bwd(scene["g"], scene["frag"], scene["uvs"], scene["fuv"], scene["tex"][64], want_uv=True,
+                                       want_bary=True)
+        torch.cuda.synchronize()
+    finally:
+        ops.set_deterministic(was_det)
+        torch.utils.deterministic.fill_uninitialized_memory = was_fill
+        torch.use_deterministic_algorithms(was_alg, warn_only=was_warn)
+    empty = scene["frag_np"][0] < 0
+    assert not _bits(guv)[empty].any() and not _bits(gbary)[empty].any()
+    assert _bits(guv)[~empty].any() and _bits(gbary)[~empty].any()
+    for t in (gt, guv, gbary):
+        assert torch.isfinite(t).all()

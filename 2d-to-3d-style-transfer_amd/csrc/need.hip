@@ -29,6 +29,11 @@
 // launches: the front one writes the segment map and B_0 (one lane per block, straight from the mask, the wave's ballot is
 // the word); then one workgroup per list walks the levels up to its own in LDS, one thread per word, takes each tile's flag
 // from the words and compacts as above.
+//
+// PER STRIP (tile_cols[k] = 16).  The F(4x4,3x3) kernel's four-row geometry gives every tile row of a workgroup step an origin of
+// its own (wino43.hip, STRIPS), so list k names strips of 1 x 4 blocks (4 x 16 pixels), (n * strips_y + sy) * strips_x + sx, four
+// entries to a step: the strips that hold a block of B_k, ascending within an image, each image padded with -1 to whole steps
+// (a step's strips share their image's buffer descriptors), the count in steps.  Need propagation is the same.
 #include "common.h"
 
 namespace {
@@ -139,7 +144,7 @@ constexpr int kListUnpools[kLists] = {1, 0, 1, 0, 0, 0};     // launch k reads i
 struct BlockLevels {
     int nlists;
     int bw[kLists];                  // blocks per row (and per column) of the map
-    int trows[kLists], tcols[kLists];        // a tile in blocks: 1 x 16 or 2 x 8
+    int trows[kLists], tcols[kLists];        // a tile in blocks: 1 x 16 or 2 x 8; 1 x 4 = strips, four entries to a step
     int unpools[kLists];
     int N;                           // images
     int total[kLists + 1];           // tiles of list k (all images), then the Gram runs
@@ -276,6 +281,7 @@ constexpr int kMaxMapWords = 896;    // one image's B_0 at the largest side bloc
 __global__ __launch_bounds__(1024) void need_block_lists_kernel(const u64 *__restrict__ b0, BlockLevels L, int *__restrict__ counts) {
     __shared__ u64 map_even[kMapWords], map_odd[kMapWords / 2];
     __shared__ int wave_sum[16];
+    __shared__ int img_first[kMapWords / 16 + 2];        // strips: per image of the chunk, the strips listed before its first
     const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool gram = k == L.nlists;
     int *__restrict__ list = gram ? L.gram_list : L.list[k];
@@ -302,6 +308,63 @@ __global__ __launch_bounds__(1024) void need_block_lists_kernel(const u64 *__res
         }
         const int total = nc * per_img, per = (total + 1023) / 1024;
         const int lo = min(total, tid * per), hi = min(total, lo + per);
+        if (!gram && tc == 4) {
+            // Strips: at most 16 items per word of B_0, 64 per thread.  The same ordered scan gives every listed strip its rank in
+            // the chunk; the thread that owns an image's first item leaves the rank there in img_first, so an image's count is a
+            // difference, its padded offset a sum over the images before it, and a strip goes to offset + rank within its image.
+            int n = lo / per_img, row = (lo - n * per_img) / ncol, col = lo - n * per_img - row * ncol;
+            u64 mask = 0;
+            for (int i = 0; lo + i < hi; ++i) {
+                mask |= (u64)(tile_flag(cur, bwk, Wk, 1, 4, n, row, col) ? 1 : 0) << i;
+                if (++col == ncol) {
+                    col = 0;
+                    if (++row == nrow) { row = 0; ++n; }
+                }
+            }
+            const int cnt = __popcll(mask);
+            int incl = cnt;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int v = __shfl_up(incl, d);
+                if (lane >= d) incl += v;
+            }
+            if (lane == 63) wave_sum[wave] = incl;
+            __syncthreads();
+            int before = 0, all = 0;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) {
+                const int v = wave_sum[w];
+                before += w < wave ? v : 0;
+                all += v;
+            }
+            const int rank0 = before + incl - cnt;       // listed strips of the chunk before this thread's items
+            for (int m = (lo + per_img - 1) / per_img; m < nc && m * per_img < hi; ++m) {       // the images that start in [lo, hi)
+                const int i = m * per_img - lo;
+                img_first[m] = rank0 + __popcll(mask & ((1ull << i) - 1ull));       // (i < 64: the item is this thread's)
+            }
+            if (tid == 0) img_first[nc] = all;
+            __syncthreads();
+            // the padded offset of image m: whole steps of the images before it (nc <= 256: a short loop of independent reads)
+            auto padded_before = [&](int m) {
+                int o = 0;
+                for (int j = 0; j < m; ++j) o += (img_first[j + 1] - img_first[j] + 3) & ~3;
+                return o;
+            };
+            if (lo < hi) {
+                int m = lo / per_img, base = listed + padded_before(m) - img_first[m], r = rank0, next = (m + 1) * per_img;
+                for (int i = 0; lo + i < hi; ++i) {
+                    if (lo + i == next) { ++m; base = listed + padded_before(m) - img_first[m]; next += per_img; }
+                    if (mask >> i & 1ull) list[base + r++] = n0 * per_img + lo + i;
+                }
+            }
+            if (tid < nc) {          // the voids behind image tid's last strip
+                const int c = img_first[tid + 1] - img_first[tid], o = listed + padded_before(tid);
+                for (int i = c; i < ((c + 3) & ~3); ++i) list[o + i] = -1;
+            }
+            listed += padded_before(nc);
+            __syncthreads();                         // (the maps, wave_sum and img_first are the next chunk's)
+            continue;
+        }
         // (a chunk has at most 4 items per word of B_0, 16 per thread: the flags of a thread's items fit a mask, and the
         // items are walked by carrying (image, row, column) along instead of dividing each time)
         int n = lo / per_img, row = (lo - n * per_img) / ncol, col = lo - n * per_img - row * ncol;
@@ -336,7 +399,7 @@ __global__ __launch_bounds__(1024) void need_block_lists_kernel(const u64 *__res
         listed += all;
         __syncthreads();                             // (the maps and wave_sum are the next chunk's)
     }
-    if (tid == 0) (gram ? L.gram_count : counts + k)[0] = listed;
+    if (tid == 0) (gram ? L.gram_count : counts + k)[0] = (!gram && tc == 4) ? listed / 4 : listed;
 }
 
 // the sizes the per-block lists cover: one image's B_0 has to fit kMaxMapWords (b0_words(1, S), below; S <= 896)
@@ -413,6 +476,12 @@ extern "C" size_t st3d_need_blocks_tiles(int N, int S, int k) {
     return (size_t)N * bw * bw / 16;         // 16 blocks per tile in either geometry
 }
 
+// the entries list k holds: its tiles, or four strips to each (tile_cols = 16: every image's strips fill whole steps, so the
+// padded worst case is the full list)
+extern "C" size_t st3d_need_blocks_entries(int N, int S, int k, int tile_cols) {
+    return st3d_need_blocks_tiles(N, S, k) * (tile_cols == 16 ? 4 : 1);
+}
+
 extern "C" size_t st3d_need_blocks_gram_runs(int N, int S) {
     const int R = S / 2;
     if (N <= 0 || st3d_need_blocks_lists(S) < 2 || (R % 64) != 0) return 0;
@@ -450,9 +519,10 @@ extern "C" int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nli
         st3d_wino43_tile_geometry(R, R, &rows, &cols);
         if (tile_cols && tile_cols[k]) cols = tile_cols[k];
         ST3D_CHECK_ARG(lists[k]);
-        ST3D_CHECK_ARG((cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0));      // (R % 8 == 0 with it: S % 64 == 0)
+        ST3D_CHECK_ARG((cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0) || cols == 16);      // (R % 8 == 0, R % 16 == 0 with it: S % 64 == 0)
+        ST3D_CHECK_ARG(cols != 16 || ((uintptr_t)lists[k] & 15) == 0);
         L.bw[k] = R / 4;
-        L.trows[k] = cols == 64 ? 1 : 2;
+        L.trows[k] = cols == 32 ? 2 : 1;
         L.tcols[k] = cols / 4;
         L.unpools[k] = kListUnpools[k];
         L.total[k] = (int)st3d_need_blocks_tiles(N, S, k);

@@ -217,7 +217,7 @@ struct st3d_plan {
     // 3 + the conv2_1 input gradient -- as many as the size has, the routes allow and ST3D_NEED_DEPTH leaves.
     // need_blocks: the lists are the per-block ones (st3d_need_blocks_build; ST3D_NEED_BLOCKS=0: the tile-granular ones of
     // st3d_need_build).  They stay thin further up, so the levels go on: 4 + conv2_2, 5 + conv3_1, 6 + conv3_2, 7 + conv3_3,
-    // each in the geometry need_cols says (64 / 32 pixels across; 0 = the kernel's own choice for the map).
+    // each in the geometry need_cols says (64 / 32 pixels across, 16 = strips; 0 = the kernel's own choice for the map).
     int need_levels = 0;
     bool need_blocks = false;
     uint8_t *need_seg = nullptr, *need_flags = nullptr;
@@ -497,7 +497,8 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
         // conv2_1, or a geometry other than the kernel's own, engages only where the full launch walks at least two tiles per
         // persistent workgroup, N tiles_x tiles_y >= 2 (CUs / n_ct): below that every workgroup has one tile at the most and a
         // list saves nothing (ST3D_NEED_FORCE=1 lifts the rule: tests reach every level at small sizes).
-        // ST3D_NEED_TILE=64|32 (or one value per list, comma-separated): that geometry on every listed level it fits.
+        // ST3D_NEED_TILE=64|32|16 (or one value per list, comma-separated): that geometry on every listed level it fits
+        // (16 = strips of 4 x 16 pixels, four to a step: it fits every map the kernel covers).
         need_max = 1 + st3d_need_blocks_lists(S);
         const bool force = flag("ST3D_NEED_FORCE", false);
         int cus = 0, dev = 0;
@@ -509,8 +510,9 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
         // conv2_2 and conv3_1 .. conv3_3: F(4x4,3x3) launches whose gradient arrives gated (from the launch above, or the taps)
         for (int cs = 3; cs <= ST3D_NEED_MAX_LISTS && need_ok == cs; ++cs)
             if (p->route[cs].dgrad_w43 && (cs == 4 ? p->route[cs].gate_taps : p->route[cs + 1].gate_dst) && two_rounds(cs)) need_ok = cs + 1;
-        // measured defaults: 8 x 32 tiles from conv2_2 up
-        static const int kDefaultCols[ST3D_NEED_MAX_LISTS] = {0, 0, 32, 32, 32, 32};
+        // measured defaults: strips of 4 x 16 pixels on every level but conv3_1, which no geometry finer than 8 x 32
+        // tiles brings under its three rounds
+        static const int kDefaultCols[ST3D_NEED_MAX_LISTS] = {16, 16, 16, 32, 16, 16};
         const char *tile = getenv("ST3D_NEED_TILE");
         for (int k = 0; k < ST3D_NEED_MAX_LISTS; ++k) {
             const int R = p->H[kConvIdx[k + 1]];
@@ -521,7 +523,7 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
             }
             int rows0 = 0, cols0 = 0;
             st3d_wino43_tile_geometry(R, R, &rows0, &cols0);
-            const bool fits = (cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0 && R % 8 == 0);
+            const bool fits = (cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0 && R % 8 == 0) || (cols == 16 && rows0 != 0);
             p->need_cols[k] = (fits && cols != cols0 && two_rounds(k + 1)) ? cols : 0;
         }
     }
@@ -572,7 +574,7 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
         }
         for (int l = 0; l + 2 <= p->need_levels; ++l) {
             if (p->need_blocks) {
-                alloc(&p->need_list[l], st3d_need_blocks_tiles(B, S, l));
+                alloc(&p->need_list[l], st3d_need_blocks_entries(B, S, l, p->need_cols[l]));
                 continue;
             }
             int rows = 0, cols = 0;

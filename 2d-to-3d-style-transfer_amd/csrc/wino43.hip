@@ -10,7 +10,7 @@
 //   Y = A^T [ sum_ci (G g G^T) (.) (B^T d B) ] A       per (cout, 4x4 tile), 6x6 Winograd domain xi = (a, b)
 //
 // Mapping.  One 768-thread workgroup (12 waves, three per SIMD, one workgroup per CU) = 64 cout x 16 tiles (4 rows x 64
-// columns of pixels, or 8 x 32: Geo43).  Wave w = (a = w >> 1, bh = w & 1) accumulates row a of the domain for b in {3 bh .. 3 bh + 2} and
+// columns of pixels, or 8 x 32, or four listed strips of 4 x 16 anywhere in one image: Geo43).  Wave w = (a = w >> 1, bh = w & 1) accumulates row a of the domain for b in {3 bh .. 3 bh + 2} and
 // all 64 couts on v_mfma_f32_16x16x4_f32 (M = 16 cout, N = 16 tiles, K = 4 input channels): 3 b x 4 cout blocks = 12
 // accumulator tiles = 48 VGPRs, and every B operand feeds FOUR MFMAs.
 //   * B operands V = B^T d B.  The ROW half of the transform (T_a = sum_r B^T[a][r] d[r], 13 VALU per column for all six
@@ -47,6 +47,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int KS6 = 16;                  // input channels per stage (four k-steps of 4): one barrier and one staging turn per 48 MFMAs
 constexpr int NK6 = KS6 / 4;
@@ -56,16 +57,21 @@ constexpr int EX6 = 6 * 32 * 16 * 2 * 2;         // exchange floats per pass: [a
 //   512^2, conv4_x at the reference's default 768^2).  The ring holds, per channel and tile row, the six row-transformed rows
 //   of the patch columns x0 - 4 .. x0 + 4 TC + 3, stored from index 1 of a PITCH-float row: a tile's six columns 4 t + 3 .. + 8
 //   then start 16-byte aligned (one 16-byte + one 8-byte LDS read).
+//   TC = 4: four tile rows of 4 x 16 pixels, each with an origin of its own (STRIPS, below).  Staged as above the ring would
+//   take 166 KB; the patch needs the columns x0 - 1 .. x0 + 4 TC only, so the staging starts at x0 - 2 (XLEFT) and stores from
+//   index 3 (LOFF0): column x0 + c still sits at index c + 5 of its row, the reads are the same, and a row is 24 floats.
 template <int TC>
 struct Geo43 {
     static constexpr int TR = 16 / TC;
     static constexpr int ROWS = 4 * TR, COLS = 4 * TC;       // output pixels per workgroup step
-    static constexpr int PAIRS = 2 * TC + 4;                 // column pairs per patch row
-    static constexpr int PITCH = 4 * TC + 12;                // 76 / 44
-    static constexpr int CHS = TR * 6 * PITCH;               // floats per channel: 456 / 528
-    static constexpr int TSTAGE = KS6 * CHS;                 // floats per ring stage: 29 / 34 KB
-    static constexpr int HALF_ITEMS = KS6 * TR * PAIRS;      // staging half-items (channel, tile row, column pair) per stage: 576 / 640 of 768 threads
-    static constexpr int SMEM = 3 * TSTAGE + EX6;            // 134 / 147 KB of dynamic LDS: the ring AND the exchange region -- a persistent
+    static constexpr int XLEFT = TC == 4 ? 2 : 4;            // the staged columns start at x0 - XLEFT ..
+    static constexpr int LOFF0 = 5 - XLEFT;                  // .. and are stored from this (odd) index of the row
+    static constexpr int PAIRS = TC == 4 ? 2 * TC + 2 : 2 * TC + 4;      // column pairs per patch row
+    static constexpr int PITCH = TC == 4 ? 4 * TC + 8 : 4 * TC + 12;     // 76 / 44 / 24
+    static constexpr int CHS = TR * 6 * PITCH;               // floats per channel: 456 / 528 / 576
+    static constexpr int TSTAGE = KS6 * CHS;                 // floats per ring stage: 29 / 34 / 37 KB
+    static constexpr int HALF_ITEMS = KS6 * TR * PAIRS;      // staging half-items (channel, tile row, column pair) per stage: 576 / 640 / 640 of 768 threads
+    static constexpr int SMEM = 3 * TSTAGE + EX6;            // 134 / 147 / 156 KB of dynamic LDS: the ring AND the exchange region -- a persistent
                                                              // workgroup keeps staging its next tile while the finished one is written out
     static_assert(HALF_ITEMS <= 768 && SMEM * 4 <= 160 * 1024, "tile geometry does not fit the workgroup");
 };
@@ -87,6 +93,8 @@ struct Wino43Args {
     unsigned magic_x, magic_y;      // floor(2^32 / tiles_x) + 1, likewise tiles_y: pix / tiles_x = umulhi(pix, magic_x) for pix * tiles_x < 2^32 (tiles_x >= 2)
     const int *tile_list;           // LIST: the pixel tiles to compute, ascending (need.hip); the others are not written
     const int *n_active;            // LIST: how many (device memory: the host never knows)
+                                    // STRIPS: TR entries per list position, each a 4 x 4 TC strip (n * strips_y + sy) * strips_x + sx
+                                    // (tiles_x / tiles_y = strips_x / strips_y) of ONE image or -1; n_active counts positions
 };
 
 // T_a = sum_r B^T[a][r] d[r] for a = 0..5 (and, applied to t0..t5, the column half V_b = sum_c B^T[b][c] t[c])
@@ -117,9 +125,15 @@ __device__ __forceinline__ void bt6(T d0, T d1, T d2, T d3, T d4, T d5, T &t0, T
 // LIST: the workgroup walks positions slot, slot + nslots, ... of a.tile_list instead of the pixel tiles themselves; the
 // walk, the ring and the epilogue are the same, a tile sees the inputs and the order of operations it sees unlisted.
 // (the input-gradient chain over a need list, and the forward -- EPI 0 or 1, bias and ReLU -- over a flat-field list)
-template <int MODE, int EPI, int GATE, int BH, int TC, bool LIST>
+// STRIPS: the TR tile rows of a step are independent all the way -- a staging thread loads its own tile row's six patch
+// rows, the ring is per tile row, the MFMA N index is the block, a reader owns one block -- so each gets an origin of its
+// own: a list position is TR strips of 4 x 4 TC pixels anywhere in one image (-1: none; staged out of range, not stored).
+// Every block still sees the inputs and the order of operations of the unlisted launch.
+template <int MODE, int EPI, int GATE, int BH, int TC, bool LIST, bool STRIPS>
 __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     using G = Geo43<TC>;
+    static_assert(!STRIPS || (LIST && EPI == 0 && G::TR == 4), "strips come from a list and leave through the plain epilogue");
+    constexpr int SROWS = STRIPS ? 4 : G::ROWS;         // rows of pixels per decoded unit
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);     // (scalar: every role test below is a scalar branch)
     const int wa = wave >> 1;                           // row a of the domain
@@ -147,7 +161,25 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
         const int r2 = a.tiles_x == 1 ? pix : (int)__umulhi((unsigned)pix, a.magic_x);
         const int txi = pix - r2 * a.tiles_x;
         tn = a.tiles_y == 1 ? r2 : (int)__umulhi((unsigned)r2, a.magic_y);
-        tx0 = txi * G::COLS; ty0 = (r2 - tn * a.tiles_y) * G::ROWS;
+        tx0 = txi * G::COLS; ty0 = (r2 - tn * a.tiles_y) * SROWS;
+    };
+    // STRIPS: the step's entries -> its image and per strip the origin packed y0 << 16 | x0, -1 = none (all scalar)
+    // (vectors of four, not arrays: a per-thread choice among array elements becomes an indexed load from scratch)
+    auto decode_step = [&](const i32x4 &ent, int &tn, i32x4 &org) __attribute__((always_inline)) {
+        tn = 0;
+#pragma unroll
+        for (int i = 3; i >= 0; --i) {
+            int en, ey, ex;
+            decode(ent[i] < 0 ? 0 : ent[i], en, ey, ex);
+            org[i] = ent[i] < 0 ? -1 : (ey << 16 | ex);
+            tn = ent[i] < 0 ? tn : en;
+        }
+    };
+    auto pick = [&](const i32x4 &org, int i) __attribute__((always_inline)) {      // org[i] for a per-thread i
+        int v = org[0];
+#pragma unroll
+        for (int j = 1; j < 4; ++j) v = i == j ? org[j] : v;
+        return v;
     };
     const int H = a.H, W = a.W;
     const size_t HW = (size_t)H * W;
@@ -177,15 +209,39 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     int stile = 0, ctile = 0;
     unsigned nxt = 0;
     auto list_at = [&](int pos) __attribute__((always_inline)) { return pos < npix ? (unsigned)a.tile_list[pos] : 0u; };
+    // STRIPS: the same three, TR entries each; corg = the computed step's origins (decode_step), for the epilogue
+    i32x4 sent = {-1, -1, -1, -1}, cent = sent, corg = sent, nxts = sent;
+    auto step_at = [&](int pos) __attribute__((always_inline)) {
+        return pos < npix ? *reinterpret_cast<const i32x4 *>(a.tile_list + (size_t)pos * 4) : i32x4{-1, -1, -1, -1};
+    };
+    auto uniform4 = [&](const i32x4 &v) __attribute__((always_inline)) {
+        return i32x4{__builtin_amdgcn_readfirstlane(v[0]), __builtin_amdgcn_readfirstlane(v[1]),
+                     __builtin_amdgcn_readfirstlane(v[2]), __builtin_amdgcn_readfirstlane(v[3])};
+    };
     auto stage_tile = [&](int pix) __attribute__((always_inline)) {
         const bool live = pix < npix;
+        if (STRIPS) {
+            i32x4 org;
+            decode_step(sent, n, org);
+            const int mine = pick(org, s_tr);
+            const bool on = live && s_on && mine >= 0;
+            const int sy0 = mine >> 16, sx0 = mine & 0xffff;
+#pragma unroll
+            for (int r = 0; r < 6; ++r) {
+                const int gy = sy0 - 1 + r, gx0 = sx0 - G::XLEFT + s_col;
+                const bool ok = on && gy >= 0 && gy < H && gx0 >= 0 && gx0 < W;
+                if (UNPOOL) voff[r] = ok ? (unsigned)((s_ci * in_plane + (size_t)(gy >> 1) * Wp + (gx0 >> 1)) * 4) : kOob;
+                else voff[r] = ok ? (unsigned)((s_ci * in_plane + (size_t)gy * W + gx0) * 4) : kOob;
+            }
+        } else {
         decode(live ? (LIST ? stile : pix) : 0, n, y0, x0);
 #pragma unroll
         for (int r = 0; r < 6; ++r) {
-            const int gy = y0 - 1 + 4 * s_tr + r, gx0 = x0 - 4 + s_col;
+            const int gy = y0 - 1 + 4 * s_tr + r, gx0 = x0 - G::XLEFT + s_col;
             const bool ok = live && s_on && gy >= 0 && gy < H && gx0 >= 0 && gx0 < W;
             if (UNPOOL) voff[r] = ok ? (unsigned)((s_ci * in_plane + (size_t)(gy >> 1) * Wp + (gx0 >> 1)) * 4) : kOob;   // one pooled element covers the row's two columns
             else voff[r] = ok ? (unsigned)((s_ci * in_plane + (size_t)gy * W + gx0) * 4) : kOob;
+        }
         }
         rx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.x + (size_t)n * a.Cin * in_plane), 0, img_bytes, 0x00020000);
         ridx = rx;
@@ -193,7 +249,10 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
             ridx = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t *>(a.idx + (size_t)n * a.Cin * in_plane), 0, img_bytes / 4, 0x00020000);
     };
     int spix = slot;                           // pixel tile being staged
-    if (LIST) {
+    if (STRIPS) {
+        sent = cent = uniform4(step_at(spix));
+        nxts = step_at(spix + nslots);
+    } else if (LIST) {
         stile = ctile = __builtin_amdgcn_readfirstlane((int)list_at(spix));
         nxt = list_at(spix + nslots);
     }
@@ -201,7 +260,7 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
 #if defined(ST3D_W43_DIAG) && ST3D_W43_DIAG == 10       // 10: staging loads out of range (issued, no memory traffic)
     if (a.N >= 0) spix = npix;
 #endif
-    const int loff = s_on ? (s_ci * G::CHS + s_tr * 6 * G::PITCH + s_col + 1) : 0;      // + a * PITCH per transformed row (odd index: two 4-byte stores in one ds_write2)
+    const int loff = s_on ? (s_ci * G::CHS + s_tr * 6 * G::PITCH + s_col + G::LOFF0) : 0;      // + a * PITCH per transformed row (odd index: two 4-byte stores in one ds_write2)
     const unsigned stage_bytes = (unsigned)(KS6 * in_plane * 4);
     const int nksteps = a.Cin / 4;
     const __amdgpu_buffer_rsrc_t ru = __builtin_amdgcn_make_buffer_rsrc(
@@ -374,7 +433,13 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     const unsigned out_bytes = (unsigned)((size_t)a.Cout * HW * 4);
     const size_t HpWp = (size_t)Hp * Wp;
     const int col_l = tid >> 4, tl = tid & 15;     // reader: cout within the half, tile
-    const int oy = y0 + 4 * (tl / TC), ox = x0 + 4 * (tl % TC);
+    int oy = y0 + 4 * (tl / TC), ox = x0 + 4 * (tl % TC);
+    bool strip_on = true;
+    if (STRIPS) {                                  // the reader's block belongs to strip tl / TC of the computed step
+        const int mine = pick(corg, tl / TC);
+        strip_on = mine >= 0;
+        oy = mine >> 16; ox = (mine & 0xffff) + 4 * (tl % TC);
+    }
     __amdgpu_buffer_rsrc_t rg = ru, ry = ru, ryp = ru, ryi = ru, rt = ru;
     if (GATE >= 1) rg = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.gate + (size_t)n * a.Cout * HW), 0, out_bytes, 0x00020000);
     if (a.y) ry = __builtin_amdgcn_make_buffer_rsrc(a.y + (size_t)n * a.Cout * HW, 0, out_bytes, 0x00020000);
@@ -391,7 +456,7 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     f32x4 gq[GATE >= 1 ? 4 : 1];
     auto request = [&](int h) __attribute__((always_inline)) {
         const int col = 32 * h + col_l;
-        const bool inb = reader && oy < H && ox < W;   // H, W multiples of the step: every reader (kept for the descriptor sentinel)
+        const bool inb = reader && strip_on && oy < H && ox < W;   // H, W multiples of the step: every reader (kept for the descriptor sentinel)
         vo = inb ? (unsigned)((((size_t)co0 + col) * HW + (size_t)oy * W + ox) * 4) : kOob;
 #if defined(ST3D_W43_DIAG) && ST3D_W43_DIAG == 4       // diagnostic build: gate reads and output stores out of range (issued, no memory traffic)
         if (a.N >= 0) vo = kOob;
@@ -530,15 +595,17 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
             int sc = c + 2;
             if (sc == nstages) {                                          // the staging runs on into the next tile's patch
                 spix += nslots;
-                if (LIST) stile = __builtin_amdgcn_readfirstlane((int)nxt);
+                if (STRIPS) sent = uniform4(nxts);
+                else if (LIST) stile = __builtin_amdgcn_readfirstlane((int)nxt);
                 stage_tile(spix);
             }
             if (sc >= nstages) sc -= nstages;
             stage(c, sc, pb);
             pb = pb == 2 ? 0 : pb + 1;
         }
-        int cn, cy0, cx0;
-        decode(LIST ? ctile : cpix, cn, cy0, cx0);
+        int cn, cy0 = 0, cx0 = 0;
+        if (STRIPS) decode_step(cent, cn, corg);
+        else decode(LIST ? ctile : cpix, cn, cy0, cx0);
 #if defined(ST3D_W43_DIAG) && ST3D_W43_DIAG == 2       // diagnostic build: no epilogue at all -- no results, timing only
         if (a.N < 0) { float sacc = 0.f; for (int b = 0; b < 3; ++b) for (int cb = 0; cb < 4; ++cb) for (int r = 0; r < 4; ++r) sacc += acc[b][cb][r]; ex[tid] = sacc; }
         uload(0, u4[0]); uload(1, u4[1]); uload(2, u4[2]);
@@ -547,7 +614,10 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
 #endif
         // (the staged tile's addresses are recomputed rather than carried through the epilogue's register peak)
         asm volatile("" : "+s"(spix));
-        if (LIST) {
+        if (STRIPS) {
+            cent = sent;
+            nxts = step_at(spix + nslots);
+        } else if (LIST) {
             ctile = stile;
             nxt = list_at(spix + nslots);
         }
@@ -559,11 +629,11 @@ __device__ __forceinline__ void wino43_body(const Wino43Args &a, float *smem) {
     }
 }
 
-template <int MODE, int EPI, int GATE, int TC, bool LIST = false>
+template <int MODE, int EPI, int GATE, int TC, bool LIST = false, bool STRIPS = false>
 __global__ __launch_bounds__(NT6, 3) void wino43_kernel(const Wino43Args a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) wino43_body<MODE, EPI, GATE, 1, TC, LIST>(a, smem);
-    else wino43_body<MODE, EPI, GATE, 0, TC, LIST>(a, smem);
+    if (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 1) wino43_body<MODE, EPI, GATE, 1, TC, LIST, STRIPS>(a, smem);
+    else wino43_body<MODE, EPI, GATE, 0, TC, LIST, STRIPS>(a, smem);
 }
 
 // w (Cout,Cin,3,3) -> U = G g G^T (6x6, fp64 -> fp32), forward and transposed (180-degree rotated filter, channel roles
@@ -620,8 +690,9 @@ bool shape_ok43(int Cin, int Cout, int H, int W) {
 template <int MODE, int TC>
 int launch_wino43_tc(Wino43Args a, hipStream_t s) {
     using G = Geo43<TC>;
+    constexpr bool kStrips = TC == 4;       // (the only use of four tile rows: a step is four listed strips of 4 x 16 pixels)
     a.tiles_x = a.W / G::COLS;
-    a.tiles_y = a.H / G::ROWS;
+    a.tiles_y = kStrips ? a.H / 4 : a.H / G::ROWS;
     a.n_ct = a.Cout / 64;
     a.magic_x = (unsigned)((1ull << 32) / (unsigned)a.tiles_x + 1ull);      // (tiles_x == 1: unused)
     a.magic_y = (unsigned)((1ull << 32) / (unsigned)a.tiles_y + 1ull);
@@ -631,7 +702,7 @@ int launch_wino43_tc(Wino43Args a, hipStream_t s) {
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
         return n;
     }();
-    const long npix = (long)a.tiles_x * a.tiles_y * a.N;
+    const long npix = (long)a.tiles_x * a.tiles_y * a.N / (kStrips ? G::TR : 1);       // steps at the most
     long nslots = cus / a.n_ct;
     if (const char *e = getenv("ST3D_W43_SLOTS")) nslots = atol(e);       // lab: 0 = one workgroup per tile
     if (nslots < 1 || nslots > npix) nslots = npix;
@@ -647,6 +718,17 @@ int launch_wino43_tc(Wino43Args a, hipStream_t s) {
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     };
+    if constexpr (kStrips) {        // the input-gradient chain over a strip list (need.hip), nothing else
+        if (!a.tile_list || !a.n_active) { st3d::set_error("wino43: 16-pixel tile columns come with a strip list and its count"); return ST3D_E_INVALID; }
+        if (((uintptr_t)a.tile_list & 15) != 0) { st3d::set_error("wino43: a strip list is 16-byte aligned"); return ST3D_E_INVALID; }
+        if (a.yp || a.bias || a.relu) { st3d::set_error("wino43: strip lists are for the input-gradient chain"); return ST3D_E_INVALID; }
+        if (a.gate && a.addt) {
+            if (MODE != 0) { st3d::set_error("wino43: the content-target term rides on ungated input (MODE 0) only"); return ST3D_E_INVALID; }
+            return go(wino43_kernel<0, 0, 2, TC, true, true>);
+        }
+        if (a.gate) return go(wino43_kernel<MODE, 0, 1, TC, true, true>);
+        return go(wino43_kernel<MODE, 0, 0, TC, true, true>);
+    } else {
     if (a.tile_list) {      // the listed walk: the input-gradient chain (need.hip) and the plain forward (flat.hip)
         if (!a.n_active) { st3d::set_error("wino43: a tile list without its count"); return ST3D_E_INVALID; }
         if ((a.yp || a.bias || a.relu) && (MODE != 0 || a.gate)) { st3d::set_error("wino43: bias, ReLU and the fused pool belong to the plain forward"); return ST3D_E_INVALID; }
@@ -668,18 +750,21 @@ int launch_wino43_tc(Wino43Args a, hipStream_t s) {
     }
     if (a.gate) return go(wino43_kernel<MODE, 0, 1, TC>);
     return go(wino43_kernel<MODE, 0, 0, TC>);
+    }
 }
 
 // cols: the caller's choice of geometry (listed launches: the lists number the tiles of one geometry) -- 64 or 32 pixels
-// across where the map allows it, 0 = tc43's
+// across where the map allows it, 16 = strips (any map the kernel covers: an image's strips fill whole steps), 0 = tc43's
 template <int MODE>
 int launch_wino43(Wino43Args a, hipStream_t s, int cols = 0) {
     const int native = tc43(a.H, a.W);
-    if (cols != 0 && !((cols == 64 && native == 16) || (cols == 32 && a.H > 0 && a.W > 0 && (a.H % 8) == 0 && (a.W % 32) == 0))) {
+    if (cols != 0 && !((cols == 64 && native == 16) || (cols == 32 && a.H > 0 && a.W > 0 && (a.H % 8) == 0 && (a.W % 32) == 0) ||
+                       (cols == 16 && native != 0))) {
         st3d::set_error("wino43: %d-pixel tile columns do not fit a %d x %d map", cols, a.H, a.W);
         return ST3D_E_INVALID;
     }
     const int tc = cols ? cols / 4 : native;
+    if (tc == 4) return launch_wino43_tc<MODE, 4>(a, s);
     return tc == 16 ? launch_wino43_tc<MODE, 16>(a, s) : launch_wino43_tc<MODE, 8>(a, s);
 }
 

@@ -151,6 +151,7 @@ SIGNATURES = {
     "st3d_need_build": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, ctypes.c_void_p, c_size, c_i32p, c_i32p, c_i32p, c_stream]),
     "st3d_need_blocks_lists": (c_int, [c_int]),
     "st3d_need_blocks_tiles": (c_size, [c_int, c_int, c_int]),
+    "st3d_need_blocks_entries": (c_size, [c_int, c_int, c_int, c_int]),
     "st3d_need_blocks_workspace_bytes": (c_size, [c_int, c_int]),
     "st3d_need_blocks_build": (c_int, [c_u8p, c_int, c_int, c_int, ctypes.POINTER(c_int), c_u8p, ctypes.c_void_p, c_size,
                                        ctypes.POINTER(ctypes.c_void_p), c_i32p, c_i32p, c_i32p, c_stream]),

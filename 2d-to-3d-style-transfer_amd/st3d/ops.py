@@ -772,18 +772,20 @@ def need_blocks_lists(S):
 
 def need_blocks_build(mask, nlists=None, tile_cols=None, gram=False):
     """mask (N,S,S) uint8 -> (seg (N,S,S/64) uint8, [(list, count)] per list): the per-block need lists of the input
-    gradients of conv1_2, conv2_1, conv2_2, conv3_1, conv3_2, conv3_3 (st3d_need_blocks_build).  tile_cols: 64 / 32 / 0 per
-    list (0 or None = the kernel's own geometry for the map).  Lists are sized for every tile and start as -1.
+    gradients of conv1_2, conv2_1, conv2_2, conv3_1, conv3_2, conv3_3 (st3d_need_blocks_build).  tile_cols: 64 / 32 / 16 / 0
+    per list (0 or None = the kernel's own geometry for the map; 16 = strips of 4 x 16 pixels, four entries to a step, every
+    image padded with -1 to whole steps, the count in steps).  Lists are sized for every tile (strip) and start as -1.
     gram=True: a third value, (list, count) of the 64-pixel runs of the relu2_1 Gram backward (gram_bwd_gated_segs)."""
     lib = _lib.load()
     N, S, _ = mask.shape
     nlists = need_blocks_lists(S) if nlists is None else nlists
     seg = torch.empty((N, S, S // 64), dtype=U8, device=mask.device)
     counts = torch.zeros((max(nlists, 1),), dtype=I32, device=mask.device)
-    lists = [torch.full((lib.st3d_need_blocks_tiles(N, S, k),), -1, dtype=I32, device=mask.device) for k in range(nlists)]
+    tcols = [int(c or 0) for c in (tile_cols or [0] * nlists)]
+    lists = [torch.full((lib.st3d_need_blocks_entries(N, S, k, tcols[k]),), -1, dtype=I32, device=mask.device) for k in range(nlists)]
     nb = lib.st3d_need_blocks_workspace_bytes(N, S)
     ws = torch.empty((max(nb, 1),), dtype=U8, device=mask.device)
-    cols = (ctypes.c_int * max(nlists, 1))(*[int(c or 0) for c in (tile_cols or [0] * nlists)])
+    cols = (ctypes.c_int * max(nlists, 1))(*tcols)
     ptrs = (ctypes.c_void_p * max(nlists, 1))(*[l.data_ptr() for l in lists])
     glist = torch.full((lib.st3d_need_blocks_gram_runs(N, S),), -1, dtype=I32, device=mask.device) if gram else None
     gcount = torch.zeros((1,), dtype=I32, device=mask.device) if gram else None
@@ -896,7 +898,8 @@ def wino43_dgrad_chain_tiles(gy, ud, Cin, tile_list, n_active, out, pool_idx=Non
                              tile_cols=None):
     """wino43_dgrad_chain over the first n_active (device int32 scalar) tiles of tile_list (device int32), written into
     `out` (N,Cin,H,W) in place: the other tiles of `out` are left alone (st3d_wino43_dgrad_chain_tiles).  tile_cols = 64 /
-    32: the list numbers the 4 x 64 / 8 x 32 tiles (st3d_wino43_dgrad_chain_tiles_geo)."""
+    32: the list numbers the 4 x 64 / 8 x 32 tiles (st3d_wino43_dgrad_chain_tiles_geo); 16: tile_list holds four strips of 4 x 16
+    pixels ((n * H/4 + sy) * W/16 + sx, or -1) of one image per step and n_active counts steps."""
     N, Cout = gy.shape[:2]
     H, W = (2 * gy.shape[2], 2 * gy.shape[3]) if pool_idx is not None else gy.shape[2:]
     assert tuple(out.shape) == (N, Cin, H, W)

@@ -468,10 +468,14 @@ int st3d_need_build(const uint8_t *mask, int N, int S, int levels, uint8_t *seg,
  * (S/4).  list k holds the tiles that hold a block of B_k, in the geometry tile_cols[k] (host array; 64 = 4 x 64 pixels, 32 =
  * 8 x 32, 0 or tile_cols == NULL = st3d_wino43_tile_geometry's), ascending, st3d_need_blocks_tiles(N, S, k) entries long;
  * counts[k] the number listed.  lists: HOST array of nlists device pointers.  seg as st3d_need_build.  Device memory
- * throughout, no atomics.  st3d_need_blocks_lists(S): how many lists exist at this size (0: not covered). */
+ * throughout, no atomics.  st3d_need_blocks_lists(S): how many lists exist at this size (0: not covered).
+ * tile_cols[k] = 16: strips.  list k holds the strips of 4 x 16 pixels, (n * strips_y + sy) * strips_x + sx, that hold a block
+ * of B_k, ascending within an image, FOUR entries to a workgroup step, every image padded with -1 to whole steps; counts[k] =
+ * steps.  The list is st3d_need_blocks_entries(N, S, k, 16) = 4 st3d_need_blocks_tiles entries long and 16-byte aligned. */
 #define ST3D_NEED_MAX_LISTS 6
 int st3d_need_blocks_lists(int S);
 size_t st3d_need_blocks_tiles(int N, int S, int k);
+size_t st3d_need_blocks_entries(int N, int S, int k, int tile_cols);
 size_t st3d_need_blocks_workspace_bytes(int N, int S);
 /* gram_list / gram_count (device; NULL = not wanted): the 64-pixel runs of the (S/2)^2 map that meet need_2, the pixels at
  * which the conv2_1 input gradient reads the gradient of relu2_1 -- what st3d_gram_bwd_gated_segs takes; numbered image *
@@ -488,7 +492,9 @@ int st3d_gram_bwd_gated_segs(const float *D, const float *feat, const float *q, 
                              const int *seg_list, const int *seg_count, float *gfeat, st3d_stream_t stream);
 /* st3d_wino43_dgrad_chain_tiles / st3d_wino43_fwd_tiles with the tile geometry as an argument: tile_cols = 64 (4 x 64 pixels,
  * W % 64 == 0) or 32 (8 x 32 pixels, H % 8 == 0 and W % 32 == 0); tile_list numbers the tiles of THAT geometry.  0 = the
- * geometry of st3d_wino43_tile_geometry. */
+ * geometry of st3d_wino43_tile_geometry.  The input-gradient chain also takes tile_cols = 16: tile_list (16-byte aligned) holds
+ * FOUR entries per step, each a strip of 4 x 16 pixels (n * H/4 + sy) * W/16 + sx or -1 (none), all of one image, anywhere in
+ * it; *n_active counts steps.  Every block of a listed strip is bitwise the unlisted call's, nothing else is written. */
 int st3d_wino43_dgrad_chain_tiles_geo(const float *gy, const uint8_t *pool_idx, const float *u_dgrad, const float *out_gate,
                                       const float *add_target, float add_coef, float *gx, int N, int Cin, int Cout, int H, int W,
                                       int tile_cols, const int *tile_list, const int *n_active, st3d_stream_t stream);

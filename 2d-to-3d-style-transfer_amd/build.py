@@ -46,6 +46,9 @@ SOURCES = {
     "loss.hip": ["-ffp-contract=off"],
     "mesh.hip": [],
     "texpyr.hip": ["-ffp-contract=off"],       # the roundings its tests count are the ones written in the source
+    # shade.hip's flags: its level-0 taps and blend are those of the plain kernels bit for bit, the chain is compared bit for
+    # bit with its ordered numpy restatement
+    "mipmap.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "plan.hip": [],
     "comm.hip": [],
 }

@@ -69,6 +69,12 @@ SHARED_FLAGS = [
     Flag("supersample", int, 1, "rasterise and shade every render of the run (current, content, final) at N x size and hand the "
          "loss the N x N box-filtered image at size: each pixel then carries gradient to N^2 texture footprints and "
          "silhouette pixels get a fractional coverage; 1..4, N x size <= 4096, 1 = off"),
+    Flag("texture_mip_levels", int, 1, "sample the texture of every render trilinearly from a mip chain of N levels at each "
+         "pixel's own level of detail, so that a pixel over several texels reads and moves all of them; 1 = off (bilinear on "
+         "the map itself), 0 = the full chain (down to a side of 2 or the first odd side).  White ambient light, "
+         "--supersample 1 only"),
+    Flag("texture_lod_bias", float, 0.0, "added to every pixel's level of detail before it is clamped to the chain "
+         "(--texture_mip_levels): negative = sharper, positive = blurrier"),
 ]
 
 # regularisers the reference defines but never switches on (losses.py:48-65, notes.txt:36,39); weight 0 = off
@@ -103,6 +109,24 @@ def check_args(args):
     if n > 1 and getattr(args, "silhouette_weight", 0.0):
         return ("--supersample > 1 cannot be combined with --silhouette_weight: alpha-only (silhouette) renders are not "
                 "supersampled")
+    mip = getattr(args, "texture_mip_levels", 1)
+    if not 0 <= mip <= 16:
+        return "--texture_mip_levels must be 0 (full chain), 1 (off) or the number of levels, at most 16"
+    bias = getattr(args, "texture_lod_bias", 0.0)
+    if not math.isfinite(bias):
+        return "--texture_lod_bias must be finite"
+    if mip != 1:
+        if n > 1:
+            return "--texture_mip_levels cannot be combined with --supersample > 1: the supersampled kernels do not mip-map"
+        if getattr(args, "lights", "ambient") != "ambient":
+            return (f"--texture_mip_levels needs --lights ambient: the lit kernels do not mip-map (got --lights "
+                    f"{args.lights})")
+        size = getattr(args, "size", 0)
+        if mip > 1 and getattr(args, "resize_texture", True) and (size % (1 << (mip - 1)) or size >> (mip - 1) < 2):
+            return (f"--texture_mip_levels {mip} needs a texture side divisible by {1 << (mip - 1)} with a coarsest side >= 2; "
+                    f"--resize_texture makes it --size = {size}")
+    elif bias != 0.0:
+        return "--texture_lod_bias needs --texture_mip_levels other than 1"
     return None
 
 
@@ -241,7 +265,12 @@ class Run:
 
         cams = FoVPerspectiveCameras(device=self.device)
         supersample = getattr(args, "supersample", 1)
-        if supersample == 1:
+        mip_levels = getattr(args, "texture_mip_levels", 1)
+        if mip_levels != 1:
+            settings = RasterizationSettings(image_size=args.size, blur_radius=0.0, faces_per_pixel=1,
+                                             texture_mip_levels=mip_levels,
+                                             texture_lod_bias=getattr(args, "texture_lod_bias", 0.0))
+        elif supersample == 1:
             settings = RasterizationSettings(image_size=args.size, blur_radius=0.0, faces_per_pixel=1)
         else:
             settings = RasterizationSettings(image_size=args.size, blur_radius=0.0, faces_per_pixel=1, supersample=supersample)

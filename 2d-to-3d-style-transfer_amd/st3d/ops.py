@@ -1200,6 +1200,140 @@ def texpyr_adjoint(grad_texture, T, L, out=None):
     return out
 
 
+# ------------------------------------------------------------------ mip-mapped sampling (csrc/mipmap.hip)
+MIP_MAX_LEVELS = 16
+
+
+def check_mip(levels, T=None):
+    """texture_mip_levels -> the resolved level count L >= 1 under a T x T map (ValueError otherwise).  0 = the full chain:
+    the largest L with T divisible by 2^(L-1) and a coarsest side >= 2 (64 -> 6, 48 -> 5, 37 -> 1); 1 = off; L >= 2 needs
+    exactly that of T.  Without T only the value itself is checked and returned."""
+    if isinstance(levels, bool) or not isinstance(levels, int) or not 0 <= levels <= MIP_MAX_LEVELS:
+        raise ValueError(f"texture_mip_levels must be an int in 0..{MIP_MAX_LEVELS} (0 = full chain, 1 = off), got {levels!r}")
+    if T is None:
+        return levels
+    T = int(T)
+    if T < 2:
+        raise ValueError(f"mip-mapping needs a texture side >= 2, got {T}")
+    if levels == 0:
+        L = 1
+        while L < MIP_MAX_LEVELS and T % (1 << L) == 0 and T >> L >= 2:
+            L += 1
+        return L
+    if levels > 1 and (T % (1 << (levels - 1)) or T >> (levels - 1) < 2):
+        raise ValueError(f"texture_mip_levels = {levels} needs a texture side divisible by {1 << (levels - 1)} with a coarsest "
+                         f"side >= 2, got {T}")
+    return levels
+
+
+def check_lod_bias(bias):
+    bias = float(bias)
+    if not math.isfinite(bias):
+        raise ValueError(f"texture_lod_bias must be finite, got {bias!r}")
+    return bias
+
+
+def mip_numel(T, L):
+    """3 * sum_l (T >> l)^2: the length of the packed mip chain (the texture pyramid's layout) of L >= 1 levels."""
+    L = check_mip(int(L), T)
+    n = _lib.load().st3d_mip_numel(int(T), L)
+    if n == 0:
+        raise ValueError(f"no mip chain of {L} levels under a side of {T}")
+    return n
+
+
+def mip_build(texture, L, out=None):
+    """texture (T*T*3 values, HWC) -> packed chain (P,): level_{l+1} = 2 x 2 box mean of level_l, ((a + b) + (c + d)) * 0.25"""
+    T = texture.shape[-2]
+    P = mip_numel(T, L)
+    if texture.numel() != 3 * T * T:
+        raise ValueError(f"texture must hold {T}x{T}x3 values, got {tuple(texture.shape)}")
+    if out is None:
+        out = torch.empty((P,), dtype=F32, device=texture.device)
+    call("st3d_mip_build", dptr(texture.contiguous(), F32), int(T), int(L), dptr(out, F32), stream_ptr())
+    return out
+
+
+def mip_adjoint(grad_pyramid, T, L, out=None):
+    """packed per-level gradient (P,) -> (T,T,3): the adjoint of mip_build, folded coarse to fine in a fixed order.  `out`:
+    an existing gradient the result is ADDED to."""
+    P = mip_numel(T, L)
+    if grad_pyramid.numel() != P:
+        raise ValueError(f"a {L}-level chain under side {T} holds {P} values, got {grad_pyramid.numel()}")
+    acc = 1
+    if out is None:
+        out = torch.empty((T, T, 3), dtype=F32, device=grad_pyramid.device)
+        acc = 0
+    call("st3d_mip_adjoint", dptr(grad_pyramid.contiguous(), F32), int(T), int(L), acc, dptr(out, F32), stream_ptr())
+    return out
+
+
+def mip_lod(frag, verts_ndc, faces_i32, verts_uvs, faces_uvs_i32, T, L, bias=0.0):
+    """-> lod (B,S,S): the level of detail lambda in [0, L-1] of every covered pixel (0 elsewhere), analytic per fragment"""
+    p2f, zbuf, bary, _dists = frag
+    B, S, _ = p2f.shape
+    L, bias = check_mip(int(L), T), check_lod_bias(bias)
+    lod = torch.empty((B, S, S), dtype=F32, device=p2f.device)
+    call("st3d_mip_lod", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(verts_ndc, F32), dptr(faces_i32, I32),
+         dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), B, S, int(T), L, verts_ndc.shape[1], faces_i32.shape[0],
+         verts_uvs.shape[0], bias, dptr(lod), stream_ptr())
+    return lod
+
+
+def _mip_check_planes(p2f, pyramid, lod, T, L):
+    P = mip_numel(T, L)
+    if pyramid.numel() != P:
+        raise ValueError(f"a {L}-level chain under side {T} holds {P} values, got {pyramid.numel()}")
+    if tuple(lod.shape) != tuple(p2f.shape):
+        raise ValueError(f"lod must be {tuple(p2f.shape)}, got {tuple(lod.shape)}")
+
+
+def shade_mip_fwd(frag, verts_uvs, faces_uvs_i32, pyramid, lod, T, L):
+    """shade_fwd sampling the packed chain trilinearly at lod -> rgb (B,3,S,S), mask (B,1,S,S)"""
+    p2f, zbuf, bary, dists = frag
+    B, S, _ = p2f.shape
+    _mip_check_planes(p2f, pyramid, lod, T, L)
+    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
+    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
+    call("st3d_shade_mip_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
+         dptr(faces_uvs_i32, I32), dptr(pyramid, F32), dptr(lod, F32), B, S, int(T), int(L), faces_uvs_i32.shape[0],
+         verts_uvs.shape[0], dptr(rgb), dptr(mask), stream_ptr())
+    return rgb, mask
+
+
+def shade_mip_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, pyramid, lod, T, L, grad_texture=None, want_uv=False,
+                  want_bary=False, want_texture=True, want_levels=False):
+    """-> grad_texture (T,T,3) [, grad_uv (B,S,S,2)] [, grad_bary (B,S,S,3)] [, the per-level gradient (P,) before the
+    fold]; lod is a constant.  Fixed point (bitwise reproducible) unless set_deterministic(False)."""
+    p2f, zbuf, bary, dists = frag
+    B, S, _ = p2f.shape
+    dev = p2f.device
+    _mip_check_planes(p2f, pyramid, lod, T, L)
+    if tuple(grad_rgb.shape) != (B, 3, S, S):
+        raise ValueError(f"grad_rgb must be {(B, 3, S, S)}, got {tuple(grad_rgb.shape)}")
+    if grad_texture is None and want_texture:
+        grad_texture = torch.zeros((T, T, 3), dtype=F32, device=dev)
+    gpyr = torch.empty((pyramid.numel(),), dtype=F32, device=dev) if grad_texture is not None else None
+    guv = torch.empty((B, S, S, 2), dtype=F32, device=dev) if want_uv else None
+    gbary = torch.empty((B, S, S, 3), dtype=F32, device=dev) if want_bary else None
+    ws, nb = None, 0
+    if _DETERMINISTIC and grad_texture is not None:
+        nb = _lib.load().st3d_shade_mip_bwd_workspace_bytes(int(T), int(L))
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
+    call("st3d_shade_mip_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
+         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(pyramid, F32), dptr(lod, F32), B, S, int(T),
+         int(L), faces_uvs_i32.shape[0], verts_uvs.shape[0], dptr(gpyr), dptr(grad_texture, F32) if grad_texture is not None
+         else None, dptr(guv), dptr(gbary), dptr(ws), nb, stream_ptr())
+    out = (grad_texture,)
+    if want_uv:
+        out += (guv,)
+    if want_bary:
+        out += (gbary,)
+    if want_levels:
+        out += (gpyr,)
+    return out if len(out) > 1 else out[0]
+
+
 def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8):
     call("st3d_adam_step", dptr(p, F32), dptr(g.contiguous(), F32), dptr(m, F32), dptr(v, F32), p.numel(), int(step),
          float(lr), float(b1), float(b2), float(eps), stream_ptr())

@@ -230,6 +230,22 @@ class RotateAxisAngle:
 # ------------------------------------------------------------------------ renderer
 
 
+# what a mip-mapped render (texture_mip_levels != 1) refuses, by limitation (NotImplementedError, before any launch)
+MIP_REFUSALS = {
+    "lights": "texture_mip_levels != 1 is implemented for unlit renders only (lights=None or white AmbientLights with default "
+              "Materials): the lit kernels have no mip-mapped sampling",
+    "supersample": "texture_mip_levels != 1 cannot be combined with supersample > 1: the supersampled kernels have no mip-mapped "
+                   "sampling",
+    "soft": "texture_mip_levels != 1 is implemented for the hard settings only (faces_per_pixel = 1, blur_radius = 0, default "
+            "clipping, culling and BlendParams): the general soft kernels have no mip-mapped sampling",
+    "silhouette": "texture_mip_levels != 1 means nothing to an alpha-only (silhouette) render, which samples no texture: a "
+                  "SoftSilhouetteShader takes RasterizationSettings(texture_mip_levels=1)",
+}
+MIP_NEAR_PLANE_MESSAGE = ("the mesh reaches the near clipping plane (z < znear / 2) under texture_mip_levels != 1: the clipping "
+                          "kernels have no mip-mapped sampling, and the render is not silently rerouted to unfiltered sampling "
+                          "-- render with texture_mip_levels=1 or keep the mesh in front of the plane")
+
+
 class RasterizationSettings:
     """PyTorch3D RasterizationSettings: image_size, blur_radius, faces_per_pixel, clip_barycentric_coords
     (None = clip iff blur_radius > 0, the PyTorch3D default), perspective_correct (None = True: every camera here is a
@@ -237,14 +253,17 @@ class RasterizationSettings:
     accepted and ignored.  Anything but the reference's own values (first_approach.py:107) runs on the general kernels.
     supersample = a in 1..4 (not PyTorch3D's; 1 = off): rasterise and shade at a * image_size, hand out the a x a
     box-filtered image at image_size (PyTorch3D's documented anti-aliasing, render larger then avg_pool2d, without the
-    larger image: csrc/shade.hip).  Coverage then is the covered share of the pixel's a^2 sub-pixels."""
+    larger image: csrc/shade.hip).  Coverage then is the covered share of the pixel's a^2 sub-pixels.
+    texture_mip_levels = L (not PyTorch3D's; 1 = off, 0 = the full chain under the map's side) and texture_lod_bias: sample the
+    texture trilinearly from an L-level mip chain at each pixel's own level of detail (csrc/mipmap.hip) -- hard
+    settings, unlit, supersample = 1 only.  The levels are checked against the map's side when a render knows it."""
     MAX_FACES_PER_PIXEL = 8
 
     Z_CLIP_DEFAULT = 0.5        # PyTorch3D MeshRasterizer: z_clip_value None -> znear / 2 for perspective cameras (znear = 1)
 
     def __init__(self, image_size=256, blur_radius=0.0, faces_per_pixel=1, bin_size=None, max_faces_per_bin=None,
                  perspective_correct=None, clip_barycentric_coords=None, cull_backfaces=False, z_clip_value=None,
-                 cull_to_frustum=False, supersample=1, **kw):
+                 cull_to_frustum=False, supersample=1, texture_mip_levels=1, texture_lod_bias=0.0, **kw):
         if isinstance(image_size, (tuple, list)):
             if len(image_size) != 2 or image_size[0] != image_size[1]:
                 raise NotImplementedError("square images only")
@@ -266,6 +285,10 @@ class RasterizationSettings:
         # (st3d.ops.check_near_plane) -- an explicit value sends the render to the general kernels
         self.z_clip_value = None if z_clip_value is None else float(z_clip_value)
         self.supersample = ops.check_supersample(supersample, self.image_size)
+        self.texture_mip_levels = ops.check_mip(texture_mip_levels)
+        self.texture_lod_bias = ops.check_lod_bias(texture_lod_bias)
+        if self.texture_mip_levels != 1 and self.supersample > 1:
+            raise NotImplementedError(MIP_REFUSALS["supersample"])
 
     @property
     def z_clip(self):
@@ -288,6 +311,8 @@ class SilhouetteRasterizationSettings(RasterizationSettings):
         super().__init__(*a, **kw)
         if self.supersample > 1:
             raise NotImplementedError("supersample > 1 is not implemented for alpha-only (silhouette) renders")
+        if self.texture_mip_levels != 1:
+            raise NotImplementedError(MIP_REFUSALS["silhouette"])
 
 
 class BlendParams:
@@ -564,6 +589,8 @@ def _refuse_supersampled_silhouette(raster_settings):
     if getattr(raster_settings, "supersample", 1) > 1:
         raise NotImplementedError("supersample > 1 is not implemented for alpha-only (silhouette) renders: a "
                                   "SoftSilhouetteShader takes RasterizationSettings(supersample=1)")
+    if getattr(raster_settings, "texture_mip_levels", 1) != 1:
+        raise NotImplementedError(MIP_REFUSALS["silhouette"])
 
 
 class _SilhouetteFn(torch.autograd.Function):
@@ -696,6 +723,51 @@ class _RenderFn(torch.autograd.Function):
                 gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
                 gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
         return gverts, gtex, None, None, None, None, None, None, None
+
+
+class _MipRenderFn(torch.autograd.Function):
+    """_RenderFn with mip-mapped trilinear sampling (L >= 2 levels): project, raster, mip_build, mip_lod, shade_mip_fwd.  The
+    chain and the level-of-detail plane are kept for the backward, which treats the plane as a constant: texel gradients of
+    both levels of every pixel's pair are folded back onto the map by the chain's adjoint; d/d(bary) goes through the
+    unchanged raster / projection backward."""
+
+    @staticmethod
+    def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, L, bias):
+        v = verts.detach().to(torch.float32).contiguous()
+        tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
+        if tex.shape[0] != tex.shape[1]:
+            raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
+        side = tex.shape[0]
+        uvs = verts_uvs.detach().to(torch.float32).reshape(-1, 2).contiguous()
+        ndc = ops.project_verts(v, R, T)
+        frag = ops.raster_fwd(ndc, faces_i32, S)
+        pyr = ops.mip_build(tex, L)
+        lod = ops.mip_lod(frag, ndc, faces_i32, uvs, faces_uvs_i32, side, L, bias)
+        rgb, mask = ops.shade_mip_fwd(frag, uvs, faces_uvs_i32, pyr, lod, side, L)
+        ctx.frag, ctx.uvs, ctx.fuv, ctx.pyr, ctx.lod, ctx.mip = frag, uvs, faces_uvs_i32, pyr, lod, (side, L)
+        ctx.tex_shape = tex_map.shape
+        ctx.geom = (v, ndc, faces_i32, R, T)
+        ctx.verts_shape = verts.shape
+        ctx.mark_non_differentiable(mask)
+        return rgb, mask
+
+    @staticmethod
+    def backward(ctx, grad_rgb, _grad_mask):
+        with ops.trace("render_backward"):
+            need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            gtex = gverts = None
+            if need_v or need_t:
+                side, L = ctx.mip
+                res = ops.shade_mip_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.pyr, ctx.lod, side, L,
+                                        want_bary=need_v, want_texture=need_t)
+                gt, gbary = (res if need_v else (res, None))
+                if need_t:
+                    gtex = gt.reshape(ctx.tex_shape)
+                if need_v:
+                    v, ndc, faces_i32, R, T = ctx.geom
+                    gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
+                    gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
+            return (gverts, gtex) + (None,) * 8
 
 
 class _SSRenderFn(torch.autograd.Function):
@@ -955,6 +1027,10 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
                                   "only: they need a SoftSilhouetteShader")
     R, T = R.to(dev), T.to(dev)
     lighting = lighting_of(lights, materials, dev)
+    if getattr(rs, "texture_mip_levels", 1) != 1:
+        out = _render_views_mip(meshes, R, T, int(image_size), rs, bp, lighting)
+        if out is not None:
+            return out
     if getattr(rs, "supersample", 1) > 1:
         return _render_views_ss(meshes, R, T, int(image_size), rs, bp, lighting)
     hard_settings = uses_hard_path(rs, bp)
@@ -989,6 +1065,33 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
         # (alpha of a K = 1 / blur 0 blend is in [0.5, 1) on covered pixels; the reference thresholds it, utils.py:72)
         alpha = (alpha.detach() > 0).to(torch.float32)
     return rgb, alpha
+
+
+def _render_views_mip(meshes, R, T, S, rs, bp, lighting):
+    """_render_views at texture_mip_levels != 1 -> (rgb, 0/1 mask) from the mip-mapped kernels, or None when the map's side
+    allows one level only (texture_mip_levels = 0 under an odd side: the plain render).  Everything the kernels do not cover
+    is refused before any launch; a batch at the near plane is an error, never a silent unfiltered render."""
+    if lighting is not None:
+        raise NotImplementedError(MIP_REFUSALS["lights"])
+    if getattr(rs, "supersample", 1) > 1:
+        raise NotImplementedError(MIP_REFUSALS["supersample"])
+    if not uses_hard_path(rs, bp):
+        raise NotImplementedError(MIP_REFUSALS["soft"])
+    tex = meshes.textures
+    maps = tex.maps_padded()
+    if maps.shape[-3] != maps.shape[-2]:
+        raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
+    L = ops.check_mip(rs.texture_mip_levels, maps.shape[-2])
+    if L == 1:
+        return None
+    if ops.near_plane_triggered() or reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT):
+        raise RuntimeError(MIP_NEAR_PLANE_MESSAGE)
+    rgb, mask = _MipRenderFn.apply(meshes.verts_packed(), maps, meshes.faces_i32(), tex.verts_uvs_padded(), tex.faces_uvs_i32(),
+                                   R, T, S, L, rs.texture_lod_bias)
+    if rgb.requires_grad:
+        tag_need(rgb, rgb.grad_fn.frag[0])
+    tag_flat(rgb, (1.0, 1.0, 1.0))
+    return rgb, mask
 
 
 def ss_fused():
@@ -1058,6 +1161,10 @@ class MeshRenderer:
     @property
     def supersample(self):
         return getattr(self.rasterizer.raster_settings, "supersample", 1)
+
+    @property
+    def texture_mip_levels(self):
+        return getattr(self.rasterizer.raster_settings, "texture_mip_levels", 1)
 
     @property
     def is_hard(self):

@@ -665,6 +665,42 @@ size_t st3d_texpyr_numel(int T, int L);
 int st3d_texpyr_synth(const float *params, int T, int L, float *texture, st3d_stream_t stream);
 int st3d_texpyr_adjoint(const float *grad_texture, int T, int L, float *grad_params, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ mip-mapped trilinear sampling (csrc/mipmap.hip,
+ * DESIGN 7), hard settings, K = 1, unlit.  The chain lives in the texture pyramid's packed layout and has its limits
+ * (T_l = T >> l; level l at float offset 3 * sum_{k<l} T_k^2; L >= 2 needs T divisible by 2^(L-1) and T_{L-1} >= 2;
+ * T <= 16384, L <= 16); st3d_mip_numel returns 0 for a shape the others refuse.
+ *   build:   level_0 = texture; level_{l+1}[r][x] = ((a + b) + (c + d)) * 0.25f over a = level_l[2r][2x], b = [2r][2x+1],
+ *            c = [2r+1][2x], d = [2r+1][2x+1].  One launch, two for L > 6.
+ *   adjoint: acc_{L-1} = g_{L-1}; acc_l[r][x] = g_l[r][x] + 0.25f * acc_{l+1}[r>>1][x>>1]; grad_texture = acc_0, added to
+ *            what grad_texture holds when `accumulate`.  A gather in a fixed order, no atomics, one launch.
+ *   lod:     lod (B,S,S): lambda = clamp(log2 rho + bias, 0, L-1) of every covered pixel from its fragment (face,
+ *            barycentrics, zbuf) and the face's projected vertices (verts_ndc (B,V,3): x_ndc, y_ndc, view depth): rho is the
+ *            larger of the lengths of d(u,v)/dx and d(u,v)/dy, times (T-1) texels and 2/S per pixel step.  0 where
+ *            !(rho > 1), where the face's screen area is 0 and on uncovered pixels.  No neighbouring pixel is read.
+ *   shade_mip_fwd: st3d_shade_fwd with texel = (1 - t) bil(l0) + t bil(l0 + 1), l0 = floor(lambda), t = lambda - l0; level
+ *            l >= 1 is tapped at (ix + 0.5) / 2^l - 0.5 of the clamped level-0 index, clamped to its side.  t == 0 reads
+ *            one level: lambda == 0 everywhere is st3d_shade_fwd bit for bit.
+ *   shade_mip_bwd: lambda is a constant.  The texel gradients of both levels are scattered into grad_pyramid
+ *            (st3d_mip_numel floats of the caller's, OVERWRITTEN; required iff grad_texture is given) and folded by the
+ *            adjoint INTO grad_texture (accumulated).  workspace == NULL: float atomics; else the 64-bit fixed-point
+ *            scatter (bitwise reproducible; a NaN / Inf in grad_rgb makes every element NaN), workspace of
+ *            st3d_shade_mip_bwd_workspace_bytes(T, L) bytes, 16-byte aligned.  grad_uv (B,S,S,2), grad_bary (B,S,S,3) as
+ *            st3d_shade_bwd, through both levels' taps.  Nothing is allocated. */
+size_t st3d_mip_numel(int T, int L);
+int st3d_mip_build(const float *texture, int T, int L, float *pyramid, st3d_stream_t stream);
+int st3d_mip_adjoint(const float *grad_pyramid, int T, int L, int accumulate, float *grad_texture, st3d_stream_t stream);
+int st3d_mip_lod(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *verts_ndc,
+                 const int32_t *faces, const float *verts_uvs, const int32_t *faces_uvs, int B, int S, int T, int L, int V,
+                 int F, int VT, float bias, float *lod, st3d_stream_t stream);
+int st3d_shade_mip_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                       const float *verts_uvs, const int32_t *faces_uvs, const float *pyramid, const float *lod, int B, int S,
+                       int T, int L, int F, int VT, float *rgb, float *mask, st3d_stream_t stream);
+size_t st3d_shade_mip_bwd_workspace_bytes(int T, int L);
+int st3d_shade_mip_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                       const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *pyramid,
+                       const float *lod, int B, int S, int T, int L, int F, int VT, float *grad_pyramid, float *grad_texture,
+                       float *grad_uv, float *grad_bary, void *workspace, size_t workspace_bytes, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ optimiser:
  * torch.optim.Adam defaults (utils.py:185-195, style_transfer.py:57) */
 int st3d_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,

@@ -49,6 +49,8 @@ SOURCES = {
     # shade.hip's flags: its level-0 taps and blend are those of the plain kernels bit for bit, the chain is compared bit for
     # bit with its ordered numpy restatement
     "mipmap.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # shade.hip's flags: blend and mask are the plain kernels' bit for bit, the interpolation is compared with its numpy restatement
+    "vcolor.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "plan.hip": [],
     "comm.hip": [],
 }

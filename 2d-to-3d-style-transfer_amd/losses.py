@@ -113,23 +113,34 @@ def _on_gpu(t):
     return t.to(torch.float32)
 
 
+def _texture_values(mesh):
+    """what the texture regularisers read: the map of a TexturesUV, the (V,3) colours of a TexturesVertex"""
+    if isinstance(mesh.textures, _render.TexturesVertex):
+        return mesh.textures.verts_features_packed()
+    return mesh.textures.maps_padded()
+
+
 def rgb_range_loss(mesh):
-    """Sum of the texture map's excursions outside [0,1] (reference losses.py:48-51; every call site in the
-    reference is commented out).  One fused launch: value + sign gradient."""
-    tex = _on_gpu(mesh.textures.maps_padded())
+    """Sum of the texture map's (or the vertex colours') excursions outside [0,1] (reference losses.py:48-51; every call
+    site in the reference is commented out).  One fused launch: value + sign gradient."""
+    tex = _on_gpu(_texture_values(mesh))
     return _FusedLossFn.apply(tex, _ops.range_loss)
 
 
 def compute_tv_loss(images, masks):
     """Masked anisotropic L1 total variation / sum(masks) (reference losses.py:55-65; call sites commented out
-    there too).  Value and d/d images from one fused pass."""
+    there too).  Value and d/d images from one fused pass.  Handed a mesh with per-vertex colours in the images' place
+    (total variation of the texture itself): ValueError -- vertex colours lie on no grid."""
+    if isinstance(getattr(images, "textures", None), _render.TexturesVertex):
+        raise ValueError("compute_tv_loss: a TexturesVertex mesh has per-vertex colours, which lie on no pixel grid; total "
+                         "variation is defined for images (and texture maps) only")
     return _FusedLossFn.apply(_on_gpu(images), _ops.tv_loss, _on_gpu(masks).detach())
 
 
 def texture_l2_loss(mesh, original_map):
     """mean((texture - original)^2): the "l2 regularization w.r.t. the original texture" idea of the reference's
-    notes.txt:39 (not implemented there)."""
-    tex = _on_gpu(mesh.textures.maps_padded())
+    notes.txt:39 (not implemented there).  A TexturesVertex mesh: its colours against the original (V,3) colours."""
+    tex = _on_gpu(_texture_values(mesh))
     return _FusedLossFn.apply(tex, _l2_to, _on_gpu(original_map).detach())
 
 

@@ -197,6 +197,13 @@ SIGNATURES = {
     "st3d_shade_mip_bwd_workspace_bytes": (c_size, [c_int, c_int]),
     "st3d_shade_mip_bwd": (c_int, [c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_int, c_int, c_int,
                                    c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, ctypes.c_void_p, c_size, c_stream]),
+    "st3d_shade_vc_fwd": (c_int, [c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_f32p,
+                                  c_stream]),
+    "st3d_shade_vc_bwd": (c_int, [c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_f32p,
+                                  c_f32p, c_stream]),
+    "st3d_shade_vc_bwd_det_workspace_bytes": (c_size, [c_int]),
+    "st3d_shade_vc_bwd_det": (c_int, [c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_f32p,
+                                      c_f32p, ctypes.c_void_p, c_size, c_stream]),
     "st3d_adam_step": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_size, c_int, c_float, c_float, c_float, c_float, c_stream]),
     "st3d_vgg_create": (c_int, [ctypes.POINTER(ctypes.c_void_p)]),
     "st3d_vgg_set_conv": (c_int, [ctypes.c_void_p, c_int, c_f32p, c_f32p, c_stream]),

@@ -24,6 +24,7 @@ _BACKGROUNDS = ['noise', 'style', 'white']
 _TARGETS = ['texture', 'mesh', 'both']
 _LIGHTS = ['ambient', 'point', 'directional', 'headlight']
 _STYLE_MASKS = ['none', 'object']
+_TEXTURE_TYPES = ['uv', 'vertex']
 
 # name, type, default and choices are the reference's (first_approach.py:23-45, second_approach.py:23-42); note
 # `type=bool` flags keep argparse's "any non-empty string is True" behaviour of the reference.
@@ -73,6 +74,11 @@ SHARED_FLAGS = [
          "pixel's own level of detail, so that a pixel over several texels reads and moves all of them; 1 = off (bilinear on "
          "the map itself), 0 = the full chain (down to a side of 2 or the first odd side).  White ambient light, "
          "--supersample 1 only"),
+    Flag("texture_type", str, 'uv', "what carries the colour: 'uv' = the OBJ's UV atlas and texture map (the reference's "
+         "TexturesUV), 'vertex' = one RGB triple per vertex interpolated over each face (PyTorch3D's TexturesVertex), for "
+         "meshes without UVs; started from the map sampled at each vertex's UV when the OBJ has one, else from seeded grey "
+         "noise.  White ambient light, --supersample 1, --texture_mip_levels 1, --texture_pyramid_levels 1, no --tv_weight",
+         _TEXTURE_TYPES),
     Flag("texture_lod_bias", float, 0.0, "added to every pixel's level of detail before it is clamped to the chain "
          "(--texture_mip_levels): negative = sharper, positive = blurrier"),
 ]
@@ -127,6 +133,18 @@ def check_args(args):
                     f"--resize_texture makes it --size = {size}")
     elif bias != 0.0:
         return "--texture_lod_bias needs --texture_mip_levels other than 1"
+    if getattr(args, "texture_type", "uv") == "vertex":
+        if levels != 1:
+            return "--texture_type vertex needs --texture_pyramid_levels 1: per-vertex colours have no map to build a pyramid of"
+        if mip != 1:
+            return "--texture_type vertex needs --texture_mip_levels 1: per-vertex colours have no map to filter"
+        if n > 1:
+            return "--texture_type vertex needs --supersample 1: the supersampled kernels have no vertex-colour path"
+        if getattr(args, "lights", "ambient") != "ambient":
+            return (f"--texture_type vertex needs --lights ambient: the lit kernels have no vertex-colour path (got --lights "
+                    f"{args.lights})")
+        if getattr(args, "tv_weight", 0.0) > 0:
+            return "--texture_type vertex cannot be combined with --tv_weight > 0: per-vertex colours lie on no grid"
     return None
 
 
@@ -188,6 +206,41 @@ def load_scene(obj_path, size, resize_texture, device):
         nchw = F.interpolate(tex.permute(0, 3, 1, 2), size=size, mode='bilinear', align_corners=False)
         tex = nchw.permute(0, 2, 3, 1).contiguous()
     return verts.to(device), faces.verts_idx.to(device), uvs[None].to(device), uv_faces[None].to(device), tex
+
+
+def vertex_colors_from_map(n_verts, faces, verts_uvs, faces_uvs, texture_map):
+    """Initial per-vertex colours from a UV-mapped texture -> (V,3): every vertex takes the map sampled at the UV of its
+    first incident corner (the smallest 3 f + j with faces[f, j] == v), with the renderer's sampling conventions (SURVEY.md
+    A.3: rows flipped, grid = uv * 2 - 1, bilinear, align_corners=True, border clamp).  A vertex no face uses gets 0.5.
+    faces (F,3), verts_uvs (VT,2), faces_uvs (F,3), texture_map (T,T',3).  Done once, in torch."""
+    flat = faces.reshape(-1).to(torch.int64)
+    n_corners = flat.numel()
+    first = torch.full((n_verts,), n_corners, dtype=torch.int64, device=flat.device)
+    first.scatter_reduce_(0, flat, torch.arange(n_corners, dtype=torch.int64, device=flat.device), reduce="amin")
+    used = first < n_corners
+    colors = torch.full((n_verts, 3), 0.5, dtype=torch.float32, device=flat.device)
+    if bool(used.any()):
+        uv = verts_uvs.reshape(-1, 2).to(torch.float32)[faces_uvs.reshape(-1).to(torch.int64)[first[used]]]
+        image = texture_map.reshape(texture_map.shape[-3], texture_map.shape[-2], 3).to(torch.float32)
+        nchw = image.flip(0).permute(2, 0, 1)[None]
+        grid = (uv * 2.0 - 1.0).reshape(1, 1, -1, 2)
+        sampled = F.grid_sample(nchw, grid, mode='bilinear', padding_mode='border', align_corners=True)
+        colors[used] = sampled[0, :, 0, :].t()
+    return colors
+
+
+def load_scene_vertex(obj_path, device):
+    """--texture_type vertex: OBJ -> (verts (V,3), faces (F,3), colours (V,3)) on `device`.  An OBJ with UVs and a texture
+    map starts from the map (vertex_colors_from_map); one without -- the case the flag exists for -- from
+    (0.5 + 0.1 randn(V,3), seed 0) clamped to [0,1], without a warning: nothing is synthesised that the mesh lacks."""
+    verts, faces, aux = st3d_io.load_obj(obj_path)
+    if aux.verts_uvs is None or faces.textures_idx is None or not aux.texture_images:
+        noise = torch.randn((verts.shape[0], 3), generator=torch.Generator().manual_seed(0))
+        colors = (0.5 + 0.1 * noise).clamp(0, 1)
+    else:
+        colors = vertex_colors_from_map(verts.shape[0], faces.verts_idx, aux.verts_uvs, faces.textures_idx,
+                                        next(iter(aux.texture_images.values())))
+    return verts.to(device), faces.verts_idx.to(device), colors.to(device)
 
 
 ViewBatch = namedtuple("ViewBatch", "index size lo hi")      # batch number, its global size, this rank's [lo, hi)
@@ -259,9 +312,14 @@ class Run:
             'mesh_verts_weight', 'main_loss_weight')}
 
         self.say("Loading mesh...")
-        verts, faces, verts_uvs, faces_uvs, tex = load_scene(args.obj_path, args.size, args.resize_texture, self.device)
+        self.vertex_colors = getattr(args, "texture_type", "uv") == "vertex"
+        if self.vertex_colors:
+            verts, faces, tex = load_scene_vertex(args.obj_path, self.device)       # tex: the (V,3) colours
+            self.content_mesh = _u.build_mesh_vertex(tex, verts, faces)
+        else:
+            verts, faces, verts_uvs, faces_uvs, tex = load_scene(args.obj_path, args.size, args.resize_texture, self.device)
+            self.content_mesh = _u.build_mesh(verts_uvs, faces_uvs, tex, verts, faces)
         self.original_verts = verts
-        self.content_mesh = _u.build_mesh(verts_uvs, faces_uvs, tex, verts, faces)
 
         cams = FoVPerspectiveCameras(device=self.device)
         supersample = getattr(args, "supersample", 1)
@@ -297,7 +355,7 @@ class Run:
             self.opt = _u.setup_optimizations(args.optimization_target, self.content_mesh, lr, texture_pyramid_levels=levels)
         self.pyramid = self.opt.get('texture_pyramid')      # None: the texture is the plain leaf opt['texture_map']
         if args.verts_lr is not None and args.optimization_target == 'both':
-            texture_leaf = self.pyramid.params if self.pyramid is not None else self.opt['texture_map']
+            texture_leaf = self.pyramid.params if self.pyramid is not None else self.opt[self.texture_key]
             self.opt['optimizer'] = st3d_optim.Adam([{"params": [self.opt['verts']], "lr": args.verts_lr},
                                                      {"params": [texture_leaf], "lr": lr}])
         self.optimizer = self.opt['optimizer']
@@ -314,6 +372,11 @@ class Run:
         self.writer = AsyncImageWriter()
 
     # ---- small helpers
+    @property
+    def texture_key(self):
+        """the entry of self.opt that holds the colour leaf: the map, or the (V,3) colours of a --texture_type vertex run"""
+        return 'verts_features' if self.vertex_colors else 'texture_map'
+
     @property
     def main(self):
         return self.rank == 0
@@ -333,6 +396,8 @@ class Run:
 
     def current_mesh(self):
         o = self.opt
+        if self.vertex_colors:
+            return self._utils.build_mesh_vertex(o['verts_features'], o['verts'], o['faces'])
         texture = self.pyramid.texture() if self.pyramid is not None else o['texture_map']      # synthesised every step
         return self._utils.build_mesh(o['verts_uvs'], o['faces_uvs'], texture, o['verts'], o['faces'])
 
@@ -375,12 +440,13 @@ class Run:
         if not self.main:
             return
         if self.pyramid is None:
-            texture = self.opt['texture_map']
+            texture = self.opt[self.texture_key]
         else:
             with torch.no_grad():
                 texture = self.pyramid.texture()
         blob = {"progress": int(progress), "optimization_target": self.args.optimization_target,
-                "texture_map": texture.detach().cpu(), "verts": self.opt['verts'].detach().cpu(),
+                "texture_type": "vertex" if self.vertex_colors else "uv",
+                self.texture_key: texture.detach().cpu(), "verts": self.opt['verts'].detach().cpu(),
                 "optimizer": self.optimizer.state_dict()}
         if self.pyramid is not None:        # the flat parameters are the state of record; texture_map is what they sum to
             blob["texture_pyramid"] = self.pyramid.params.detach().cpu()
@@ -393,6 +459,9 @@ class Run:
         blob = torch.load(path, map_location="cpu", weights_only=True)
         if blob["optimization_target"] != self.args.optimization_target:
             raise ValueError("checkpoint was written for optimization_target=%r" % blob["optimization_target"])
+        have_type, want_type = blob.get("texture_type", "uv"), "vertex" if self.vertex_colors else "uv"
+        if have_type != want_type:
+            raise ValueError("checkpoint was written with --texture_type %s, this run has %s" % (have_type, want_type))
         have = int(blob.get("texture_pyramid_levels", 1))
         want = self.pyramid.levels if self.pyramid is not None else 1
         if have != want:
@@ -401,7 +470,7 @@ class Run:
             if self.pyramid is not None:
                 self.pyramid.load_params(blob["texture_pyramid"].to(self.device))
             else:
-                self.opt['texture_map'].copy_(blob["texture_map"])
+                self.opt[self.texture_key].copy_(blob[self.texture_key])
             self.opt['verts'].copy_(blob["verts"])
         self.optimizer.load_state_dict(blob["optimizer"])
         self.progress = int(blob["progress"])
@@ -448,8 +517,12 @@ class Run:
             final = u.finalize_mesh(mesh)
             u.save_render(self.renderer, final, u.build_fixed_cameras(12), os.path.join(self.out_dir, "final_render"))
             tex = final.textures
-            st3d_io.save_obj(os.path.join(self.out_dir, "final.obj"), final.verts_packed(), final.faces_packed(),
-                             tex.verts_uvs_padded()[0], tex.faces_uvs_padded()[0], tex.maps_padded()[0])
+            if self.vertex_colors:          # v x y z r g b lines; no MTL, no PNG
+                st3d_io.save_obj(os.path.join(self.out_dir, "final.obj"), final.verts_packed(), final.faces_packed(),
+                                 verts_colors=tex.verts_features_packed())
+            else:
+                st3d_io.save_obj(os.path.join(self.out_dir, "final.obj"), final.verts_packed(), final.faces_packed(),
+                                 tex.verts_uvs_padded()[0], tex.faces_uvs_padded()[0], tex.maps_padded()[0])
         if self.world > 1:
             torch.distributed.barrier()
             torch.distributed.destroy_process_group()

@@ -135,9 +135,28 @@ def synthesize_uvs(verts):
     return torch.stack([u, w], dim=1).to(torch.float32)
 
 
-def save_obj(path, verts, faces, verts_uvs=None, faces_uvs=None, texture_map=None, decimal_places=6):
+def load_vertex_colors(path):
+    """The per-vertex colours of an OBJ written with ``v x y z r g b`` lines (``save_obj(verts_colors=...)``, MeshLab's
+    convention) -> (V,3) float32, or None when its ``v`` lines carry three numbers.  (``load_obj`` does not read them.)"""
+    cols, plain = [], False
+    with open(path, "r") as fh:
+        for line in fh:
+            tok = line.split("#", 1)[0].split()
+            if not tok or tok[0] != "v":
+                continue
+            if len(tok) >= 7:
+                cols.append((float(tok[4]), float(tok[5]), float(tok[6])))
+            else:
+                plain = True
+    if plain or not cols:
+        return None
+    return torch.tensor(cols, dtype=torch.float32)
+
+
+def save_obj(path, verts, faces, verts_uvs=None, faces_uvs=None, texture_map=None, decimal_places=6, verts_colors=None):
     """Writes ``<path>`` (+ ``.mtl`` + ``.png`` next to it when a texture is given), the
-    artefact set of ``IO().save_mesh(final_mesh, .../final.obj)`` (first_approach.py:225)."""
+    artefact set of ``IO().save_mesh(final_mesh, .../final.obj)`` (first_approach.py:225).
+    verts_colors (V,3): ``v x y z r g b`` lines with the colours clamped to [0,1] and the same decimal places."""
     from PIL import Image
     base, _ = os.path.splitext(path)
     stem = os.path.basename(base)
@@ -148,6 +167,11 @@ def save_obj(path, verts, faces, verts_uvs=None, faces_uvs=None, texture_map=Non
         if has_tex:
             f.write(f"\nmtllib {stem}.mtl\nusemtl mesh\n\n")
         fmt = f"%.{decimal_places}f"
+        if verts_colors is not None:
+            cols = verts_colors.detach().cpu().reshape(-1, 3).clamp(0, 1).numpy()
+            if cols.shape[0] != verts.shape[0]:
+                raise ValueError(f"verts_colors holds {cols.shape[0]} colours for {verts.shape[0]} vertices")
+            verts = np.concatenate([verts, cols], axis=1)
         for v in verts:
             f.write("v " + " ".join(fmt % x for x in v) + "\n")
         if has_tex:

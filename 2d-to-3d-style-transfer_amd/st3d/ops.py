@@ -170,6 +170,59 @@ def shade_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, grad_texture=No
     return out if len(out) > 1 else out[0]
 
 
+# ---- per-vertex colours (csrc/vcolor.hip): TexturesVertex on the hard settings, unlit
+def _vc_check(p2f, faces_i32, colours):
+    """the shapes the kernels index with: colours (V,3), faces (F,3); the CALLER guarantees faces < V (Meshes.faces_i32)"""
+    if colours.dim() != 2 or colours.shape[1] != 3 or colours.shape[0] < 1:
+        raise ValueError(f"vertex colours must be (V, 3), got {tuple(colours.shape)}")
+    if faces_i32.dim() != 2 or faces_i32.shape[1] != 3 or faces_i32.shape[0] < 1:
+        raise ValueError(f"faces must be (F, 3), got {tuple(faces_i32.shape)}")
+    if p2f.dim() != 3 or p2f.shape[1] != p2f.shape[2]:
+        raise ValueError(f"pix_to_face must be (B, S, S), got {tuple(p2f.shape)}")
+
+
+def shade_vc_fwd(frag, faces_i32, colours):
+    """frag, faces (F,3) int32, colours (V,3) -> rgb (B,3,S,S), mask (B,1,S,S)"""
+    p2f, zbuf, bary, dists = frag
+    _vc_check(p2f, faces_i32, colours)
+    B, S, _ = p2f.shape
+    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
+    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
+    call("st3d_shade_vc_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(faces_i32, I32),
+         dptr(colours, F32), B, S, faces_i32.shape[0], colours.shape[0], dptr(rgb), dptr(mask), stream_ptr())
+    return rgb, mask
+
+
+def shade_vc_bwd(grad_rgb, frag, faces_i32, colours, grad_colours=None, want_colours=True, want_bary=False):
+    """-> grad_colours (V,3) (accumulated into `grad_colours` when given) [, grad_bary (B,S,S,3)]; want_colours=False
+    (the vertices alone are optimised): grad_bary alone, nothing is scattered.  The scatter follows is_deterministic()."""
+    p2f, zbuf, bary, dists = frag
+    _vc_check(p2f, faces_i32, colours)
+    B, S, _ = p2f.shape
+    V, F = colours.shape[0], faces_i32.shape[0]
+    if tuple(grad_rgb.shape) != (B, 3, S, S):
+        raise ValueError(f"grad_rgb must be {(B, 3, S, S)}, got {tuple(grad_rgb.shape)}")
+    if not (want_colours or want_bary):
+        raise ValueError("shade_vc_bwd: nothing asked for (want_colours and want_bary are both False)")
+    if not want_colours:
+        grad_colours = None
+    elif grad_colours is None:
+        grad_colours = torch.zeros((V, 3), dtype=F32, device=p2f.device)
+    gbary = torch.empty((B, S, S, 3), dtype=F32, device=p2f.device) if want_bary else None
+    grad_rgb = grad_rgb.contiguous()
+    head = (dptr(grad_rgb, F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(faces_i32, I32),
+            dptr(colours, F32), B, S, F, V, dptr(grad_colours, F32), dptr(gbary))
+    if _DETERMINISTIC and grad_colours is not None:
+        nb = _lib.load().st3d_shade_vc_bwd_det_workspace_bytes(V)
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=p2f.device)
+        call("st3d_shade_vc_bwd_det", *head, dptr(ws), nb, stream_ptr())
+    else:
+        call("st3d_shade_vc_bwd", *head, stream_ptr())
+    if want_colours and want_bary:
+        return grad_colours, gbary
+    return grad_colours if want_colours else gbary
+
+
 # ---- supersampling (csrc/shade.hip): fragments at side a * S, images and their gradients at side S
 MAX_RASTER_SIDE = 4096
 SUPERSAMPLE_MAX = 4

@@ -25,6 +25,9 @@ gradient flows to lights, materials or cameras (a parameter with requires_grad r
 Silhouettes: SoftSilhouetteShader (sigmoid_alpha_blend: alpha = 1 - prod_k (1 - sigmoid(-dists_k / sigma))) renders alpha
 alone, without a texture, and alpha -- its own and SoftPhongShader's under soft settings -- is differentiable in the
 vertices through the signed edge distance (csrc/silhouette.hip); losses.compute_silhouette_loss is the fused loss on it.
+
+Per-vertex colours: a mesh whose textures are a TexturesVertex renders on csrc/vcolor.hip (hard settings, unlit): the colour
+is the barycentric interpolation of the three vertex colours of the fragment's face, differentiable in colours and vertices.
 """
 import math
 import os
@@ -93,6 +96,46 @@ class TexturesUV:
         return TexturesUV(self._maps.detach(), self._faces_uvs, self._verts_uvs.detach())
 
 
+class TexturesVertex:
+    """PyTorch3D ``TexturesVertex(verts_features=...)``: one RGB triple per vertex, interpolated with each fragment's
+    barycentrics (csrc/vcolor.hip).  verts_features: (V,3), (1,V,3) or a one-element list of (V,3); indexed by
+    the mesh's own faces."""
+
+    def __init__(self, verts_features):
+        if isinstance(verts_features, (list, tuple)):
+            if len(verts_features) != 1:
+                raise ValueError("one mesh per batch: verts_features takes a one-element list")
+            verts_features = verts_features[0]
+        if verts_features.dim() == 3:
+            if verts_features.shape[0] != 1:
+                raise ValueError(f"one mesh per batch: verts_features must be (V, 3) or (1, V, 3), got "
+                                 f"{tuple(verts_features.shape)}")
+            self._padded, self._packed = verts_features, None
+        elif verts_features.dim() == 2:
+            self._padded, self._packed = None, verts_features
+        else:
+            raise ValueError(f"verts_features must be (V, 3) or (1, V, 3), got {tuple(verts_features.shape)}")
+        if verts_features.shape[-1] != 3:
+            raise ValueError(f"verts_features holds RGB triples: the last dimension must be 3, got "
+                             f"{tuple(verts_features.shape)}")
+
+    def verts_features_padded(self):
+        if self._padded is None:
+            self._padded = self._packed[None]
+        return self._padded
+
+    def verts_features_packed(self):
+        if self._packed is None:
+            self._packed = self._padded[0]
+        return self._packed
+
+    def clone(self):
+        return TexturesVertex(self.verts_features_packed().clone())
+
+    def detach(self):
+        return TexturesVertex(self.verts_features_packed().detach())
+
+
 class Meshes:
     """utils.py:209 ``Meshes(verts=[verts], faces=[faces], textures=textures)`` (one mesh)."""
 
@@ -112,6 +155,8 @@ class Meshes:
         self._faces = faces[0] if faces.dim() == 3 else faces
         self.textures = textures
         self._faces_i32 = None
+        if isinstance(textures, TexturesVertex):
+            vertex_colours_of(self)         # one colour per vertex, or a ValueError now rather than at the first render
 
     def verts_packed(self):
         if self._verts is None:
@@ -145,6 +190,17 @@ class Meshes:
     @property
     def device(self):
         return self.verts_packed().device
+
+
+def vertex_colours_of(meshes):
+    """The (V,3) colours of a mesh whose textures are a TexturesVertex, checked against its vertex count: the kernels index
+    the colours with the mesh's own faces, so a shorter array would be read out of bounds on the GPU (ValueError)."""
+    col = meshes.textures.verts_features_packed()
+    V = meshes.verts_packed().shape[0]
+    if col.shape[0] != V:
+        raise ValueError(f"TexturesVertex holds {col.shape[0]} colours for a mesh of {V} vertices: verts_features must have "
+                         "one row per vertex (it is indexed by the mesh's faces)")
+    return col
 
 
 # ------------------------------------------------------------------------ cameras (SURVEY.md A.1)
@@ -244,6 +300,24 @@ MIP_REFUSALS = {
 MIP_NEAR_PLANE_MESSAGE = ("the mesh reaches the near clipping plane (z < znear / 2) under texture_mip_levels != 1: the clipping "
                           "kernels have no mip-mapped sampling, and the render is not silently rerouted to unfiltered sampling "
                           "-- render with texture_mip_levels=1 or keep the mesh in front of the plane")
+
+
+# what a render of a TexturesVertex mesh refuses, by limitation (NotImplementedError, before any launch)
+VERTEX_COLOUR_REFUSALS = {
+    "lights": "TexturesVertex is implemented for unlit renders only (lights=None or white AmbientLights with default "
+              "Materials): the lit kernels have no vertex-colour path",
+    "supersample": "TexturesVertex cannot be combined with supersample > 1: the supersampled kernels have no vertex-colour "
+                   "path",
+    "mip": "TexturesVertex cannot be combined with texture_mip_levels != 1: there is no texture map to filter",
+    "soft": "TexturesVertex is implemented for the hard settings only (faces_per_pixel = 1, blur_radius = 0, default "
+            "clipping, culling and BlendParams): the general soft kernels have no vertex-colour path",
+    "silhouette": "SilhouetteRasterizationSettings render on the silhouette rasteriser, which produces alpha only: the "
+                  "colours of a TexturesVertex mesh need RasterizationSettings and a SoftPhongShader (a "
+                  "SoftSilhouetteShader renders the same mesh's alpha)",
+}
+VERTEX_COLOUR_NEAR_PLANE_MESSAGE = ("the mesh reaches the near clipping plane (z < znear / 2) and its textures are a "
+                                    "TexturesVertex: the clipping kernels have no vertex-colour path, and the render is not "
+                                    "silently rerouted -- keep the mesh in front of the plane")
 
 
 class RasterizationSettings:
@@ -770,6 +844,43 @@ class _MipRenderFn(torch.autograd.Function):
             return (gverts, gtex) + (None,) * 8
 
 
+class _VertexColourRenderFn(torch.autograd.Function):
+    """(verts, colours (V,3)) -> (rgb (B,3,S,S), mask (B,1,S,S)) for a TexturesVertex mesh: project, raster, shade_vc_fwd.
+    Backward: the colour scatter and, when the vertices need a gradient, d/d(bary) -> the unchanged raster / projection
+    backward.  With the vertices alone under optimisation nothing is scattered."""
+
+    @staticmethod
+    def forward(ctx, verts, colours, faces_i32, R, T, S):
+        v = verts.detach().to(torch.float32).contiguous()
+        col = colours.detach().to(torch.float32).reshape(-1, 3).contiguous()
+        ndc = ops.project_verts(v, R, T)
+        frag = ops.raster_fwd(ndc, faces_i32, S)
+        rgb, mask = ops.shade_vc_fwd(frag, faces_i32, col)
+        ctx.frag, ctx.col = frag, col
+        ctx.col_shape = colours.shape
+        ctx.geom = (v, ndc, faces_i32, R, T)
+        ctx.verts_shape = verts.shape
+        ctx.mark_non_differentiable(mask)
+        return rgb, mask
+
+    @staticmethod
+    def backward(ctx, grad_rgb, _grad_mask):
+        with ops.trace("render_backward"):
+            need_v, need_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            gcol = gverts = None
+            if need_v or need_c:
+                v, ndc, faces_i32, R, T = ctx.geom
+                res = ops.shade_vc_bwd(grad_rgb.to(torch.float32), ctx.frag, faces_i32, ctx.col, want_colours=need_c,
+                                       want_bary=need_v)
+                gc, gbary = res if (need_v and need_c) else ((res, None) if need_c else (None, res))
+                if need_c:
+                    gcol = gc.reshape(ctx.col_shape)
+                if need_v:
+                    gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
+                    gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
+            return gverts, gcol, None, None, None, None
+
+
 class _SSRenderFn(torch.autograd.Function):
     """_RenderFn supersampled: fragments at side a * S on the same rasteriser, (rgb (B,3,S,S), coverage (B,1,S,S)) from the
     fused kernels (st3d.ops.shade_ss_*); the backward hands the S-sized gradient to them and the a * S barycentric
@@ -1022,6 +1133,8 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
     tex = meshes.textures
     dev = meshes.device
     rs, bp = raster_settings, blend_params
+    if isinstance(tex, TexturesVertex):         # decided on the texture's type before any path is chosen
+        return _render_views_vertex(meshes, R, T, int(image_size), rs, bp, lights, materials)
     if isinstance(rs, SilhouetteRasterizationSettings):
         raise NotImplementedError("SilhouetteRasterizationSettings render on the silhouette rasteriser, which produces alpha "
                                   "only: they need a SoftSilhouetteShader")
@@ -1065,6 +1178,33 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
         # (alpha of a K = 1 / blur 0 blend is in [0.5, 1) on covered pixels; the reference thresholds it, utils.py:72)
         alpha = (alpha.detach() > 0).to(torch.float32)
     return rgb, alpha
+
+
+def _render_views_vertex(meshes, R, T, S, rs, bp, lights, materials):
+    """_render_views for a mesh whose textures are a TexturesVertex -> (rgb, 0/1 mask) from csrc/vcolor.hip.  Everything
+    the kernels do not cover is refused before any launch; a batch at the near plane is an error whatever ST3D_NEAR_PLANE
+    says, never a silent reroute (the clipping kernels have no vertex-colour path)."""
+    if isinstance(rs, SilhouetteRasterizationSettings):
+        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["silhouette"])
+    dev = meshes.device
+    if lighting_of(lights, materials, dev) is not None:
+        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["lights"])
+    if getattr(rs, "supersample", 1) > 1:
+        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["supersample"])
+    if getattr(rs, "texture_mip_levels", 1) != 1:
+        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["mip"])
+    if not uses_hard_path(rs, bp):
+        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["soft"])
+    colours = vertex_colours_of(meshes)
+    faces_i32 = meshes.faces_i32()              # range-checked against the vertex count (= the colour count)
+    R, T = R.to(dev), T.to(dev)
+    if ops.near_plane_triggered() or reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT):
+        raise RuntimeError(VERTEX_COLOUR_NEAR_PLANE_MESSAGE)
+    rgb, mask = _VertexColourRenderFn.apply(meshes.verts_packed(), colours, faces_i32, R, T, S)
+    if rgb.requires_grad:
+        tag_need(rgb, rgb.grad_fn.frag[0])
+    tag_flat(rgb, (1.0, 1.0, 1.0))
+    return rgb, mask
 
 
 def _render_views_mip(meshes, R, T, S, rs, bp, lighting):

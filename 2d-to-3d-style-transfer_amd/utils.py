@@ -20,7 +20,8 @@ from st3d import ops as _ops
 from st3d import optim as _st3d_optim
 from st3d import render as _render
 from st3d import vgg as _vgg
-from st3d.render import FoVPerspectiveCameras, Meshes, RotateAxisAngle, TexturesUV, look_at_view_transform  # noqa: F401
+from st3d.render import (FoVPerspectiveCameras, Meshes, RotateAxisAngle, TexturesUV, TexturesVertex,  # noqa: F401
+                         look_at_view_transform)
 from style_transfer import *  # noqa: F401,F403  (star re-export relied on by the CLIs, reference utils.py:12)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -109,6 +110,9 @@ def finalize_tensor(tensor):
 def finalize_mesh(mesh):
     """Same geometry and UVs, texture clamped to displayable range and detached (:95-104)."""
     tex = mesh.textures
+    if isinstance(tex, TexturesVertex):
+        return Meshes(verts=mesh.verts_padded(), faces=mesh.faces_padded(),
+                      textures=TexturesVertex(finalize_tensor(tex.verts_features_packed())))
     clamped = TexturesUV(maps=finalize_tensor(tex.maps_padded()), faces_uvs=tex.faces_uvs_padded(),
                          verts_uvs=tex.verts_uvs_padded())
     return Meshes(verts=mesh.verts_padded(), faces=mesh.faces_padded(), textures=clamped)
@@ -118,6 +122,11 @@ def build_mesh(verts_uvs, faces_uvs, texture_map, verts, faces):
     """Fresh containers around the (possibly leaf) tensors, rebuilt every step like the reference (:207-210)."""
     return Meshes(verts=[verts], faces=[faces],
                   textures=TexturesUV(maps=texture_map, faces_uvs=faces_uvs, verts_uvs=verts_uvs))
+
+
+def build_mesh_vertex(verts_features, verts, faces):
+    """build_mesh for per-vertex colours: verts_features (V,3) or (1,V,3), one RGB triple per vertex (TexturesVertex)."""
+    return Meshes(verts=[verts], faces=[faces], textures=TexturesVertex(verts_features))
 
 
 # ------------------------------------------------------------------------------------------ cameras
@@ -147,6 +156,7 @@ def build_random_cameras(n_views, dist=2.10, generator=None):
 
 # ------------------------------------------------------------------------------------------ optimiser
 _LEAVES = {'texture': ('texture_map',), 'mesh': ('verts',), 'both': ('verts', 'texture_map')}
+_VERTEX_LEAVES = {'texture': ('verts_features',), 'mesh': ('verts',), 'both': ('verts', 'verts_features')}
 
 
 def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1):
@@ -155,7 +165,23 @@ def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1)
 
     texture_pyramid_levels != 1 (0 = auto, L >= 2; targets 'texture' / 'both'): the texture leaf is the flat parameter
     tensor of an st3d.texpyr.TexturePyramid, returned under 'texture_pyramid' (for 'both' Adam sees the vertices first,
-    then the pyramid).  The dict then has NO 'texture_map' entry -- the map is pyramid.texture(), rebuilt every step."""
+    then the pyramid).  The dict then has NO 'texture_map' entry -- the map is pyramid.texture(), rebuilt every step.
+
+    A mesh whose textures are a TexturesVertex: 'verts_features' (V,3) takes the place of 'texture_map' / 'verts_uvs' /
+    'faces_uvs'; leaves are 'texture' -> the colours, 'mesh' -> the vertices, 'both' -> the vertices, then the colours.
+    There is no map to build a pyramid of: texture_pyramid_levels != 1 is a ValueError."""
+    if isinstance(mesh.textures, TexturesVertex):
+        if optimization_target not in _VERTEX_LEAVES:
+            raise UnboundLocalError("local variable 'optimizer' referenced before assignment "
+                                    f"(optimization_target={optimization_target!r})")
+        if texture_pyramid_levels != 1:
+            raise ValueError("texture_pyramid_levels != 1 needs a texture map: a TexturesVertex mesh has per-vertex colours "
+                             "and no map to build a pyramid of")
+        work = mesh.clone()
+        parts = {'verts_features': work.textures.verts_features_packed(), 'verts': work.verts_packed(),
+                 'faces': work.faces_packed()}
+        leaves = [parts[name].requires_grad_(True) for name in _VERTEX_LEAVES[optimization_target]]
+        return dict(parts, optimizable_mesh=work, optimizer=_st3d_optim.Adam(leaves, lr=lr))
     work = mesh.clone()
     parts = {
         'texture_map': work.textures.maps_padded(),

@@ -701,6 +701,34 @@ int st3d_shade_mip_bwd(const float *grad_rgb, const int32_t *pix_to_face, const 
                        const float *lod, int B, int S, int T, int L, int F, int VT, float *grad_pyramid, float *grad_texture,
                        float *grad_uv, float *grad_bary, void *workspace, size_t workspace_bytes, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ per-vertex colours (csrc/vcolor.hip):
+ * PyTorch3D TexturesVertex on the hard settings (K = 1, blur 0, default BlendParams), unlit.  verts_colors (V,3) fp32 is
+ * indexed by the mesh's own faces (F,3); there is no second index array.  Indices are NOT checked on the device: the
+ * caller guarantees 0 <= faces < V and pix_to_face < F.
+ *   shade_vc_fwd  replaces TexturesVertex.sample_textures (interpolate_face_attributes) + the ambient SoftPhongShader +
+ *            softmax_rgb_blend: t_c = b0 C[v0][c] + b1 C[v1][c] + b2 C[v2][c] (left to right, uncontracted),
+ *            rgb_c = (wnum t_c + delta) / denom with the blend and the mask of the UV forward; pixels without a face are
+ *            white with mask 0.  rgb (B,3,S,S), mask (B,1,S,S).
+ *   shade_vc_bwd  replaces the autograd backward of interpolate_face_attributes: with gk_c = grad_rgb_c wnum / denom,
+ *            grad_colors[v_i][c] += b_i gk_c (float atomics; ACCUMULATED into grad_colors (V,3)) and grad_bary (B,S,S,3)
+ *            = sum_c gk_c C[v_i][c], 0 on uncovered pixels, the input of st3d_raster_bwd.  Either output may be NULL, not
+ *            both; without grad_colors nothing is scattered.
+ *   shade_vc_bwd_det  the same with the scatter in 64-bit fixed point (bitwise reproducible; a NaN / Inf in grad_rgb,
+ *            on a covered pixel or not, makes every element of grad_colors NaN; finite values on uncovered pixels change no
+ *            bit).  grad_colors is required; workspace of st3d_shade_vc_bwd_det_workspace_bytes(V) bytes, 16-byte aligned.
+ * S <= 4096.  Nothing is allocated. */
+int st3d_shade_vc_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                      const int32_t *faces, const float *verts_colors, int B, int S, int F, int V, float *rgb, float *mask,
+                      st3d_stream_t stream);
+int st3d_shade_vc_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                      const float *dists, const int32_t *faces, const float *verts_colors, int B, int S, int F, int V,
+                      float *grad_colors, float *grad_bary, st3d_stream_t stream);
+size_t st3d_shade_vc_bwd_det_workspace_bytes(int V);
+int st3d_shade_vc_bwd_det(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                          const float *dists, const int32_t *faces, const float *verts_colors, int B, int S, int F, int V,
+                          float *grad_colors, float *grad_bary, void *workspace, size_t workspace_bytes,
+                          st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ optimiser:
  * torch.optim.Adam defaults (utils.py:185-195, style_transfer.py:57) */
 int st3d_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,

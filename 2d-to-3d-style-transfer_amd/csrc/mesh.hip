@@ -227,3 +227,264 @@ extern "C" int st3d_mesh_reg(const float *verts, const float *target_verts, int 
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// st3d_mesh_reg_ex: the same four terms with PyTorch3D's cotangent Laplacian ('cot' / 'cotcurv') and an edge target
+// length t > 0.  At method 0 / t = 0 every launch above is issued unchanged.  The cotangent weights are
+// constants of the backward; they change with the vertices, so every call rebuilds them:
+//   cot_face_kernel    per face: the three cotangents and the clamped area
+//   cot_vertex_kernel  per vertex i: every adjacency slot's weight L_ij (its edge's incident (face, corner) entries summed
+//                      in list order -- both ends of an edge walk the same list, so L is symmetric to the bit), Lsum_i,
+//                      sum_j L_ij v_j, Asum_i over the vertex's faces, the residual, |r_i| and what the gradient gathers
+//   cot_bwd_kernel     per vertex k: sum_i L_ki q_i - s_k over its adjacency row
+// All sums are gathers over static host-built lists in list order: no float atomics, two runs are bit-equal.  The new
+// kernels compute in fp64 from the fp32 vertices and keep their intermediates in fp64 (a few hundred KB at most, the
+// work is latency-bound): each output is rounded to fp32 once, so the result does not depend on how well conditioned
+// Heron's formula or B^2 + C^2 - A^2 is on a needle triangle.
+namespace {
+
+struct D3 { double x, y, z; };
+__device__ __forceinline__ D3 ldd(const float *p, int i) { return {(double)p[3 * i], (double)p[3 * i + 1], (double)p[3 * i + 2]}; }
+__device__ __forceinline__ D3 ldd(const double *p, int i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
+__device__ __forceinline__ D3 sub(D3 a, D3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ D3 add(D3 a, D3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+__device__ __forceinline__ D3 mul(D3 a, double s) { return {a.x * s, a.y * s, a.z * s}; }
+__device__ __forceinline__ double dot(D3 a, D3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+__device__ __forceinline__ D3 cross(D3 a, D3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+__device__ __forceinline__ void std3(double *p, int i, D3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
+
+__device__ __forceinline__ void block_partial_d(double v, double *partials) {
+    __shared__ double s[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// fc[4 f + c] = cot of corner c, fc[4 f + 3] = area.  area^2 = s(s-A)(s-B)(s-C) = |(v1-v0) x (v2-v0)|^2 / 4 inside the same
+// 1e-12 clamp, and B^2 + C^2 - A^2 = 2 (v1-v0).(v2-v0), so cot_0 = (v1-v0).(v2-v0) / (2 area), likewise at v1 and v2.
+// A NaN passes the clamp (nothing is clamped away).
+__global__ __launch_bounds__(256) void cot_face_kernel(const float *__restrict__ v, const int32_t *__restrict__ faces, int F,
+                                                       double *__restrict__ fc) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= F) return;
+    const D3 p0 = ldd(v, faces[3 * f]), p1 = ldd(v, faces[3 * f + 1]), p2 = ldd(v, faces[3 * f + 2]);
+    const D3 e01 = sub(p1, p0), e02 = sub(p2, p0), e12 = sub(p2, p1);
+    const D3 n = cross(e01, e02);
+    const double a2 = 0.25 * dot(n, n);
+    const double area = sqrt(a2 <= 1e-12 ? 1e-12 : a2);
+    const double h = 0.5 / area;
+    fc[4 * f] = dot(e01, e02) * h;
+    fc[4 * f + 1] = -dot(e01, e12) * h;
+    fc[4 * f + 2] = dot(e02, e12) * h;
+    fc[4 * f + 3] = area;
+}
+
+// method 1 (cot):     r_i = (sum_j L_ij v_j) nw_i - v_i,  nw_i = 1 / Lsum_i where Lsum_i > 0, else Lsum_i itself;
+//                     q_i = nw_i u_i, s_i = u_i
+// method 2 (cotcurv): r_i = (sum_j L_ij v_j - Lsum_i v_i) c_i,  c_i = 0.25 / Asum_i (0 where Asum_i is not > 0);
+//                     q_i = c_i u_i, s_i = Lsum_i c_i u_i
+// u_i = r_i / |r_i| (0 at |r_i| = 0).  edge_ref / inc_ref entries are face * 3 + corner.
+__global__ __launch_bounds__(256) void cot_vertex_kernel(const float *__restrict__ v, const int32_t *__restrict__ off,
+                                                         const int32_t *__restrict__ nbr, const int32_t *__restrict__ nbr_edge,
+                                                         const int32_t *__restrict__ edge_off, const int32_t *__restrict__ edge_ref,
+                                                         const int32_t *__restrict__ inc_off, const int32_t *__restrict__ inc_ref,
+                                                         const double *__restrict__ fc, int V, int method,
+                                                         double *__restrict__ wslot, double *__restrict__ q, double *__restrict__ sv,
+                                                         double *__restrict__ partials) {
+    double acc = 0.0;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < V; i += gridDim.x * blockDim.x) {
+        const D3 vi = ldd(v, i);
+        double lsum = 0.0;
+        D3 d = {0.0, 0.0, 0.0};          // sum_j L_ij (v_j - v_i): a neighbour AT v_i contributes exactly 0, whatever its weight
+        for (int k = off[i]; k < off[i + 1]; ++k) {
+            const int e = nbr_edge[k];
+            double w = 0.0;
+            for (int r = edge_off[e]; r < edge_off[e + 1]; ++r) {
+                const int ref = edge_ref[r];
+                w += fc[ref + ref / 3];          // 4 * face + corner
+            }
+            wslot[k] = w;
+            lsum += w;
+            d = add(d, mul(sub(ldd(v, nbr[k]), vi), w));
+        }
+        D3 r;
+        double cq, cs;
+        if (method == 1) {
+            // (sum_j L_ij v_j) / Lsum_i - v_i = d / Lsum_i where Lsum_i > 0; else nw_i = Lsum_i and sum_j L_ij v_j = d + Lsum_i v_i
+            const double nw = lsum > 0.0 ? 1.0 / lsum : lsum;
+            r = lsum > 0.0 ? mul(d, nw) : sub(mul(add(d, mul(vi, lsum)), nw), vi);
+            cq = nw;
+            cs = 1.0;
+        } else {
+            double asum = 0.0;
+            for (int k = inc_off[i]; k < inc_off[i + 1]; ++k) asum += fc[4 * (inc_ref[k] / 3) + 3];
+            const double c = asum > 0.0 ? 0.25 / asum : 0.0;
+            r = mul(d, c);
+            cq = c;
+            cs = lsum * c;
+        }
+        const double n = sqrt(dot(r, r));
+        acc += n;
+        const D3 u = n == 0.0 ? D3{0.0, 0.0, 0.0} : mul(r, 1.0 / n);
+        std3(q, i, mul(u, cq));
+        std3(sv, i, mul(u, cs));
+    }
+    block_partial_d(acc, partials);
+}
+
+// grad_k += c ( sum_i L_ki q_i - s_k ), L_ki = the slot's weight (L is symmetric)
+__global__ __launch_bounds__(256) void cot_bwd_kernel(const double *__restrict__ q, const double *__restrict__ sv,
+                                                      const int32_t *__restrict__ off, const int32_t *__restrict__ nbr,
+                                                      const double *__restrict__ wslot, int V, double c, float *__restrict__ g) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= V) return;
+    D3 s = {0.0, 0.0, 0.0};
+    for (int t = off[k]; t < off[k + 1]; ++t) s = add(s, mul(ldd(q, nbr[t]), wslot[t]));
+    s = mul(sub(s, ldd(sv, k)), c);
+    g[3 * k] += (float)s.x; g[3 * k + 1] += (float)s.y; g[3 * k + 2] += (float)s.z;
+}
+
+// mean over edges of (|a - b| - t)^2
+__global__ __launch_bounds__(256) void edge_target_kernel(const float *__restrict__ v, const int32_t *__restrict__ edges, int E,
+                                                          double t, double *__restrict__ partials) {
+    double acc = 0.0;
+    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += gridDim.x * blockDim.x) {
+        const D3 d = sub(ldd(v, edges[2 * e]), ldd(v, edges[2 * e + 1]));
+        const double x = sqrt(dot(d, d)) - t;
+        acc += x * x;
+    }
+    block_partial_d(acc, partials);
+}
+
+// d(l - t)^2/da = 2 (l - t)(a - b)/l, the direction 0 at l = 0; a gather over the adjacency row like edge_bwd_kernel
+__global__ __launch_bounds__(256) void edge_target_bwd_kernel(const float *__restrict__ v, const int32_t *__restrict__ off,
+                                                              const int32_t *__restrict__ nbr, int V, double t, double gcoef,
+                                                              float *__restrict__ g) {
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= V) return;
+    const D3 vk = ldd(v, k);
+    D3 s = {0.0, 0.0, 0.0};
+    for (int j = off[k]; j < off[k + 1]; ++j) {
+        const D3 d = sub(vk, ldd(v, nbr[j]));
+        const double l = sqrt(dot(d, d));
+        if (l != 0.0) s = add(s, mul(d, (l - t) / l));
+    }
+    g[3 * k] += (float)(gcoef * s.x); g[3 * k + 1] += (float)(gcoef * s.y); g[3 * k + 2] += (float)(gcoef * s.z);
+}
+
+// mesh_finish_kernel with the edge (bit 1 of dmask) and / or Laplacian (bit 2) partials in fp64: dparts[(k - 1) * NPART + i]
+__global__ __launch_bounds__(256) void mesh_finish_ex_kernel(const float *__restrict__ partials, const double *__restrict__ dparts,
+                                                             int dmask, int n0, int n1, int n2, int n3, float s0, float s1,
+                                                             float s2, float s3, int E, int V, float w0, float w1, float w2,
+                                                             float w3, float *__restrict__ out) {
+    __shared__ double red[256];
+    const int cnt[4] = {n0, n1, n2, n3};
+    const float sc[4] = {s0, s1, s2, s3};
+    const int div[4] = {1, E, V, 1};
+    const float w[4] = {w0, w1, w2, w3};
+    double total = 0.0;
+    for (int k = 0; k < 4; ++k) {
+        const bool dbl = (dmask >> k) & 1;
+        double a = 0.0;
+        for (int i = threadIdx.x; i < cnt[k]; i += 256) a += dbl ? dparts[(k - 1) * NPART + i] : (double)partials[k * NPART + i];
+        red[threadIdx.x] = a;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) {
+            if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+            __syncthreads();
+        }
+        const double term = dbl ? red[0] / (double)div[k] : red[0] * (double)sc[k];      // an fp64 term is rounded once, at the store
+        if (threadIdx.x == 0) out[1 + k] = (float)term;
+        total += (double)w[k] * term;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = (float)total;
+}
+
+inline size_t even_up(size_t n) { return (n + 1) & ~(size_t)1; }
+
+}  // namespace
+
+extern "C" size_t st3d_mesh_reg_ex_scratch_floats(int V, int E, int F, int P) {
+    if (V <= 0 || E <= 0 || F < 0 || P < 0) return 0;
+    const size_t doubles = (size_t)2 * NPART + (size_t)4 * F + (size_t)2 * E + (size_t)6 * V;
+    return even_up(st3d_mesh_reg_scratch_floats(V, P)) + 2 * doubles;
+}
+
+extern "C" int st3d_mesh_reg_ex(const float *verts, const float *target_verts, int V, const int32_t *edges, int E,
+                                const int32_t *nbr_off, const int32_t *nbr_idx, const int32_t *pairs, int P,
+                                const int32_t *pair_off, const int32_t *pair_ref, const int32_t *faces, int F,
+                                const int32_t *nbr_edge, const int32_t *edge_off, const int32_t *edge_ref,
+                                const int32_t *inc_off, const int32_t *inc_ref, int laplacian_method, float edge_target_length,
+                                const float *weights, float *scratch, float *partials, float *loss_out, float *grad_verts,
+                                st3d_stream_t stream) {
+    ST3D_CHECK_ARG(verts && target_verts && edges && nbr_off && nbr_idx && weights && scratch && partials && loss_out);
+    ST3D_CHECK_ARG(V > 0 && E > 0 && P >= 0 && (P == 0 || (pairs && pair_off && pair_ref)));
+    ST3D_CHECK_ARG(laplacian_method >= 0 && laplacian_method <= 2);
+    ST3D_CHECK_ARG(edge_target_length >= 0.f && edge_target_length <= 3.0e38f);      // finite; a NaN fails the first
+    ST3D_CHECK_ARG(laplacian_method == 0 || (faces && F > 0 && nbr_edge && edge_off && edge_ref && inc_off && inc_ref));
+    ST3D_CHECK_ARG(((uintptr_t)scratch & 7) == 0);
+    hipStream_t s = st3d::as_stream(stream);
+    const float wv = weights[0], we = weights[1], wl = weights[2], wn = weights[3];
+    const bool wg = grad_verts != nullptr;
+    const bool cot = laplacian_method != 0, tgt = edge_target_length != 0.f;
+    const int g0 = grid_for(3 * V), g1 = grid_for(E), g2 = grid_for(V), g3 = P > 0 ? grid_for(P) : 0;
+    double *dparts = reinterpret_cast<double *>(scratch + even_up(st3d_mesh_reg_scratch_floats(V, P)));
+    double *fc = dparts + 2 * NPART, *wslot = fc + (size_t)4 * (cot ? F : 0), *q = wslot + (size_t)2 * E, *sv = q + (size_t)3 * V;
+    verts_mse_kernel<<<g0, 256, 0, s>>>(verts, target_verts, 3 * V, wg ? 2.0f * wv / (3.0f * V) : 0.f, grad_verts, partials);
+    ST3D_LAUNCH_CHECK();
+    if (!tgt) {
+        edge_kernel<<<g1, 256, 0, s>>>(verts, edges, E, partials + NPART);
+        ST3D_LAUNCH_CHECK();
+        if (wg && we != 0.f) {
+            edge_bwd_kernel<<<st3d::cdiv(V, 256), 256, 0, s>>>(verts, nbr_off, nbr_idx, V, 2.0f * we / (float)E, grad_verts);
+            ST3D_LAUNCH_CHECK();
+        }
+    } else {
+        edge_target_kernel<<<g1, 256, 0, s>>>(verts, edges, E, (double)edge_target_length, dparts);
+        ST3D_LAUNCH_CHECK();
+        if (wg && we != 0.f) {
+            edge_target_bwd_kernel<<<st3d::cdiv(V, 256), 256, 0, s>>>(verts, nbr_off, nbr_idx, V, (double)edge_target_length,
+                                                                      2.0 * (double)we / (double)E, grad_verts);
+            ST3D_LAUNCH_CHECK();
+        }
+    }
+    if (!cot) {
+        laplacian_fwd_kernel<<<g2, 256, 0, s>>>(verts, nbr_off, nbr_idx, V, scratch, partials + 2 * NPART);
+        ST3D_LAUNCH_CHECK();
+        if (wg && wl != 0.f) {
+            laplacian_bwd_kernel<<<st3d::cdiv(V, 256), 256, 0, s>>>(scratch, nbr_off, nbr_idx, V, wl / (float)V, grad_verts);
+            ST3D_LAUNCH_CHECK();
+        }
+    } else {
+        cot_face_kernel<<<st3d::cdiv(F, 256), 256, 0, s>>>(verts, faces, F, fc);
+        ST3D_LAUNCH_CHECK();
+        cot_vertex_kernel<<<g2, 256, 0, s>>>(verts, nbr_off, nbr_idx, nbr_edge, edge_off, edge_ref, inc_off, inc_ref, fc, V,
+                                            laplacian_method, wslot, q, sv, dparts + NPART);
+        ST3D_LAUNCH_CHECK();
+        if (wg && wl != 0.f) {
+            cot_bwd_kernel<<<st3d::cdiv(V, 256), 256, 0, s>>>(q, sv, nbr_off, nbr_idx, wslot, V, (double)wl / (double)V, grad_verts);
+            ST3D_LAUNCH_CHECK();
+        }
+    }
+    if (P > 0) {
+        float *pg = scratch + (size_t)3 * V;        // (P, 4, 3) per-pair gradients
+        const bool ng = wg && wn != 0.f;
+        normal_kernel<<<g3, 256, 0, s>>>(verts, pairs, P, ng ? wn / (float)P : 0.f, pg, partials + 3 * NPART);
+        ST3D_LAUNCH_CHECK();
+        if (ng) {
+            normal_gather_kernel<<<st3d::cdiv(V, 256), 256, 0, s>>>(pg, pair_off, pair_ref, V, grad_verts);
+            ST3D_LAUNCH_CHECK();
+        }
+    }
+    const float s0 = 1.0f / (3.0f * V), s1 = 1.0f / (float)E, s2 = 1.0f / (float)V, s3 = P > 0 ? 1.0f / (float)P : 0.f;
+    if (!cot && !tgt)
+        mesh_finish_kernel<<<1, 256, 0, s>>>(partials, g0, g1, g2, g3, s0, s1, s2, s3, wv, we, wl, wn, loss_out);
+    else
+        mesh_finish_ex_kernel<<<1, 256, 0, s>>>(partials, dparts, (tgt ? 2 : 0) | (cot ? 4 : 0), g0, g1, g2, g3, s0, s1, s2, s3,
+                                               E, V, wv, we, wl, wn, loss_out);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}

@@ -25,6 +25,17 @@ _TARGETS = ['texture', 'mesh', 'both']
 _LIGHTS = ['ambient', 'point', 'directional', 'headlight']
 _STYLE_MASKS = ['none', 'object']
 _TEXTURE_TYPES = ['uv', 'vertex']
+_LAPLACIANS = ['uniform', 'cot', 'cotcurv']
+
+
+def edge_target_length(text):
+    """--edge_target_length: a length, or the literal 'mean' (the loaded mesh's mean edge length, resolved by Run)"""
+    if text == 'mean':
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a number or 'mean', got {text!r}")
 
 # name, type, default and choices are the reference's (first_approach.py:23-45, second_approach.py:23-42); note
 # `type=bool` flags keep argparse's "any non-empty string is True" behaviour of the reference.
@@ -79,6 +90,13 @@ SHARED_FLAGS = [
          "meshes without UVs; started from the map sampled at each vertex's UV when the OBJ has one, else from seeded grey "
          "noise.  White ambient light, --supersample 1, --texture_mip_levels 1, --texture_pyramid_levels 1, no --tv_weight",
          _TEXTURE_TYPES),
+    Flag("laplacian_method", str, 'uniform', "Laplacian of the smoothing regulariser (PyTorch3D's mesh_laplacian_smoothing "
+         "methods): 'uniform' = the plain mean of the neighbours (the reference's), 'cot' = cotangent weights, zero on a flat "
+         "patch whatever its triangulation, 'cotcurv' = cotangent weights over the vertex's area (mean curvature).  "
+         "--optimization_target mesh / both only", _LAPLACIANS),
+    Flag("edge_target_length", edge_target_length, 0.0, "length the edge regulariser pulls every edge to: 0 = the reference's "
+         "(edges can only shrink), 'mean' = the mean edge length of the loaded mesh, or a length >= 0.  "
+         "--optimization_target mesh / both only"),
     Flag("texture_lod_bias", float, 0.0, "added to every pixel's level of detail before it is clamped to the chain "
          "(--texture_mip_levels): negative = sharper, positive = blurrier"),
 ]
@@ -96,6 +114,12 @@ def check_args(args):
     if getattr(args, "silhouette_weight", 0.0) and getattr(args, "optimization_target", None) == 'texture':
         return ("--silhouette_weight needs --optimization_target mesh or both: with 'texture' the vertices do not move and "
                 "the term would be a constant")
+    method, target = getattr(args, "laplacian_method", "uniform"), getattr(args, "edge_target_length", 0.0)
+    if target != 'mean' and not (math.isfinite(target) and target >= 0.0):
+        return "--edge_target_length must be 'mean' or a finite length >= 0"
+    if (method != "uniform" or target != 0.0) and getattr(args, "optimization_target", None) == 'texture':
+        return ("--laplacian_method / --edge_target_length need --optimization_target mesh or both: with 'texture' the vertices "
+                "do not move and the mesh regularisers do not run")
     if not getattr(args, "silhouette_sigma", 1e-4) > 0.0:
         return "--silhouette_sigma must be positive"
     k = getattr(args, "silhouette_faces_per_pixel", None)
@@ -229,6 +253,31 @@ def vertex_colors_from_map(n_verts, faces, verts_uvs, faces_uvs, texture_map):
     return colors
 
 
+def mean_edge_length(verts, faces):
+    """mean length of the unique undirected edges of (verts (V,3), faces (F,3)); once per run, in torch fp64"""
+    f = faces.detach().long().cpu()
+    he = torch.sort(torch.cat([f[:, [1, 2]], f[:, [2, 0]], f[:, [0, 1]]], dim=0), dim=1).values
+    e = torch.unique(he, dim=0)
+    v = verts.detach().double().cpu()
+    return float((v[e[:, 0]] - v[e[:, 1]]).norm(dim=1).mean())
+
+
+def mesh_regulariser_keys(args, verts, faces, say=print):
+    """--laplacian_method / --edge_target_length -> the optional keys of the weights dict that st3d.mesh_losses.mesh_terms
+    reads.  A key is present only when its flag is set, so the dict of a default run is what it always was.  'mean' becomes
+    the mean edge length of the loaded mesh, computed once and printed."""
+    keys = {}
+    if getattr(args, "laplacian_method", "uniform") != "uniform":
+        keys['mesh_laplacian_method'] = args.laplacian_method
+    target = getattr(args, "edge_target_length", 0.0)
+    if target == 'mean':
+        target = mean_edge_length(verts, faces)
+        say(f"Mean edge length of the loaded mesh: {target:.6g} (--edge_target_length mean)")
+    if target != 0.0:
+        keys['mesh_edge_target_length'] = float(target)
+    return keys
+
+
 def load_scene_vertex(obj_path, device):
     """--texture_type vertex: OBJ -> (verts (V,3), faces (F,3), colours (V,3)) on `device`.  An OBJ with UVs and a texture
     map starts from the map (vertex_colors_from_map); one without -- the case the flag exists for -- from
@@ -320,6 +369,7 @@ class Run:
             verts, faces, verts_uvs, faces_uvs, tex = load_scene(args.obj_path, args.size, args.resize_texture, self.device)
             self.content_mesh = _u.build_mesh(verts_uvs, faces_uvs, tex, verts, faces)
         self.original_verts = verts
+        self.loss_weights.update(mesh_regulariser_keys(args, verts, faces, self.say))
 
         cams = FoVPerspectiveCameras(device=self.device)
         supersample = getattr(args, "supersample", 1)

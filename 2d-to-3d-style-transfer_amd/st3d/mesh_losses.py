@@ -9,12 +9,21 @@ vertex tensor's identity/version, so the reference's four separate calls cost on
 Topology (unique edges, CSR adjacency, face pairs and their per-vertex inverse) is static: built
 once per faces tensor on the host, cached.  Every gradient is a fixed-order gather over it (no
 float atomics): bitwise reproducible.
+
+``mesh_laplacian_smoothing(mesh, method=)`` takes PyTorch3D's three methods, ``"uniform"`` (default), ``"cot"`` and
+``"cotcurv"``; ``mesh_edge_loss(mesh, target_length=)`` any finite length >= 0; ``mesh_terms`` reads them from the optional
+weights keys ``'mesh_laplacian_method'`` / ``'mesh_edge_target_length'``.  The formulas are in DESIGN.md 7.  At the defaults
+every function makes the call it always made (st3d_mesh_reg); anything else goes to st3d_mesh_reg_ex, which needs three more
+static lists (``build_cot_topology``: edge -> incident corners, adjacency slot -> edge, vertex -> incident corners), cached
+per faces tensor like the rest.  The cotangent weights change with the vertices and are constants of the gradient, as in
+PyTorch3D: they are rebuilt by every call and never cached across vertex versions.
 """
 import torch
 
 from . import ops
 
 _TOPO_CACHE = {}
+_COT_CACHE = {}
 _REG_CACHE = {}
 
 
@@ -71,6 +80,59 @@ def build_topology(faces, num_verts):
             "pair_ref": i32(pair_ref)}
 
 
+def build_cot_topology(faces, num_verts):
+    """faces (F,3) int64 -> dict of int32 device tensors, the static lists of the cotangent Laplacian beside build_topology's
+    (same edge numbering and adjacency order): faces (F,3); nbr_edge (2E) = for every slot of nbr_idx the row of `edges` it
+    stands for; edge_off (E+1) / edge_ref (3F) = CSR edge -> face * 3 + c for every face on the edge, c the corner opposite
+    it (whose cotangent the edge receives), ascending -- one entry on a boundary edge, as many as faces on a non-manifold
+    one; inc_off (V+1) / inc_ref (3F) = CSR vertex -> face * 3 + corner, ascending (render.vertex_incidence).
+    An index outside [0, num_verts) is a ValueError here: on the device it would be a fault."""
+    from .render import vertex_incidence
+    dev = faces.device
+    f = faces.detach().long().cpu()
+    V = int(num_verts)
+    if f.dim() != 2 or f.shape[1] != 3 or f.shape[0] < 1:
+        raise ValueError(f"faces must be (F,3) with F >= 1, got {tuple(f.shape)}")
+    if V < 1 or int(f.min()) < 0 or int(f.max()) >= V:
+        raise ValueError(f"faces name vertices outside [0, {V})")
+    F = f.shape[0]
+    he = torch.cat([f[:, [1, 2]], f[:, [2, 0]], f[:, [0, 1]]], dim=0)               # half-edge c * F + face: opposite corner c
+    he = torch.sort(he, dim=1).values
+    ukey, inv = torch.unique(he[:, 0] * V + he[:, 1], sorted=True, return_inverse=True)
+    E = ukey.shape[0]
+    h = torch.arange(3 * F)
+    ref = (h % F) * 3 + h // F                                                       # face * 3 + corner
+    edge_ref = ref[torch.sort(inv * (3 * F) + ref).indices]
+    edge_off = torch.zeros(E + 1, dtype=torch.int64)
+    edge_off[1:] = torch.cumsum(torch.bincount(inv, minlength=E), 0)
+    e0, e1 = ukey // V, ukey % V
+    src, dst = torch.cat([e0, e1]), torch.cat([e1, e0])                              # build_topology's adjacency order
+    nbr_edge = torch.arange(E).repeat(2)[torch.sort(src * V + dst).indices]
+    inc_off, inc_ref = vertex_incidence(f.to(torch.int32), V)
+    i32 = lambda t: t.to(torch.int32).contiguous().to(dev)
+    return {"faces": i32(f), "nbr_edge": i32(nbr_edge), "edge_off": i32(edge_off), "edge_ref": i32(edge_ref),
+            "inc_off": i32(inc_off), "inc_ref": i32(inc_ref)}
+
+
+def _cot_topology(mesh):
+    faces = mesh.faces_packed()
+    V = mesh.verts_packed().shape[0]
+    key = (faces.data_ptr(), tuple(faces.shape), faces._version, V, str(faces.device))
+    hit = _COT_CACHE.get(key)
+    if hit is None:
+        if len(_COT_CACHE) > 16:
+            _COT_CACHE.clear()
+        hit = (build_cot_topology(faces, V), faces)
+        _COT_CACHE[key] = hit
+    return hit[0]
+
+
+def check_laplacian_method(method):
+    if method not in ops.LAPLACIAN_METHODS:
+        raise ValueError(f"method must be 'uniform', 'cot' or 'cotcurv', got {method!r}")
+    return method
+
+
 def _topology(mesh):
     faces = mesh.faces_packed()
     V = mesh.verts_packed().shape[0]
@@ -97,12 +159,16 @@ class _TermFn(torch.autograd.Function):
         return ctx.grad * g, None, None
 
 
-def _term(verts, target, topo, k):
+def _term(verts, target, topo, k, mesh=None, method="uniform", target_length=0.0):
     """k: 0 mse, 1 edge, 2 laplacian, 3 normal.  Terms are evaluated with unit weight each (four
-    calls of st3d_mesh_reg would be wasteful: results are cached per (verts version, k))."""
+    calls of st3d_mesh_reg would be wasteful: results are cached per (verts version, k)).
+    method / target_length other than the defaults: st3d_mesh_reg_ex on `mesh`'s extra lists."""
     if not verts.is_cuda:
         raise RuntimeError("st3d runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
     key = (verts.data_ptr(), verts._version, k, None if target is None else target.data_ptr())
+    extended = method != "uniform" or target_length != 0.0
+    if extended:
+        key = key + (method, target_length, topo["edges"].data_ptr())
     hit = _REG_CACHE.get(key)
     if hit is None:
         if len(_REG_CACHE) > 8:
@@ -110,7 +176,11 @@ def _term(verts, target, topo, k):
         w = [0.0, 0.0, 0.0, 0.0]
         w[k] = 1.0
         tgt = target if target is not None else verts
-        out, grad = ops.mesh_reg(verts.detach(), tgt.detach(), topo, w, want_grad=True)
+        if extended:
+            out, grad = ops.mesh_reg_ex(verts.detach(), tgt.detach(), topo, _cot_topology(mesh) if method != "uniform" else None,
+                                        w, method, target_length, want_grad=True)
+        else:
+            out, grad = ops.mesh_reg(verts.detach(), tgt.detach(), topo, w, want_grad=True)
         hit = (out[1 + k], grad)
         _REG_CACHE[key] = hit
     return _TermFn.apply(verts, hit[0], hit[1])
@@ -138,15 +208,14 @@ def verts_mse(verts, target_verts):
 
 
 def mesh_edge_loss(mesh, target_length=0.0):
-    if target_length != 0.0:
-        raise NotImplementedError("the reference calls mesh_edge_loss(mesh) with the default target_length=0")
-    return _term(mesh.verts_packed(), None, _topology(mesh), 1)
+    """mean over the unique edges of (length - target_length)^2; target_length finite and >= 0, else ValueError"""
+    t = ops.check_edge_target_length(target_length)
+    return _term(mesh.verts_packed(), None, _topology(mesh), 1, mesh, "uniform", t)
 
 
 def mesh_laplacian_smoothing(mesh, method="uniform"):
-    if method != "uniform":
-        raise NotImplementedError("the reference uses the default method='uniform'")
-    return _term(mesh.verts_packed(), None, _topology(mesh), 2)
+    """mean over the vertices of |Laplacian residual|, method 'uniform' | 'cot' | 'cotcurv' (DESIGN 7); else ValueError"""
+    return _term(mesh.verts_packed(), None, _topology(mesh), 2, mesh, check_laplacian_method(method), 0.0)
 
 
 def mesh_normal_consistency(mesh):
@@ -155,7 +224,11 @@ def mesh_normal_consistency(mesh):
 
 def mesh_terms(verts, target_verts, mesh, weights):
     """All four weighted terms in ONE st3d_mesh_reg call (what losses._mesh_terms uses):
-    weights: dict with the reference's keys (first_approach.py:69-75)."""
+    weights: dict with the reference's keys (first_approach.py:69-75) and, optionally, 'mesh_laplacian_method'
+    ('uniform' | 'cot' | 'cotcurv', default 'uniform') and 'mesh_edge_target_length' (finite, >= 0, default 0.0); with both
+    absent or at their defaults the call is today's, otherwise ONE st3d_mesh_reg_ex call."""
+    method = check_laplacian_method(weights.get('mesh_laplacian_method', 'uniform'))
+    t = ops.check_edge_target_length(weights.get('mesh_edge_target_length', 0.0))
     if not verts.is_cuda:
         raise RuntimeError("st3d runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
     topo = _topology(mesh)
@@ -166,7 +239,11 @@ def mesh_terms(verts, target_verts, mesh, weights):
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         w = [x / dist.get_world_size() for x in w]
-    out, grad = ops.mesh_reg(verts.detach(), target_verts.detach(), topo, w, want_grad=verts.requires_grad)
+    if method != "uniform" or t != 0.0:
+        out, grad = ops.mesh_reg_ex(verts.detach(), target_verts.detach(), topo, _cot_topology(mesh) if method != "uniform" else None,
+                                    w, method, t, want_grad=verts.requires_grad)
+    else:
+        out, grad = ops.mesh_reg(verts.detach(), target_verts.detach(), topo, w, want_grad=verts.requires_grad)
     if grad is None:
         return out[0].clone()
     return _TermFn.apply(verts, out[0], grad)

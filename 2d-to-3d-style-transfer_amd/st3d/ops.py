@@ -357,6 +357,50 @@ def mesh_reg(verts, target, topo, weights, want_grad=True):
     return out, g
 
 
+LAPLACIAN_METHODS = {"uniform": 0, "cot": 1, "cotcurv": 2}
+
+
+def check_edge_target_length(t):
+    """a finite float >= 0; else ValueError"""
+    if isinstance(t, bool) or not isinstance(t, (int, float)) or not (math.isfinite(t) and t >= 0.0):
+        raise ValueError(f"target_length must be a finite number >= 0, got {t!r}")
+    return float(t)
+
+
+def mesh_reg_ex(verts, target, topo, cot_topo, weights, laplacian_method="uniform", edge_target_length=0.0, want_grad=True):
+    """mesh_reg with the Laplacian of `laplacian_method` ('uniform' | 'cot' | 'cotcurv') and an edge target length >= 0.
+    cot_topo: mesh_losses.build_cot_topology's dict (faces (F,3), nbr_edge (2E), edge_off (E+1), edge_ref (3F), inc_off (V+1),
+    inc_ref (3F), all i32); may be None for 'uniform'.  Same returns as mesh_reg; at 'uniform' / 0 the same bits."""
+    if laplacian_method not in LAPLACIAN_METHODS:
+        raise ValueError(f"laplacian_method must be one of {sorted(LAPLACIAN_METHODS)}, got {laplacian_method!r}")
+    method = LAPLACIAN_METHODS[laplacian_method]
+    t = check_edge_target_length(edge_target_length)
+    if method and cot_topo is None:
+        raise ValueError(f"laplacian_method {laplacian_method!r} needs the topology of mesh_losses.build_cot_topology")
+    verts, target = _f32c(verts), _f32c(target)
+    V = verts.shape[0]
+    dev = verts.device
+    E, P = topo["edges"].shape[0], topo["pairs"].shape[0]
+    c = cot_topo if method else None
+    F = c["faces"].shape[0] if c else 0
+    if c and (tuple(c["nbr_edge"].shape) != (2 * E,) or tuple(c["edge_off"].shape) != (E + 1,) or tuple(c["edge_ref"].shape) != (3 * F,)
+              or tuple(c["inc_off"].shape) != (V + 1,) or tuple(c["inc_ref"].shape) != (3 * F,)
+              or tuple(topo["nbr_off"].shape) != (V + 1,) or tuple(topo["nbr_idx"].shape) != (2 * E,)):
+        raise ValueError("cot_topo does not belong to this topology / vertex count")
+    scratch = torch.empty((_lib.load().st3d_mesh_reg_ex_scratch_floats(V, E, F, P),), dtype=F32, device=dev)
+    parts = torch.empty((4 * _lib.load().st3d_reduce_partials(),), dtype=F32, device=dev)
+    out = torch.zeros((5,), dtype=F32, device=dev)
+    g = torch.zeros_like(verts) if want_grad else None
+    w = (ctypes.c_float * 4)(*[float(x) for x in weights])
+    cp = (lambda k: dptr(c[k], I32)) if c else (lambda k: None)
+    call("st3d_mesh_reg_ex", dptr(verts), dptr(target), V, dptr(topo["edges"], I32), E,
+         dptr(topo["nbr_off"], I32), dptr(topo["nbr_idx"], I32), dptr(topo["pairs"], I32) if P else None, P,
+         dptr(topo["pair_off"], I32) if P else None, dptr(topo["pair_ref"], I32) if P else None,
+         cp("faces"), F, cp("nbr_edge"), cp("edge_off"), cp("edge_ref"), cp("inc_off"), cp("inc_ref"), method, t, w,
+         dptr(scratch), dptr(parts), dptr(out), dptr(g), stream_ptr())
+    return out, g
+
+
 # ------------------------------------------------------------------ general soft renderer (K faces per pixel, blur)
 def raster_soft_fwd(verts_ndc, faces_i32, S, K, blur_radius=0.0, clip_bary=None, cull_backfaces=False,
                     perspective_correct=True, z_clip=None):

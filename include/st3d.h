@@ -650,6 +650,32 @@ int st3d_mesh_reg(const float *verts, const float *target_verts, int V, const in
                   const float *weights, float *scratch, float *partials, float *loss_out,
                   float *grad_verts, st3d_stream_t stream);
 
+/* The same four terms, loss_out layout and `grad_verts +=` with PyTorch3D's other two Laplacians and an edge target length
+ * (DESIGN 7).  laplacian_method: 0 uniform, 1 cot, 2 cotcurv.  With, per face (v0,v1,v2), A=|v1-v2|, B=|v0-v2|, C=|v0-v1|,
+ * s=(A+B+C)/2, area = sqrt(max(s(s-A)(s-B)(s-C), 1e-12)), cot_0 = (B^2+C^2-A^2)/(4 area) (cot_1, cot_2 alike), L symmetric with
+ * L[v1,v2] += cot_0, L[v2,v0] += cot_1, L[v0,v1] += cot_2 over all faces, Lsum_i = sum_j L_ij, Asum_i = the areas of i's faces:
+ *   cot:     r_i = (sum_j L_ij v_j) nw_i - v_i, nw_i = 1/Lsum_i where Lsum_i > 0, else Lsum_i itself
+ *   cotcurv: r_i = (sum_j L_ij v_j - Lsum_i v_i) * 0.25 / Asum_i (0 where Asum_i is not > 0)
+ * laplacian = (1/V) sum_i |r_i|; L, nw, Asum and Lsum are constants of the gradient, as in PyTorch3D.
+ * edge_target_length t >= 0, finite: edge = (1/E) sum_e (|a-b| - t)^2, gradient direction 0 at |a-b| = 0.
+ * At method 0 and t = 0 the launches and the bits are st3d_mesh_reg's.
+ * Static lists beyond st3d_mesh_reg's (needed for method 1 / 2 only, else may be NULL), all host-built, every index in
+ * range (nothing is checked on the device): faces (F,3); nbr_edge (2E) = for every slot of nbr_idx the row of `edges` it
+ * stands for; CSR edge -> incident corners edge_off (E+1), edge_ref = face * 3 + (corner opposite the edge), ascending;
+ * CSR vertex -> incident corners inc_off (V+1), inc_ref = face * 3 + corner, ascending.  Every sum is a gather over these
+ * lists in list order: no float atomics, two runs are bit-equal.  The cot / target-length kernels compute in fp64 and round
+ * each output once.  scratch >= st3d_mesh_reg_ex_scratch_floats(V, E, F, P) floats (0 for sizes the call refuses), 8-byte
+ * aligned; partials as for st3d_mesh_reg.  ST3D_E_INVALID: null pointers, non-positive sizes, an unknown method, a negative
+ * or non-finite t. */
+size_t st3d_mesh_reg_ex_scratch_floats(int V, int E, int F, int P);
+int st3d_mesh_reg_ex(const float *verts, const float *target_verts, int V, const int32_t *edges, int E,
+                     const int32_t *nbr_off, const int32_t *nbr_idx, const int32_t *pairs, int P,
+                     const int32_t *pair_off, const int32_t *pair_ref, const int32_t *faces, int F,
+                     const int32_t *nbr_edge, const int32_t *edge_off, const int32_t *edge_ref,
+                     const int32_t *inc_off, const int32_t *inc_ref, int laplacian_method, float edge_target_length,
+                     const float *weights, float *scratch, float *partials, float *loss_out,
+                     float *grad_verts, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ texture pyramid (csrc/texpyr.hip):
  * the texture map (T,T,3) as the sum of L maps of sides T_l = T / 2^l, each upsampled to T x T.  `params` is one flat
  * fp32 tensor of st3d_texpyr_numel(T, L) = 3 * sum_l T_l^2 elements; level l is the (T_l, T_l, 3) row-major block at

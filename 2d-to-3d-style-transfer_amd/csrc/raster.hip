@@ -11,8 +11,17 @@
 //   raster_tile_kernel     one 256-thread workgroup per 16x16 pixel tile: per super-round of 2048 faces every
 //                          wave sweeps the packed tile ranges of its own 512 faces (4 B per face, not the
 //                          record) and compacts the hits in face order (wave ballots) without a barrier; then
-//                          only the hits' records are fetched into LDS and every lane (= pixel) walks the list
-//                          (same-address broadcast reads, no bank conflicts).
+//                          only the hits' records are fetched into LDS and (phase 2) evaluated: faces in parallel,
+//                          as (face, 4x4 block) items with a 64-bit depth|index key per pixel in LDS, or
+//                          (ST3D_RASTER_WALK=1, the earlier variant) every lane (= pixel) walks the list (same-address
+//                          broadcast reads, no bank conflicts).  See the comment above raster_tile_kernel.
+// Phase 2 in numbers (config 2, kernel trace of bench.py, DESIGN section 6 "Rasteriser: faces in parallel per tile"):
+// raster_tile_kernel 153.5 -> 71.8 us (8 views, 512^2, cow), raster_fwd's three launches 167.7 -> 83.9 us in alternating
+// windows of one process; 28.4 us of either with the mesh off screen.  Two triangles over every image: 37.6 -> 44.4 us (the
+// one regime that loses; DESIGN says why).  Face-parallel variant: 77 VGPRs (capped at 80: six waves per SIMD), 24.8 KB of
+// LDS, no scratch; the walk: 61 VGPRs, 28.7 KB.
+// The walk, as measured before that (its variants that did not help are kept here because they explain why the
+// structure, not the loop body, had to change):
 // Measured at config 2 (8 views, 512^2, cow): 0.18 ms (0.19 before the sweep was decoupled from the record fetch,
 // round 2), of which ~0.05 ms is the sweep (mesh pushed off screen: every tile reads every face's word, 192 MB of L2
 // reads per 8-view batch); the rest is the per-pixel walk, bounded by the densest tiles (up to 330 one-pixel faces per
@@ -129,11 +138,14 @@ struct Best {
     float z, b0, b1, b2;
 };
 
-__device__ __forceinline__ void eval_face(int f, float x0, float y0, float z0, float x1, float y1, float z1, float x2,
-                                          float y2, float z2, float xf, float yf, Best &best) {
+// One face at one pixel centre, the operation sequence of oracle/raster_ref.c: true when the pixel is inside (blur_radius == 0)
+// and not behind the image plane; pz and the barycentrics are then set.  Both phase-2 variants and the final re-evaluation
+// of the face-parallel one go through this one function, so they produce the same bits.
+__device__ __forceinline__ bool face_at_pixel(float x0, float y0, float z0, float x1, float y1, float z1, float x2, float y2,
+                                              float z2, float xf, float yf, float &pz, float &b0, float &b1, float &b2) {
     const float xmin = fminf(x0, fminf(x1, x2)), xmax = fmaxf(x0, fmaxf(x1, x2));
     const float ymin = fminf(y0, fminf(y1, y2)), ymax = fmaxf(y0, fmaxf(y1, y2));
-    if (xf > xmax || xf < xmin || yf > ymax || yf < ymin) return;
+    if (xf > xmax || xf < xmin || yf > ymax || yf < ymin) return false;
     const float area = edge_fn(x2, y2, x0, y0, x1, y1) + kEps;
     const float w0 = edge_fn(xf, yf, x1, y1, x2, y2) / area;
     const float w1 = edge_fn(xf, yf, x2, y2, x0, y0) / area;
@@ -142,13 +154,31 @@ __device__ __forceinline__ void eval_face(int f, float x0, float y0, float z0, f
     const float t1 = z0 * w1 * z2;
     const float t2 = z0 * z1 * w2;
     const float den = fmaxf(t0 + t1 + t2, kEps);
-    const float b0 = t0 / den, b1 = t1 / den, b2 = t2 / den;
-    const float pz = b0 * z0 + b1 * z1 + b2 * z2;
-    if (pz < 0.f) return;
-    if (!((b0 > 0.f) && (b1 > 0.f) && (b2 > 0.f))) return;  // blur_radius == 0: only inside pixels survive
+    b0 = t0 / den; b1 = t1 / den; b2 = t2 / den;
+    pz = b0 * z0 + b1 * z1 + b2 * z2;
+    if (pz < 0.f) return false;
+    return (b0 > 0.f) && (b1 > 0.f) && (b2 > 0.f);          // blur_radius == 0: only inside pixels survive
+}
+
+__device__ __forceinline__ void eval_face(int f, float x0, float y0, float z0, float x1, float y1, float z1, float x2,
+                                          float y2, float z2, float xf, float yf, Best &best) {
+    float pz, b0, b1, b2;
+    if (!face_at_pixel(x0, y0, z0, x1, y1, z1, x2, y2, z2, xf, yf, pz, b0, b1, b2)) return;
     if (best.f < 0 || pz < best.z) {                          // list is in face order: ties keep the smaller index
         best.f = f; best.z = pz; best.b0 = b0; best.b1 = b1; best.b2 = b2;
     }
+}
+
+// The face-parallel phase 2 (ST3D_RASTER_WALK unset): the pixels of the tile a face's bounding box can contain, as an
+// inclusive range of tile-local indices [lo, hi] clipped to 0..15 (lo > hi: none).  Pixel i has the NDC centre
+// 1 - (2i+1)/S, so the pixels with cmin <= centre <= cmax are a = ((1-cmax)S-1)/2 <= i <= b = ((1-cmin)S-1)/2; floor(a) and
+// ceil(b) are a superset as long as the rounding of a and b stays below one pixel (S <= 4096: below 2^-10 of one) -- the
+// exact test is face_at_pixel's.  Tighter than pixel_span's range (which leaves more than a pixel each side): every 4x4
+// block a face is listed for costs sixteen lanes one evaluation.
+__device__ __forceinline__ void tile_span(float cmin, float cmax, int S, int origin, int &lo, int &hi) {
+    const float a = fminf(fmaxf(((1.0f - cmax) * (float)S - 1.0f) * 0.5f, -4.0f), (float)S + 4.0f);
+    const float b = fminf(fmaxf(((1.0f - cmin) * (float)S - 1.0f) * 0.5f, -4.0f), (float)S + 4.0f);
+    lo = max((int)floorf(a) - origin, 0); hi = min((int)ceilf(b) - origin, TILE - 1);
 }
 
 // Coarse level (round 2): bins of BIN x BIN tiles.  raster_bin_kernel sweeps every face's packed tile range ONCE per bin and
@@ -214,15 +244,78 @@ __global__ __launch_bounds__(256) void raster_bin_kernel(const unsigned *__restr
     }
 }
 
-__global__ __launch_bounds__(256) void raster_tile_kernel(const float4 *__restrict__ rec, const unsigned *__restrict__ words,
+// The blocks of `mask` (bit 4*row + column of the tile's sixteen 4x4 blocks) in which some pixel can still pass
+// face_at_pixel, decided with that function's own float expressions so that no block is dropped that holds an accepted pixel:
+//  - the bounding-box test fails for a whole block when its outermost column or row already fails it;
+//  - b_k > 0 needs t_k > 0 (den >= kEps > 0), that is sign(e_k) = sign(area) * sign(z_i) * sign(z_j) and e_k != 0 for the edge
+//    function e_k of the two other vertices i, j (IEEE sign rules of w_k = e_k / area, t_k = w_k * z * z).  As computed in
+//    float, e(px, py) = fl(fl(fl(px - ax) * dy) - fl(fl(py - ay) * dx)) is monotone in px and in py (every rounded operation is
+//    monotone in each operand), and so are the pixel centres in the pixel index: over the 16 pixels of a block e is largest
+//    (smallest) at the corner pixel picked by the signs of dy and dx.  The block goes when that extreme has the wrong sign or
+//    is zero for one edge.  A NaN anywhere fails the comparison and keeps the block.
+// On the bench's views (cow, 8 views, 512^2) this takes the (face, block) items from 498 k to 260 k.
+__device__ __forceinline__ unsigned cull_blocks(unsigned mask, float x0, float y0, float z0, float x1, float y1, float z1,
+                                                float x2, float y2, float z2, const float (*xy)[TILE]) {
+    const float xmin = fminf(x0, fminf(x1, x2)), xmax = fmaxf(x0, fmaxf(x1, x2));
+    const float ymin = fminf(y0, fminf(y1, y2)), ymax = fmaxf(y0, fmaxf(y1, y2));
+    const float area = edge_fn(x2, y2, x0, y0, x1, y1) + kEps;
+    const unsigned sa = __float_as_uint(area) >> 31, s0 = __float_as_uint(z0) >> 31, s1 = __float_as_uint(z1) >> 31,
+                   s2 = __float_as_uint(z2) >> 31;
+    const float ax[3] = {x1, x2, x0}, ay[3] = {y1, y2, y0};
+    const float dx[3] = {x2 - x1, x0 - x2, x1 - x0}, dy[3] = {y2 - y1, y0 - y2, y1 - y0};
+    const bool neg[3] = {(sa ^ s1 ^ s2) != 0u, (sa ^ s2 ^ s0) != 0u, (sa ^ s0 ^ s1) != 0u};        // acceptance needs e_k < 0
+    unsigned keep = 0;
+    for (unsigned m = mask; m != 0u; m &= m - 1u) {
+        const int blk = __ffs(m) - 1, c = (blk & 3) << 2, r = blk & 12;
+        const float xa = xy[0][c], xb = xy[0][c + 3], ya = xy[1][r], yb = xy[1][r + 3];          // xa >= xb, ya >= yb
+        bool out = xa < xmin || xb > xmax || ya < ymin || yb > ymax;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float px = ((dy[k] > 0.f) != neg[k]) ? xa : xb, py = ((dx[k] < 0.f) != neg[k]) ? ya : yb;
+            const float e = (px - ax[k]) * dy[k] - (py - ay[k]) * dx[k];
+            out = out || (neg[k] ? e >= 0.f : e <= 0.f);
+        }
+        if (!out) keep |= 1u << blk;
+    }
+    return keep;
+}
+
+// Phase 2, two variants (template switch, ST3D_RASTER_WALK=1 selects the walk):
+//  WALK  every lane (= pixel) walks the tile's whole list: a face costs its wave the full evaluation as soon as one of its
+//        64 pixels is inside the bounding box, a tile with 330 faces is a serial chain of 330 iterations;
+//  else  faces in parallel: per chunk of PAR_CAP listed faces a thread per face clips the face's pixel box to the tile and
+//        marks the 4x4 blocks it meets (tile_span), then drops the blocks no pixel of which can be inside (cull_blocks);
+//        a prefix sum turns the marks into (face, block) items; the 16 quarter-waves take the items sixteen at a time,
+//        lane = one pixel of the block, and an accepted face does an LDS atomicMin of the 64-bit key (depth bits << 32 |
+//        face index) of its pixel.  pz is never negative or NaN when accepted (pz < 0 has returned; a NaN depth is
+//        not a mesh this path is specified for), so unsigned order of the bits is depth order and equal depth falls to the
+//        smaller index -- the oracle's rule, whatever order the items run in; pz + 0.0f makes -0.0 tie with +0.0 as
+//        `pz < best_z` does.  A face whose box spans more than CULL_MAX blocks of the tile makes no items: every pixel
+//        evaluates it and keeps the smaller key in a register pair (sixteen items would be as many evaluations, plus the
+//        list and the atomics).  The keys only order candidates: after the last chunk every pixel re-evaluates its winner
+//        from the record and stores those values.  A tile no face is listed for never touches the keys.
+//        LDS 24.8 KB (the walk: 28.7 KB), 77 VGPRs under the cap of 80 set below (six waves per SIMD; without the cap
+//        the compiler takes 87 and the kernel is 4 us slower on config 2), no scratch, no spills.
+constexpr int PAR_CAP = 256;     // faces per chunk of the face-parallel variant: one per thread
+constexpr int CULL_MAX = 9;      // blocks of a face's box up to which cull_blocks tests them one by one
+constexpr int ITEM_CAP = 2048;   // (face, block) items staged per pass (a chunk of 256 whole-tile faces has 4096: two passes)
+
+template <bool WALK>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(80))) void raster_tile_kernel(const float4 *__restrict__ rec, const unsigned *__restrict__ words,
                                                           int F, int Fp, int S, int32_t *__restrict__ pix_to_face,
                                                           float *__restrict__ zbuf, float *__restrict__ bary,
                                                           float *__restrict__ dists, const int *__restrict__ bin_count,
                                                           const int *__restrict__ bin_list, int nbx, int cap) {
-    __shared__ float s_face[LIST_CAP][9];
-    __shared__ int s_fidx[LIST_CAP];
+    constexpr int CAP = WALK ? LIST_CAP : PAR_CAP;
+    __shared__ float s_face[CAP][9];
+    __shared__ int s_fidx[CAP];
     __shared__ int s_wcnt[4];
     __shared__ int s_list[4][512];       // per wave: the faces of its slice of the super-round that touch this tile
+    __shared__ unsigned long long s_key[WALK ? 1 : TILE * TILE];
+    __shared__ unsigned short s_item[WALK ? 1 : ITEM_CAP];       // slot << 4 | block
+    __shared__ int s_isum[4];                                    // items of each wave's 64 faces
+    __shared__ unsigned long long s_big[4];                      // per wave: which of its 64 faces every pixel evaluates
+    __shared__ float s_xy[2][TILE];                              // NDC centres of the tile's columns and rows
 
     const int b = blockIdx.z;
     const int tid = threadIdx.x;
@@ -230,13 +323,15 @@ __global__ __launch_bounds__(256) void raster_tile_kernel(const float4 *__restri
     const int px = blockIdx.x * TILE + (tid & (TILE - 1));
     const int py = blockIdx.y * TILE + (tid >> 4);
     const bool in_img = px < S && py < S;
-    const float xf = pix_to_ndc(S - 1 - px, S);
-    const float yf = pix_to_ndc(S - 1 - py, S);
+    float xf = 0.f, yf = 0.f;            // this thread's pixel centre (the face-parallel variant reads it from s_xy with the first listed face)
+    if constexpr (WALK) { xf = pix_to_ndc(S - 1 - px, S); yf = pix_to_ndc(S - 1 - py, S); }
     const float4 *rb = rec + (size_t)b * F * 3;
     const uint2 *wb = reinterpret_cast<const uint2 *>(words + (size_t)b * Fp);
     const unsigned bx = blockIdx.x, by = blockIdx.y;
     Best best;
     best.f = -1; best.z = 0.f; best.b0 = best.b1 = best.b2 = 0.f;
+    bool any = false;                    // (workgroup-uniform) a face has been listed for this tile: the keys are set
+    unsigned long long own = ~0ull;      // this pixel's key among the large faces (those that make no items)
 
     // Two decoupled phases per super-round of 2048 faces (round 2; before, every 512-face pass had its own barrier ->
     // record fetch -> barrier -> walk -> barrier chain, twelve times over for the cow):
@@ -256,6 +351,10 @@ __global__ __launch_bounds__(256) void raster_tile_kernel(const float4 *__restri
         }
     }
     const unsigned *wsv = words + (size_t)b * Fp;
+    if constexpr (!WALK) {      // 32 threads, under the sweep's loads; the sweep's barrier orders it (an empty tile never reads it)
+        if (tid < TILE) s_xy[0][tid] = pix_to_ndc(S - 1 - ((int)bx * TILE + tid), S);
+        else if (tid < 2 * TILE) s_xy[1][tid - TILE] = pix_to_ndc(S - 1 - ((int)by * TILE + tid - TILE), S);
+    }
     for (int base = 0; base < ncand; base += SUPER) {
         int cnt = 0;
         uint2 w4[4];
@@ -296,31 +395,127 @@ __global__ __launch_bounds__(256) void raster_tile_kernel(const float4 *__restri
         if (lane == 0) s_wcnt[wave] = cnt;
         __syncthreads();
         const int o1 = s_wcnt[0], o2 = o1 + s_wcnt[1], o3 = o2 + s_wcnt[2], total = o3 + s_wcnt[3];
-        for (int cb = 0; cb < total; cb += LIST_CAP) {
-            const int n = min(LIST_CAP, total - cb);
-#pragma unroll
-            for (int h = 0; h < LIST_CAP / 256; ++h) {
-                const int slot = tid + 256 * h, i = cb + slot;
-                if (slot < n) {
+        if constexpr (!WALK) {
+            if (total > 0 && !any) {        // (workgroup-uniform) the first listed face: the barrier of the item counts orders this
+                any = true;
+                s_key[tid] = ~0ull;
+            }
+            for (int cb = 0; cb < total; cb += PAR_CAP) {
+                const int n = min(PAR_CAP, total - cb);
+                // a thread per face: record into LDS, the 4x4 blocks of the tile its pixel box meets (bit 4*row + column)
+                unsigned mask = 0;
+                bool big = false;
+                if (tid < n) {
+                    const int i = cb + tid;
                     const int f = i < o1 ? s_list[0][i] : (i < o2 ? s_list[1][i - o1] : (i < o3 ? s_list[2][i - o2] : s_list[3][i - o3]));
                     const float4 r0 = rb[3 * (size_t)f], r1 = rb[3 * (size_t)f + 1], r2 = rb[3 * (size_t)f + 2];
-                    s_fidx[slot] = f;
-                    s_face[slot][0] = r0.x; s_face[slot][1] = r0.y; s_face[slot][2] = r0.z;
-                    s_face[slot][3] = r0.w; s_face[slot][4] = r1.x; s_face[slot][5] = r1.y;
-                    s_face[slot][6] = r1.z; s_face[slot][7] = r1.w; s_face[slot][8] = r2.x;
+                    s_fidx[tid] = f;
+                    s_face[tid][0] = r0.x; s_face[tid][1] = r0.y; s_face[tid][2] = r0.z;
+                    s_face[tid][3] = r0.w; s_face[tid][4] = r1.x; s_face[tid][5] = r1.y;
+                    s_face[tid][6] = r1.z; s_face[tid][7] = r1.w; s_face[tid][8] = r2.x;
+                    int xlo, xhi, ylo, yhi;
+                    tile_span(fminf(r0.x, fminf(r0.w, r1.z)), fmaxf(r0.x, fmaxf(r0.w, r1.z)), S, (int)bx * TILE, xlo, xhi);
+                    tile_span(fminf(r0.y, fminf(r1.x, r1.w)), fmaxf(r0.y, fmaxf(r1.x, r1.w)), S, (int)by * TILE, ylo, yhi);
+                    if (xlo <= xhi && ylo <= yhi) {
+                        const unsigned cols = (2u << (xhi >> 2)) - (1u << (xlo >> 2));         // block columns xlo/4 .. xhi/4
+                        const unsigned rows = (2u << (yhi >> 2)) - (1u << (ylo >> 2));
+                        mask = cols * ((rows & 1u) | ((rows & 2u) << 3) | ((rows & 4u) << 6) | ((rows & 8u) << 9));
+                        // a face whose box spans more than 3 x 3 blocks of the tile makes no items: every pixel evaluates it
+                        // below (as many evaluations as sixteen items, without the list and the atomics)
+                        big = __popc(mask) > CULL_MAX;
+                        mask = big ? 0u : cull_blocks(mask, r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, s_xy);
+                    }
                 }
+                const unsigned long long bigs = __ballot(big);
+                // exclusive prefix sum of the block counts: within the wave by shuffles, across waves through s_isum
+                const int mine = __popc(mask);
+                int incl = mine;
+#pragma unroll
+                for (int d = 1; d < 64; d <<= 1) {
+                    const int up = __shfl_up(incl, d);
+                    if (lane >= d) incl += up;
+                }
+                if (lane == 63) s_isum[wave] = incl;
+                if (lane == 0) s_big[wave] = bigs;
+                __syncthreads();
+                // the large faces of the chunk: this thread's own pixel, the same key, kept in registers
+#pragma unroll 1
+                for (int w = 0; w < 4; ++w) {
+#pragma unroll 1
+                    for (unsigned long long m = s_big[w]; m != 0ull; m &= m - 1ull) {
+                        const int slot = 64 * w + __ffsll((long long)m) - 1;
+                        float pz, b0, b1, b2;
+                        if (face_at_pixel(s_face[slot][0], s_face[slot][1], s_face[slot][2], s_face[slot][3], s_face[slot][4],
+                                          s_face[slot][5], s_face[slot][6], s_face[slot][7], s_face[slot][8], s_xy[0][tid & (TILE - 1)],
+                                          s_xy[1][tid >> 4], pz, b0, b1, b2)) {
+                            const unsigned long long k = ((unsigned long long)__float_as_uint(pz + 0.0f) << 32) | (unsigned)s_fidx[slot];
+                            own = k < own ? k : own;
+                        }
+                    }
+                }
+                const int i1 = s_isum[0], i2 = i1 + s_isum[1], i3 = i2 + s_isum[2], items = i3 + s_isum[3];
+                const int first = (wave == 0 ? 0 : (wave == 1 ? i1 : (wave == 2 ? i2 : i3))) + incl - mine;
+                for (int ib = 0; ib < items; ib += ITEM_CAP) {
+                    unsigned m = mask;
+                    for (int o = first - ib; m != 0u && o < ITEM_CAP; ++o, m &= m - 1u)
+                        if (o >= 0) s_item[o] = (unsigned short)((tid << 4) | (__ffs(m) - 1));
+                    __syncthreads();
+                    const int ni = min(ITEM_CAP, items - ib);
+                    const int l = tid & 15;
+                    for (int i = tid >> 4; i < ni; i += 16) {
+                        const unsigned it = s_item[i];
+                        const int slot = it >> 4, blk = it & 15;
+                        const int lx = ((blk & 3) << 2) | (l & 3), ly = (blk & 12) | (l >> 2);
+                        float pz, b0, b1, b2;
+                        if (face_at_pixel(s_face[slot][0], s_face[slot][1], s_face[slot][2], s_face[slot][3], s_face[slot][4],
+                                          s_face[slot][5], s_face[slot][6], s_face[slot][7], s_face[slot][8], s_xy[0][lx],
+                                          s_xy[1][ly], pz, b0, b1, b2))
+                            atomicMin(&s_key[ly * TILE + lx],
+                                      ((unsigned long long)__float_as_uint(pz + 0.0f) << 32) | (unsigned)s_fidx[slot]);
+                    }
+                    __syncthreads();      // items, records and s_isum (and, after the last chunk, the index lists) are rewritten next
+                }
+                if (items == 0) __syncthreads();        // (workgroup-uniform) s_isum, s_big and the records are rewritten next
             }
-            __syncthreads();
-            for (int i = 0; i < n; ++i) {
-                eval_face(s_fidx[i], s_face[i][0], s_face[i][1], s_face[i][2], s_face[i][3], s_face[i][4], s_face[i][5],
-                          s_face[i][6], s_face[i][7], s_face[i][8], xf, yf, best);
+        }
+        if constexpr (WALK) {
+            for (int cb = 0; cb < total; cb += LIST_CAP) {
+                const int n = min(LIST_CAP, total - cb);
+#pragma unroll
+                for (int h = 0; h < LIST_CAP / 256; ++h) {
+                    const int slot = tid + 256 * h, i = cb + slot;
+                    if (slot < n) {
+                        const int f = i < o1 ? s_list[0][i] : (i < o2 ? s_list[1][i - o1] : (i < o3 ? s_list[2][i - o2] : s_list[3][i - o3]));
+                        const float4 r0 = rb[3 * (size_t)f], r1 = rb[3 * (size_t)f + 1], r2 = rb[3 * (size_t)f + 2];
+                        s_fidx[slot] = f;
+                        s_face[slot][0] = r0.x; s_face[slot][1] = r0.y; s_face[slot][2] = r0.z;
+                        s_face[slot][3] = r0.w; s_face[slot][4] = r1.x; s_face[slot][5] = r1.y;
+                        s_face[slot][6] = r1.z; s_face[slot][7] = r1.w; s_face[slot][8] = r2.x;
+                    }
+                }
+                __syncthreads();
+                for (int i = 0; i < n; ++i) {
+                    eval_face(s_fidx[i], s_face[i][0], s_face[i][1], s_face[i][2], s_face[i][3], s_face[i][4], s_face[i][5],
+                              s_face[i][6], s_face[i][7], s_face[i][8], xf, yf, best);
+                }
+                __syncthreads();          // the record list (and, after the last chunk, the index lists) are rewritten next
             }
-            __syncthreads();          // the record list (and, after the last chunk, the index lists) are rewritten next
         }
         if (total == 0) __syncthreads();    // (workgroup-uniform) s_wcnt is rewritten by the next super-round
     }
     if (!in_img) return;
     const size_t p = ((size_t)b * S + py) * S + px;
+    if constexpr (!WALK) {
+        // the keys only ordered the candidates: what is stored is the winner evaluated again from its record
+        const unsigned long long shared = any ? s_key[tid] : ~0ull;       // (the last chunk ended with a barrier)
+        const unsigned long long key = shared < own ? shared : own;
+        if (key != ~0ull) {
+            best.f = (int)(unsigned)key;
+            xf = s_xy[0][tid & (TILE - 1)]; yf = s_xy[1][tid >> 4];
+            const float4 r0 = rb[3 * (size_t)best.f], r1 = rb[3 * (size_t)best.f + 1], r2 = rb[3 * (size_t)best.f + 2];
+            face_at_pixel(r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w, r2.x, xf, yf, best.z, best.b0, best.b1, best.b2);
+        }
+    }
     if (best.f >= 0) {
         const float4 r0 = rb[3 * (size_t)best.f], r1 = rb[3 * (size_t)best.f + 1];
         const float d01 = point_line_dist2(xf, yf, r0.x, r0.y, r0.w, r1.x);
@@ -394,17 +589,19 @@ extern "C" int st3d_raster_fwd(const float *verts_ndc, const int32_t *faces, int
     // enough for the all-faces sweep to matter; ST3D_RASTER_BINS=0 keeps the flat sweep (A/B runs)
     static const bool allow_bins = [] { const char *e = getenv("ST3D_RASTER_BINS"); return !(e && e[0] == '0'); }();
     const int nb = st3d::cdiv(tiles, BIN), cap = raster_bin_cap(F);
+    // ST3D_RASTER_WALK=1 (read per call: same-process A/B runs): the per-pixel walk instead of the face-parallel phase 2
+    const char *wk = getenv("ST3D_RASTER_WALK");
+    const auto tile_kernel = (wk && wk[0] == '1') ? raster_tile_kernel<true> : raster_tile_kernel<false>;
     if (allow_bins && Fp > 2048 && workspace_bytes >= st3d_raster_workspace_bytes_binned(B, F, S)) {
         const size_t base = (st3d_raster_workspace_bytes(B, F) + 15) & ~(size_t)15;
         int *bin_count = reinterpret_cast<int *>(reinterpret_cast<char *>(workspace) + base);
         int *bin_list = bin_count + (((size_t)B * nb * nb + 1) & ~(size_t)1);      // 8-byte aligned: read as int2 (cap is even)
         raster_bin_kernel<<<dim3(nb * nb, B), 256, 0, s>>>(words, Fp, nb, cap, bin_count, bin_list);
         ST3D_LAUNCH_CHECK();
-        raster_tile_kernel<<<dim3(tiles, tiles, B), 256, 0, s>>>(rec, words, F, Fp, S, pix_to_face, zbuf, bary, dists, bin_count,
-                                                                bin_list, nb, cap);
+        tile_kernel<<<dim3(tiles, tiles, B), 256, 0, s>>>(rec, words, F, Fp, S, pix_to_face, zbuf, bary, dists, bin_count, bin_list,
+                                                         nb, cap);
     } else {
-        raster_tile_kernel<<<dim3(tiles, tiles, B), 256, 0, s>>>(rec, words, F, Fp, S, pix_to_face, zbuf, bary, dists, nullptr,
-                                                                nullptr, 0, 0);
+        tile_kernel<<<dim3(tiles, tiles, B), 256, 0, s>>>(rec, words, F, Fp, S, pix_to_face, zbuf, bary, dists, nullptr, nullptr, 0, 0);
     }
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;

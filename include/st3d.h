@@ -32,6 +32,7 @@
  *   ST3D_GRAM_FAST=0, ST3D_GRAM_DIAG_TRI=0, ST3D_GRAM_TARGET_WGS, ST3D_GRAM_NSPLIT   Gram forward: generic / full-tile kernels, split counts
  *   ST3D_GRAM_BWD_MT, ST3D_GRAM_BWD_K64, ST3D_GRAM_BWD_SYM=0   Gram backward tile shapes / the general kernel
  *   ST3D_RASTER_BINS=0          flat face sweep instead of the coarse 64x64-pixel bins
+ *   ST3D_RASTER_WALK=1          hard rasteriser: every pixel walks its tile's face list instead of faces in parallel per tile (read per call)
  *   ST3D_POISON_PLAN=1          plan workspaces start as 0xFF (read-before-write detector of the tests)
  *   ST3D_ROCTX=1                roctx ranges around the phases of a step (st3d_trace_push / st3d_trace_pop below)
  * Read by the Python host (st3d/): ST3D_DETERMINISTIC=0 (float-atomic scatters), ST3D_GRAPH=1 (HIP-graph replay of

@@ -66,6 +66,42 @@ static __global__ __launch_bounds__(256) void det_convert_kernel(const long long
     out[i] = accumulate ? out[i] + v : v;
 }
 
+// partial count of the bound pass of the per-pixel scatters (texels, vertex colours): a fixed grid, whatever the image
+constexpr int kPixelPartials = 1024;
+
+// The host side of a fixed-point scatter.  An entry point carves the workspace, launches its own bound kernel into
+// `partials`, calls scale_and_clear(), launches its own scatter kernel with `hdr` and `acc`, and calls convert():
+//     DetRun det(workspace, n_partials, n_accum);
+//     bound_kernel<<<..., s>>>(..., det.partials);           ST3D_LAUNCH_CHECK();
+//     ST3D_TRY(det.scale_and_clear(s));
+//     scatter_kernel<<<..., s>>>(..., det.acc, det.hdr);     ST3D_LAUNCH_CHECK();
+//     ST3D_TRY(det.convert(accumulate, out, s));
+struct DetRun {
+    DetHeader *hdr;
+    float *partials;
+    long long *acc;
+    size_t n_partials, n_accum;
+
+    DetRun(void *ws, size_t n_partials_, size_t n_accum_)
+        : hdr(reinterpret_cast<DetHeader *>(ws)), partials(partials_of(ws)), acc(accum_of(ws, n_partials_)),
+          n_partials(n_partials_), n_accum(n_accum_) {}
+
+    // partials -> the header's scale; accumulators = 0
+    int scale_and_clear(hipStream_t s) const {
+        det_scale_kernel<<<1, 256, 0, s>>>(partials, (int)n_partials, hdr);
+        ST3D_LAUNCH_CHECK();
+        ST3D_HIP(hipMemsetAsync(acc, 0, n_accum * sizeof(long long), s));
+        return ST3D_OK;
+    }
+
+    // out[i] (+)= accumulators[i] / scale; accumulate = 1: `out` is a gradient the result is added to
+    int convert(int accumulate, float *out, hipStream_t s) const {
+        det_convert_kernel<<<st3d::cdiv((long)n_accum, 256), 256, 0, s>>>(acc, n_accum, hdr, accumulate, out);
+        ST3D_LAUNCH_CHECK();
+        return ST3D_OK;
+    }
+};
+
 __device__ __forceinline__ float det_block_sum(float v, float *s4) {      // 256 threads, fixed tree
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = v;

@@ -10,7 +10,7 @@
 //   sample   l0 = floor(lambda), t = lambda - l0; texel = (1 - t) bil(l0) + t bil(l0 + 1); level 0 is tapped exactly as
 //            shade.hip's plain kernel taps it, level l >= 1 at ix_l = (ix + 0.5) / 2^l - 0.5 of the clamped level-0 index.
 //            t == 0: the upper level is neither read nor deposited into (lambda == 0 is the plain kernel bit for bit).
-//   backward d/d(level texels) scattered into a packed-pyramid gradient through shade.hip's per-tile LDS table, run once per
+//   backward d/d(level texels) scattered into a packed-pyramid gradient through the per-tile texel table (tilebins.h), run once per
 //            level of the pair (lower, then upper) in the same 36 KB, then folded by the chain's adjoint; d/d(u,v) through
 //            both levels' taps.  lambda is a constant of the backward.
 //
@@ -23,10 +23,13 @@
 
 #include "common.h"
 #include "det.h"
+#include "shadek1.h"
+#include "tilebins.h"
 
 namespace {
 
-constexpr float kSigma = 1e-4f, kGamma = 1e-4f, kBlendEps = 1e-10f, kZnear = 1.0f, kZfar = 100.0f;
+using namespace st3d_k1;
+
 constexpr int kMaxLevels = 16;
 constexpr int kMaxSide = 16384;          // texpyr.hip's limits: 3 * T^2 < 2^31
 constexpr int kMaxRaster = 4096;         // the rasteriser's limit: fragments exist up to this side
@@ -177,34 +180,6 @@ __global__ __launch_bounds__(256) void mip_lod_kernel(const int32_t *__restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------- sample
-struct Footprint {
-    int x0, x1, r0, r1;
-    float wx0, wx1, wy0, wy1;
-    bool vx0, vx1, vy0, vy1, cx, cy;
-    float ix, iy;                        // the clamped continuous level-0 indices (unflipped frame)
-};
-
-// shade.hip's uv_footprint: the same expressions in the same order (that file is pinned and keeps its own copy)
-__device__ __forceinline__ Footprint uv_footprint(float u, float v, int T) {
-    Footprint o;
-    const float gx = u * 2.0f - 1.0f, gy = v * 2.0f - 1.0f;
-    float ix = ((gx + 1.0f) / 2.0f) * (float)(T - 1);
-    float iy = ((gy + 1.0f) / 2.0f) * (float)(T - 1);
-    o.cx = false; o.cy = false;
-    if (!(ix >= 0.f)) { ix = 0.f; o.cx = true; } else if (ix > (float)(T - 1)) { ix = (float)(T - 1); o.cx = true; }
-    if (!(iy >= 0.f)) { iy = 0.f; o.cy = true; } else if (iy > (float)(T - 1)) { iy = (float)(T - 1); o.cy = true; }
-    const float fx = floorf(ix), fy = floorf(iy);
-    o.x0 = (int)fx; o.x1 = o.x0 + 1;
-    const int yf0 = (int)fy, yf1 = yf0 + 1;
-    o.wx1 = ix - fx; o.wx0 = 1.0f - o.wx1;
-    o.wy1 = iy - fy; o.wy0 = 1.0f - o.wy1;
-    o.vx0 = o.x0 >= 0 && o.x0 < T; o.vx1 = o.x1 >= 0 && o.x1 < T;
-    o.vy0 = yf0 >= 0 && yf0 < T;   o.vy1 = yf1 >= 0 && yf1 < T;
-    o.r0 = (T - 1) - yf0; o.r1 = (T - 1) - yf1;
-    o.ix = ix; o.iy = iy;
-    return o;
-}
-
 // the footprint on level l >= 1 (side n = T >> l) of the level-0 position (ix, iy); cx / cy: this level's own clamp acted
 __device__ __forceinline__ Footprint level_footprint(float ix, float iy, int l, int n) {
     Footprint o;
@@ -222,19 +197,6 @@ __device__ __forceinline__ Footprint level_footprint(float ix, float iy, int l, 
     o.vy0 = yf0 >= 0 && yf0 < n;   o.vy1 = yf1 >= 0 && yf1 < n;
     o.r0 = (n - 1) - yf0; o.r1 = (n - 1) - yf1;
     o.ix = jx; o.iy = jy;
-    return o;
-}
-
-struct Blend { float prob, wnum, delta, denom; };
-
-__device__ __forceinline__ Blend blend_k1(float dist, float z) {
-    Blend o;
-    o.prob = 1.0f / (1.0f + expf(dist / kSigma));
-    const float z_inv = (kZfar - z) / (kZfar - kZnear);
-    const float z_max = fmaxf(z_inv, kBlendEps);
-    o.wnum = o.prob * expf((z_inv - z_max) / kGamma);
-    o.delta = fmaxf(expf((kBlendEps - z_max) / kGamma), kBlendEps);
-    o.denom = o.wnum + o.delta;
     return o;
 }
 
@@ -297,83 +259,6 @@ __global__ __launch_bounds__(256) void shade_mip_fwd_kernel(const int32_t *__res
 }
 
 // ---------------------------------------------------------------------------------------------------- backward
-constexpr int kTexSlots = 2048;      // shade.hip's table: >= 2 x the 4 x 256 corners a tile deposits on ONE level
-constexpr int kTexMax = 1024;
-
-// One pass of shade_bwd_kernel's per-tile pre-aggregation: every lane brings up to four (texel, weight) corners of one level
-// and its three channel factors; texel is the flat index into the packed pyramid.  All 256 lanes call it.
-template <int DET, typename acc_t>
-__device__ __forceinline__ void tile_scatter(int *s_key, int *s_texel, acc_t (*s_acc)[3], int *s_count, const int dep_texel[4],
-                                             const float dep_w[4], const float dep_g[3], unsigned dep_valid, double dscale,
-                                             float *__restrict__ gtex) {
-    const int tid = threadIdx.x;
-    for (int e = tid; e < kTexSlots; e += 256) s_key[e] = -1;
-    if (tid == 0) *s_count = 0;
-    __syncthreads();
-    int slot[4];
-    unsigned mine = 0;               // bit c: this lane's CAS claimed the slot of corner c
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        slot[c] = 0;
-        if (dep_valid >> c & 1) {
-            const int texel = dep_texel[c];
-            int s = (int)(((unsigned)texel * 2654435761u) >> 21) & (kTexSlots - 1);
-            for (;;) {
-                const int prev = atomicCAS(&s_key[s], -1, texel);
-                if (prev == -1) mine |= 1u << c;
-                if (prev == -1 || prev == texel) break;
-                s = (s + 1) & (kTexSlots - 1);
-            }
-            slot[c] = s;
-        }
-    }
-    __syncthreads();                 // every key is in: nobody probes any more
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        const bool own = mine >> c & 1;
-        const unsigned long long owners = __ballot(own);
-        if (owners == 0) continue;
-        const int lane = tid & 63, leader = __ffsll((long long)owners) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(s_count, __popcll(owners));
-        base = __shfl(base, leader);
-        if (own) {
-            const int e = base + __popcll(owners & ((1ull << lane) - 1ull));
-            s_texel[e] = dep_texel[c];
-            s_acc[e][0] = (acc_t)0; s_acc[e][1] = (acc_t)0; s_acc[e][2] = (acc_t)0;
-            s_key[slot[c]] = e;
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-        if (!(dep_valid >> c & 1)) continue;
-        const int e = s_key[slot[c]];
-        const float w = dep_w[c];
-        if (DET) {
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)
-                atomicAdd(reinterpret_cast<unsigned long long *>(&s_acc[e][ch]),
-                          (unsigned long long)st3d_det::det_quantise(dep_g[ch] * w, dscale));
-        } else {
-            atomicAdd(reinterpret_cast<float *>(&s_acc[e][0]), dep_g[0] * w);
-            atomicAdd(reinterpret_cast<float *>(&s_acc[e][1]), dep_g[1] * w);
-            atomicAdd(reinterpret_cast<float *>(&s_acc[e][2]), dep_g[2] * w);
-        }
-    }
-    __syncthreads();
-    const int used = *s_count * 3;
-    for (int e = tid; e < used; e += 256) {
-        const int entry = e / 3, c = e - entry * 3;
-        const acc_t v = s_acc[entry][c];
-        if (v == (acc_t)0) continue;
-        const int texel = s_texel[entry];
-        if (DET) atomicAdd(reinterpret_cast<unsigned long long *>(gtex) + (size_t)texel * 3 + c, (unsigned long long)v);
-        else atomicAdd(gtex + (size_t)texel * 3 + c, (float)v);
-    }
-    __syncthreads();                 // the table is free for the next pass
-}
-
 // what one level of a pixel's pair hands to the scatter and to d/d(ix, iy)
 struct LevelDep {
     int texel[4];
@@ -418,10 +303,7 @@ __global__ __launch_bounds__(256) void shade_mip_bwd_kernel(const float *__restr
                                                             float *__restrict__ gbary,
                                                             const st3d_det::DetHeader *__restrict__ det) {
     typedef typename std::conditional<DET != 0, unsigned long long, float>::type acc_t;
-    __shared__ int s_key[kTexSlots];
-    __shared__ int s_texel[kTexMax];
-    __shared__ acc_t s_acc[kTexMax][3];
-    __shared__ int s_count;
+    ST3D_TEXEL_BINS(bins, acc_t);          // >= 2 x the 4 x 256 corners a tile deposits on ONE level
     const int tid = threadIdx.x;
     const double dscale = DET ? det->scale : 1.0;
     const size_t HW = (size_t)S * S;
@@ -476,12 +358,15 @@ __global__ __launch_bounds__(256) void shade_mip_bwd_kernel(const float *__restr
         }
     }
     if (!gpyr) return;
-    tile_scatter<DET, acc_t>(s_key, s_texel, s_acc, &s_count, lo.texel, lo.w, lo.g, lo.valid, dscale, gpyr);
+    bins.reset();
+    bins.scatter(lo.texel, lo.w, lo.g, lo.valid, dscale, gpyr);
+    __syncthreads();                                     // the table is free for the next pass
     if (!__syncthreads_or(up.valid != 0)) return;        // no pixel of the tile sits between two levels
-    tile_scatter<DET, acc_t>(s_key, s_texel, s_acc, &s_count, up.texel, up.w, up.g, up.valid, dscale, gpyr);
+    bins.reset();
+    bins.scatter(up.texel, up.w, up.g, up.valid, dscale, gpyr);
 }
 
-constexpr int kDetPartials = 1024;
+using st3d_det::kPixelPartials;
 
 int launch_adjoint(const float *gp, int T, int L, int accumulate, float *gtex, hipStream_t s) {
     const size_t n = (size_t)T * T * 3;
@@ -547,7 +432,7 @@ extern "C" int st3d_shade_mip_fwd(const int32_t *pix_to_face, const float *bary,
 
 extern "C" size_t st3d_shade_mip_bwd_workspace_bytes(int T, int L) {
     const size_t n = st3d_mip_numel(T, L);
-    return n ? st3d_det::workspace_bytes(n, kDetPartials) : 0;
+    return n ? st3d_det::workspace_bytes(n, kPixelPartials) : 0;
 }
 
 // grad_pyramid: st3d_mip_numel(T, L) floats of the caller's, OVERWRITTEN with the per-level texel gradient before the fold
@@ -577,18 +462,13 @@ extern "C" int st3d_shade_mip_bwd(const float *grad_rgb, const int32_t *pix_to_f
         return grad_texture ? launch_adjoint(grad_pyramid, T, L, 1, grad_texture, s) : ST3D_OK;
     }
     ST3D_CHECK_ARG(workspace_bytes >= st3d_shade_mip_bwd_workspace_bytes(T, L) && ((uintptr_t)workspace & 15) == 0);
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, kDetPartials);
-    st3d_det::det_abs_sum_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, (size_t)B * 3 * S * S, partials);
+    const st3d_det::DetRun det(workspace, kPixelPartials, nacc);
+    st3d_det::det_abs_sum_kernel<<<kPixelPartials, 256, 0, s>>>(grad_rgb, (size_t)B * 3 * S * S, det.partials);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kDetPartials, hdr);
-    ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    ST3D_TRY(det.scale_and_clear(s));
     shade_mip_bwd_kernel<1><<<grid, 256, 0, s>>>(grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, pyramid, lod, B, S,
-                                                 T, L, lv, tiles, reinterpret_cast<float *>(acc), grad_uv, grad_bary, hdr);
+                                                 T, L, lv, tiles, reinterpret_cast<float *>(det.acc), grad_uv, grad_bary, det.hdr);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 0, grad_pyramid);
-    ST3D_LAUNCH_CHECK();
+    ST3D_TRY(det.convert(0, grad_pyramid, s));
     return launch_adjoint(grad_pyramid, T, L, 1, grad_texture, s);
 }

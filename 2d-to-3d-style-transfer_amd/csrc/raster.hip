@@ -772,21 +772,15 @@ extern "C" int st3d_raster_bwd_det(const float *grad_bary, const int32_t *pix_to
     hipStream_t s = st3d::as_stream(stream);
     const int tiles = (S + 15) / 16;
     const size_t np = (size_t)tiles * tiles * B, nacc = (size_t)B * V * 3;
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, np);
+    const st3d_det::DetRun det(workspace, np, nacc);
     raster_bwd_kernel<1><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_bary, pix_to_face, verts_ndc, faces, B, V, S, tiles, nullptr,
-                                                                nullptr, partials);
+                                                                nullptr, det.partials);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, (int)np, hdr);
-    ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    ST3D_TRY(det.scale_and_clear(s));
     raster_bwd_kernel<2><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_bary, pix_to_face, verts_ndc, faces, B, V, S, tiles,
-                                                                reinterpret_cast<float *>(acc), hdr, nullptr);
+                                                                reinterpret_cast<float *>(det.acc), det.hdr, nullptr);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 0, grad_verts_ndc);
-    ST3D_LAUNCH_CHECK();
-    return ST3D_OK;
+    return det.convert(0, grad_verts_ndc, s);
 }
 
 extern "C" int st3d_project_verts_bwd(const float *verts, int V, const float *R, const float *T, int B,

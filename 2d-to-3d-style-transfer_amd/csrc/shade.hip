@@ -16,50 +16,12 @@
 #include "common.h"
 #include "det.h"
 #include "phong.h"
+#include "shadek1.h"
+#include "tilebins.h"
 
 namespace {
 
-constexpr float kSigma = 1e-4f, kGamma = 1e-4f, kBlendEps = 1e-10f, kZnear = 1.0f, kZfar = 100.0f;
-
-struct Footprint {
-    int x0, x1, r0, r1;
-    float wx0, wx1, wy0, wy1;
-    bool vx0, vx1, vy0, vy1, cx, cy;
-};
-
-// UV -> bilinear footprint in ORIGINAL texture rows: grid = uv*2-1, map flipped vertically,
-// grid_sample(bilinear, align_corners=True, padding_mode='border').
-__device__ __forceinline__ Footprint uv_footprint(float u, float v, int T) {
-    Footprint o;
-    const float gx = u * 2.0f - 1.0f, gy = v * 2.0f - 1.0f;
-    float ix = ((gx + 1.0f) / 2.0f) * (float)(T - 1);
-    float iy = ((gy + 1.0f) / 2.0f) * (float)(T - 1);
-    o.cx = false; o.cy = false;
-    if (!(ix >= 0.f)) { ix = 0.f; o.cx = true; } else if (ix > (float)(T - 1)) { ix = (float)(T - 1); o.cx = true; }
-    if (!(iy >= 0.f)) { iy = 0.f; o.cy = true; } else if (iy > (float)(T - 1)) { iy = (float)(T - 1); o.cy = true; }
-    const float fx = floorf(ix), fy = floorf(iy);
-    o.x0 = (int)fx; o.x1 = o.x0 + 1;
-    const int yf0 = (int)fy, yf1 = yf0 + 1;
-    o.wx1 = ix - fx; o.wx0 = 1.0f - o.wx1;
-    o.wy1 = iy - fy; o.wy0 = 1.0f - o.wy1;
-    o.vx0 = o.x0 >= 0 && o.x0 < T; o.vx1 = o.x1 >= 0 && o.x1 < T;
-    o.vy0 = yf0 >= 0 && yf0 < T;   o.vy1 = yf1 >= 0 && yf1 < T;
-    o.r0 = (T - 1) - yf0; o.r1 = (T - 1) - yf1;
-    return o;
-}
-
-struct Blend { float prob, wnum, delta, denom; };
-
-__device__ __forceinline__ Blend blend_k1(float dist, float z) {
-    Blend o;
-    o.prob = 1.0f / (1.0f + expf(dist / kSigma));
-    const float z_inv = (kZfar - z) / (kZfar - kZnear);
-    const float z_max = fmaxf(z_inv, kBlendEps);
-    o.wnum = o.prob * expf((z_inv - z_max) / kGamma);
-    o.delta = fmaxf(expf((kBlendEps - z_max) / kGamma), kBlendEps);
-    o.denom = o.wnum + o.delta;
-    return o;
-}
+using namespace st3d_k1;
 
 // LIT 1: the texel is lit first (phong.h): colour = ad * texel + sp replaces it in the blend
 template <int LIT = 0>
@@ -180,17 +142,9 @@ __global__ __launch_bounds__(256) void shade_ss_fwd_kernel(const int32_t *__rest
 // per step at config 2): they are first summed per texel in LDS and each distinct texel of the tile then costs three
 // global atomics.  d/d(u,v) and d/d(bary) (vertex path) are per-pixel outputs written directly.
 // A tile in which no pixel has a face writes its zero rows and leaves (one workgroup-wide OR): three quarters of the tiles
-// of a typical view.  The others sum in two pieces, so that only the keys are cleared and only what the tile used is
-// zeroed and flushed:
-//   s_key    open addressing on the texel index, kTexSlots >= 2 x the 4 x 256 footprint corners a tile can deposit: the
-//            probe always terminates.  The lane whose CAS claimed a slot owns the texel.
-//   s_texel, s_acc   one compact entry per distinct texel, kTexMax = 4 x 256 of them: after a barrier every owner takes the
-//            next entry (one LDS atomic per wave and corner), zeroes its three sums, notes the texel and replaces the key by
-//            the entry's number; after the next barrier every lane reads the entry of its slots and deposits.
-// 36 KB + 4 B of LDS in fixed point, 24 KB + 4 B in float: four and six workgroups per CU (the one 56 KB table allowed two).
-constexpr int kTexSlots = 2048;
-constexpr int kTexMax = 1024;
-
+// of a typical view.  The others sum through the texel table of tilebins.h: 36 KB + 4 B of LDS in fixed point, 24 KB + 4 B
+// in float: four and six workgroups per CU (the one 56 KB table it replaced allowed two).
+//
 // DET 0: float LDS table + float global atomics (fast default).  DET 1: the same binning in 64-bit fixed point (LDS and
 // global integer atomics; `gtex` is then the int64 accumulator array and `det` holds the power-of-two scale): bitwise
 // reproducible whatever the order (det.h).
@@ -198,7 +152,7 @@ constexpr int kTexMax = 1024;
 // lighting's own d/dN, d/dP go to grad_np (per pixel) and, through N = sum b_i n_i and P = sum b_i v_i, into gbary.
 // A > 1 (supersampling): S and every per-pixel array are at the SUB-PIXEL side; grad_rgb is (B,3,S/A,S/A) and sub-pixel
 // (yi, xi) takes grad_rgb(yi / A, xi / A) / A^2 -- the backward of the ordered box sum of shade_ss_fwd_kernel.  The tile is
-// still 16 x 16 sub-pixels = 256 footprints, so kTexSlots and kTexMax stay.
+// still 16 x 16 sub-pixels = 256 footprints, so the table's sizes stay.
 template <int DET, int LIT = 0, int A = 1>
 __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict__ grad_rgb, const int32_t *__restrict__ p2f,
                                                         const float *__restrict__ bary, const float *__restrict__ zbuf,
@@ -209,10 +163,7 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
                                                         const st3d_det::DetHeader *__restrict__ det,
                                                         const st3d_phong::LitArgs la = {}) {
     typedef typename std::conditional<DET != 0, unsigned long long, float>::type acc_t;
-    __shared__ int s_key[kTexSlots];
-    __shared__ int s_texel[kTexMax];
-    __shared__ acc_t s_acc[kTexMax][3];
-    __shared__ int s_count;
+    ST3D_TEXEL_BINS(bins, acc_t);
     const int tid = threadIdx.x;
     const double dscale = DET ? det->scale : 1.0;
     const size_t HW = (size_t)S * S;
@@ -228,9 +179,7 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
     }
     if (gtex) {
         if (!__syncthreads_or(f >= 0)) return;           // the same answer in every lane: the whole workgroup leaves
-        for (int e = tid; e < kTexSlots; e += 256) s_key[e] = -1;
-        if (tid == 0) s_count = 0;
-        __syncthreads();
+        bins.reset();                                    // here, so that its barrier is long past when the deposits arrive
     }
     int dep_texel[4];            // this pixel's footprint corners: texel, weight; dep_valid: bit c = corner c deposits
     float dep_w[4], dep_g[3] = {0.f, 0.f, 0.f};
@@ -305,69 +254,7 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
         dep_g[0] = gk[0]; dep_g[1] = gk[1]; dep_g[2] = gk[2];
         dep_valid = (q.vy0 && q.vx0 ? 1u : 0u) | (q.vy0 && q.vx1 ? 2u : 0u) | (q.vy1 && q.vx0 ? 4u : 0u) | (q.vy1 && q.vx1 ? 8u : 0u);
     }
-    if (gtex) {
-        int slot[4];
-        unsigned mine = 0;               // bit c: this lane's CAS claimed the slot of corner c
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            slot[c] = 0;
-            if (dep_valid >> c & 1) {
-                const int texel = dep_texel[c];
-                int s = (int)(((unsigned)texel * 2654435761u) >> 21) & (kTexSlots - 1);
-                for (;;) {
-                    const int prev = atomicCAS(&s_key[s], -1, texel);
-                    if (prev == -1) mine |= 1u << c;
-                    if (prev == -1 || prev == texel) break;
-                    s = (s + 1) & (kTexSlots - 1);
-                }
-                slot[c] = s;
-            }
-        }
-        __syncthreads();                 // every key is in: nobody probes any more
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const bool own = mine >> c & 1;
-            const unsigned long long owners = __ballot(own);
-            if (owners == 0) continue;
-            const int lane = tid & 63, leader = __ffsll((long long)owners) - 1;
-            int base = 0;
-            if (lane == leader) base = atomicAdd(&s_count, __popcll(owners));
-            base = __shfl(base, leader);
-            if (own) {
-                const int e = base + __popcll(owners & ((1ull << lane) - 1ull));
-                s_texel[e] = dep_texel[c];
-                s_acc[e][0] = (acc_t)0; s_acc[e][1] = (acc_t)0; s_acc[e][2] = (acc_t)0;
-                s_key[slot[c]] = e;
-            }
-        }
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            if (!(dep_valid >> c & 1)) continue;
-            const int e = s_key[slot[c]];
-            const float w = dep_w[c];
-            if (DET) {
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch)
-                    atomicAdd(reinterpret_cast<unsigned long long *>(&s_acc[e][ch]),
-                              (unsigned long long)st3d_det::det_quantise(dep_g[ch] * w, dscale));
-            } else {
-                atomicAdd(reinterpret_cast<float *>(&s_acc[e][0]), dep_g[0] * w);
-                atomicAdd(reinterpret_cast<float *>(&s_acc[e][1]), dep_g[1] * w);
-                atomicAdd(reinterpret_cast<float *>(&s_acc[e][2]), dep_g[2] * w);
-            }
-        }
-        __syncthreads();
-        const int used = s_count * 3;
-        for (int e = tid; e < used; e += 256) {
-            const int entry = e / 3, c = e - entry * 3;
-            const acc_t v = s_acc[entry][c];
-            if (v == (acc_t)0) continue;
-            const int texel = s_texel[entry];
-            if (DET) atomicAdd(reinterpret_cast<unsigned long long *>(gtex) + (size_t)texel * 3 + c, (unsigned long long)v);
-            else atomicAdd(gtex + (size_t)texel * 3 + c, (float)v);
-        }
-    }
+    if (gtex) bins.scatter(dep_texel, dep_w, dep_g, dep_valid, dscale, gtex);
 }
 
 // out = img*mask + bg*(1-mask)   (utils.py:23,27); bg == nullptr: out = img*mask
@@ -593,13 +480,11 @@ extern "C" int st3d_shade_ss_bwd(const float *grad_rgb, const int32_t *pix_to_fa
     return ST3D_OK;
 }
 
-namespace {
 // (bound on any texel-channel sum: sum over the batch of |grad_rgb| -- blend weight and bilinear weights are <= 1: st3d_det::det_abs_sum_kernel)
-constexpr int kDetPartials = 1024;
-}  // namespace
+using st3d_det::kPixelPartials;
 
 extern "C" size_t st3d_shade_bwd_det_workspace_bytes(int T) {
-    return st3d_det::workspace_bytes((size_t)T * T * 3, kDetPartials);
+    return st3d_det::workspace_bytes((size_t)T * T * 3, kPixelPartials);
 }
 
 // st3d_shade_bwd with a bitwise reproducible texture gradient: fixed-point accumulation (det.h); measured no slower than the
@@ -624,27 +509,21 @@ extern "C" int st3d_shade_ss_bwd_det(const float *grad_rgb, const int32_t *pix_t
     ST3D_CHECK_ARG(a >= 1 && a <= 4 && S <= kMaxSide / a);
     ST3D_CHECK_ARG(workspace_bytes >= st3d_shade_bwd_det_workspace_bytes(T) && ((uintptr_t)workspace & 15) == 0);
     hipStream_t s = st3d::as_stream(stream);
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, kDetPartials);
-    const size_t npx = (size_t)B * 3 * S * S, nacc = (size_t)T * T * 3;
+    const st3d_det::DetRun det(workspace, kPixelPartials, (size_t)T * T * 3);
+    const size_t npx = (size_t)B * 3 * S * S;
     if (a == 1) {
-        st3d_det::det_abs_sum_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, npx, partials);
+        st3d_det::det_abs_sum_kernel<<<kPixelPartials, 256, 0, s>>>(grad_rgb, npx, det.partials);
     } else {
-        ST3D_SS_DISPATCH(a, (ss_abs_sum_kernel<A_><<<kDetPartials, 256, 0, s>>>(grad_rgb, pix_to_face, B, S, 1.f, partials)));
+        ST3D_SS_DISPATCH(a, (ss_abs_sum_kernel<A_><<<kPixelPartials, 256, 0, s>>>(grad_rgb, pix_to_face, B, S, 1.f, det.partials)));
     }
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kDetPartials, hdr);
-    ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    ST3D_TRY(det.scale_and_clear(s));
     const int SS = a * S, tiles = (SS + 15) / 16;
     ST3D_SS_DISPATCH(a, (shade_bwd_kernel<1, 0, A_><<<dim3(tiles * tiles, B), 256, 0, s>>>(
                             grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, SS, T, tiles,
-                            reinterpret_cast<float *>(acc), grad_uv, grad_bary, hdr)));
+                            reinterpret_cast<float *>(det.acc), grad_uv, grad_bary, det.hdr)));
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_texture);
-    ST3D_LAUNCH_CHECK();
-    return ST3D_OK;
+    return det.convert(1, grad_texture, s);
 }
 
 extern "C" int st3d_apply_background(const float *img, const float *mask, const float *bg, int bg_batch, int B, int S,
@@ -740,24 +619,18 @@ extern "C" int st3d_shade_ss_lit_bwd(const float *grad_rgb, const int32_t *pix_t
     // fixed point: every texture contribution is |g| k ad_c w <= |g| weight_bound (k, w <= 1; weight_bound >= max ad_c)
     ST3D_CHECK_ARG(grad_texture);
     ST3D_CHECK_ARG(workspace_bytes >= st3d_shade_bwd_det_workspace_bytes(T) && ((uintptr_t)workspace & 15) == 0);
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, kDetPartials);
-    const size_t npx = (size_t)B * 3 * S * S, nacc = (size_t)T * T * 3;
+    const st3d_det::DetRun det(workspace, kPixelPartials, (size_t)T * T * 3);
+    const size_t npx = (size_t)B * 3 * S * S;
     if (a == 1) {
-        st3d_det::det_abs_sum_scaled_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, npx, weight_bound, partials);
+        st3d_det::det_abs_sum_scaled_kernel<<<kPixelPartials, 256, 0, s>>>(grad_rgb, npx, weight_bound, det.partials);
     } else {
-        ST3D_SS_DISPATCH(a, (ss_abs_sum_kernel<A_><<<kDetPartials, 256, 0, s>>>(grad_rgb, pix_to_face, B, S, weight_bound, partials)));
+        ST3D_SS_DISPATCH(a, (ss_abs_sum_kernel<A_><<<kPixelPartials, 256, 0, s>>>(grad_rgb, pix_to_face, B, S, weight_bound, det.partials)));
     }
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kDetPartials, hdr);
-    ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    ST3D_TRY(det.scale_and_clear(s));
     ST3D_SS_DISPATCH(a, (shade_bwd_kernel<1, 1, A_><<<dim3(tiles * tiles, B), 256, 0, s>>>(
                             grad_rgb, pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, SS, T, tiles,
-                            reinterpret_cast<float *>(acc), nullptr, grad_bary, hdr, la)));
+                            reinterpret_cast<float *>(det.acc), nullptr, grad_bary, det.hdr, la)));
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_texture);
-    ST3D_LAUNCH_CHECK();
-    return ST3D_OK;
+    return det.convert(1, grad_texture, s);
 }

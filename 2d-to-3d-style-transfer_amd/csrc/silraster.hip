@@ -492,19 +492,13 @@ extern "C" int st3d_silraster_bwd(const float *face_records, const float *verts_
     }
     ST3D_CHECK_ARG(workspace_bytes >= st3d_silraster_bwd_workspace_bytes(B, V, S) && ((uintptr_t)workspace & 15) == 0);
     const size_t np = (size_t)tiles * tiles * B;
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, np);
+    const st3d_det::DetRun det(workspace, np, nacc);
     silraster_bwd_kernel<1><<<grid, 256, 0, s>>>(a, state, n, grad_alpha, grad_scale, verts_ndc, faces, V, z_clip, nullptr, nullptr,
-                                                 partials);
+                                                 det.partials);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, (int)np, hdr);
-    ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    ST3D_TRY(det.scale_and_clear(s));
     silraster_bwd_kernel<2><<<grid, 256, 0, s>>>(a, state, n, grad_alpha, grad_scale, verts_ndc, faces, V, z_clip,
-                                                 reinterpret_cast<float *>(acc), hdr, nullptr);
+                                                 reinterpret_cast<float *>(det.acc), det.hdr, nullptr);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 0, grad_verts_ndc);
-    ST3D_LAUNCH_CHECK();
-    return ST3D_OK;
+    return det.convert(0, grad_verts_ndc, s);
 }

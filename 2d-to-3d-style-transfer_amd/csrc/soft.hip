@@ -15,6 +15,7 @@
 #include "common.h"
 #include "det.h"
 #include "phong.h"
+#include "shadek1.h"
 #include "softgeom.h"
 
 namespace {
@@ -270,25 +271,8 @@ __global__ __launch_bounds__(256) void raster_k_kernel(const float4 *__restrict_
 }
 
 // ------------------------------------------------------------------------------------------ shading
-struct Footprint { int x0, x1, r0, r1; float wx0, wx1, wy0, wy1; bool vx0, vx1, vy0, vy1, cx, cy; };
-__device__ __forceinline__ Footprint uv_footprint(float u, float v, int T) {
-    Footprint o;
-    const float gx = u * 2.0f - 1.0f, gy = v * 2.0f - 1.0f;
-    float ix = ((gx + 1.0f) / 2.0f) * (float)(T - 1);
-    float iy = ((gy + 1.0f) / 2.0f) * (float)(T - 1);
-    o.cx = false; o.cy = false;
-    if (!(ix >= 0.f)) { ix = 0.f; o.cx = true; } else if (ix > (float)(T - 1)) { ix = (float)(T - 1); o.cx = true; }
-    if (!(iy >= 0.f)) { iy = 0.f; o.cy = true; } else if (iy > (float)(T - 1)) { iy = (float)(T - 1); o.cy = true; }
-    const float fx = floorf(ix), fy = floorf(iy);
-    o.x0 = (int)fx; o.x1 = o.x0 + 1;
-    const int yf0 = (int)fy, yf1 = yf0 + 1;
-    o.wx1 = ix - fx; o.wx0 = 1.0f - o.wx1;
-    o.wy1 = iy - fy; o.wy0 = 1.0f - o.wy1;
-    o.vx0 = o.x0 >= 0 && o.x0 < T; o.vx1 = o.x1 >= 0 && o.x1 < T;
-    o.vy0 = yf0 >= 0 && yf0 < T;   o.vy1 = yf1 >= 0 && yf1 < T;
-    o.r0 = (T - 1) - yf0; o.r1 = (T - 1) - yf1;
-    return o;
-}
+using st3d_k1::Footprint;           // the bilinear footprint of the K = 1 kernels: the same texels and weights
+using st3d_k1::uv_footprint;
 
 struct SoftArgs {
     const int32_t *p2f; const float *bary, *zbuf, *dists, *uvs; const int32_t *fuv; const float *tex;
@@ -853,10 +837,10 @@ extern "C" int st3d_shade_soft_bwd(const float *grad_rgb, const int32_t *pix_to_
     return ST3D_OK;
 }
 
-namespace { constexpr int kSoftDetPartials = 1024; }
+using st3d_det::kPixelPartials;
 
 extern "C" size_t st3d_shade_soft_bwd_det_workspace_bytes(int T) {
-    return st3d_det::workspace_bytes((size_t)T * T * 3, kSoftDetPartials);
+    return st3d_det::workspace_bytes((size_t)T * T * 3, kPixelPartials);
 }
 
 // st3d_shade_soft_bwd with a bitwise reproducible texture gradient (64-bit fixed-point accumulation, det.h; the bound of
@@ -873,22 +857,15 @@ extern "C" int st3d_shade_soft_bwd_det(const float *grad_rgb, const int32_t *pix
     hipStream_t s = st3d::as_stream(stream);
     SoftArgs a{pix_to_face, bary, zbuf, dists, verts_uvs, faces_uvs, texture, B, S, T, K, sigma, gamma, background[0],
                background[1], background[2]};
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, kSoftDetPartials);
-    const size_t npx = (size_t)B * 3 * S * S, nacc = (size_t)T * T * 3;
-    st3d_det::det_abs_sum_kernel<<<kSoftDetPartials, 256, 0, s>>>(grad_rgb, npx, partials);
+    const st3d_det::DetRun det(workspace, kPixelPartials, (size_t)T * T * 3);
+    st3d_det::det_abs_sum_kernel<<<kPixelPartials, 256, 0, s>>>(grad_rgb, (size_t)B * 3 * S * S, det.partials);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kSoftDetPartials, hdr);
-    ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    ST3D_TRY(det.scale_and_clear(s));
     const int tiles = (S + 15) / 16;
-    soft_shade_kernel<1, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(a, nullptr, nullptr, grad_rgb, reinterpret_cast<float *>(acc),
-                                                                   grad_bary, grad_zbuf, grad_dists, tiles, hdr);
+    soft_shade_kernel<1, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(a, nullptr, nullptr, grad_rgb, reinterpret_cast<float *>(det.acc),
+                                                                   grad_bary, grad_zbuf, grad_dists, tiles, det.hdr);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_texture);
-    ST3D_LAUNCH_CHECK();
-    return ST3D_OK;
+    return det.convert(1, grad_texture, s);
 }
 
 extern "C" int st3d_raster_soft_bwd(const float *grad_bary, const float *grad_zbuf, const float *grad_dists,
@@ -925,23 +902,17 @@ extern "C" int st3d_raster_soft_bwd_det(const float *grad_bary, const float *gra
     hipStream_t s = st3d::as_stream(stream);
     const int tiles = (S + 15) / 16;
     const size_t np = (size_t)tiles * tiles * B, nacc = (size_t)B * V * 3;
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, np);
+    const st3d_det::DetRun det(workspace, np, nacc);
     raster_k_bwd_kernel<1><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_bary, grad_zbuf, grad_dists, pix_to_face, verts_ndc, faces, B,
                                                                   V, S, K, clip_bary, perspective_correct, tiles, nullptr, frag_slot,
-                                                                  z_clip, nullptr, partials);
+                                                                  z_clip, nullptr, det.partials);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, (int)np, hdr);
-    ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    ST3D_TRY(det.scale_and_clear(s));
     raster_k_bwd_kernel<2><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_bary, grad_zbuf, grad_dists, pix_to_face, verts_ndc, faces, B,
                                                                   V, S, K, clip_bary, perspective_correct, tiles,
-                                                                  reinterpret_cast<float *>(acc), frag_slot, z_clip, hdr, nullptr);
+                                                                  reinterpret_cast<float *>(det.acc), frag_slot, z_clip, det.hdr, nullptr);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 0, grad_verts_ndc);
-    ST3D_LAUNCH_CHECK();
-    return ST3D_OK;
+    return det.convert(0, grad_verts_ndc, s);
 }
 
 // ------------------------------------------------------------------------------------------ lit shading (phong.h)
@@ -1004,19 +975,12 @@ extern "C" int st3d_shade_soft_lit_bwd(const float *grad_rgb, const int32_t *pix
     // fixed point: every texture contribution is |g| kw ad_c w <= |g| weight_bound
     ST3D_CHECK_ARG(grad_texture);
     ST3D_CHECK_ARG(workspace_bytes >= st3d_shade_soft_bwd_det_workspace_bytes(T) && ((uintptr_t)workspace & 15) == 0);
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, kSoftDetPartials);
-    const size_t npx = (size_t)B * 3 * S * S, nacc = (size_t)T * T * 3;
-    st3d_det::det_abs_sum_scaled_kernel<<<kSoftDetPartials, 256, 0, s>>>(grad_rgb, npx, weight_bound, partials);
+    const st3d_det::DetRun det(workspace, kPixelPartials, (size_t)T * T * 3);
+    st3d_det::det_abs_sum_scaled_kernel<<<kPixelPartials, 256, 0, s>>>(grad_rgb, (size_t)B * 3 * S * S, weight_bound, det.partials);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kSoftDetPartials, hdr);
+    ST3D_TRY(det.scale_and_clear(s));
+    soft_shade_kernel<1, 1, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(a, nullptr, nullptr, grad_rgb, reinterpret_cast<float *>(det.acc),
+                                                                      grad_bary, grad_zbuf, grad_dists, tiles, det.hdr, la);
     ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
-    soft_shade_kernel<1, 1, 1><<<dim3(tiles * tiles, B), 256, 0, s>>>(a, nullptr, nullptr, grad_rgb, reinterpret_cast<float *>(acc),
-                                                                      grad_bary, grad_zbuf, grad_dists, tiles, hdr, la);
-    ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_texture);
-    ST3D_LAUNCH_CHECK();
-    return ST3D_OK;
+    return det.convert(1, grad_texture, s);
 }

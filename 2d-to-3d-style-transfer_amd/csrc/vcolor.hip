@@ -3,7 +3,7 @@
 // TexturesVertex.sample_textures / interpolate_face_attributes under SoftPhongShader(AmbientLights) and of their autograd
 // backward.  No UV atlas and no texture map: the colour of a covered pixel is
 //     t_c = b0 C[v0][c] + b1 C[v1][c] + b2 C[v2][c]        (v_i = faces[f][i], left to right, no contraction)
-//     rgb_c = (wnum t_c + delta 1.0f) / denom               (blend_k1 and the mask exactly as shade.hip's shade_fwd_kernel)
+//     rgb_c = (wnum t_c + delta 1.0f) / denom               (shadek1.h's blend_k1, the mask as in shade.hip's shade_fwd_kernel)
 // and white with mask 0 where there is no face.  Backward, with k = wnum / denom and gk_c = g_c k:
 //     dC[v_i][c] += b_i gk_c  (nine deposits per covered pixel),   db_i = sum_c gk_c C[v_i][c]  (0 on uncovered pixels);
 // nothing flows through dists / zbuf (as on the UV path).
@@ -14,24 +14,12 @@
 
 #include "common.h"
 #include "det.h"
+#include "shadek1.h"
+#include "tilebins.h"
 
 namespace {
 
-constexpr float kSigma = 1e-4f, kGamma = 1e-4f, kBlendEps = 1e-10f, kZnear = 1.0f, kZfar = 100.0f;
-
-struct Blend { float prob, wnum, delta, denom; };
-
-// (shade.hip's blend_k1: the same expressions in the same order)
-__device__ __forceinline__ Blend blend_k1(float dist, float z) {
-    Blend o;
-    o.prob = 1.0f / (1.0f + expf(dist / kSigma));
-    const float z_inv = (kZfar - z) / (kZfar - kZnear);
-    const float z_max = fmaxf(z_inv, kBlendEps);
-    o.wnum = o.prob * expf((z_inv - z_max) / kGamma);
-    o.delta = fmaxf(expf((kBlendEps - z_max) / kGamma), kBlendEps);
-    o.denom = o.wnum + o.delta;
-    return o;
-}
+using namespace st3d_k1;
 
 // one thread per pixel, coalesced per colour plane
 __global__ __launch_bounds__(256) void shade_vc_fwd_kernel(const int32_t *__restrict__ p2f, const float *__restrict__ bary,
@@ -61,21 +49,12 @@ __global__ __launch_bounds__(256) void shade_vc_fwd_kernel(const int32_t *__rest
 }
 
 // Colour backward.  One workgroup per 16x16-pixel tile of one view, the structure of shade.hip's shade_bwd_kernel with the
-// vertex index in the texel's place: the nine contributions of a pixel are summed per vertex in LDS first and each distinct
-// vertex of the tile then costs three global atomics.  A tile in which no pixel has a face writes its zero rows of gbary and
-// leaves (one workgroup-wide OR).
-//   s_key   open addressing on the vertex index; kVcSlots >= 2 x the 3 x 256 corners a tile can deposit into, so the probe
-//           always terminates and no overflow path to global memory exists.  The lane whose CAS claimed a slot owns the vertex.
-//   s_vert, s_acc   one compact entry per distinct vertex, kVcMax = 3 x 256: after a barrier every owner takes the next
-//           entry (one LDS atomic per wave and corner), zeroes its three sums, notes the vertex and replaces the key by the
-//           entry's number; after the next barrier every lane reads the entries of its slots and deposits.
-// 29 KB + 4 B of LDS in fixed point, 20 KB + 4 B in float.
+// vertex index in the texel's place: the nine contributions of a pixel are summed per vertex in LDS first (the vertex table
+// of tilebins.h: 29 KB + 4 B of LDS in fixed point, 20 KB + 4 B in float) and each distinct vertex of the tile then costs
+// three global atomics.  A tile in which no pixel has a face writes its zero rows of gbary and leaves (one workgroup-wide OR).
 // DET 0: float table + float global atomics into gcol (V,3).  DET 1: the same binning in 64-bit fixed point (det.h): gcol is
 // the int64 accumulator array and `det` holds the power-of-two scale.  gcol == nullptr (the vertices alone are optimised):
 // no table, gbary only.
-constexpr int kVcSlots = 2048;
-constexpr int kVcMax = 768;
-
 template <int DET>
 __global__ __launch_bounds__(256) void shade_vc_bwd_kernel(const float *__restrict__ grad_rgb, const int32_t *__restrict__ p2f,
                                                            const float *__restrict__ bary, const float *__restrict__ zbuf,
@@ -84,10 +63,7 @@ __global__ __launch_bounds__(256) void shade_vc_bwd_kernel(const float *__restri
                                                            float *__restrict__ gcol, float *__restrict__ gbary,
                                                            const st3d_det::DetHeader *__restrict__ det) {
     typedef typename std::conditional<DET != 0, unsigned long long, float>::type acc_t;
-    __shared__ int s_key[kVcSlots];
-    __shared__ int s_vert[kVcMax];
-    __shared__ acc_t s_acc[kVcMax][3];
-    __shared__ int s_count;
+    ST3D_VERTEX_BINS(bins, acc_t);
     const int tid = threadIdx.x;
     const double dscale = DET ? det->scale : 1.0;
     const size_t HW = (size_t)S * S;
@@ -100,9 +76,7 @@ __global__ __launch_bounds__(256) void shade_vc_bwd_kernel(const float *__restri
     if (in_img && f < 0 && gbary) { gbary[3 * i] = 0.f; gbary[3 * i + 1] = 0.f; gbary[3 * i + 2] = 0.f; }
     if (gcol) {
         if (!__syncthreads_or(f >= 0)) return;           // the same answer in every lane: the whole workgroup leaves
-        for (int e = tid; e < kVcSlots; e += 256) s_key[e] = -1;
-        if (tid == 0) s_count = 0;
-        __syncthreads();
+        bins.reset();
     }
     int dep_vert[3] = {0, 0, 0};        // this pixel's three vertices, their barycentric weights and g k per channel
     float dep_w[3] = {0.f, 0.f, 0.f}, dep_g[3] = {0.f, 0.f, 0.f};
@@ -123,69 +97,7 @@ __global__ __launch_bounds__(256) void shade_vc_bwd_kernel(const float *__restri
         }
         dep_g[0] = gk[0]; dep_g[1] = gk[1]; dep_g[2] = gk[2];
     }
-    if (!gcol) return;
-    const bool dep = f >= 0;
-    int slot[3] = {0, 0, 0};
-    unsigned mine = 0;               // bit j: this lane's CAS claimed the slot of corner j
-    if (dep) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int v = dep_vert[j];
-            int s = (int)(((unsigned)v * 2654435761u) >> 21) & (kVcSlots - 1);
-            for (;;) {
-                const int prev = atomicCAS(&s_key[s], -1, v);
-                if (prev == -1) mine |= 1u << j;
-                if (prev == -1 || prev == v) break;
-                s = (s + 1) & (kVcSlots - 1);
-            }
-            slot[j] = s;
-        }
-    }
-    __syncthreads();                 // every key is in: nobody probes any more
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const bool own = mine >> j & 1;
-        const unsigned long long owners = __ballot(own);
-        if (owners == 0) continue;
-        const int lane = tid & 63, leader = __ffsll((long long)owners) - 1;
-        int base = 0;
-        if (lane == leader) base = atomicAdd(&s_count, __popcll(owners));
-        base = __shfl(base, leader);
-        if (own) {
-            const int e = base + __popcll(owners & ((1ull << lane) - 1ull));
-            s_vert[e] = dep_vert[j];
-            s_acc[e][0] = (acc_t)0; s_acc[e][1] = (acc_t)0; s_acc[e][2] = (acc_t)0;
-            s_key[slot[j]] = e;
-        }
-    }
-    __syncthreads();
-    if (dep) {
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int e = s_key[slot[j]];
-            const float w = dep_w[j];
-            if (DET) {
-#pragma unroll
-                for (int ch = 0; ch < 3; ++ch)
-                    atomicAdd(reinterpret_cast<unsigned long long *>(&s_acc[e][ch]),
-                              (unsigned long long)st3d_det::det_quantise(w * dep_g[ch], dscale));
-            } else {
-                atomicAdd(reinterpret_cast<float *>(&s_acc[e][0]), w * dep_g[0]);
-                atomicAdd(reinterpret_cast<float *>(&s_acc[e][1]), w * dep_g[1]);
-                atomicAdd(reinterpret_cast<float *>(&s_acc[e][2]), w * dep_g[2]);
-            }
-        }
-    }
-    __syncthreads();
-    const int used = s_count * 3;
-    for (int e = tid; e < used; e += 256) {
-        const int entry = e / 3, c = e - entry * 3;
-        const acc_t v = s_acc[entry][c];
-        if (v == (acc_t)0) continue;
-        const int vert = s_vert[entry];
-        if (DET) atomicAdd(reinterpret_cast<unsigned long long *>(gcol) + (size_t)vert * 3 + c, (unsigned long long)v);
-        else atomicAdd(gcol + (size_t)vert * 3 + c, (float)v);
-    }
+    if (gcol) bins.scatter(dep_vert, dep_w, dep_g, f >= 0 ? 7u : 0u, dscale, gcol);
 }
 
 // The fixed-point bound of the colour scatter: partials[block] = sum over the block's grid-stride share of the B*S^2 pixels
@@ -223,7 +135,7 @@ __global__ __launch_bounds__(256) void vc_abs_sum_kernel(const float *__restrict
 }
 
 constexpr int kMaxSide = 4096;      // the rasteriser's limit: fragments exist up to this side
-constexpr int kDetPartials = 1024;
+using st3d_det::kPixelPartials;
 
 }  // namespace
 
@@ -253,7 +165,7 @@ extern "C" int st3d_shade_vc_bwd(const float *grad_rgb, const int32_t *pix_to_fa
 }
 
 extern "C" size_t st3d_shade_vc_bwd_det_workspace_bytes(int V) {
-    return V > 0 ? st3d_det::workspace_bytes((size_t)V * 3, kDetPartials) : 0;
+    return V > 0 ? st3d_det::workspace_bytes((size_t)V * 3, kPixelPartials) : 0;
 }
 
 extern "C" int st3d_shade_vc_bwd_det(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
@@ -265,20 +177,13 @@ extern "C" int st3d_shade_vc_bwd_det(const float *grad_rgb, const int32_t *pix_t
     ST3D_CHECK_ARG(B > 0 && S > 0 && S <= kMaxSide && F > 0 && V > 0);
     ST3D_CHECK_ARG(workspace_bytes >= st3d_shade_vc_bwd_det_workspace_bytes(V) && ((uintptr_t)workspace & 15) == 0);
     hipStream_t s = st3d::as_stream(stream);
-    auto *hdr = reinterpret_cast<st3d_det::DetHeader *>(workspace);
-    float *partials = st3d_det::partials_of(workspace);
-    long long *acc = st3d_det::accum_of(workspace, kDetPartials);
-    const size_t nacc = (size_t)V * 3;
-    vc_abs_sum_kernel<<<kDetPartials, 256, 0, s>>>(grad_rgb, pix_to_face, bary, B, S, partials);
+    const st3d_det::DetRun det(workspace, kPixelPartials, (size_t)V * 3);
+    vc_abs_sum_kernel<<<kPixelPartials, 256, 0, s>>>(grad_rgb, pix_to_face, bary, B, S, det.partials);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_scale_kernel<<<1, 256, 0, s>>>(partials, kDetPartials, hdr);
-    ST3D_LAUNCH_CHECK();
-    ST3D_HIP(hipMemsetAsync(acc, 0, nacc * sizeof(long long), s));
+    ST3D_TRY(det.scale_and_clear(s));
     const int tiles = (S + 15) / 16;
     shade_vc_bwd_kernel<1><<<dim3(tiles * tiles, B), 256, 0, s>>>(grad_rgb, pix_to_face, bary, zbuf, dists, faces, verts_colors, B,
-                                                                  S, tiles, reinterpret_cast<float *>(acc), grad_bary, hdr);
+                                                                  S, tiles, reinterpret_cast<float *>(det.acc), grad_bary, det.hdr);
     ST3D_LAUNCH_CHECK();
-    st3d_det::det_convert_kernel<<<st3d::cdiv((long)nacc, 256), 256, 0, s>>>(acc, nacc, hdr, 1, grad_colors);
-    ST3D_LAUNCH_CHECK();
-    return ST3D_OK;
+    return det.convert(1, grad_colors, s);
 }

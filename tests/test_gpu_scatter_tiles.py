@@ -7,7 +7,14 @@ Fixed point (the default): integer sums are order-free, so the texture gradient 
 tests/golden/scatter_tiles_parent.npz -- the non-zero texels (and d/d bary entries) recorded on the GPU from the build
 before the table was split.  Float atomics: against the fp64 CPU oracle at 1e-5 of its max, the bound of
 test_gpu_kernels.py::test_shade_fwd_bwd_match_oracle.  Per-pixel outputs of uncovered pixels are exactly zero, with
-torch.empty handing out NaN-filled memory."""
+torch.empty handing out NaN-filled memory.
+
+The variants (tests/_scatter_scene.py::variants): the same scene through the other kernels that share the K = 1 arithmetic
+(csrc/shadek1.h) and the tile table (csrc/tilebins.h) -- the forward kernels, the supersampled, lit, mip-mapped and
+per-vertex-colour backward and the soft backward at K = 1, all in fixed point -- twice the same bits, and the bits of
+tests/golden/scatter_variants_parent.npz, recorded by tools/record_scatter_parent.py on a build of the commit before the
+copies were folded together.  That file holds a SHA-256 and the non-zero count per output, not the values: stored like
+the plain case's fixture they are 119 686 values and 587 KB compressed, two and a half times that fixture."""
 import os
 
 import numpy as np
@@ -135,3 +142,47 @@ def test_uncovered_pixels_get_exact_zeros_over_poison(dev, ops, scene, det):
     assert _bits(guv)[~empty].any() and _bits(gbary)[~empty].any()
     for t in (gt, guv, gbary):
         assert torch.isfinite(t).all()
+
+
+@pytest.fixture(scope="module")
+def variants_parent(golden_dir):
+    d = np.load(os.path.join(golden_dir, "scatter_variants_parent.npz"))
+    return {k: d[k] for k in d.files}
+
+
+@pytest.fixture(scope="module")
+def variant_runs(dev, ops):
+    """every variant, run twice, once for all the cases below"""
+    return sc.variants(ops, dev), sc.variants(ops, dev)
+
+
+VARIANTS = {
+    "forward": ("fwd.rgb", "fwd.mask", "ss_fwd.rgb", "ss_fwd.coverage", "mip_fwd.rgb", "mip_fwd.mask", "vc_fwd.rgb",
+                "vc_fwd.mask", "soft_fwd.rgb", "soft_fwd.alpha"),
+    "ss_bwd": ("ss_bwd_T4.grad_texture", "ss_bwd_T4.grad_bary", "ss_bwd_T64.grad_texture", "ss_bwd_T64.grad_bary"),
+    "lit_bwd": ("lit_bwd.grad_texture", "lit_bwd.grad_bary"),
+    "mip_bwd": ("mip_bwd_T64.grad_texture", "mip_bwd_T64.grad_bary", "mip_bwd_T4.grad_texture", "mip_bwd_T4.grad_bary"),
+    "vc_bwd": ("vc_bwd_shared.grad_colors", "vc_bwd_shared.grad_bary", "vc_bwd_own.grad_colors", "vc_bwd_own.grad_bary"),
+    "soft_bwd": ("soft_bwd.grad_texture",),
+}
+
+
+def test_variant_cases_are_all_recorded(variants_parent):
+    names = sorted(n for group in VARIANTS.values() for n in group)
+    assert sorted(k[:-len(".sha256")] for k in variants_parent if k.endswith(".sha256")) == names
+    own_p2f, own_faces = sc.own_faces()
+    tile = own_p2f[2, :16, :16]
+    assert len(np.unique(own_faces[tile.reshape(-1)])) == 768           # the vertex table's worst case: a full tile
+    lod = sc.lod_plane(3)[2]
+    assert lod.min() == 0 and lod.max() == 2 and (lod == 1).any() and (lod % 1 != 0).any()
+
+
+@pytest.mark.parametrize("group", sorted(VARIANTS))
+def test_variants_are_reproducible_and_the_parents_bits(variant_runs, variants_parent, group):
+    first, second = variant_runs
+    for name in VARIANTS[group]:
+        np.testing.assert_array_equal(first[name].view(np.uint32), second[name].view(np.uint32), err_msg=name)
+        nnz, sha = sc.digest(first[name])
+        print(f"{name}: {nnz} non-zero, sha256 {sha.tobytes().hex()[:16]}")
+        assert nnz > 0 and nnz == variants_parent[name + ".nnz"], name
+        assert sha.tobytes() == variants_parent[name + ".sha256"].tobytes(), f"{name}: bits differ from the parent's"

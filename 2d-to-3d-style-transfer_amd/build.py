@@ -51,6 +51,9 @@ SOURCES = {
     "mipmap.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # shade.hip's flags: blend and mask are the plain kernels' bit for bit, the interpolation is compared with its numpy restatement
     "vcolor.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # vcolor.hip's flags: blend and mask are the plain kernels' bit for bit, the texel index (atlas.h) is compared with its numpy
+    # restatement index for index
+    "atlas.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "plan.hip": [],
     "comm.hip": [],
 }
@@ -67,6 +70,7 @@ def build(force=False, jobs=4, verbose=True):
     os.makedirs(OBJDIR, exist_ok=True)
     hdrs = (os.path.join(CSRC, "common.h"), os.path.join(CSRC, "det.h"), os.path.join(CSRC, "phong.h"),
             os.path.join(CSRC, "softgeom.h"), os.path.join(CSRC, "shadek1.h"), os.path.join(CSRC, "tilebins.h"),
+            os.path.join(CSRC, "atlas.h"),
             os.path.join(CSRC, "lab", "wino8.inc"),
             os.path.join(HERE, "..", "include", "st3d.h"), os.path.abspath(__file__))
     todo = []

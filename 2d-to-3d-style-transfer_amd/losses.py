@@ -114,9 +114,12 @@ def _on_gpu(t):
 
 
 def _texture_values(mesh):
-    """what the texture regularisers read: the map of a TexturesUV, the (V,3) colours of a TexturesVertex"""
+    """what the texture regularisers read: the map of a TexturesUV, the (V,3) colours of a TexturesVertex, the (F,R,R,3)
+    texels of a TexturesAtlas"""
     if isinstance(mesh.textures, _render.TexturesVertex):
         return mesh.textures.verts_features_packed()
+    if isinstance(mesh.textures, _render.TexturesAtlas):
+        return mesh.textures.atlas_packed()
     return mesh.textures.maps_padded()
 
 
@@ -130,16 +133,20 @@ def rgb_range_loss(mesh):
 def compute_tv_loss(images, masks):
     """Masked anisotropic L1 total variation / sum(masks) (reference losses.py:55-65; call sites commented out
     there too).  Value and d/d images from one fused pass.  Handed a mesh with per-vertex colours in the images' place
-    (total variation of the texture itself): ValueError -- vertex colours lie on no grid."""
+    (total variation of the texture itself): ValueError -- vertex colours lie on no grid; nor do the blocks of a TexturesAtlas."""
     if isinstance(getattr(images, "textures", None), _render.TexturesVertex):
         raise ValueError("compute_tv_loss: a TexturesVertex mesh has per-vertex colours, which lie on no pixel grid; total "
+                         "variation is defined for images (and texture maps) only")
+    if isinstance(getattr(images, "textures", None), _render.TexturesAtlas):
+        raise ValueError("compute_tv_loss: a TexturesAtlas mesh has per-face texel blocks, which lie on no pixel grid; total "
                          "variation is defined for images (and texture maps) only")
     return _FusedLossFn.apply(_on_gpu(images), _ops.tv_loss, _on_gpu(masks).detach())
 
 
 def texture_l2_loss(mesh, original_map):
     """mean((texture - original)^2): the "l2 regularization w.r.t. the original texture" idea of the reference's
-    notes.txt:39 (not implemented there).  A TexturesVertex mesh: its colours against the original (V,3) colours."""
+    notes.txt:39 (not implemented there).  A TexturesVertex mesh: its colours against the original (V,3) colours; a
+    TexturesAtlas mesh: its texels against the original (F,R,R,3) atlas."""
     tex = _on_gpu(_texture_values(mesh))
     return _FusedLossFn.apply(tex, _l2_to, _on_gpu(original_map).detach())
 

@@ -90,6 +90,11 @@ SHARED_FLAGS = [
          "meshes without UVs; started from the map sampled at each vertex's UV when the OBJ has one, else from seeded grey "
          "noise.  White ambient light, --supersample 1, --texture_mip_levels 1, --texture_pyramid_levels 1, no --tv_weight",
          _TEXTURE_TYPES),
+    Flag("texture_atlas", int, 0, "optimise a per-face texel atlas (PyTorch3D's TexturesAtlas) of N x N texels per face instead "
+         "of a UV-mapped texture: no UV chart, no seams, F N^2 texels addressed by each fragment's barycentrics (nearest "
+         "texel; --supersample is its anti-aliasing); 0 = off, 1...64.  Started from the map sampled at every texel's centre "
+         "when the OBJ has UVs and a map, else from seeded grey noise.  --optimization_target texture, --texture_type uv, white "
+         "ambient light, --texture_mip_levels 1, --texture_pyramid_levels 1, no --tv_weight"),
     Flag("laplacian_method", str, 'uniform', "Laplacian of the smoothing regulariser (PyTorch3D's mesh_laplacian_smoothing "
          "methods): 'uniform' = the plain mean of the neighbours (the reference's), 'cot' = cotangent weights, zero on a flat "
          "patch whatever its triangulation, 'cotcurv' = cotangent weights over the vertex's area (mean curvature).  "
@@ -169,6 +174,26 @@ def check_args(args):
                     f"{args.lights})")
         if getattr(args, "tv_weight", 0.0) > 0:
             return "--texture_type vertex cannot be combined with --tv_weight > 0: per-vertex colours lie on no grid"
+    atlas = getattr(args, "texture_atlas", 0)
+    if not 0 <= atlas <= 64:
+        return "--texture_atlas must be 0 (off) or the texels per face side, 1...64"
+    if atlas:
+        if getattr(args, "texture_type", "uv") != "uv":
+            return (f"--texture_atlas cannot be combined with --texture_type {args.texture_type}: the atlas takes the place of "
+                    "the colour carrier")
+        if levels != 1:
+            return "--texture_atlas needs --texture_pyramid_levels 1: an atlas has no map to build a pyramid of"
+        if mip != 1:
+            return "--texture_atlas needs --texture_mip_levels 1: the atlas is sampled at its nearest texel and has no mip chain"
+        if getattr(args, "lights", "ambient") != "ambient":
+            return f"--texture_atlas needs --lights ambient: the lit kernels have no atlas path (got --lights {args.lights})"
+        if getattr(args, "tv_weight", 0.0) > 0:
+            return ("--texture_atlas cannot be combined with --tv_weight > 0: the term's gradient reaches an atlas through no "
+                    "filter, texel by texel")
+        target_ = getattr(args, "optimization_target", "texture")
+        if target_ != "texture":
+            return (f"--texture_atlas needs --optimization_target texture: the nearest-texel colour moves no vertex (got "
+                    f"--optimization_target {target_})")
     return None
 
 
@@ -292,6 +317,65 @@ def load_scene_vertex(obj_path, device):
     return verts.to(device), faces.verts_idx.to(device), colors.to(device)
 
 
+def atlas_texel_centres(R):
+    """The barycentrics (b0, b1) of the centre of every texel of an R x R block -> two (R,R) float64 tensors indexed [y][x]:
+    (x + 1/3, y + 1/3) / R where x + y < R, else (R - 1 - x + 2/3, R - 1 - y + 2/3) / R (make_material_atlas's)."""
+    y, x = torch.meshgrid(torch.arange(R, dtype=torch.float64), torch.arange(R, dtype=torch.float64), indexing="ij")
+    below = x + y < R
+    b0 = torch.where(below, x + 1.0 / 3.0, R - 1 - x + 2.0 / 3.0) / R
+    b1 = torch.where(below, y + 1.0 / 3.0, R - 1 - y + 2.0 / 3.0) / R
+    return b0, b1
+
+
+def atlas_from_map(R, verts_uvs, faces_uvs, texture_map):
+    """Initial atlas from a UV-mapped texture -> (F,R,R,3): the map sampled at the UV of every texel's centre (sum_i b_i uv_i
+    over the face's corners, atlas_texel_centres) with the renderer's sampling conventions (rows flipped,
+    grid = uv * 2 - 1, bilinear, align_corners=True, border clamp).  verts_uvs (VT,2), faces_uvs (F,3), texture_map
+    (T,T',3).  Done once, in torch."""
+    b0, b1 = atlas_texel_centres(R)
+    b0, b1 = b0.to(torch.float32).to(verts_uvs.device), b1.to(torch.float32).to(verts_uvs.device)
+    b2 = 1.0 - b0 - b1
+    corner = verts_uvs.reshape(-1, 2).to(torch.float32)[faces_uvs.reshape(-1, 3).to(torch.int64)]        # (F,3,2)
+    uv = (b0[None, :, :, None] * corner[:, 0, None, None, :] + b1[None, :, :, None] * corner[:, 1, None, None, :]
+          + b2[None, :, :, None] * corner[:, 2, None, None, :])                                         # (F,R,R,2)
+    image = texture_map.reshape(texture_map.shape[-3], texture_map.shape[-2], 3).to(torch.float32)
+    nchw = image.flip(0).permute(2, 0, 1)[None]
+    grid = (uv * 2.0 - 1.0).reshape(1, 1, -1, 2)
+    sampled = F.grid_sample(nchw, grid, mode='bilinear', padding_mode='border', align_corners=True)
+    return sampled[0, :, 0, :].t().reshape(uv.shape[0], R, R, 3).contiguous()
+
+
+def load_scene_atlas(obj_path, R, device):
+    """--texture_atlas R: OBJ -> (verts (V,3), faces (F,3), atlas (F,R,R,3)) on `device`.  An OBJ with UVs and a texture map
+    starts from the map (atlas_from_map); one without -- the case the flag exists for -- from (0.5 + 0.1 randn(F,R,R,3),
+    seed 0) clamped to [0,1], without a warning: nothing is synthesised that the mesh lacks."""
+    verts, faces, aux = st3d_io.load_obj(obj_path)
+    n_faces = faces.verts_idx.shape[0]
+    if aux.verts_uvs is None or faces.textures_idx is None or not aux.texture_images:
+        noise = torch.randn((n_faces, R, R, 3), generator=torch.Generator().manual_seed(0))
+        atlas = (0.5 + 0.1 * noise).clamp(0, 1)
+    else:
+        atlas = atlas_from_map(R, aux.verts_uvs, faces.textures_idx, next(iter(aux.texture_images.values())))
+    return verts.to(device), faces.verts_idx.to(device), atlas.to(device)
+
+
+def export_atlas_mesh(out_dir, final):
+    """What the final export of a --texture_atlas run writes besides the turntable: final.obj (geometry only),
+    final_atlas.npy (the clamped texels, st3d.io.load_atlas reads them back) and, while F R^2 <= 2^20, final_colored.obj --
+    the atlas as the exact triangle soup it renders as, with ``v x y z r g b`` lines (opens in MeshLab).  -> the line to
+    print: what was written, or that the soup was skipped."""
+    st3d_io.save_obj(os.path.join(out_dir, "final.obj"), final.verts_packed(), final.faces_packed())
+    atlas = final.textures.atlas_packed()
+    st3d_io.save_atlas(os.path.join(out_dir, "final_atlas.npy"), atlas)
+    n_soup = atlas.shape[0] * atlas.shape[1] * atlas.shape[2]
+    if n_soup > st3d_io.ATLAS_SOUP_MAX_FACES:
+        return (f"final_colored.obj skipped: the triangle soup of the atlas would have {n_soup} faces (more than "
+                f"{st3d_io.ATLAS_SOUP_MAX_FACES}); final_atlas.npy holds the texels")
+    sv, sf, sc = st3d_io.atlas_to_triangle_soup(final.verts_packed().cpu(), final.faces_packed().cpu(), atlas.cpu())
+    st3d_io.save_obj(os.path.join(out_dir, "final_colored.obj"), sv, sf, verts_colors=sc)
+    return f"final_colored.obj: the atlas as a triangle soup of {n_soup} faces"
+
+
 ViewBatch = namedtuple("ViewBatch", "index size lo hi")      # batch number, its global size, this rank's [lo, hi)
 
 
@@ -362,7 +446,11 @@ class Run:
 
         self.say("Loading mesh...")
         self.vertex_colors = getattr(args, "texture_type", "uv") == "vertex"
-        if self.vertex_colors:
+        self.atlas_r = int(getattr(args, "texture_atlas", 0))
+        if self.atlas_r:
+            verts, faces, tex = load_scene_atlas(args.obj_path, self.atlas_r, self.device)      # tex: the (F,R,R,3) atlas
+            self.content_mesh = _u.build_mesh_atlas(tex, verts, faces)
+        elif self.vertex_colors:
             verts, faces, tex = load_scene_vertex(args.obj_path, self.device)       # tex: the (V,3) colours
             self.content_mesh = _u.build_mesh_vertex(tex, verts, faces)
         else:
@@ -424,7 +512,10 @@ class Run:
     # ---- small helpers
     @property
     def texture_key(self):
-        """the entry of self.opt that holds the colour leaf: the map, or the (V,3) colours of a --texture_type vertex run"""
+        """the entry of self.opt that holds the colour leaf: the map, the (V,3) colours of a --texture_type vertex run or the
+        (F,R,R,3) texels of a --texture_atlas run"""
+        if self.atlas_r:
+            return 'atlas'
         return 'verts_features' if self.vertex_colors else 'texture_map'
 
     @property
@@ -446,6 +537,8 @@ class Run:
 
     def current_mesh(self):
         o = self.opt
+        if self.atlas_r:
+            return self._utils.build_mesh_atlas(o['atlas'], o['verts'], o['faces'])
         if self.vertex_colors:
             return self._utils.build_mesh_vertex(o['verts_features'], o['verts'], o['faces'])
         texture = self.pyramid.texture() if self.pyramid is not None else o['texture_map']      # synthesised every step
@@ -495,7 +588,7 @@ class Run:
             with torch.no_grad():
                 texture = self.pyramid.texture()
         blob = {"progress": int(progress), "optimization_target": self.args.optimization_target,
-                "texture_type": "vertex" if self.vertex_colors else "uv",
+                "texture_type": "vertex" if self.vertex_colors else "uv", "texture_atlas": self.atlas_r,
                 self.texture_key: texture.detach().cpu(), "verts": self.opt['verts'].detach().cpu(),
                 "optimizer": self.optimizer.state_dict()}
         if self.pyramid is not None:        # the flat parameters are the state of record; texture_map is what they sum to
@@ -512,6 +605,9 @@ class Run:
         have_type, want_type = blob.get("texture_type", "uv"), "vertex" if self.vertex_colors else "uv"
         if have_type != want_type:
             raise ValueError("checkpoint was written with --texture_type %s, this run has %s" % (have_type, want_type))
+        have_atlas = int(blob.get("texture_atlas", 0))
+        if have_atlas != self.atlas_r:
+            raise ValueError("checkpoint was written with --texture_atlas %d, this run has %d" % (have_atlas, self.atlas_r))
         have = int(blob.get("texture_pyramid_levels", 1))
         want = self.pyramid.levels if self.pyramid is not None else 1
         if have != want:
@@ -567,7 +663,9 @@ class Run:
             final = u.finalize_mesh(mesh)
             u.save_render(self.renderer, final, u.build_fixed_cameras(12), os.path.join(self.out_dir, "final_render"))
             tex = final.textures
-            if self.vertex_colors:          # v x y z r g b lines; no MTL, no PNG
+            if self.atlas_r:
+                self.say(export_atlas_mesh(self.out_dir, final))
+            elif self.vertex_colors:        # v x y z r g b lines; no MTL, no PNG
                 st3d_io.save_obj(os.path.join(self.out_dir, "final.obj"), final.verts_packed(), final.faces_packed(),
                                  verts_colors=tex.verts_features_packed())
             else:

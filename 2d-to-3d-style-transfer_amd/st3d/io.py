@@ -153,6 +153,61 @@ def load_vertex_colors(path):
     return torch.tensor(cols, dtype=torch.float32)
 
 
+ATLAS_MAX_R = 64
+ATLAS_SOUP_MAX_FACES = 2 ** 20      # the final export writes the triangle soup of an atlas up to this many sub-triangles
+
+
+def _check_atlas_shape(shape, what):
+    if len(shape) != 4 or shape[3] != 3 or shape[1] != shape[2] or not 1 <= shape[1] <= ATLAS_MAX_R or shape[0] < 1:
+        raise ValueError(f"{what}: an atlas is (F, R, R, 3) with 1 <= R <= {ATLAS_MAX_R}, got {tuple(shape)}")
+
+
+def save_atlas(path, atlas):
+    """The (F,R,R,3) texels of a TexturesAtlas as a float32 ``.npy`` array."""
+    _check_atlas_shape(tuple(atlas.shape), "save_atlas")
+    with open(path, "wb") as fh:                # (np.save would append .npy to a path that lacks it)
+        np.save(fh, atlas.detach().cpu().to(torch.float32).numpy())
+
+
+def load_atlas(path):
+    """``save_atlas``'s array -> (F,R,R,3) float32 tensor; ValueError when the file holds anything else."""
+    arr = np.load(path, allow_pickle=False)
+    _check_atlas_shape(arr.shape, f"load_atlas({path!r})")
+    if arr.dtype.kind != "f":
+        raise ValueError(f"load_atlas({path!r}): an atlas holds floats, got {arr.dtype}")
+    return torch.from_numpy(np.ascontiguousarray(arr, dtype=np.float32))
+
+
+def atlas_to_triangle_soup(verts, faces, atlas):
+    """A mesh with a per-face texel atlas as the exact mesh it renders as: every face split into its R^2 sub-triangles, each
+    with three vertices of its own that carry its texel's colour -> (verts' (3 F R^2, 3), faces' (F R^2, 3) int64, colours'
+    (3 F R^2, 3)); sub-triangle (f R + y) R + x is texel atlas[f][y][x].  On the face's barycentric grid (b0, b1) = (i, j) / R:
+    the lower sub-triangle of cell (i, j) has corners (i,j), (i+1,j), (i,j+1) and texel [j][i]; for i + j <= R - 2 the upper
+    one has corners (i+1,j), (i+1,j+1), (i,j+1) and texel [R-1-j][R-1-i].  The winding is the parent's.  Pure torch, in the
+    dtype of `verts`."""
+    _check_atlas_shape(tuple(atlas.shape), "atlas_to_triangle_soup")
+    faces = faces.reshape(-1, 3).to(torch.int64)
+    verts = verts.reshape(-1, 3)
+    n_faces, R = atlas.shape[0], atlas.shape[1]
+    if faces.shape[0] != n_faces:
+        raise ValueError(f"the atlas holds {n_faces} blocks for a mesh of {faces.shape[0]} faces")
+    y, x = torch.meshgrid(torch.arange(R), torch.arange(R), indexing="ij")
+    below = x + y < R
+    i, j = torch.where(below, x, R - 1 - x), torch.where(below, y, R - 1 - y)
+    # integer barycentric corners (a, b) of the three vertices of every texel's sub-triangle, (R,R,3)
+    a = torch.stack([torch.where(below, i, i + 1), i + 1, i], dim=-1)
+    b = torch.stack([j, torch.where(below, j, j + 1), j + 1], dim=-1)
+    wa = a.reshape(-1).to(verts.dtype).to(verts.device)
+    wb = b.reshape(-1).to(verts.dtype).to(verts.device)
+    wc = R - wa - wb
+    p = verts[faces]                                                                         # (F,3,3)
+    pts = (wa[None, :, None] * p[:, 0, None, :] + wb[None, :, None] * p[:, 1, None, :] + wc[None, :, None] * p[:, 2, None, :]) / R
+    soup_verts = pts.reshape(-1, 3)
+    soup_faces = torch.arange(soup_verts.shape[0], dtype=torch.int64, device=verts.device).reshape(-1, 3)
+    colours = atlas.reshape(-1, 1, 3).expand(-1, 3, 3).reshape(-1, 3)
+    return soup_verts, soup_faces, colours
+
+
 def save_obj(path, verts, faces, verts_uvs=None, faces_uvs=None, texture_map=None, decimal_places=6, verts_colors=None):
     """Writes ``<path>`` (+ ``.mtl`` + ``.png`` next to it when a texture is given), the
     artefact set of ``IO().save_mesh(final_mesh, .../final.obj)`` (first_approach.py:225).

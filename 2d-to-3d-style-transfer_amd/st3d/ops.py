@@ -223,6 +223,59 @@ def shade_vc_bwd(grad_rgb, frag, faces_i32, colours, grad_colours=None, want_col
     return grad_colours if want_colours else gbary
 
 
+# ---- per-face texel atlas (csrc/atlas.hip): TexturesAtlas on the hard settings, unlit
+ATLAS_MAX_R = 64
+
+
+def _atlas_check(p2f, F, R):
+    """the sizes the kernels index with; the CALLER guarantees pix_to_face < F (the fragments of a mesh of F faces)"""
+    if not 1 <= R <= ATLAS_MAX_R:
+        raise ValueError(f"atlas resolution R must be 1...{ATLAS_MAX_R}, got {R}")
+    if F < 1 or F * R * R > 2 ** 31 - 1:
+        raise ValueError(f"an atlas needs 1 <= F and F R^2 <= 2^31 - 1 (the tile table's keys are int), got F = {F}, R = {R}")
+    if p2f.dim() != 3 or p2f.shape[1] != p2f.shape[2]:
+        raise ValueError(f"pix_to_face must be (B, S, S), got {tuple(p2f.shape)}")
+
+
+def shade_atlas_fwd(frag, atlas):
+    """frag, atlas (F,R,R,3) -> rgb (B,3,S,S), mask (B,1,S,S)"""
+    p2f, zbuf, bary, dists = frag
+    if atlas.dim() != 4 or atlas.shape[3] != 3 or atlas.shape[1] != atlas.shape[2]:
+        raise ValueError(f"atlas must be (F, R, R, 3), got {tuple(atlas.shape)}")
+    F, R = atlas.shape[0], atlas.shape[1]
+    _atlas_check(p2f, F, R)
+    B, S, _ = p2f.shape
+    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
+    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
+    call("st3d_shade_atlas_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(atlas, F32), B, S,
+         F, R, dptr(rgb), dptr(mask), stream_ptr())
+    return rgb, mask
+
+
+def shade_atlas_bwd(grad_rgb, frag, R, F, grad_atlas=None):
+    """-> grad_atlas (F,R,R,3) (accumulated into `grad_atlas` when given).  The scatter follows is_deterministic()."""
+    p2f, zbuf, bary, dists = frag
+    R, F = int(R), int(F)
+    _atlas_check(p2f, F, R)
+    B, S, _ = p2f.shape
+    if tuple(grad_rgb.shape) != (B, 3, S, S):
+        raise ValueError(f"grad_rgb must be {(B, 3, S, S)}, got {tuple(grad_rgb.shape)}")
+    if grad_atlas is None:
+        grad_atlas = torch.zeros((F, R, R, 3), dtype=F32, device=p2f.device)
+    elif tuple(grad_atlas.shape) != (F, R, R, 3):
+        raise ValueError(f"grad_atlas must be {(F, R, R, 3)}, got {tuple(grad_atlas.shape)}")
+    grad_rgb = grad_rgb.contiguous()
+    head = (dptr(grad_rgb, F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), B, S, F, R,
+            dptr(grad_atlas, F32))
+    if _DETERMINISTIC:
+        nb = _lib.load().st3d_shade_atlas_bwd_det_workspace_bytes(F, R)
+        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=p2f.device)
+        call("st3d_shade_atlas_bwd_det", *head, dptr(ws), nb, stream_ptr())
+    else:
+        call("st3d_shade_atlas_bwd", *head, stream_ptr())
+    return grad_atlas
+
+
 # ---- supersampling (csrc/shade.hip): fragments at side a * S, images and their gradients at side S
 MAX_RASTER_SIDE = 4096
 SUPERSAMPLE_MAX = 4

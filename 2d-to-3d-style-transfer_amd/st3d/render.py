@@ -28,6 +28,9 @@ vertices through the signed edge distance (csrc/silhouette.hip); losses.compute_
 
 Per-vertex colours: a mesh whose textures are a TexturesVertex renders on csrc/vcolor.hip (hard settings, unlit): the colour
 is the barycentric interpolation of the three vertex colours of the fragment's face, differentiable in colours and vertices.
+
+Texel atlas: a mesh whose textures are a TexturesAtlas renders on csrc/atlas.hip (hard settings, unlit, supersample 1...4):
+the colour is the nearest texel of the R x R block its face owns, differentiable in the atlas alone.
 """
 import math
 import os
@@ -136,6 +139,51 @@ class TexturesVertex:
         return TexturesVertex(self.verts_features_packed().detach())
 
 
+class TexturesAtlas:
+    """PyTorch3D ``TexturesAtlas(atlas=...)``: every face owns an R x R block of RGB texels, addressed by the fragment's
+    barycentrics (nearest texel, csrc/atlas.hip) -- no UV chart, no seams.  atlas: (F,R,R,3), (1,F,R,R,3) or a
+    one-element list of (F,R,R,3), 1 <= R <= 64, one block per face of the mesh.
+
+    The lookup is piecewise constant in the barycentrics, so NO gradient reaches the vertices through the colour: a render
+    of such a mesh is differentiable in the atlas only (``verts.grad`` stays None)."""
+
+    def __init__(self, atlas):
+        if isinstance(atlas, (list, tuple)):
+            if len(atlas) != 1:
+                raise ValueError("one mesh per batch: atlas takes a one-element list")
+            atlas = atlas[0]
+        if atlas.dim() == 5:
+            if atlas.shape[0] != 1:
+                raise ValueError(f"one mesh per batch: atlas must be (F, R, R, 3) or (1, F, R, R, 3), got {tuple(atlas.shape)}")
+            self._padded, self._packed = atlas, None
+        elif atlas.dim() == 4:
+            self._padded, self._packed = None, atlas
+        else:
+            raise ValueError(f"atlas must be (F, R, R, 3) or (1, F, R, R, 3), got {tuple(atlas.shape)}")
+        if atlas.shape[-1] != 3:
+            raise ValueError(f"atlas holds RGB triples: the last dimension must be 3, got {tuple(atlas.shape)}")
+        if atlas.shape[-2] != atlas.shape[-3]:
+            raise ValueError(f"atlas blocks are square (F, R, R, 3), got {tuple(atlas.shape)}")
+        if not 1 <= atlas.shape[-2] <= ops.ATLAS_MAX_R:
+            raise ValueError(f"atlas resolution R must be 1...{ops.ATLAS_MAX_R}, got {atlas.shape[-2]}")
+
+    def atlas_padded(self):
+        if self._padded is None:
+            self._padded = self._packed[None]
+        return self._padded
+
+    def atlas_packed(self):
+        if self._packed is None:
+            self._packed = self._padded[0]
+        return self._packed
+
+    def clone(self):
+        return TexturesAtlas(self.atlas_packed().clone())
+
+    def detach(self):
+        return TexturesAtlas(self.atlas_packed().detach())
+
+
 class Meshes:
     """utils.py:209 ``Meshes(verts=[verts], faces=[faces], textures=textures)`` (one mesh)."""
 
@@ -157,6 +205,8 @@ class Meshes:
         self._faces_i32 = None
         if isinstance(textures, TexturesVertex):
             vertex_colours_of(self)         # one colour per vertex, or a ValueError now rather than at the first render
+        if isinstance(textures, TexturesAtlas):
+            atlas_of(self)                  # one block per face, likewise
 
     def verts_packed(self):
         if self._verts is None:
@@ -201,6 +251,17 @@ def vertex_colours_of(meshes):
         raise ValueError(f"TexturesVertex holds {col.shape[0]} colours for a mesh of {V} vertices: verts_features must have "
                          "one row per vertex (it is indexed by the mesh's faces)")
     return col
+
+
+def atlas_of(meshes):
+    """The (F,R,R,3) atlas of a mesh whose textures are a TexturesAtlas, checked against its face count: the kernels index
+    the atlas with the rasterised face, so a shorter array would be read out of bounds on the GPU (ValueError)."""
+    atlas = meshes.textures.atlas_packed()
+    F = meshes.faces_packed().shape[0]
+    if atlas.shape[0] != F:
+        raise ValueError(f"TexturesAtlas holds {atlas.shape[0]} blocks for a mesh of {F} faces: atlas must have one R x R block "
+                         "per face (it is indexed by the rasterised face)")
+    return atlas
 
 
 # ------------------------------------------------------------------------ cameras (SURVEY.md A.1)
@@ -318,6 +379,23 @@ VERTEX_COLOUR_REFUSALS = {
 VERTEX_COLOUR_NEAR_PLANE_MESSAGE = ("the mesh reaches the near clipping plane (z < znear / 2) and its textures are a "
                                     "TexturesVertex: the clipping kernels have no vertex-colour path, and the render is not "
                                     "silently rerouted -- keep the mesh in front of the plane")
+
+
+# what a render of a TexturesAtlas mesh refuses, by limitation (NotImplementedError, before any launch)
+ATLAS_REFUSALS = {
+    "lights": "TexturesAtlas is implemented for unlit renders only (lights=None or white AmbientLights with default "
+              "Materials): the lit kernels have no atlas path",
+    "mip": "TexturesAtlas cannot be combined with texture_mip_levels != 1: the atlas is sampled at its nearest texel and has "
+           "no mip chain (supersample is its anti-aliasing)",
+    "soft": "TexturesAtlas is implemented for the hard settings only (faces_per_pixel = 1, blur_radius = 0, default "
+            "clipping, culling and BlendParams): the general soft kernels have no atlas path",
+    "silhouette": "SilhouetteRasterizationSettings render on the silhouette rasteriser, which produces alpha only: the "
+                  "colours of a TexturesAtlas mesh need RasterizationSettings and a SoftPhongShader (a "
+                  "SoftSilhouetteShader renders the same mesh's alpha)",
+}
+ATLAS_NEAR_PLANE_MESSAGE = ("the mesh reaches the near clipping plane (z < znear / 2) and its textures are a "
+                            "TexturesAtlas: the clipping kernels have no atlas path, and the render is not "
+                            "silently rerouted -- keep the mesh in front of the plane")
 
 
 class RasterizationSettings:
@@ -881,6 +959,33 @@ class _VertexColourRenderFn(torch.autograd.Function):
             return gverts, gcol, None, None, None, None
 
 
+class _AtlasRenderFn(torch.autograd.Function):
+    """(verts, atlas (F,R,R,3)) -> (rgb (B,3,S,S), mask (B,1,S,S)) for a TexturesAtlas mesh: project, raster,
+    shade_atlas_fwd.  Backward: the atlas scatter alone.  The nearest-texel lookup is piecewise constant in the barycentrics
+    and the hard path sends nothing through dists / zbuf, so the vertices get None."""
+
+    @staticmethod
+    def forward(ctx, verts, atlas, faces_i32, R, T, S):
+        v = verts.detach().to(torch.float32).contiguous()
+        at = atlas.detach().to(torch.float32).reshape(atlas.shape[-4:]).contiguous()
+        ndc = ops.project_verts(v, R, T)
+        frag = ops.raster_fwd(ndc, faces_i32, S)
+        rgb, mask = ops.shade_atlas_fwd(frag, at)
+        ctx.frag = frag
+        ctx.atlas_shape = atlas.shape
+        ctx.block = (at.shape[1], at.shape[0])          # R, F
+        ctx.mark_non_differentiable(mask)
+        return rgb, mask
+
+    @staticmethod
+    def backward(ctx, grad_rgb, _grad_mask):
+        with ops.trace("render_backward"):
+            gatlas = None
+            if ctx.needs_input_grad[1]:
+                gatlas = ops.shade_atlas_bwd(grad_rgb.to(torch.float32), ctx.frag, *ctx.block).reshape(ctx.atlas_shape)
+            return None, gatlas, None, None, None, None
+
+
 class _SSRenderFn(torch.autograd.Function):
     """_RenderFn supersampled: fragments at side a * S on the same rasteriser, (rgb (B,3,S,S), coverage (B,1,S,S)) from the
     fused kernels (st3d.ops.shade_ss_*); the backward hands the S-sized gradient to them and the a * S barycentric
@@ -1135,6 +1240,8 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
     rs, bp = raster_settings, blend_params
     if isinstance(tex, TexturesVertex):         # decided on the texture's type before any path is chosen
         return _render_views_vertex(meshes, R, T, int(image_size), rs, bp, lights, materials)
+    if isinstance(tex, TexturesAtlas):
+        return _render_views_atlas(meshes, R, T, int(image_size), rs, bp, lights, materials)
     if isinstance(rs, SilhouetteRasterizationSettings):
         raise NotImplementedError("SilhouetteRasterizationSettings render on the silhouette rasteriser, which produces alpha "
                                   "only: they need a SoftSilhouetteShader")
@@ -1201,6 +1308,42 @@ def _render_views_vertex(meshes, R, T, S, rs, bp, lights, materials):
     if ops.near_plane_triggered() or reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT):
         raise RuntimeError(VERTEX_COLOUR_NEAR_PLANE_MESSAGE)
     rgb, mask = _VertexColourRenderFn.apply(meshes.verts_packed(), colours, faces_i32, R, T, S)
+    if rgb.requires_grad:
+        tag_need(rgb, rgb.grad_fn.frag[0])
+    tag_flat(rgb, (1.0, 1.0, 1.0))
+    return rgb, mask
+
+
+def _render_views_atlas(meshes, R, T, S, rs, bp, lights, materials):
+    """_render_views for a mesh whose textures are a TexturesAtlas -> (rgb, coverage) from csrc/atlas.hip.  supersample = a
+    > 1: fragments and shading at a * S, then the box filter (rgb through _BoxDownFn, whose backward is the filter's
+    transpose; the mask through ops.box_down_fwd) -- the composition of the ST3D_SS_FUSED=0 branch of _render_views_ss;
+    coverage is then fractional.  Everything the kernels do not cover is refused before any launch; a batch at the near
+    plane is an error whatever ST3D_NEAR_PLANE says, never a silent reroute (the clipping kernels have no atlas path)."""
+    if isinstance(rs, SilhouetteRasterizationSettings):
+        raise NotImplementedError(ATLAS_REFUSALS["silhouette"])
+    dev = meshes.device
+    if lighting_of(lights, materials, dev) is not None:
+        raise NotImplementedError(ATLAS_REFUSALS["lights"])
+    if getattr(rs, "texture_mip_levels", 1) != 1:
+        raise NotImplementedError(ATLAS_REFUSALS["mip"])
+    if not uses_hard_path(rs, bp):
+        raise NotImplementedError(ATLAS_REFUSALS["soft"])
+    a = getattr(rs, "supersample", 1)
+    if a > 1:
+        a = ops.check_supersample(a, S)
+    atlas = atlas_of(meshes)
+    faces_i32 = meshes.faces_i32()
+    R, T = R.to(dev), T.to(dev)
+    if ops.near_plane_triggered() or reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT):
+        raise RuntimeError(ATLAS_NEAR_PLANE_MESSAGE)
+    if a > 1:
+        rgb_hi, mask_hi = _AtlasRenderFn.apply(meshes.verts_packed(), atlas, faces_i32, R, T, a * S)
+        rgb, cov = _BoxDownFn.apply(rgb_hi, a), ops.box_down_fwd(mask_hi, a)
+        tag_need_mask(rgb, cov[:, 0] > 0)
+        tag_flat(rgb, (1.0, 1.0, 1.0))
+        return rgb, cov
+    rgb, mask = _AtlasRenderFn.apply(meshes.verts_packed(), atlas, faces_i32, R, T, S)
     if rgb.requires_grad:
         tag_need(rgb, rgb.grad_fn.frag[0])
     tag_flat(rgb, (1.0, 1.0, 1.0))

@@ -20,8 +20,8 @@ from st3d import ops as _ops
 from st3d import optim as _st3d_optim
 from st3d import render as _render
 from st3d import vgg as _vgg
-from st3d.render import (FoVPerspectiveCameras, Meshes, RotateAxisAngle, TexturesUV, TexturesVertex,  # noqa: F401
-                         look_at_view_transform)
+from st3d.render import (FoVPerspectiveCameras, Meshes, RotateAxisAngle, TexturesAtlas, TexturesUV,  # noqa: F401
+                         TexturesVertex, look_at_view_transform)
 from style_transfer import *  # noqa: F401,F403  (star re-export relied on by the CLIs, reference utils.py:12)
 
 device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
@@ -113,6 +113,9 @@ def finalize_mesh(mesh):
     if isinstance(tex, TexturesVertex):
         return Meshes(verts=mesh.verts_padded(), faces=mesh.faces_padded(),
                       textures=TexturesVertex(finalize_tensor(tex.verts_features_packed())))
+    if isinstance(tex, TexturesAtlas):
+        return Meshes(verts=mesh.verts_padded(), faces=mesh.faces_padded(),
+                      textures=TexturesAtlas(finalize_tensor(tex.atlas_packed())))
     clamped = TexturesUV(maps=finalize_tensor(tex.maps_padded()), faces_uvs=tex.faces_uvs_padded(),
                          verts_uvs=tex.verts_uvs_padded())
     return Meshes(verts=mesh.verts_padded(), faces=mesh.faces_padded(), textures=clamped)
@@ -127,6 +130,11 @@ def build_mesh(verts_uvs, faces_uvs, texture_map, verts, faces):
 def build_mesh_vertex(verts_features, verts, faces):
     """build_mesh for per-vertex colours: verts_features (V,3) or (1,V,3), one RGB triple per vertex (TexturesVertex)."""
     return Meshes(verts=[verts], faces=[faces], textures=TexturesVertex(verts_features))
+
+
+def build_mesh_atlas(atlas, verts, faces):
+    """build_mesh for a per-face texel atlas: atlas (F,R,R,3) or (1,F,R,R,3), one R x R block per face (TexturesAtlas)."""
+    return Meshes(verts=[verts], faces=[faces], textures=TexturesAtlas(atlas))
 
 
 # ------------------------------------------------------------------------------------------ cameras
@@ -157,6 +165,7 @@ def build_random_cameras(n_views, dist=2.10, generator=None):
 # ------------------------------------------------------------------------------------------ optimiser
 _LEAVES = {'texture': ('texture_map',), 'mesh': ('verts',), 'both': ('verts', 'texture_map')}
 _VERTEX_LEAVES = {'texture': ('verts_features',), 'mesh': ('verts',), 'both': ('verts', 'verts_features')}
+_ATLAS_LEAVES = {'texture': ('atlas',), 'mesh': ('verts',), 'both': ('verts', 'atlas')}
 
 
 def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1):
@@ -169,7 +178,22 @@ def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1)
 
     A mesh whose textures are a TexturesVertex: 'verts_features' (V,3) takes the place of 'texture_map' / 'verts_uvs' /
     'faces_uvs'; leaves are 'texture' -> the colours, 'mesh' -> the vertices, 'both' -> the vertices, then the colours.
-    There is no map to build a pyramid of: texture_pyramid_levels != 1 is a ValueError."""
+    There is no map to build a pyramid of: texture_pyramid_levels != 1 is a ValueError.
+
+    A mesh whose textures are a TexturesAtlas: 'atlas' (F,R,R,3) takes that place in the same way ('texture' -> the atlas,
+    'mesh' -> the vertices, 'both' -> the vertices, then the atlas; the colour moves no vertex, so under 'mesh' and 'both'
+    the vertices move by the other terms of the loss alone); texture_pyramid_levels != 1 is a ValueError."""
+    if isinstance(mesh.textures, TexturesAtlas):
+        if optimization_target not in _ATLAS_LEAVES:
+            raise UnboundLocalError("local variable 'optimizer' referenced before assignment "
+                                    f"(optimization_target={optimization_target!r})")
+        if texture_pyramid_levels != 1:
+            raise ValueError("texture_pyramid_levels != 1 needs a texture map: a TexturesAtlas mesh has per-face texel blocks "
+                             "and no map to build a pyramid of")
+        work = mesh.clone()
+        parts = {'atlas': work.textures.atlas_packed(), 'verts': work.verts_packed(), 'faces': work.faces_packed()}
+        leaves = [parts[name].requires_grad_(True) for name in _ATLAS_LEAVES[optimization_target]]
+        return dict(parts, optimizable_mesh=work, optimizer=_st3d_optim.Adam(leaves, lr=lr))
     if isinstance(mesh.textures, TexturesVertex):
         if optimization_target not in _VERTEX_LEAVES:
             raise UnboundLocalError("local variable 'optimizer' referenced before assignment "

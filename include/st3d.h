@@ -756,6 +756,34 @@ int st3d_shade_vc_bwd_det(const float *grad_rgb, const int32_t *pix_to_face, con
                           float *grad_colors, float *grad_bary, void *workspace, size_t workspace_bytes,
                           st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ per-face texel atlas (csrc/atlas.hip):
+ * PyTorch3D TexturesAtlas on the hard settings (K = 1, blur 0, default BlendParams), unlit.  atlas (F,R,R,3) fp32, 1 <= R
+ * <= 64, F R^2 <= 2^31 - 1; every face owns an R x R block of texels addressed by the fragment's barycentrics.  Face
+ * indices are NOT checked on the device: the caller guarantees pix_to_face < F.
+ *   atlas_texel_index  host only, no GPU: the row wy and column wx of the texel of barycentrics (b0, b1) -- the function
+ *            the kernels call (csrc/atlas.h): t_i = clamp(b_i R, 0, R - 1) in float (NaN -> 0), wx = (int)t0, wy = (int)t1,
+ *            and (R-1-wx, R-1-wy) instead when (b0 + b1) R - (wx + wy) > 1.  Always within [0, R-1].
+ *   shade_atlas_fwd  replaces TexturesAtlas.sample_textures + the ambient SoftPhongShader + softmax_rgb_blend:
+ *            rgb_c = (wnum atlas[f][wy][wx][c] + delta) / denom with the blend and the mask of the UV forward; pixels
+ *            without a face are white with mask 0.  rgb (B,3,S,S), mask (B,1,S,S).
+ *   shade_atlas_bwd  its autograd backward: grad_atlas[f][wy][wx][c] += grad_rgb_c wnum / denom, one deposit per covered
+ *            pixel (float atomics; ACCUMULATED into grad_atlas (F,R,R,3)).  The lookup is piecewise constant: there is no
+ *            gradient towards the barycentrics.
+ *   shade_atlas_bwd_det  the same with the scatter in 64-bit fixed point (bitwise reproducible; a NaN / Inf in grad_rgb,
+ *            on a covered pixel or not, makes every element of grad_atlas NaN; finite values on uncovered pixels change no
+ *            bit).  Workspace of st3d_shade_atlas_bwd_det_workspace_bytes(F, R) bytes (0 for arguments out of range),
+ *            16-byte aligned.
+ * S <= 4096.  Nothing is allocated. */
+int st3d_atlas_texel_index(float b0, float b1, int R, int *wy, int *wx);
+int st3d_shade_atlas_fwd(const int32_t *pix_to_face, const float *bary, const float *zbuf, const float *dists,
+                         const float *atlas, int B, int S, int F, int R, float *rgb, float *mask, st3d_stream_t stream);
+int st3d_shade_atlas_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                         const float *dists, int B, int S, int F, int R, float *grad_atlas, st3d_stream_t stream);
+size_t st3d_shade_atlas_bwd_det_workspace_bytes(int F, int R);
+int st3d_shade_atlas_bwd_det(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
+                             const float *dists, int B, int S, int F, int R, float *grad_atlas, void *workspace,
+                             size_t workspace_bytes, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ optimiser:
  * torch.optim.Adam defaults (utils.py:185-195, style_transfer.py:57) */
 int st3d_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n,

@@ -20,6 +20,7 @@ from st3d import ops as _ops
 from st3d import render as _render
 from st3d import vgg as _vgg
 from st3d.mesh_losses import mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency  # noqa: F401
+from st3d.mesh_losses import chamfer_distance, knn_points, sample_points_from_meshes  # noqa: F401
 from style_transfer import *  # noqa: F401,F403  (the reference does the same, losses.py:5)
 
 # Check if CUDA is available

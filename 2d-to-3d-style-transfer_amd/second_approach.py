@@ -78,6 +78,9 @@ def main(argv=None):
             outline_term = run.silhouette_term(mesh, cams, outline, vb.size)
             if torch.is_tensor(outline_term):
                 loss = loss + outline_term
+            anchor_term = run.chamfer_term(mesh)    # --chamfer_weight, off by default
+            if torch.is_tensor(anchor_term):
+                loss = loss + anchor_term
 
             if args.save_every and steps_done % args.save_every == 0:
                 run.save_views(current, vb.lo)          # encoded by worker threads, off the step's critical path

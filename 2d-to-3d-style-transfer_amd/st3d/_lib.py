@@ -45,6 +45,18 @@ SIGNATURES = {
     "st3d_mesh_reg_ex": (c_int, [c_f32p, c_f32p, c_int, c_i32p, c_int, c_i32p, c_i32p, c_i32p, c_int, c_i32p, c_i32p, c_i32p, c_int,
                                  c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_int, c_float, ctypes.POINTER(c_float), c_f32p, c_f32p,
                                  c_f32p, c_f32p, c_stream]),
+    "st3d_knn1_geometry": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "st3d_knn1_workspace_bytes": (c_size, [c_int, c_int]),
+    "st3d_knn1": (c_int, [c_f32p, c_f32p, c_int, c_int, ctypes.c_void_p, c_size, c_i32p, c_f32p, c_stream]),
+    "st3d_face_area_cdf_scratch_bytes": (c_size, [c_int]),
+    "st3d_face_area_cdf": (c_int, [c_f32p, c_i32p, c_int, ctypes.c_void_p, c_size, ctypes.c_void_p, c_stream]),
+    "st3d_sample_points_fwd": (c_int, [c_f32p, c_i32p, c_int, ctypes.c_void_p, c_f32p, c_int, c_f32p, c_i32p, c_stream]),
+    "st3d_sample_points_bwd_scratch_bytes": (c_size, [c_int]),
+    "st3d_sample_points_bwd": (c_int, [c_f32p, c_f32p, c_i32p, c_int, c_int, c_int, c_i32p, c_i32p, ctypes.c_void_p, c_size,
+                                       c_f32p, c_stream]),
+    "st3d_chamfer_sum": (c_int, [c_f32p, c_int, ctypes.c_double, c_f32p, c_stream]),
+    "st3d_chamfer_bwd": (c_int, [c_f32p, c_f32p, c_int, c_int, c_i32p, c_i32p, c_i32p, ctypes.c_double, ctypes.c_double, c_f32p,
+                                 c_stream]),
     "st3d_face_setup": (c_int, [c_f32p, c_i32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_stream]),
     "st3d_clip_records_bytes": (c_size, [c_int, c_int]),
     "st3d_face_setup_clip": (c_int, [c_f32p, c_i32p, c_int, c_int, c_int, c_float, c_int, ctypes.c_void_p, c_size, c_stream]),

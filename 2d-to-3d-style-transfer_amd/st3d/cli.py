@@ -102,6 +102,11 @@ SHARED_FLAGS = [
     Flag("edge_target_length", edge_target_length, 0.0, "length the edge regulariser pulls every edge to: 0 = the reference's "
          "(edges can only shrink), 'mean' = the mean edge length of the loaded mesh, or a length >= 0.  "
          "--optimization_target mesh / both only"),
+    Flag("chamfer_weight", float, 0.0, "weight of the Chamfer term that ties the moving surface to the loaded one: N points "
+         "redrawn every step from the current mesh against N points sampled once from the loaded mesh (PyTorch3D's "
+         "sample_points_from_meshes + chamfer_distance).  Unlike --mesh_verts_weight it leaves a vertex free to slide along "
+         "the surface; at its optimum it is about 2 area / (pi N), not 0.  --optimization_target mesh / both only; 0 = off"),
+    Flag("chamfer_samples", int, 5000, "points per cloud of the Chamfer term, 1...1048576"),
     Flag("texture_lod_bias", float, 0.0, "added to every pixel's level of detail before it is clamped to the chain "
          "(--texture_mip_levels): negative = sharper, positive = blurrier"),
 ]
@@ -125,6 +130,14 @@ def check_args(args):
     if (method != "uniform" or target != 0.0) and getattr(args, "optimization_target", None) == 'texture':
         return ("--laplacian_method / --edge_target_length need --optimization_target mesh or both: with 'texture' the vertices "
                 "do not move and the mesh regularisers do not run")
+    chamfer = getattr(args, "chamfer_weight", 0.0)
+    if not (math.isfinite(chamfer) and chamfer >= 0.0):
+        return "--chamfer_weight must be finite and >= 0"
+    if chamfer and getattr(args, "optimization_target", None) == 'texture':
+        return ("--chamfer_weight needs --optimization_target mesh or both: with 'texture' the vertices do not move and the "
+                "term would be a constant")
+    if not 1 <= getattr(args, "chamfer_samples", 5000) <= 1 << 20:
+        return "--chamfer_samples must be in 1...1048576"
     if not getattr(args, "silhouette_sigma", 1e-4) > 0.0:
         return "--silhouette_sigma must be positive"
     k = getattr(args, "silhouette_faces_per_pixel", None)
@@ -498,6 +511,9 @@ class Run:
                                                      {"params": [texture_leaf], "lr": lr}])
         self.optimizer = self.opt['optimizer']
         self.original_map = tex
+        self.chamfer_generator = self.chamfer_target = None
+        if getattr(args, "chamfer_weight", 0.0):        # off (the default): nothing runs, no generator is created
+            self.setup_chamfer()
         self.progress = 0               # epochs (second approach) / view batches (first approach) already done
         if args.resume:
             self.load_checkpoint(args.resume)
@@ -568,6 +584,7 @@ class Run:
         total = self.regularisers(None, None, mesh, 0, 1)
         if self.args.optimization_target in ('mesh', 'both'):
             total = total + _l._mesh_terms(self.opt['verts'], self.original_verts, mesh, self.loss_weights)
+        total = total + self.chamfer_term(mesh)      # view-independent too; the draw keeps this rank's generator in step
         if torch.is_tensor(total) and total.requires_grad:
             total.backward()                      # accumulates into the zero gradients
         return total.detach() if torch.is_tensor(total) else torch.zeros((), device=self.device)
@@ -594,6 +611,9 @@ class Run:
         if self.pyramid is not None:        # the flat parameters are the state of record; texture_map is what they sum to
             blob["texture_pyramid"] = self.pyramid.params.detach().cpu()
             blob["texture_pyramid_levels"] = self.pyramid.levels
+        generator = getattr(self, "chamfer_generator", None)
+        if generator is not None:           # --chamfer_weight: where the point draws of the run have got to
+            blob["chamfer_generator_state"] = generator.get_state().cpu()
         tmp = os.path.join(self.out_dir, "checkpoint.pt.tmp")
         torch.save(blob, tmp)
         os.replace(tmp, os.path.join(self.out_dir, "checkpoint.pt"))
@@ -612,6 +632,12 @@ class Run:
         want = self.pyramid.levels if self.pyramid is not None else 1
         if have != want:
             raise ValueError("checkpoint was written with %d texture pyramid level(s), this run has %d" % (have, want))
+        generator = getattr(self, "chamfer_generator", None)
+        if ("chamfer_generator_state" in blob) != (generator is not None):
+            raise ValueError("checkpoint was written %s --chamfer_weight, this run is %s it"
+                             % (("with", "without") if "chamfer_generator_state" in blob else ("without", "with")))
+        if generator is not None:
+            generator.set_state(blob["chamfer_generator_state"])
         with torch.no_grad():
             if self.pyramid is not None:
                 self.pyramid.load_params(blob["texture_pyramid"].to(self.device))
@@ -652,6 +678,32 @@ class Run:
         return a.silhouette_weight * _l.compute_silhouette_loss(self.renderer, mesh, cams, target,
                                                                 sigma=a.silhouette_sigma, batch_denom=batch_size,
                                                                 faces_per_pixel=getattr(a, "silhouette_faces_per_pixel", None))
+
+    def setup_chamfer(self):
+        """--chamfer_weight > 0: the run's generator, seeded with --seed (0 when unset) identically on every rank, and the
+        target cloud -- --chamfer_samples points sampled once from the loaded mesh, before any checkpoint is read, so that a
+        resumed run holds the same target.  Prints N, the surface area and the level the term settles at."""
+        from . import mesh_losses as _ml
+        a = self.args
+        self.chamfer_generator = torch.Generator(device=self.device)
+        self.chamfer_generator.manual_seed(a.seed if a.seed is not None else 0)
+        with torch.no_grad():
+            self.chamfer_target = _ml.sample_points_from_meshes(self.content_mesh, a.chamfer_samples,
+                                                                generator=self.chamfer_generator).detach()
+        area = _ml.surface_area(self.content_mesh)
+        self.say(f"Chamfer term: {a.chamfer_samples} points per cloud, surface area {area:.6g}, expected floor 2A/(pi N) = "
+                 f"{_ml.chamfer_floor(area, a.chamfer_samples):.6g} (the term is not 0 at its optimum)")
+
+    def chamfer_term(self, mesh):
+        """--chamfer_weight / world x chamfer_distance(--chamfer_samples points redrawn from `mesh`, the target cloud).  The
+        term is view-independent like mesh_terms: every rank draws the same points from the same generator state and adds
+        1/world of the same value, so the summed gradient counts it once.  With weight 0 (the default) nothing runs."""
+        if getattr(self, "chamfer_generator", None) is None:
+            return 0
+        from . import mesh_losses as _ml
+        a = self.args
+        points = _ml.sample_points_from_meshes(mesh, a.chamfer_samples, generator=self.chamfer_generator)
+        return (a.chamfer_weight / self.world) * _ml.chamfer_distance(points, self.chamfer_target)[0]
 
     def export(self, mesh):
         """final_render/view_k.png from 12 turntable cameras + final.obj/.mtl/.png (first_approach.py:219-225)."""

@@ -17,6 +17,14 @@ every function makes the call it always made (st3d_mesh_reg); anything else goes
 static lists (``build_cot_topology``: edge -> incident corners, adjacency slot -> edge, vertex -> incident corners), cached
 per faces tensor like the rest.  The cotangent weights change with the vertices and are constants of the gradient, as in
 PyTorch3D: they are rebuilt by every call and never cached across vertex versions.
+
+The surface-to-surface anchor of PyTorch3D's mesh-fitting tutorial is here too (csrc/chamfer.hip):
+``sample_points_from_meshes(meshes, num_samples, generator=)``, ``knn_points(p1, p2, K=1)`` and ``chamfer_distance(x, y)``,
+for one mesh and one pair of clouds of 1..2^20 points.  Faces are drawn by inverse CDF of the fp64 face areas from sorted
+uniforms, so the points come ascending in the face index and the gradient to the vertices is a fixed-order gather; the
+nearest-neighbour search is an exact brute-force scan in fp32 where the lowest index wins among equals; every sum is ordered,
+in fp64, rounded once.  The Chamfer distance of two independent N-point samplings of one surface of area A is not zero but
+about 2 A / (pi N) (``chamfer_floor``): a loss at that level is at its optimum.
 """
 import torch
 
@@ -247,3 +255,167 @@ def mesh_terms(verts, target_verts, mesh, weights):
     if grad is None:
         return out[0].clone()
     return _TermFn.apply(verts, out[0], grad)
+
+
+# ---------------------------------------------------------------------------- Chamfer loss (csrc/chamfer.hip)
+def _no_cpu(t):
+    if not t.is_cuda:
+        raise RuntimeError("st3d runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
+
+
+def sample_uniforms(num_samples, generator=None, device=None):
+    """The (3,N) fp32 uniforms in [0,1) of one sampling: ONE torch.rand((3,N)) on the generator's device (the global
+    generator of `device` when generator is None), moved to `device`, row 0 sorted ascending."""
+    n = ops.check_num_points(num_samples)
+    device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    drawn_on = generator.device if generator is not None else device
+    r = torch.rand((3, n), generator=generator, dtype=torch.float32, device=drawn_on).to(device)
+    r[0] = torch.sort(r[0]).values
+    return r
+
+
+class _SamplePointsFn(torch.autograd.Function):
+    """points = sum_k w_k verts[faces[face_idx, k]]; the face choice and the weights are constants of the backward"""
+
+    @staticmethod
+    def forward(ctx, verts, faces_i32, incidence, r):
+        v = verts.detach().to(torch.float32).contiguous()
+        points, face_idx = ops.sample_points_fwd(v, faces_i32, ops.face_area_cdf(v, faces_i32), r)
+        ctx.save_for_backward(r, face_idx)
+        ctx.incidence, ctx.shape, ctx.F = incidence, tuple(v.shape), faces_i32.shape[0]
+        ctx.mark_non_differentiable(face_idx)
+        return points, face_idx
+
+    @staticmethod
+    def backward(ctx, g, _):
+        r, face_idx = ctx.saved_tensors
+        out = torch.zeros(ctx.shape, dtype=torch.float32, device=g.device)
+        ops.sample_points_bwd(g.contiguous(), r, face_idx, ctx.F, ctx.incidence, out)
+        return out, None, None, None
+
+
+def sample_points_from_meshes(meshes, num_samples=10000, generator=None, *, return_normals=False, return_textures=False,
+                              return_face_idx=False):
+    """PyTorch3D's sample_points_from_meshes for one mesh -> points (1,N,3), uniform over the surface, with an autograd edge
+    to meshes.verts_packed().  Faces are drawn by inverse CDF of the fp64 face areas from sorted uniforms (not
+    ``multinomial``): the same law, the points ascending in the face index, and a NaN vertex gives NaN points instead of a
+    device-side assert.  generator: a torch.Generator (of the CPU or of the mesh's device); None = torch's global one.
+    return_face_idx=True also returns the (N,) int32 face of every point.  return_normals / return_textures:
+    NotImplementedError.  1 <= num_samples <= 2^20, else ValueError."""
+    if return_normals:
+        raise NotImplementedError("return_normals is not implemented")
+    if return_textures:
+        raise NotImplementedError("return_textures is not implemented")
+    if generator is not None and not isinstance(generator, torch.Generator):
+        raise TypeError(f"generator must be a torch.Generator or None, got {type(generator).__name__}")
+    ops.check_num_points(num_samples)
+    verts = meshes.verts_packed()
+    _no_cpu(verts)
+    from .render import vertex_incidence
+    faces_i32 = meshes.faces_i32()                                       # range-checked once per faces tensor
+    r = sample_uniforms(num_samples, generator, verts.device)
+    points, face_idx = _SamplePointsFn.apply(verts, faces_i32, vertex_incidence(faces_i32, verts.shape[0]), r)
+    return (points[None], face_idx) if return_face_idx else points[None]
+
+
+def surface_area(meshes):
+    """total area of the mesh's faces (the last entry of the sampling CDF) -> float; one host sync"""
+    verts = meshes.verts_packed()
+    _no_cpu(verts)
+    return float(ops.face_area_cdf(verts.detach(), meshes.faces_i32())[-1])
+
+
+def chamfer_floor(area, num_samples):
+    """2 A / (pi N): the Chamfer distance expected between two independent N-point samplings of the SAME surface of area A
+    (a Poisson process of density N / A has E[r^2] = A / (pi N) to its nearest point, once per direction)"""
+    import math
+    return 2.0 * float(area) / (math.pi * int(num_samples))
+
+
+def _as_cloud(t, what):
+    if not torch.is_tensor(t) or not (t.dim() == 2 or (t.dim() == 3 and t.shape[0] == 1)) or t.shape[-1] != 3:
+        shape = tuple(t.shape) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what} must be a (P,3) or (1,P,3) tensor (one cloud), got {shape}")
+    ops.check_num_points(int(t.shape[-2]), f"the number of points of {what}")
+    return t.reshape(-1, 3)
+
+
+def knn_points(p1, p2, K=1):
+    """PyTorch3D's knn_points at K = 1 for one pair of clouds ((P,3) or (1,P,3)) -> (dists, idx): the squared distance of
+    every point of p1 to its nearest point of p2 and that point's index (int64; the lowest among equals), shaped (1,P1,1) for
+    batched input, (P1,1) otherwise.  A brute-force scan in fp32, exact.  The distances carry NO autograd edge: the
+    differentiable user of this search is chamfer_distance.  K != 1: NotImplementedError."""
+    if K != 1:
+        raise NotImplementedError(f"K must be 1, got K={K!r}")
+    a, b = _as_cloud(p1, "p1"), _as_cloud(p2, "p2")
+    _no_cpu(a)
+    _no_cpu(b)
+    idx, dist = ops.knn1(a.detach(), b.detach())
+    lead = (1,) if p1.dim() == 3 else ()
+    return dist.reshape(lead + (-1, 1)), idx.to(torch.int64).reshape(lead + (-1, 1))
+
+
+def _inverse_list(nn):
+    s = torch.sort(nn, stable=True)
+    return s.indices.to(torch.int32), s.values
+
+
+class _ChamferFn(torch.autograd.Function):
+    """loss = sx sum_i |x_i - y_nn(i)|^2 (+ sy sum_j |y_j - x_nn(j)|^2); the neighbours are constants of the backward"""
+
+    @staticmethod
+    def forward(ctx, x, y, sx, sy, single):
+        xd, yd = x.detach().to(torch.float32).contiguous(), y.detach().to(torch.float32).contiguous()
+        out = torch.zeros((1,), dtype=torch.float32, device=xd.device)
+        nn_x, d_x = ops.knn1(xd, yd)
+        ops.chamfer_sum(d_x, sx, out)
+        nn_y = None
+        if not single:
+            nn_y, d_y = ops.knn1(yd, xd)
+            ops.chamfer_sum(d_y, sy, out)
+        ctx.state = (xd, yd, nn_x, nn_y, sx, sy)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, yd, nn_x, nn_y, sx, sy = ctx.state
+        gx = gy = None
+        if ctx.needs_input_grad[0]:
+            order, values = _inverse_list(nn_y) if nn_y is not None else (None, None)
+            gx = ops.chamfer_bwd(xd, yd, nn_x, order, values, 2.0 * sx, 2.0 * sy, torch.zeros_like(xd)) * g
+        if ctx.needs_input_grad[1]:
+            order, values = _inverse_list(nn_x)
+            gy = ops.chamfer_bwd(yd, xd, nn_y, order, values, 2.0 * sy, 2.0 * sx, torch.zeros_like(yd)) * g
+        return gx, gy, None, None, None
+
+
+def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_normals=None, weights=None,
+                     batch_reduction="mean", point_reduction="mean", norm=2, single_directional=False, abs_cosine=True):
+    """PyTorch3D's chamfer_distance for one pair of clouds ((P,3) or (1,P,3), 1 <= P <= 2^20) -> (loss, None):
+    loss = mean_i |x_i - y_nn(i)|^2 + mean_j |y_j - x_nn(j)|^2 (the first term alone with single_directional=True; sums
+    with point_reduction="sum"), each term an ordered fp64 sum rounded once; gradients to x and y, the neighbours constant.
+    Two independent N-point samplings of one surface of area A are 2 A / (pi N) apart (chamfer_floor), not 0.
+    batch_reduction "mean" / "sum" (one pair: the same).  NotImplementedError: x_lengths, y_lengths, x_normals, y_normals,
+    weights, norm=1, point_reduction=None, batch_reduction=None.  No CPU fallback."""
+    for name, value in (("x_lengths", x_lengths), ("y_lengths", y_lengths), ("x_normals", x_normals), ("y_normals", y_normals),
+                        ("weights", weights)):
+        if value is not None:
+            raise NotImplementedError(f"{name} is not implemented (one pair of full clouds, no normals, no weights)")
+    if norm == 1:
+        raise NotImplementedError("norm=1 is not implemented")
+    if norm != 2:
+        raise ValueError(f"norm must be 1 or 2, got {norm!r}")
+    if point_reduction is None:
+        raise NotImplementedError("point_reduction=None is not implemented")
+    if batch_reduction is None:
+        raise NotImplementedError("batch_reduction=None is not implemented")
+    if point_reduction not in ("mean", "sum"):
+        raise ValueError(f"point_reduction must be 'mean' or 'sum', got {point_reduction!r}")
+    if batch_reduction not in ("mean", "sum"):
+        raise ValueError(f"batch_reduction must be 'mean' or 'sum', got {batch_reduction!r}")
+    a, b = _as_cloud(x, "x"), _as_cloud(y, "y")
+    _no_cpu(a)
+    _no_cpu(b)
+    mean = point_reduction == "mean"
+    loss = _ChamferFn.apply(a, b, 1.0 / a.shape[0] if mean else 1.0, 1.0 / b.shape[0] if mean else 1.0, bool(single_directional))
+    return loss, None

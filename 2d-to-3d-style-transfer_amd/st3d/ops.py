@@ -454,6 +454,111 @@ def mesh_reg_ex(verts, target, topo, cot_topo, weights, laplacian_method="unifor
     return out, g
 
 
+# ------------------------------------------------------------------ Chamfer loss (csrc/chamfer.hip)
+CHAMFER_MAX_POINTS = 1 << 20
+F64 = torch.float64
+
+
+def check_num_points(n, what="num_samples"):
+    """an integer in 1..2^20; else ValueError"""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= CHAMFER_MAX_POINTS:
+        raise ValueError(f"{what} must be an integer in 1..{CHAMFER_MAX_POINTS}, got {n!r}")
+    return n
+
+
+def _cloud(t, what):
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError(f"{what} must be (P,3), got {tuple(t.shape)}")
+    check_num_points(int(t.shape[0]), f"the number of points of {what}")
+    return _f32c(t)
+
+
+def knn1_geometry(P1, P2):
+    """-> (tile, segments) of the launch st3d_knn1 makes: segment s scans the ceil(ceil(P2 / tile) / segments) * tile points
+    from s times that many on, in LDS tiles of `tile` points."""
+    tile, segments = ctypes.c_int(0), ctypes.c_int(0)
+    call("st3d_knn1_geometry", check_num_points(P1, "P1"), check_num_points(P2, "P2"), ctypes.byref(tile), ctypes.byref(segments))
+    return tile.value, segments.value
+
+
+def knn1(x, y):
+    """x (P1,3), y (P2,3) -> (idx (P1) int32 = the nearest y of every x, the lowest index among equals; dist2 (P1) fp32)"""
+    x, y = _cloud(x, "x"), _cloud(y, "y")
+    P1, P2 = x.shape[0], y.shape[0]
+    nbytes = _lib.load().st3d_knn1_workspace_bytes(P1, P2)
+    ws = torch.empty((nbytes // 8,), dtype=F64, device=x.device)
+    idx = torch.empty((P1,), dtype=I32, device=x.device)
+    dist = torch.empty((P1,), dtype=F32, device=x.device)
+    call("st3d_knn1", dptr(x), dptr(y), P1, P2, dptr(ws), nbytes, dptr(idx), dptr(dist), stream_ptr())
+    return idx, dist
+
+
+def face_area_cdf(verts, faces_i32):
+    """-> cdf (F) fp64: the inclusive scan of the fp64 face areas.  faces_i32: range-checked (Meshes.faces_i32())."""
+    verts = _f32c(verts)
+    F = faces_i32.shape[0]
+    nbytes = _lib.load().st3d_face_area_cdf_scratch_bytes(F)
+    scratch = torch.empty((max(nbytes // 8, 1),), dtype=F64, device=verts.device)
+    cdf = torch.empty((F,), dtype=F64, device=verts.device)
+    call("st3d_face_area_cdf", dptr(verts), dptr(faces_i32, I32), F, dptr(scratch), nbytes, dptr(cdf), stream_ptr())
+    return cdf
+
+
+def sample_points_fwd(verts, faces_i32, cdf, r):
+    """r (3,N) fp32 uniforms, row 0 ascending -> (points (N,3), face_idx (N) int32 ascending)"""
+    verts = _f32c(verts)
+    if r.dim() != 2 or r.shape[0] != 3:
+        raise ValueError(f"r must be (3,N), got {tuple(r.shape)}")
+    N, F = check_num_points(int(r.shape[1])), faces_i32.shape[0]
+    if tuple(cdf.shape) != (F,):
+        raise ValueError("cdf does not belong to these faces")
+    points = torch.empty((N, 3), dtype=F32, device=verts.device)
+    face_idx = torch.empty((N,), dtype=I32, device=verts.device)
+    call("st3d_sample_points_fwd", dptr(verts), dptr(faces_i32, I32), F, dptr(cdf, F64), dptr(r, F32), N, dptr(points),
+         dptr(face_idx), stream_ptr())
+    return points, face_idx
+
+
+def sample_points_bwd(grad_points, r, face_idx, F, incidence, out):
+    """out (V,3) += d <grad_points, points> / d verts; incidence = render.vertex_incidence(faces_i32, V)"""
+    N, V = check_num_points(int(r.shape[1])), out.shape[0]
+    if tuple(grad_points.shape) != (N, 3) or tuple(face_idx.shape) != (N,):
+        raise ValueError("grad_points / face_idx do not belong to r")
+    if tuple(incidence[0].shape) != (V + 1,) or tuple(incidence[1].shape) != (3 * F,):
+        raise ValueError("the incidence list does not belong to this mesh")
+    nbytes = _lib.load().st3d_sample_points_bwd_scratch_bytes(F)
+    scratch = torch.empty((nbytes // 8,), dtype=F64, device=out.device)
+    call("st3d_sample_points_bwd", dptr(_f32c(grad_points)), dptr(r, F32), dptr(face_idx, I32), N, F, V, dptr(incidence[0], I32),
+         dptr(incidence[1], I32), dptr(scratch), nbytes, dptr(out, F32), stream_ptr())
+    return out
+
+
+def chamfer_sum(dist, scale, out):
+    """out (1) fp32 = (float)((double)out + scale * sum(dist)), the sum ordered, in fp64"""
+    call("st3d_chamfer_sum", dptr(dist, F32), check_num_points(int(dist.numel()), "the number of distances"), float(scale),
+         dptr(out, F32), stream_ptr())
+    return out
+
+
+def chamfer_bwd(x, y, nn, order, sorted_nn, c_self, c_other, out):
+    """out (P1,3) += c_self (x_i - y[nn[i]]) + c_other sum over the y_j whose neighbour is x_i, ascending j.  nn (P1) int32 or
+    None; (order, sorted_nn) (P2) int32 = torch.sort(neighbours of y in x, stable=True) indices and values, or both None."""
+    x, y = _cloud(x, "x"), _cloud(y, "y")
+    P1, P2 = x.shape[0], y.shape[0]
+    if nn is None and order is None:
+        raise ValueError("chamfer_bwd needs nn or (order, sorted_nn)")
+    if (order is None) != (sorted_nn is None):
+        raise ValueError("order and sorted_nn come together")
+    if (nn is not None and tuple(nn.shape) != (P1,)) or (order is not None and (tuple(order.shape) != (P2,) or
+                                                                                 tuple(sorted_nn.shape) != (P2,))):
+        raise ValueError("index lists do not belong to these clouds")
+    if tuple(out.shape) != (P1, 3):
+        raise ValueError("out must be (P1,3)")
+    call("st3d_chamfer_bwd", dptr(x), dptr(y), P1, P2, dptr(nn, I32), dptr(order, I32), dptr(sorted_nn, I32), float(c_self),
+         float(c_other), dptr(out, F32), stream_ptr())
+    return out
+
+
 # ------------------------------------------------------------------ general soft renderer (K faces per pixel, blur)
 def raster_soft_fwd(verts_ndc, faces_i32, S, K, blur_radius=0.0, clip_bary=None, cull_backfaces=False,
                     perspective_correct=True, z_clip=None):

@@ -73,6 +73,9 @@ def main(argv=None):
                     outline_term = run.silhouette_term(mesh, cams, outline_of_batch[vb.index], vb.size)
                     if torch.is_tensor(outline_term):
                         loss = loss + outline_term
+                    anchor_term = run.chamfer_term(mesh)    # --chamfer_weight, off by default
+                    if torch.is_tensor(anchor_term):
+                        loss = loss + anchor_term
                     loss.backward()
                 else:
                     loss = run.idle_contribution()

@@ -677,6 +677,50 @@ int st3d_mesh_reg_ex(const float *verts, const float *target_verts, int V, const
                      const float *weights, float *scratch, float *partials, float *loss_out,
                      float *grad_verts, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ Chamfer loss (csrc/chamfer.hip):
+ * PyTorch3D's sample_points_from_meshes + knn_points(K=1) + chamfer_distance for ONE mesh and ONE pair of clouds.
+ * Clouds are (P,3) fp32 with 1 <= P <= 2^20; every sum is ordered, in fp64, rounded once (no float atomics: two runs are
+ * bit-equal).  ST3D_E_INVALID before any launch: null pointers, sizes out of range, a short or misaligned (8 bytes)
+ * workspace / scratch.  Nothing is allocated.
+ *
+ * Nearest neighbour: for query x_i scan j = 0 .. P2-1, d = (dx dx + dy dy) + dz dz in fp32 (no contraction), j replaces the
+ * best when d < best (best = +Inf, idx = 0 at the start: the lowest index wins among equals, a NaN target is never chosen).
+ * dist[i] is recomputed from x_i and y[idx[i]] (a NaN query gives NaN).  The y range is split into `segments` runs of
+ * ceil(ceil(P2 / tile) / segments) * tile points, each scanned by its own workgroups in LDS tiles of `tile` points; a second
+ * pass takes the minimum over the runs in ascending order with the same d < best.  st3d_knn1_geometry reports tile and
+ * segments of the launch st3d_knn1 makes for (P1, P2); workspace >= st3d_knn1_workspace_bytes (0 for refused sizes). */
+int st3d_knn1_geometry(int P1, int P2, int *tile, int *segments);
+size_t st3d_knn1_workspace_bytes(int P1, int P2);
+int st3d_knn1(const float *x, const float *y, int P1, int P2, void *workspace, size_t workspace_bytes, int32_t *idx, float *dist,
+              st3d_stream_t stream);
+/* cdf (F) fp64: the inclusive scan, in a fixed tree, of area_f = |(v1 - v0) x (v2 - v0)| / 2 evaluated in fp64 from the fp32
+ * vertices.  faces (F,3) int32, every index in range (checked by the caller).  scratch >= st3d_face_area_cdf_scratch_bytes. */
+size_t st3d_face_area_cdf_scratch_bytes(int F);
+int st3d_face_area_cdf(const float *verts, const int32_t *faces, int F, void *scratch, size_t scratch_bytes, double *cdf,
+                       st3d_stream_t stream);
+/* r (3,N) fp32 uniforms in [0,1), row 0 ascending.  face_idx[n] = the smallest f with cdf_f > (double)r0[n] * cdf_{F-1},
+ * clamped to [0, F-1] (ascending in n); s = sqrtf(r1), w0 = 1 - s, w1 = s (1 - r2), w2 = s r2;
+ * points[n] = (w0 a + w1 b) + w2 c per coordinate in fp32.  A total area cdf_{F-1} that is NaN or Inf (a NaN / Inf vertex)
+ * draws no face: every point is NaN (face_idx = F-1), and with it the loss -- nothing aborts. */
+int st3d_sample_points_fwd(const float *verts, const int32_t *faces, int F, const double *cdf, const float *r, int N,
+                           float *points, int32_t *face_idx, st3d_stream_t stream);
+/* grad_verts (V,3) += the gradient of <grad_points, points>: d a += w0 g, d b += w1 g, d c += w2 g (face choice and weights
+ * are constants).  One (3,3) fp64 block per face in scratch (its samples found by binary search in the ascending face_idx,
+ * added in order), then a gather per vertex over inc_off (V+1) / inc_ref (3F) = face * 3 + corner, in list order. */
+size_t st3d_sample_points_bwd_scratch_bytes(int F);
+int st3d_sample_points_bwd(const float *grad_points, const float *r, const int32_t *face_idx, int N, int F, int V,
+                           const int32_t *inc_off, const int32_t *inc_ref, void *scratch, size_t scratch_bytes, float *grad_verts,
+                           st3d_stream_t stream);
+/* loss[0] = (float)((double)loss[0] + scale * sum_i dist[i]): the sum in fp64 in a fixed order, one rounding per call */
+int st3d_chamfer_sum(const float *dist, int P, double scale, float *loss, st3d_stream_t stream);
+/* One side of the Chamfer gradient, the indices being constants:
+ *   grad_x[i] += c_self (x_i - y[nn[i]]) + c_other sum_{k: sorted[k] == i} (x_i - y[order[k]])
+ * in fp64, rounded once.  nn (P1) = the neighbour of x_i in y; order (P2) / sorted (P2) = the indices and values of a stable
+ * ascending sort of the neighbours of y_j in x (so the inner sum runs in ascending j).  nn may be NULL (no first term), or
+ * order and sorted together (no second term).  Indices outside [0, P2) are skipped. */
+int st3d_chamfer_bwd(const float *x, const float *y, int P1, int P2, const int32_t *nn, const int32_t *order,
+                     const int32_t *sorted, double c_self, double c_other, float *grad_x, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ texture pyramid (csrc/texpyr.hip):
  * the texture map (T,T,3) as the sum of L maps of sides T_l = T / 2^l, each upsampled to T x T.  `params` is one flat
  * fp32 tensor of st3d_texpyr_numel(T, L) = 3 * sum_l T_l^2 elements; level l is the (T_l, T_l, 3) row-major block at

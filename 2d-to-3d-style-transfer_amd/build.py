@@ -47,6 +47,10 @@ SOURCES = {
     "mesh.hip": [],
     # nearest-neighbour distances and sampled points are compared bit for bit with their numpy restatement (s = sqrtf(r1))
     "chamfer.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # the norms (squares added in ascending channel order, sqrtf, the division) are compared with their numpy restatement
+    # rounding for rounding; the similarities are MFMA fma chains and the explicit fmaf of the merge pass, which the flag
+    # leaves alone
+    "nnfm.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "texpyr.hip": ["-ffp-contract=off"],       # the roundings its tests count are the ones written in the source
     # shade.hip's flags: its level-0 taps and blend are those of the plain kernels bit for bit, the chain is compared bit for
     # bit with its ordered numpy restatement

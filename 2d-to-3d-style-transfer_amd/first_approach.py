@@ -66,7 +66,8 @@ def main(argv=None):
             targets = finalize_tensor(style_transfer(start, content, style, run.vgg, steps=args.n_style_transfer_steps,
                                                      style_weight=args.style_weight, content_weight=args.content_weight,
                                                      lr=args.style_transfer_lr,
-                                                     style_masks=region if args.style_mask == 'object' else None))
+                                                     style_masks=region if args.style_mask == 'object' else None,
+                                                     nnfm_weight=args.nnfm_weight, nnfm_layers=args.nnfm_layers))
             run.save_views(targets, vb.lo)
 
         # phase B: masked MSE between the renders and the stylised views

@@ -93,6 +93,31 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
     return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need, flat, style_masks)
 
 
+def compute_nnfm_loss(current_imgs, style_imgs, model, layers=('conv3_1',), *, masks=None, batch_denom=None):
+    """The NNFM style term (Zhang et al., "ARF", ECCV 2022; style_transfer.nnfm_loss) of ``current_imgs`` (B,3,S,S) against
+    ``style_imgs`` ((1 or B,3,Ss,Ss); one image expanded over the batch is searched as one style), summed over ``layers``
+    (names from conv2_1, conv3_1, conv4_1, conv4_2, conv5_1).  The taps come through ``get_features``: differentiable for
+    the current images, without gradient and cached on the style tensor's identity and version for the style.  ``masks``
+    (B,1,S,S) | (B,S,S) in [0,1], e.g. the renders' coverage, weight the positions; ``batch_denom`` is the global batch when
+    the views are sharded.  Cost: the term makes its own partial VGG forward and backward up to its deepest tap, next to
+    the fused plan's of compute_perceptual_loss."""
+    import style_transfer as _st
+    if not isinstance(model, _vgg.Vgg19Features):
+        raise TypeError("compute_nnfm_loss needs the st3d VGG returned by utils.get_vgg()")
+    if not torch.is_tensor(current_imgs) or not torch.is_tensor(style_imgs):
+        raise TypeError("current_imgs and style_imgs must be tensors")
+    if not current_imgs.is_cuda or not style_imgs.is_cuda:
+        raise RuntimeError("st3d runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
+    layers = _st.check_nnfm_layers(layers)
+    if current_imgs.dim() != 4 or current_imgs.shape[1] != 3 or style_imgs.dim() != 4 or style_imgs.shape[1] != 3:
+        raise ValueError("current_imgs and style_imgs must be (B,3,S,S)")
+    B, S = current_imgs.shape[0], current_imgs.shape[2]
+    if style_imgs.shape[0] not in (1, B):
+        raise ValueError(f"style_imgs must hold 1 or {B} images, got {style_imgs.shape[0]}")
+    masks = check_style_masks(masks, B, S)
+    return _st._nnfm_term(current_imgs, style_imgs, model, layers, masks, batch_denom)
+
+
 class _FusedLossFn(torch.autograd.Function):
     """A loss whose HIP call returns the value and its gradient together: backward only scales."""
 

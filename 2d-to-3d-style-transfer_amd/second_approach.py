@@ -81,6 +81,9 @@ def main(argv=None):
             anchor_term = run.chamfer_term(mesh)    # --chamfer_weight, off by default
             if torch.is_tensor(anchor_term):
                 loss = loss + anchor_term
+            style_term = run.nnfm_term(current, cov, style, vb.size)    # --nnfm_weight, off by default
+            if torch.is_tensor(style_term):
+                loss = loss + style_term
 
             if args.save_every and steps_done % args.save_every == 0:
                 run.save_views(current, vb.lo)          # encoded by worker threads, off the step's critical path

@@ -26,6 +26,15 @@ _LIGHTS = ['ambient', 'point', 'directional', 'headlight']
 _STYLE_MASKS = ['none', 'object']
 _TEXTURE_TYPES = ['uv', 'vertex']
 _LAPLACIANS = ['uniform', 'cot', 'cotcurv']
+_NNFM_LAYERS = ['conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.NNFM_LAYERS
+
+
+def nnfm_layers(text):
+    """--nnfm_layers: a comma list of distinct names from conv2_1,conv3_1,conv4_1,conv4_2,conv5_1 -> the tuple"""
+    names = tuple(s.strip() for s in text.split(','))
+    if not names or len(set(names)) != len(names) or any(n not in _NNFM_LAYERS for n in names):
+        raise argparse.ArgumentTypeError(f"expected a comma list of distinct names from {','.join(_NNFM_LAYERS)}, got {text!r}")
+    return names
 
 
 def edge_target_length(text):
@@ -107,6 +116,13 @@ SHARED_FLAGS = [
          "sample_points_from_meshes + chamfer_distance).  Unlike --mesh_verts_weight it leaves a vertex free to slide along "
          "the surface; at its optimum it is about 2 area / (pi N), not 0.  --optimization_target mesh / both only; 0 = off"),
     Flag("chamfer_samples", int, 5000, "points per cloud of the Chamfer term, 1...1048576"),
+    Flag("nnfm_weight", float, 0.0, "weight of the nearest-neighbour feature matching style term (ARF, Zhang et al. 2022): every "
+         "VGG feature vector of a render looks up its nearest style feature by cosine distance, the term is the mean distance.  "
+         "Keeps the stroke-level detail the Gram term averages away; joins the Gram term, or replaces it with --style_weight 0.  "
+         "--style_mask object restricts it to the object's coverage.  Costs its own partial VGG forward and backward per "
+         "step; 0 = off"),
+    Flag("nnfm_layers", nnfm_layers, ('conv3_1',), "taps of the NNFM term, a comma list from conv2_1,conv3_1,conv4_1,conv4_2,"
+         "conv5_1; their terms are added"),
     Flag("texture_lod_bias", float, 0.0, "added to every pixel's level of detail before it is clamped to the chain "
          "(--texture_mip_levels): negative = sharper, positive = blurrier"),
 ]
@@ -138,6 +154,9 @@ def check_args(args):
                 "term would be a constant")
     if not 1 <= getattr(args, "chamfer_samples", 5000) <= 1 << 20:
         return "--chamfer_samples must be in 1...1048576"
+    nnfm = getattr(args, "nnfm_weight", 0.0)
+    if not (math.isfinite(nnfm) and nnfm >= 0.0):
+        return "--nnfm_weight must be finite and >= 0"
     if not getattr(args, "silhouette_sigma", 1e-4) > 0.0:
         return "--silhouette_sigma must be positive"
     k = getattr(args, "silhouette_faces_per_pixel", None)
@@ -678,6 +697,19 @@ class Run:
         return a.silhouette_weight * _l.compute_silhouette_loss(self.renderer, mesh, cams, target,
                                                                 sigma=a.silhouette_sigma, batch_denom=batch_size,
                                                                 faces_per_pixel=getattr(a, "silhouette_faces_per_pixel", None))
+
+    def nnfm_term(self, current, cov, style, batch_size):
+        """--nnfm_weight x this rank's share of the batch mean of the NNFM style term of the `current` renders against
+        `style` over --nnfm_layers (losses.compute_nnfm_loss).  An image term like tv_weight: divided by the GLOBAL batch, so
+        a sharded run equals the unsharded one; nothing on a rank without views; --style_mask object hands the renders'
+        coverage `cov` to it as position weights.  With weight 0 (the default) nothing runs at all.  No checkpoint state."""
+        a = self.args
+        if not getattr(a, "nnfm_weight", 0.0) or current is None or current.shape[0] == 0:
+            return 0
+        import losses as _l
+        masks = cov if getattr(a, "style_mask", "none") == 'object' else None
+        return a.nnfm_weight * _l.compute_nnfm_loss(current, style, self.vgg, layers=a.nnfm_layers, masks=masks,
+                                                    batch_denom=batch_size)
 
     def setup_chamfer(self):
         """--chamfer_weight > 0: the run's generator, seeded with --seed (0 when unset) identically on every rank, and the

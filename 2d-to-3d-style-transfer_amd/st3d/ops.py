@@ -559,6 +559,117 @@ def chamfer_bwd(x, y, nn, order, sorted_nn, c_self, c_other, out):
     return out
 
 
+# ------------------------------------------------------------------ NNFM style loss (csrc/nnfm.hip)
+NNFM_MAX_POSITIONS = 1 << 20
+NNFM_MAX_CHANNELS = 512
+
+
+def _nnfm_size(n, what, hi=NNFM_MAX_POSITIONS):
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= hi:
+        raise ValueError(f"{what} must be an integer in 1..{hi}, got {n!r}")
+    return n
+
+
+def _nnfm_tap(t, what):
+    """a tap (B,C,H,W) -> (contiguous fp32 tensor, B, C, H * W)"""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what} must be a tensor (B,C,H,W)")
+    if t.dim() != 4:
+        raise ValueError(f"{what} must be (B,C,H,W), got {tuple(t.shape)}")
+    B, C, H, W = (int(s) for s in t.shape)
+    _nnfm_size(B, f"the batch of {what}", 65535)
+    _nnfm_size(C, f"the channels of {what}", NNFM_MAX_CHANNELS)
+    _nnfm_size(H * W, f"the positions of {what}")
+    return _f32c(t), B, C, H * W
+
+
+def nnfm_geometry(N, M, C):
+    """-> (tile_q, tile_s, segments) of the launch st3d_nnfm_search makes: query tiles of tile_q positions; run s scans the
+    ceil(ceil(M / tile_s) / segments) * tile_s style positions from s times that many on, in tiles of tile_s."""
+    tq, ts, seg = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    call("st3d_nnfm_geometry", _nnfm_size(N, "N"), _nnfm_size(M, "M"), _nnfm_size(C, "C", NNFM_MAX_CHANNELS), ctypes.byref(tq),
+         ctypes.byref(ts), ctypes.byref(seg))
+    return tq.value, ts.value, seg.value
+
+
+def nnfm_normalise(x, want_hat=True):
+    """x (B,C,H,W) -> (xhat (B,C,H,W) fp32 = every position's vector over its norm, a zero vector staying zero -- or None --,
+    norm (B,H*W) fp32 = sqrtf of the squares added in ascending channel order)"""
+    x, B, C, M = _nnfm_tap(x, "x")
+    xhat = torch.empty_like(x) if want_hat else None
+    norm = torch.empty((B, M), dtype=F32, device=x.device)
+    call("st3d_nnfm_normalise", dptr(x), B, C, M, dptr(xhat), dptr(norm), stream_ptr())
+    return xhat, norm
+
+
+def _nnfm_weights(weights, B, N):
+    if weights is None:
+        return None
+    if not torch.is_tensor(weights):
+        raise TypeError("weights must be a tensor (B,N) or (B,H,W)")
+    if weights.numel() != B * N or weights.shape[0] != B:
+        raise ValueError(f"weights must hold ({B},{N}) values, got {tuple(weights.shape)}")
+    return _f32c(weights).reshape(B, N)
+
+
+def _nnfm_style(style_hat, B, C):
+    style_hat, Bs, Cs, M = _nnfm_tap(style_hat, "style_hat")
+    if Cs != C:
+        raise ValueError(f"style_hat has {Cs} channels, the features {C}")
+    if Bs not in (1, B):
+        raise ValueError(f"style_hat must hold 1 or {B} images, got {Bs}")
+    return style_hat, Bs, M
+
+
+def nnfm_search(feat, style_hat, weights=None, normalised=None):
+    """feat (B,C,H,W) the render tap, style_hat (Bs,C,Hs,Ws) the unit-norm style tap (nnfm_normalise), Bs in {1, B}, weights
+    (B,H*W) | (B,H,W) >= 0 or None -> (idx (B,N) int32 = the nearest style position of every position by cosine distance, the
+    lowest index among equals, -1 where inactive or the query is zero; dist (B,N) fp32 = 1 - similarity).
+    normalised = nnfm_normalise(feat) when the caller has it already."""
+    feat, B, C, N = _nnfm_tap(feat, "feat")
+    style_hat, Bs, M = _nnfm_style(style_hat, B, C)
+    weights = _nnfm_weights(weights, B, N)
+    fhat, fnorm = normalised if normalised is not None else nnfm_normalise(feat)
+    nbytes = _lib.load().st3d_nnfm_workspace_bytes(B, N, M, C)
+    ws = torch.empty((nbytes // 8,), dtype=F64, device=feat.device)
+    idx = torch.empty((B, N), dtype=I32, device=feat.device)
+    dist = torch.empty((B, N), dtype=F32, device=feat.device)
+    call("st3d_nnfm_search", dptr(fhat, F32), dptr(fnorm, F32), dptr(style_hat), dptr(weights), B, Bs, C, N, M, dptr(ws), nbytes,
+         dptr(idx), dptr(dist), stream_ptr())
+    return idx, dist
+
+
+def nnfm_sum(dist, weights=None, batch_denom=None):
+    """dist (B,N), weights (B,N) or None -> (loss (1) fp32 = (1 / batch_denom) sum_b (sum_i w_i d_i / sum_i w_i), ordered,
+    in fp64, rounded once; wsum (B) fp64 = sum_i w_i).  An image with sum w = 0 adds 0."""
+    if dist.dim() != 2:
+        raise ValueError(f"dist must be (B,N), got {tuple(dist.shape)}")
+    B, N = int(dist.shape[0]), int(dist.shape[1])
+    weights = _nnfm_weights(weights, B, N)
+    loss = torch.empty((1,), dtype=F32, device=dist.device)
+    wsum = torch.empty((B,), dtype=F64, device=dist.device)
+    call("st3d_nnfm_sum", dptr(dist, F32), dptr(weights), B, N, 1.0 / float(batch_denom if batch_denom is not None else B),
+         dptr(loss), dptr(wsum), stream_ptr())
+    return loss, wsum
+
+
+def nnfm_bwd(feat, style_hat, idx, dist, wsum, weights=None, batch_denom=None, grad_out=None):
+    """-> d loss / d feat (B,C,H,W), one launch, every element written: -g (w_i / (W_b batch_denom n_i)) (s^_j - sim f^_i) with
+    j = idx_i, sim = 1 - dist_i; exact zeros where idx_i = -1.  grad_out: the incoming scalar g as a device tensor, or None."""
+    feat, B, C, N = _nnfm_tap(feat, "feat")
+    style_hat, Bs, M = _nnfm_style(style_hat, B, C)
+    weights = _nnfm_weights(weights, B, N)
+    if tuple(idx.shape) != (B, N) or tuple(dist.shape) != (B, N) or tuple(wsum.shape) != (B,):
+        raise ValueError("idx / dist / wsum do not belong to these features")
+    if grad_out is not None:
+        grad_out = _f32c(grad_out).reshape(1)
+    grad = torch.empty_like(feat)
+    call("st3d_nnfm_bwd", dptr(feat), dptr(style_hat), dptr(idx, I32), dptr(dist, F32), dptr(weights),
+         dptr(wsum, F64), dptr(grad_out), B, Bs, C, N, M, 1.0 / float(batch_denom if batch_denom is not None else B), dptr(grad),
+         stream_ptr())
+    return grad
+
+
 # ------------------------------------------------------------------ general soft renderer (K faces per pixel, blur)
 def raster_soft_fwd(verts_ndc, faces_i32, S, K, blur_radius=0.0, clip_bary=None, cull_backfaces=False,
                     perspective_correct=True, z_clip=None):

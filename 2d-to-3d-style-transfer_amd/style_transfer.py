@@ -141,10 +141,146 @@ def guided_gram_matrix(tensor, mask):
                      f"(sides {[int(p.shape[1]) for p in planes]})")
 
 
+# ---------------------------------------------------------------------------- NNFM style loss (csrc/nnfm.hip)
+NNFM_LAYERS = ('conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1')       # names of _DEFAULT_LAYERS the term may tap
+_NNFM_MASK_RATIOS = (1, 2, 4, 8, 16)
+
+
+class NnfmStyle:
+    """The unit-norm copy of a style tap (Bs,C,Hs,Ws), made once per style image by ``nnfm_style``."""
+
+    def __init__(self, hat):
+        self.hat = hat
+
+
+def nnfm_style(style_features):
+    """style tap (Bs,C,Hs,Ws) -> NnfmStyle: every position's vector over its norm (a zero vector stays zero)."""
+    if not torch.is_tensor(style_features):
+        raise TypeError("style_features must be a tensor (Bs,C,Hs,Ws)")
+    if not style_features.is_cuda:
+        raise RuntimeError("st3d nnfm_style runs on the GPU (libst3d); got a CPU tensor -- there is no CPU fallback")
+    hat, _ = _ops.nnfm_normalise(style_features.detach())
+    return NnfmStyle(hat)
+
+
+def nnfm_pool_mask(mask, B, H, W):
+    """mask (B,1,S,S') | (B,S,S') in [0,1] -> position weights (B,H,W): successive 2x2 averages, S / H = S' / W one of
+    1, 2, 4, 8, 16.  Plain torch pooling (not the hot path); a constant of the gradient."""
+    if not torch.is_tensor(mask):
+        raise TypeError("mask must be a tensor (B,1,S,S) or (B,S,S)")
+    m = mask.detach().to(torch.float32)
+    if m.dim() == 4 and m.shape[1] == 1:
+        m = m[:, 0]
+    if m.dim() != 3 or m.shape[0] != B:
+        raise ValueError(f"mask must be ({B},1,S,S) or ({B},S,S), got {tuple(mask.shape)}")
+    S, S2 = int(m.shape[1]), int(m.shape[2])
+    if S % H or S2 % W or S // H != S2 // W or S // H not in _NNFM_MASK_RATIOS:
+        raise ValueError(f"a mask of {S} x {S2} does not reduce to features of {H} x {W} by a factor of {_NNFM_MASK_RATIOS}")
+    m = m[:, None]
+    for _ in range((S // H).bit_length() - 1):
+        m = torch.nn.functional.avg_pool2d(m, 2)
+    return m[:, 0].contiguous()
+
+
+class _NnfmFn(torch.autograd.Function):
+    """One tap: forward = ops.nnfm_normalise (the queries), ops.nnfm_search, ops.nnfm_sum; backward = ops.nnfm_bwd, one
+    launch.  Indices and weights are constants; the style gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, features, style_hat, weights, batch_denom):
+        f = features.detach().to(torch.float32).contiguous()
+        normalised = _ops.nnfm_normalise(f)
+        idx, dist = _ops.nnfm_search(f, style_hat, weights, normalised=normalised)
+        loss, wsum = _ops.nnfm_sum(dist, weights, batch_denom)
+        ctx.saved = (f, style_hat, idx, dist, wsum, weights, batch_denom)
+        ctx.idx, ctx.dist = idx, dist
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        f, style_hat, idx, dist, wsum, weights, batch_denom = ctx.saved
+        grad = None
+        if ctx.needs_input_grad[0]:
+            grad = _ops.nnfm_bwd(f, style_hat, idx, dist, wsum, weights, batch_denom, grad_out)
+        return grad, None, None, None
+
+
+def nnfm_loss(features, style_features, mask=None, batch_denom=None):
+    """The nearest-neighbour feature matching loss of ARF (Zhang et al., ECCV 2022) over one tap: every position of
+    ``features`` (B,C,H,W) looks up its nearest position of ``style_features`` ((Bs,C,Hs,Ws), Bs 1 or B, any resolution; a
+    tensor or the ``nnfm_style`` of one) by cosine distance, and the loss is the mean distance per image, summed over the
+    images and divided by ``batch_denom`` (default B).  ``mask`` (B,1,S,S) | (B,S,S) in [0,1] weights the positions
+    (``nnfm_pool_mask``); positions of weight 0 are not searched and receive an exact zero gradient.  A zero feature vector
+    has distance 1 and gradient 0 (ARF adds 1e-8 to the norm).  Gradient to ``features`` only."""
+    if not torch.is_tensor(features):
+        raise TypeError("features must be a tensor (B,C,H,W)")
+    if not features.is_cuda:
+        raise RuntimeError("st3d nnfm_loss runs on the GPU (libst3d); got a CPU tensor -- there is no CPU fallback")
+    if features.dim() != 4:
+        raise ValueError(f"features must be (B,C,H,W), got {tuple(features.shape)}")
+    if batch_denom is not None and not (isinstance(batch_denom, int) and not isinstance(batch_denom, bool) and batch_denom >= 1):
+        raise ValueError(f"batch_denom must be a positive integer, got {batch_denom!r}")
+    style = style_features if isinstance(style_features, NnfmStyle) else nnfm_style(style_features)
+    B, C, H, W = features.shape
+    if style.hat.dim() != 4 or style.hat.shape[1] != C or style.hat.shape[0] not in (1, B):
+        raise ValueError(f"style_features must be (1 or {B},{C},Hs,Ws), got {tuple(style.hat.shape)}")
+    weights = nnfm_pool_mask(mask, B, H, W) if mask is not None else None
+    return _NnfmFn.apply(features, style.hat, weights, batch_denom)
+
+
+def check_nnfm_layers(layers):
+    """a non-empty sequence of distinct names from NNFM_LAYERS -> the tuple; else ValueError"""
+    if isinstance(layers, str):
+        layers = tuple(s for s in layers.split(',') if s)
+    layers = tuple(layers)
+    if not layers or len(set(layers)) != len(layers) or any(name not in NNFM_LAYERS for name in layers):
+        raise ValueError(f"nnfm layers must be distinct names from {','.join(NNFM_LAYERS)}, got {layers!r}")
+    return layers
+
+
+def _nnfm_tap_map(layers):
+    return {k: v for k, v in _DEFAULT_LAYERS.items() if v in layers}
+
+
+def _nnfm_style_taps(style_imgs, model, layers):
+    """{layer: NnfmStyle} of the style image(s), cached on the model under the tensor's identity and version (as the plan
+    caches the style Grams): the style VGG forward and its normalisation run once per style, not once per step.  One image
+    expanded over the batch is one style (Bs = 1)."""
+    key = (style_imgs.data_ptr(), style_imgs._version, tuple(style_imgs.shape), tuple(style_imgs.stride()), layers)
+    cache = getattr(model, "_nnfm_style_cache", None)
+    if cache is not None and cache[0] == key and cache[1].data_ptr() == style_imgs.data_ptr():
+        return cache[2]
+    s = style_imgs.detach()
+    if s.shape[0] > 1 and s.stride(0) == 0:
+        s = s[:1]
+    with torch.no_grad():
+        feats = get_features(s.to(torch.float32).contiguous(), model, _nnfm_tap_map(layers))
+        taps = {name: nnfm_style(feats[name]) for name in layers}
+    model._nnfm_style_cache = (key, style_imgs, taps)
+    return taps
+
+
+def _nnfm_term(current_imgs, style_imgs, model, layers, masks, batch_denom):
+    taps = _nnfm_style_taps(style_imgs, model, layers)
+    feats = get_features(current_imgs, model, _nnfm_tap_map(layers))
+    total = None
+    for name in layers:
+        term = nnfm_loss(feats[name], taps[name], mask=masks, batch_denom=batch_denom)
+        total = term if total is None else total + term
+    return total
+
+
 def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, steps=2000, style_weight=1e6, content_weight=1, lr=0.003,
-                   style_masks=None):
+                   style_masks=None, nnfm_weight=0.0, nnfm_layers=('conv3_1',)):
     # style_masks (B,1,S,S) | (B,S,S) in [0,1], e.g. the coverage of the renders being stylised: the guided style loss --
     # each tap's Gram of the optimised images is taken over the masked region only (default None: the reference's loss)
+    # nnfm_weight > 0: every step adds nnfm_weight x the NNFM term over nnfm_layers (its own partial VGG forward and backward
+    # next to the fused plan's) to the plan's gradient before Adam; style_masks serves both terms.  0: today's loop.
+    nnfm_weight = float(nnfm_weight)
+    if not (nnfm_weight >= 0.0 and nnfm_weight != float("inf")):
+        raise ValueError("nnfm_weight must be finite and >= 0")
+    if nnfm_weight:
+        nnfm_layers = check_nnfm_layers(nnfm_layers)
 
     # Ensure content_imgs and style_imgs are batched tensors
     assert initial_optimized_imgs.shape[0] == content_imgs.shape[0] == style_imgs.shape[0]
@@ -161,6 +297,7 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
     # content conv4_2 features and style Grams: computed once (reference :44-51)
     plan.set_content(content_imgs.to(device), force=True)
     plan.set_style(style_imgs.to(device), B, force=True)
+    nnfm_style_imgs = style_imgs.to(device) if nnfm_weight else None      # one tensor for the run: its taps are cached on it
 
     # Initialize target images  --> the ones to optimize
     optimized_imgs = initial_optimized_imgs.clone().detach().to(device).contiguous().requires_grad_(True)
@@ -170,6 +307,11 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
 
     for step in tqdm(range(steps), desc="2D Style Transfer"):
         _, grad = plan.loss(optimized_imgs, style_weight, content_weight, style_mask=style_masks)
+        if nnfm_weight:
+            # the term forwards through the same plan: taken after the fused loss has delivered its gradient
+            term = _nnfm_term(optimized_imgs, nnfm_style_imgs, model, nnfm_layers, style_masks, None)
+            (extra,) = torch.autograd.grad(term, optimized_imgs)
+            grad = grad + nnfm_weight * extra
         optimized_imgs.grad = grad
         optimizer.step()
 

@@ -57,7 +57,8 @@ def main(argv=None):
                 targets = finalize_tensor(style_transfer(start, content_of_batch[vb.index], style, run.vgg,
                                                          steps=args.n_style_transfer_steps, style_weight=args.style_weight,
                                                          content_weight=args.content_weight, lr=args.style_transfer_lr,
-                                                         style_masks=cov if args.style_mask == 'object' else None))
+                                                         style_masks=cov if args.style_mask == 'object' else None,
+                                                         nnfm_weight=args.nnfm_weight, nnfm_layers=args.nnfm_layers))
                 if rnd == args.n_rounds - 1:
                     run.save_views(targets, vb.lo)
             loss = torch.zeros((), device=run.device)

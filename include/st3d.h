@@ -721,6 +721,46 @@ int st3d_chamfer_sum(const float *dist, int P, double scale, float *loss, st3d_s
 int st3d_chamfer_bwd(const float *x, const float *y, int P1, int P2, const int32_t *nn, const int32_t *order,
                      const int32_t *sorted, double c_self, double c_other, float *grad_x, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ NNFM style loss (csrc/nnfm.hip):
+ * nearest-neighbour feature matching (Zhang et al., "ARF: Artistic Radiance Fields", ECCV 2022).  A render tap F (B,C,H,W),
+ * fp32, post-ReLU, N = H W positions; a style tap S (Bs,C,Hs,Ws), M = Hs Ws, Bs = 1 (one style for every image) or B;
+ * optional position weights w (B,N), each >= 0.  f_i / s_j: the C-vector at position i of image b / j of its style.
+ *   norms     n_i = sqrtf(sum_c f_ic^2), the squares rounded and added in ascending c in fp32; f^_i = f_i / n_i; likewise s^_j.
+ *   zeros     a zero vector has the unit copy 0: a zero style vector has similarity 0 with everything; a zero query
+ *             (n_i = 0) has distance 1, index -1, gradient 0.  (ARF adds 1e-8 to the norm instead: a gradient of 1e8 at 0.)
+ *   search    sim_ij = f^_i . s^_j, ONE fp32 fma chain in ascending c starting from 0 (the fp32 MFMA computes exactly that).
+ *             j ascending from best = -Inf, idx = 0; j replaces the best when sim_ij > best: the lowest index wins among
+ *             equals, a NaN style vector is never chosen, a NaN query keeps index 0 and gets a NaN distance.
+ *   distance  d_i = 1 - sim_{i,idx_i}.  Positions with w_i = 0 are inactive: d_i = 0, idx_i = -1, gradient exactly 0, no search.
+ *   loss      L_b = sum_i w_i d_i / sum_i w_i (w = 1 without weights), both sums in fp64 in a fixed order; an image with
+ *             sum w = 0 contributes 0 and receives no gradient; L = inv_denom sum_b L_b, rounded once (inv_denom = 1 / the
+ *             batch the mean divides by: B, or the global batch when views are sharded).
+ *   gradient  indices and w are constants, S gets none:
+ *             dL/df_i = -g (w_i inv_denom / (W_b n_i)) (s^_j - sim_ij f^_i), j = idx_i, W_b = sum_i w_i, in fp64, rounded once.
+ * Sizes: 1 <= C <= 512, 1 <= N, M <= 2^20, 1 <= B <= 65535, Bs in {1, B}; anything else is ST3D_E_INVALID before any launch.
+ * No float atomics anywhere: two runs are bit-equal.
+ * geometry: the launch st3d_nnfm_search makes -- query tiles of tile_q positions, style tiles of tile_s positions, the style
+ * range cut into `segments` runs of ceil(ceil(M / tile_s) / segments) tiles; the runs' maxima are merged in ascending order
+ * with the same strict >.  workspace: segments * B * N * 8 bytes, 8-byte aligned, contents never read before written. */
+int st3d_nnfm_geometry(int N, int M, int C, int *tile_q, int *tile_s, int *segments);
+size_t st3d_nnfm_workspace_bytes(int B, int N, int M, int C);
+/* x (B,C,M) -> xhat (B,C,M) (NULL: norms only), norm (B,M) */
+int st3d_nnfm_normalise(const float *x, int B, int C, int M, float *xhat, float *norm, st3d_stream_t stream);
+/* feat_hat (B,C,N) / feat_norm (B,N) and style_hat (Bs,C,M) from st3d_nnfm_normalise; weights (B,N) or NULL
+ * -> idx (B,N), dist (B,N).  Query tiles without an active position are skipped. */
+int st3d_nnfm_search(const float *feat_hat, const float *feat_norm, const float *style_hat, const float *weights, int B, int Bs,
+                     int C, int N, int M, void *workspace, size_t workspace_bytes, int32_t *idx, float *dist,
+                     st3d_stream_t stream);
+/* loss[0] = L (overwritten), wsum[b] = W_b (B doubles): one workgroup, fp64, a fixed tree per image, the images in order.
+ * (st3d_chamfer_sum has no weights and no per-image quotient.) */
+int st3d_nnfm_sum(const float *dist, const float *weights, int B, int N, double inv_denom, float *loss, double *wsum,
+                  st3d_stream_t stream);
+/* grad_feat (B,C,N), every element written once (exact zeros at inactive positions, zero queries and images with W_b = 0);
+ * feat is the tap itself (its norm is recomputed in fp64), sim is read back as 1 - dist; grad_out: the incoming scalar g on the device (NULL = 1). */
+int st3d_nnfm_bwd(const float *feat, const float *style_hat, const int32_t *idx, const float *dist,
+                  const float *weights, const double *wsum, const float *grad_out, int B, int Bs, int C, int N, int M,
+                  double inv_denom, float *grad_feat, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ texture pyramid (csrc/texpyr.hip):
  * the texture map (T,T,3) as the sum of L maps of sides T_l = T / 2^l, each upsampled to T x T.  `params` is one flat
  * fp32 tensor of st3d_texpyr_numel(T, L) = 3 * sum_l T_l^2 elements; level l is the (T_l, T_l, 3) row-major block at

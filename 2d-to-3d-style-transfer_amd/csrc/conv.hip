@@ -359,11 +359,15 @@ __global__ __launch_bounds__(256) void dgrad_small_kernel(const float *__restric
 // 4 consecutive pixels per thread; the 3-channel haloed patch is staged once, the thread keeps its 3 x 3 x 6 window
 // in registers and walks the output channels 16 at a time (64 accumulators): per weight row one 16-float broadcast
 // read for 64 FMAs; bias + ReLU fused; 16-byte stores.  wf is the forward pack [tap][CinP4][CoutP128].
+// skip (st3d_conv3x3_fwd_skip; one byte per tile, image-major, NULL = none): a workgroup whose byte is set returns at
+// once -- the caller knows that y holds the tile's output already.  The other tiles run the same code: the same bits.
 constexpr int SF_CG = 16;
 __global__ __launch_bounds__(256, 2) void conv_small_fwd_kernel(const float *__restrict__ x, const float *__restrict__ wf,
                                                              const float *__restrict__ bias, float *__restrict__ y, int Cout,
-                                                             int CoutP, int H, int W, int tiles_x, int relu) {
+                                                             int CoutP, int H, int W, int tiles_x, int relu,
+                                                             const uint8_t *__restrict__ skip) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    if (skip && skip[(size_t)blockIdx.y * gridDim.x + blockIdx.x]) return;      // (uniform: the whole workgroup)
     float(*tile)[SG_TH + 2][SG_PCP] = reinterpret_cast<float(*)[SG_TH + 2][SG_PCP]>(smem);      // [3]
     float *wl = smem + 3 * (SG_TH + 2) * SG_PCP;                                                 // [27][Cout], k = (ci*3+ky)*3+kx
     const int tid = threadIdx.x;
@@ -491,12 +495,70 @@ extern "C" int st3d_conv3x3_fwd(const float *x, const float *w_fwd_packed, const
         const int tiles_x = st3d::cdiv(W, SG_TW);
         const size_t lds = ((size_t)3 * (SG_TH + 2) * SG_PCP + (size_t)27 * Cout) * sizeof(float);
         conv_small_fwd_kernel<<<dim3(tiles_x * st3d::cdiv(H, SG_TH), N), 256, lds, st3d::as_stream(stream)>>>(
-            x, w_fwd_packed, bias, y, Cout, ceil_to(Cout, 128), H, W, tiles_x, relu);
+            x, w_fwd_packed, bias, y, Cout, ceil_to(Cout, 128), H, W, tiles_x, relu, nullptr);
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     }
     ConvArgs a{x, nullptr, nullptr, w_fwd_packed, bias, y, N, Cin, Cout, H, W, ceil_to(Cin, 4), ceil_to(Cout, 128), relu, 0};
     return launch_conv<0>(a, st3d::as_stream(stream));
+}
+
+// ---- conv1_1 over the tiles that see more than background (st3d_plan_loss_keyed).  The VALU kernel's tiles are 8 x 128
+// pixels, numbered image-major, then row-major: st3d_conv1_skip_tiles of them.
+extern "C" size_t st3d_conv1_skip_tiles(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0) return 0;
+    return (size_t)N * st3d::cdiv(W, SG_TW) * st3d::cdiv(H, SG_TH);
+}
+
+namespace {
+// one wave per tile: skip = no covered pixel in the tile +- 1 (clipped), i.e. every 3x3 window of the tile sees background
+__global__ __launch_bounds__(256) void conv1_skip_kernel(const uint8_t *__restrict__ cover, int H, int W, int tiles_x, int tiles_y,
+                                                         int total, uint8_t *__restrict__ skip) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (i >= total) return;                    // (the whole wave)
+    const int per_img = tiles_x * tiles_y;
+    const int n = i / per_img, r = i - n * per_img;
+    const int ty = r / tiles_x, tx = r - ty * tiles_x;
+    const int ya = max(0, ty * SG_TH - 1), yb = min(H - 1, ty * SG_TH + SG_TH);
+    const int xa = max(0, tx * SG_TW - 1), xb = min(W - 1, tx * SG_TW + SG_TW);
+    const int w = xb - xa + 1, count = (yb - ya + 1) * w;
+    const uint8_t *base = cover + (size_t)n * H * W;
+    unsigned any = 0;
+    for (int k = lane; k < count; k += 64) any |= base[(size_t)(ya + k / w) * W + xa + k % w];
+    const bool seen = __any(any != 0);
+    if (lane == 0) skip[i] = seen ? 0 : 1;
+}
+}  // namespace
+
+// cover (N,H,W bytes, non-zero = covered) -> skip (st3d_conv1_skip_tiles bytes): 1 where the tile +- 1 holds no covered pixel
+extern "C" int st3d_conv1_skip_build(const uint8_t *cover, int N, int H, int W, uint8_t *skip, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(cover && skip && N > 0 && H > 0 && W > 0);
+    const int tiles_x = st3d::cdiv(W, SG_TW), tiles_y = st3d::cdiv(H, SG_TH);
+    const long total = (long)N * tiles_x * tiles_y;
+    ST3D_CHECK_ARG(total < (1L << 31) && (long)N * H * W < (1L << 31));
+    conv1_skip_kernel<<<st3d::cdiv((int)total, 4), 256, 0, st3d::as_stream(stream)>>>(cover, H, W, tiles_x, tiles_y, (int)total, skip);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+// st3d_conv3x3_fwd of a 3-channel input (the VALU kernel; any other shape is refused, never run in full behind the
+// caller's back) that leaves out the tiles whose skip byte is set: y keeps what it held there
+extern "C" int st3d_conv3x3_fwd_skip(const float *x, const float *w_fwd_packed, const float *bias, float *y, int N, int Cin,
+                                     int Cout, int H, int W, int relu, const uint8_t *tile_skip, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(x && w_fwd_packed && y && tile_skip);
+    ST3D_CHECK_ARG(N > 0 && N < 65536 && Cout > 0 && H > 0 && W > 0);
+    ST3D_CHECK_ARG((size_t)Cin * H * W < (1u << 31) && (size_t)Cout * H * W < (1u << 31));
+    ST3D_CHECK_ARG(((uintptr_t)w_fwd_packed & 15) == 0);
+    if (!(Cin == 3 && (W % 4) == 0 && (Cout % SF_CG) == 0 && Cout <= 128)) {
+        st3d::set_error("st3d_conv3x3_fwd_skip: only the 3-channel forward (conv1_1) has a tile-skipping kernel");
+        return ST3D_E_INVALID;
+    }
+    const int tiles_x = st3d::cdiv(W, SG_TW);
+    const size_t lds = ((size_t)3 * (SG_TH + 2) * SG_PCP + (size_t)27 * Cout) * sizeof(float);
+    conv_small_fwd_kernel<<<dim3(tiles_x * st3d::cdiv(H, SG_TH), N), 256, lds, st3d::as_stream(stream)>>>(
+        x, w_fwd_packed, bias, y, Cout, ceil_to(Cout, 128), H, W, tiles_x, relu, tile_skip);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
 }
 
 extern "C" int st3d_conv3x3_dgrad(const float *gy, const float *act, const float *w_dgrad_packed, float *gx, int N, int Cin,

@@ -235,6 +235,27 @@ extern "C" size_t st3d_flat_workspace_bytes(int N, int S) {
     return (size_t)N * S * S + (size_t)N * (S / 2) * (S / 2) + (size_t)st3d_flat_tiles(N, S, 0) + 2 * (size_t)st3d_flat_tiles(N, S, 1);
 }
 
+// V2, the flags and the lists from a V0 plane (N,S,S bytes, non-zero = varying; 8-byte aligned rows)
+static int build_from_v0(const uint8_t *v0, int N, int S, int levels, void *workspace, int *list1, int *map1, int *list2, int *map2,
+                         int *list3, int *map3, int *counts, hipStream_t s) {
+    FlatGeo g1, g2;
+    geo_of(S, S, &g1);
+    geo_of(S / 2, S / 2, &g2);
+    const int t1 = N * g1.tiles_x * g1.tiles_y, t2 = N * g2.tiles_x * g2.tiles_y;
+    uint8_t *v2 = reinterpret_cast<uint8_t *>(workspace) + (size_t)N * S * S;
+    uint8_t *flags = v2 + (size_t)N * (S / 2) * (S / 2);
+    const int n2 = N * (S / 2) * (S / 2) / 4;
+    flat_v2_kernel<<<st3d::cdiv(n2, 256), 256, 0, s>>>(v0, S, n2, v2);
+    ST3D_LAUNCH_CHECK();
+    const int total = t1 + (levels - 1) * t2;
+    flat_flags_kernel<<<st3d::cdiv(total, 4), 256, 0, s>>>(v2, S, g1, g2, t1, t2, total, flags);
+    ST3D_LAUNCH_CHECK();
+    FlatLists out{{list1, list2, list3}, {map1, map2, map3}};
+    flat_lists_kernel<<<levels, 1024, 0, s>>>(flags, g1, g2, t1, t2, out, counts);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
 extern "C" int st3d_flat_build(const float *imgs, const float *color, int N, int S, int levels, void *workspace, size_t workspace_bytes,
                                int *list1, int *map1, int *list2, int *map2, int *list3, int *map3, int *counts, st3d_stream_t stream) {
     ST3D_CHECK_ARG(imgs && color && workspace && counts && N > 0);
@@ -244,23 +265,56 @@ extern "C" int st3d_flat_build(const float *imgs, const float *color, int N, int
     ST3D_CHECK_ARG(workspace_bytes >= st3d_flat_workspace_bytes(N, S));
     ST3D_CHECK_ARG(list1 && map1 && (levels < 2 || (list2 && map2)) && (levels < 3 || (list3 && map3)));
     hipStream_t s = st3d::as_stream(stream);
-    FlatGeo g1, g2;
-    geo_of(S, S, &g1);
-    geo_of(S / 2, S / 2, &g2);
-    const int t1 = N * g1.tiles_x * g1.tiles_y, t2 = N * g2.tiles_x * g2.tiles_y;
     uint8_t *v0 = reinterpret_cast<uint8_t *>(workspace);
-    uint8_t *v2 = v0 + (size_t)N * S * S;
-    uint8_t *flags = v2 + (size_t)N * (S / 2) * (S / 2);
-    const int n0 = N * S * S / 4, n2 = N * (S / 2) * (S / 2) / 4;
+    const int n0 = N * S * S / 4;
     flat_v0_kernel<<<st3d::cdiv(n0, 256), 256, 0, s>>>(imgs, color, S, n0, v0);
     ST3D_LAUNCH_CHECK();
-    flat_v2_kernel<<<st3d::cdiv(n2, 256), 256, 0, s>>>(v0, S, n2, v2);
+    return build_from_v0(v0, N, S, levels, workspace, list1, map1, list2, map2, list3, map3, counts, s);
+}
+
+// The lists of st3d_flat_build with V0 taken from a coverage mask instead of the pixels: covered = varying.  They depend on
+// the geometry alone, so a caller whose views do not move builds them once; they list a superset of the pixel lists' tiles
+// as long as every uncovered pixel holds the colour bit for bit -- the caller's premise (st3d_flat_check_cover tests it).
+extern "C" int st3d_flat_build_cover(const uint8_t *cover, int N, int S, int levels, void *workspace, size_t workspace_bytes, int *list1,
+                                     int *map1, int *list2, int *map2, int *list3, int *map3, int *counts, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(cover && workspace && counts && N > 0);
+    ST3D_CHECK_ARG(levels >= 1 && levels <= st3d_flat_levels(S));
+    ST3D_CHECK_ARG(((uintptr_t)cover & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
+    ST3D_CHECK_ARG((long)N * S * S < (1L << 31));
+    ST3D_CHECK_ARG(workspace_bytes >= st3d_flat_workspace_bytes(N, S));
+    ST3D_CHECK_ARG(list1 && map1 && (levels < 2 || (list2 && map2)) && (levels < 3 || (list3 && map3)));
+    return build_from_v0(cover, N, S, levels, workspace, list1, map1, list2, map2, list3, map3, counts, st3d::as_stream(stream));
+}
+
+namespace {
+// one thread per 4 pixels: *bad = 1 where a pixel varies (V0 of the pixels) and the mask does not cover it
+__global__ __launch_bounds__(256) void flat_subset_kernel(const uint8_t *__restrict__ v0, const uint8_t *__restrict__ cover, int total4,
+                                                          int *__restrict__ bad) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= total4) return;
+    const unsigned v = reinterpret_cast<const unsigned *>(v0)[i], c = reinterpret_cast<const unsigned *>(cover)[i];
+    bool out = false;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out |= ((v >> (8 * k)) & 0xffu) != 0 && ((c >> (8 * k)) & 0xffu) == 0;
+    if (out) *bad = 1;              // (every writer writes the same value)
+}
+}  // namespace
+
+// The premise of st3d_flat_build_cover, tested: *bad (device int) = 1 if any pixel of imgs differs from color outside cover,
+// else 0.  Uses the V0 plane of the workspace (which st3d_flat_build_cover leaves alone).
+extern "C" int st3d_flat_check_cover(const float *imgs, const float *color, const uint8_t *cover, int N, int S, void *workspace,
+                                     size_t workspace_bytes, int *bad, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(imgs && color && cover && workspace && bad && N > 0 && st3d_flat_levels(S) > 0);
+    ST3D_CHECK_ARG(((uintptr_t)imgs & 15) == 0 && ((uintptr_t)cover & 15) == 0 && ((uintptr_t)workspace & 15) == 0);
+    ST3D_CHECK_ARG((long)N * S * S < (1L << 31));
+    ST3D_CHECK_ARG(workspace_bytes >= st3d_flat_workspace_bytes(N, S));
+    hipStream_t s = st3d::as_stream(stream);
+    uint8_t *v0 = reinterpret_cast<uint8_t *>(workspace);
+    const int n0 = N * S * S / 4;
+    ST3D_HIP(hipMemsetAsync(bad, 0, sizeof(int), s));
+    flat_v0_kernel<<<st3d::cdiv(n0, 256), 256, 0, s>>>(imgs, color, S, n0, v0);
     ST3D_LAUNCH_CHECK();
-    const int total = t1 + (levels - 1) * t2;
-    flat_flags_kernel<<<st3d::cdiv(total, 4), 256, 0, s>>>(v2, S, g1, g2, t1, t2, total, flags);
-    ST3D_LAUNCH_CHECK();
-    FlatLists out{{list1, list2, list3}, {map1, map2, map3}};
-    flat_lists_kernel<<<levels, 1024, 0, s>>>(flags, g1, g2, t1, t2, out, counts);
+    flat_subset_kernel<<<st3d::cdiv(n0, 256), 256, 0, s>>>(v0, cover, n0, bad);
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "common.h"
+#include "epochs.h"
 
 namespace st3d {
 static thread_local char g_err[512] = "";
@@ -77,6 +78,7 @@ struct st3d_vgg {
     bool use_wino;     // ST3D_CONV=direct forces the direct kernels (A/B runs)
     bool pregate;      // ST3D_PREGATE=0: every input-gradient launch applies its own ReLU gate (A/B runs)
     bool fuse_tap0;    // ST3D_TAP0_FUSED=0: relu1_1 Gram backward and conv1_1 input gradient as separate launches (A/B runs)
+    uint64_t sets;     // st3d_vgg_set_conv calls so far: a plan that remembers what its buffers hold remembers this with it
 };
 
 extern "C" int st3d_vgg_create(st3d_vgg **out) {
@@ -119,6 +121,7 @@ extern "C" int st3d_vgg_set_conv(st3d_vgg *vgg, int module_idx, const float *w, 
     ST3D_CHECK_ARG(vgg && w && b);
     const int s = conv_slot(module_idx);
     ST3D_CHECK_ARG(s >= 0);
+    ++vgg->sets;            // (first: a call that fails half way has changed the packs too)
     ST3D_TRY(st3d_conv3x3_pack(w, kConvCout[s], kConvCin[s], vgg->wf[s], vgg->wd[s], stream));
     if (vgg->uf[s]) ST3D_TRY(st3d_wino_pack(w, kConvCout[s], kConvCin[s], vgg->uf[s], vgg->ud[s], stream));
     if (vgg->u6f[s]) ST3D_TRY(st3d_wino43_pack(w, kConvCout[s], kConvCin[s], vgg->u6f[s], vgg->u6d[s], stream));
@@ -220,19 +223,49 @@ struct st3d_plan {
     // each in the geometry need_cols says (64 / 32 pixels across, 16 = strips; 0 = the kernel's own choice for the map).
     int need_levels = 0;
     bool need_blocks = false;
-    uint8_t *need_seg = nullptr, *need_flags = nullptr;
+    uint8_t *need_flags = nullptr;
     size_t need_flags_bytes = 0;
-    int *need_list[ST3D_NEED_MAX_LISTS] = {}, *need_cnt = nullptr;
     int need_cols[ST3D_NEED_MAX_LISTS] = {};
     // the Gram backward at relu2_1 over the 64-pixel runs the conv2_1 input gradient reads (level 3 and up; gram.hip)
     bool need_gram = false;
-    int *need_gram_list = nullptr, *need_gram_cnt = nullptr;
     // flat-field lists of st3d_plan_loss_flat (flat.hip), rebuilt by every call that brings a colour: how many of conv1_2,
     // conv2_1, conv2_2 run listed -- as many as the size has, run F(4x4,3x3) and ST3D_FLAT_DEPTH leaves
     int flat_levels = 0;
     uint8_t *flat_ws = nullptr;
     size_t flat_ws_bytes = 0;
-    int *flat_list[3] = {}, *flat_map[3] = {}, *flat_cnt = nullptr;
+    // What the list builds write and the launches read: the need lists (segment bytes, tile lists, counts, the Gram run
+    // list) and the flat-field lists (tile lists, maps, counts).  sets[0] belongs to the unkeyed calls, which rebuild it
+    // every time; sets[1 ..] hold the lists of the last kEpochSlots geometry epochs of st3d_plan_loss_keyed (epochs.h), built
+    // once per epoch.  `ls` is the set the launches of the current call read.  A set is need_seg + the lists: 0.6 MB for 8
+    // views at 512^2 (st3d_need_blocks_entries, st3d_need_blocks_gram_runs, st3d_flat_tiles) next to the plan's 4.4 GB, so
+    // three epochs stay: what a run that alternates two or three view batches needs.
+    static constexpr int kEpochSlots = 3;
+    struct ListSet {
+        uint8_t *need_seg = nullptr;
+        int *need_list[ST3D_NEED_MAX_LISTS] = {}, *need_cnt = nullptr;
+        int *need_gram_list = nullptr, *need_gram_cnt = nullptr;
+        int *flat_list[3] = {}, *flat_map[3] = {}, *flat_cnt = nullptr;
+        uint8_t *c1_skip = nullptr;                     // (keyed sets) conv1_1's tiles that see background only (conv.hip)
+        bool have_need = false, have_flat = false;      // (keyed sets) built for the slot's epoch
+    };
+    ListSet sets[1 + kEpochSlots];
+    ListSet *ls = &sets[0];
+    st3d::EpochSlots<kEpochSlots> epochs;
+    // The clean record: which epoch's background the unlisted tiles of the buffers st3d_flat_fill writes hold -- act[4] and
+    // pidx[0] (conv1_2 pooled), act[5] (conv2_1), act[9] and pidx[1] (conv2_2 pooled) -- and with them the background tiles
+    // of act[0] (conv1_1).  A keyed call that finds its own epoch, n, colour, level count and weights here launches no
+    // fill: its lists are the epoch's, so the listed launches rewrite exactly the tiles they wrote before and the rest still
+    // hold what the fills of the epoch's first call copied.  Its conv1_1 likewise leaves out the tiles whose windows see
+    // background only (c1_skip): the full launch of the epoch's first call wrote them.
+    // The only writer of act[] and pidx[] is forward(), which clears the record on entry; its callers are st3d_plan_forward,
+    // st3d_plan_set_content, st3d_plan_set_style and plan_loss_enqueue (every st3d_plan_loss* entry, graph capture and
+    // replay included: a replay runs forward()'s captured launches, and the keyed entry never replays).  The backward
+    // passes write gbuf[] and the caller's gradient only.  st3d_plan_loss_keyed sets the record after a call whose every
+    // launch was enqueued, so a failed call leaves it cleared; st3d_vgg_set_conv changes what a fill would copy and is
+    // caught by the handle's counter.
+    st3d::CleanRecord clean;
+    bool conv1_skip = false;        // conv1_1 of a clean keyed call runs over its covered tiles only (ST3D_FLAT_CONV1=0: in full)
+    bool flat_check = false;        // ST3D_FLAT_CHECK=1 (read by st3d_plan_create): keyed calls test their premise on the pixels
     // guidance of the style term (st3d_plan_set_style_guidance; guide.hip): the q planes of the five taps for guide_n
     // images (0 = off), and w_0 = q_0^2 for the fused bottom pass.  Allocated by the first call that sets a guidance (for B
     // images: the pointers never move, so a captured loss step keeps reading them), rebuilt by every such call.
@@ -289,25 +322,58 @@ enum { F_CONV_FWD = 0, F_CONV_DGRAD = 1, F_POOL = 2, F_GRAM_FWD = 3, F_GRAM_BWD 
        // launches that ran over a need list: a fraction of the full launch's work, so not priced as one
        F_CONV43_DGRAD_NEED = 10, F_CONVX_DGRAD_NEED = 11, F_GRAM_BWD_NEED = 12,
        // forward launches over a flat-field list, and the copies that fill in the tiles they left out
-       F_CONV43_FWD_FLAT = 13, F_FLAT_FILL = 14 };
-static_assert(F_FLAT_FILL + 1 == ST3D_PROFILE_FAMILIES, "profile families");
+       F_CONV43_FWD_FLAT = 13, F_FLAT_FILL = 14,
+       // the conv1_1 launch that leaves out its background tiles: a fraction of the full launch's 537 MB write
+       F_CONVX_FWD_FLAT = 15 };
+static_assert(F_CONVX_FWD_FLAT + 1 == ST3D_PROFILE_FAMILIES, "profile families");
 
 // keep_full: also materialise the full-resolution output of convs whose 2x2 pool is fused into
 // their epilogue (needed only when a caller asks for that activation: st3d_plan_forward).
 // flat_color (device, 3 floats; the loss call only): imgs hold this colour at many pixels -- conv slots 1 .. 3 (conv1_2,
 // conv2_1, conv2_2) compute the tiles of their flat-field lists and copy the rest (flat.hip); the buffers end up bitwise
 // what the full launches write
-int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hipStream_t s, const float *flat_color = nullptr) {
+// key (st3d_plan_loss_keyed; p->ls is the epoch's list set): the flat-field lists come from the coverage and are built only
+// if the set does not hold them yet, and the fills are left out while the clean record says the buffers hold this epoch's
+// background already
+struct Keyed {
+    uint64_t epoch;
+    const uint8_t *cover;       // (n,S,S) device bytes, non-zero = covered; every other pixel holds the colour bit for bit
+    const float *rgb;           // the colour again, 3 floats in HOST memory (what the clean record compares)
+    int flat_done;              // out: how many launches ran listed
+};
+int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hipStream_t s, const float *flat_color = nullptr,
+            Keyed *key = nullptr) {
     const st3d_vgg *v = p->vgg;
     int flat = 0;               // conv slots 1 .. flat run listed
-    if (flat_color) {
+    if (flat_color)
         while (flat < p->flat_levels && kConvIdx[flat + 1] <= upto) ++flat;
-        if (flat > 0) {
+    const bool fill = !(key && flat > 0 && p->clean.matches(key->epoch, n, flat, key->rgb, v->sets));
+    p->clean.clear();           // every path below writes act[] / pidx[]; the keyed entry sets the record again when all went well
+    if (flat > 0 && !key) {
+        Scope sc(p, F_ELEM, s);
+        ST3D_TRY(st3d_flat_build(imgs, flat_color, n, p->S, flat, p->flat_ws, p->flat_ws_bytes, p->ls->flat_list[0], p->ls->flat_map[0],
+                                 p->ls->flat_list[1], p->ls->flat_map[1], p->ls->flat_list[2], p->ls->flat_map[2], p->ls->flat_cnt, s));
+    } else if (flat > 0) {
+        if (p->flat_check) {    // the premise on this call's pixels: one host read, debug runs only
+            int bad = 0;
+            ST3D_TRY(st3d_flat_check_cover(imgs, flat_color, key->cover, n, p->S, p->flat_ws, p->flat_ws_bytes, p->sets[0].flat_cnt + 3, s));
+            ST3D_HIP(hipMemcpyAsync(&bad, p->sets[0].flat_cnt + 3, sizeof(int), hipMemcpyDeviceToHost, s));
+            ST3D_HIP(hipStreamSynchronize(s));
+            if (bad) {
+                st3d::set_error("st3d_plan_loss_keyed: a pixel outside the coverage differs from the background colour");
+                return ST3D_E_STATE;
+            }
+        }
+        if (!p->ls->have_flat) {
             Scope sc(p, F_ELEM, s);
-            ST3D_TRY(st3d_flat_build(imgs, flat_color, n, p->S, flat, p->flat_ws, p->flat_ws_bytes, p->flat_list[0], p->flat_map[0],
-                                     p->flat_list[1], p->flat_map[1], p->flat_list[2], p->flat_map[2], p->flat_cnt, s));
+            ST3D_TRY(st3d_flat_build_cover(key->cover, n, p->S, flat, p->flat_ws, p->flat_ws_bytes, p->ls->flat_list[0], p->ls->flat_map[0],
+                                           p->ls->flat_list[1], p->ls->flat_map[1], p->ls->flat_list[2], p->ls->flat_map[2],
+                                           p->ls->flat_cnt, s));
+            if (p->ls->c1_skip) ST3D_TRY(st3d_conv1_skip_build(key->cover, n, p->S, p->S, p->ls->c1_skip, s));
+            p->ls->have_flat = true;
         }
     }
+    if (key) key->flat_done = flat;
     const float *x = imgs;
     for (int m = 0; m <= upto; ++m) {
         const int cs = conv_slot(m), ps = pool_slot(m);
@@ -318,6 +384,12 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
             }
             const int Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
             const uint8_t route = p->route[cs].fwd;
+            if (route == DIRECT && cs == 0 && !fill && p->ls->c1_skip) {     // conv1_1 of a clean keyed call: the covered tiles
+                Scope sc(p, F_CONVX_FWD_FLAT, s, m);
+                ST3D_TRY(st3d_conv3x3_fwd_skip(x, v->wf[cs], v->bias[cs], p->act[m], n, Cin, Cout, H, W, 1, p->ls->c1_skip, s));
+                x = p->act[m];
+                continue;
+            }
             if (route == DIRECT) {
                 Scope sc(p, F_CONVX_FWD, s, m);
                 ST3D_TRY(st3d_conv3x3_fwd(x, v->wf[cs], v->bias[cs], p->act[m], n, Cin, Cout, H, W, 1, s));
@@ -333,11 +405,13 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
             if (cs >= 1 && cs <= flat) {           // an F(4x4,3x3) launch over its flat-field list, then the copies
                 {
                     Scope sc(p, F_CONV43_FWD_FLAT, s, m);
-                    ST3D_TRY(st3d_wino43_fwd_tiles(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->flat_list[cs - 1],
-                                                   p->flat_cnt + (cs - 1), s));
+                    ST3D_TRY(st3d_wino43_fwd_tiles(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->ls->flat_list[cs - 1],
+                                                   p->ls->flat_cnt + (cs - 1), s));
                 }
-                Scope sc(p, F_FLAT_FILL, s, m);
-                ST3D_TRY(st3d_flat_fill(p->flat_map[cs - 1], yfull, yp, yi, n, Cout, H, W, s));
+                if (fill) {
+                    Scope sc(p, F_FLAT_FILL, s, m);
+                    ST3D_TRY(st3d_flat_fill(p->ls->flat_map[cs - 1], yfull, yp, yi, n, Cout, H, W, s));
+                }
             } else if (route == WINO43) {
                 Scope sc(p, F_CONV43_FWD, s, m);
                 ST3D_TRY(st3d_wino43_fwd(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
@@ -564,34 +638,44 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     alloc(&p->g_loss, (size_t)4);
     if (p->need_levels >= 1) {
         alloc(&p->g_mask, (size_t)B * S * S);
-        alloc(&p->need_seg, (size_t)B * S * (S / 64));
-        alloc(&p->need_cnt, (size_t)ST3D_NEED_MAX_LISTS);
         p->need_flags_bytes = p->need_blocks ? st3d_need_blocks_workspace_bytes(B, S) : st3d_need_workspace_bytes(B, S);
         if (p->need_levels >= 2) alloc(&p->need_flags, p->need_flags_bytes);
-        if (p->need_gram) {
-            alloc(&p->need_gram_list, st3d_need_blocks_gram_runs(B, S));
-            alloc(&p->need_gram_cnt, (size_t)1);
-        }
-        for (int l = 0; l + 2 <= p->need_levels; ++l) {
-            if (p->need_blocks) {
-                alloc(&p->need_list[l], st3d_need_blocks_entries(B, S, l, p->need_cols[l]));
-                continue;
-            }
-            int rows = 0, cols = 0;
-            st3d_wino43_tile_geometry(S >> l, S >> l, &rows, &cols);
-            alloc(&p->need_list[l], (size_t)B * ((S >> l) / rows) * ((S >> l) / cols));
-        }
     }
     if (p->flat_levels >= 1) {
         p->flat_ws_bytes = st3d_flat_workspace_bytes(B, S);
         alloc(&p->flat_ws, p->flat_ws_bytes);
-        alloc(&p->flat_cnt, (size_t)4);
         alloc(&p->g_color, (size_t)4);
-        for (int k = 0; k < p->flat_levels; ++k) {
-            alloc(&p->flat_list[k], (size_t)st3d_flat_tiles(B, S, k));
-            alloc(&p->flat_map[k], (size_t)st3d_flat_tiles(B, S, k));
+    }
+    for (st3d_plan::ListSet &ls : p->sets) {     // the lists themselves: the unkeyed set and one per epoch slot
+        if (p->need_levels >= 1) {
+            alloc(&ls.need_seg, (size_t)B * S * (S / 64));
+            alloc(&ls.need_cnt, (size_t)ST3D_NEED_MAX_LISTS);
+            if (p->need_gram) {
+                alloc(&ls.need_gram_list, st3d_need_blocks_gram_runs(B, S));
+                alloc(&ls.need_gram_cnt, (size_t)1);
+            }
+            for (int l = 0; l + 2 <= p->need_levels; ++l) {
+                if (p->need_blocks) {
+                    alloc(&ls.need_list[l], st3d_need_blocks_entries(B, S, l, p->need_cols[l]));
+                    continue;
+                }
+                int rows = 0, cols = 0;
+                st3d_wino43_tile_geometry(S >> l, S >> l, &rows, &cols);
+                alloc(&ls.need_list[l], (size_t)B * ((S >> l) / rows) * ((S >> l) / cols));
+            }
+        }
+        if (p->flat_levels >= 1) {
+            alloc(&ls.flat_cnt, (size_t)4);
+            for (int k = 0; k < p->flat_levels; ++k) {
+                alloc(&ls.flat_list[k], (size_t)st3d_flat_tiles(B, S, k));
+                alloc(&ls.flat_map[k], (size_t)st3d_flat_tiles(B, S, k));
+            }
         }
     }
+    p->flat_check = flag("ST3D_FLAT_CHECK", false);
+    p->conv1_skip = p->flat_levels >= 1 && p->route[0].fwd == DIRECT && flag("ST3D_FLAT_CONV1", true);
+    if (p->conv1_skip)
+        for (int k = 1; k <= st3d_plan::kEpochSlots; ++k) alloc(&p->sets[k].c1_skip, st3d_conv1_skip_tiles(B, S, S));
     if (rc != ST3D_OK) { st3d_plan_destroy(p); return rc; }
     *out = p;
     return ST3D_OK;
@@ -710,7 +794,8 @@ extern "C" int st3d_plan_set_style(st3d_plan *p, const float *style, int style_b
 }
 
 static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
-                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, const float *flat_color, hipStream_t s);
+                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, const float *flat_color, hipStream_t s,
+                             Keyed *key = nullptr);
 
 extern "C" int st3d_plan_graph(st3d_plan *p, int enable) {
     ST3D_CHECK_ARG(p);
@@ -735,6 +820,8 @@ extern "C" int st3d_plan_loss_flat(st3d_plan *p, const float *current, int n, in
                                    float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask,
                                    const float *flat_color, st3d_stream_t stream) {
     ST3D_CHECK_ARG(p && current && loss_out);
+    p->clean.clear();           // (before anything can fail or replay a graph: an unkeyed call fills whatever it lists)
+    p->ls = &p->sets[0];
     ST3D_CHECK_ARG(((uintptr_t)need_mask & 15) == 0);
     if (!grad_current || p->need_levels < 1) need_mask = nullptr;      // nothing to thin out: the ordinary call
     if (flat_color) {           // ST3D_FLAT=0 (A/B runs, read per call), a size without lists, an unaligned image: the full forward
@@ -794,11 +881,63 @@ extern "C" int st3d_plan_loss_flat(st3d_plan *p, const float *current, int n, in
     return ST3D_OK;
 }
 
+// st3d_plan_loss_flat for a caller that knows when the coverage of its views is the one it brought before (a geometry epoch:
+// vertices, faces and cameras unchanged, only the texture moves).  Everything that depends on the coverage alone is then
+// kept: the need lists and the flat-field lists -- the latter from the coverage, not the pixels -- are built by the first
+// call of an epoch, and the fills are launched only when the buffers do not hold this epoch's background already (the
+// clean record of st3d_plan).  Results are bitwise those of st3d_plan_loss_flat.
+extern "C" int st3d_plan_loss_keyed(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
+                                    float content_weight, float *loss_out, float *grad_current, const uint8_t *cover,
+                                    const float *flat_color, const float *flat_rgb, uint64_t epoch, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(p);
+    // no epoch, or graph replay (whose captured sequence stays static): the unkeyed call, launch for launch
+    if (epoch == 0 || p->use_graph || !cover)
+        return st3d_plan_loss_flat(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, cover, flat_color, stream);
+    const st3d::CleanRecord held = p->clean;
+    p->clean.clear();           // a call refused below leaves it cleared; one that goes through sets it again
+    p->ls = &p->sets[0];
+    ST3D_CHECK_ARG(current && loss_out && (!flat_color || flat_rgb));
+    ST3D_CHECK_ARG(((uintptr_t)cover & 15) == 0);
+    const uint8_t *need_mask = (grad_current && p->need_levels >= 1) ? cover : nullptr;
+    if (flat_color) {
+        const char *fl = getenv("ST3D_FLAT");
+        if ((fl && fl[0] == '0') || p->flat_levels < 1 || ((uintptr_t)current & 15) != 0) flat_color = nullptr;
+    }
+    ST3D_CHECK_ARG(n > 0 && n <= p->B && batch_denom >= n);
+    if (!p->have_content || !p->have_style) {
+        st3d::set_error("st3d_plan_loss: content/style targets not set");
+        return ST3D_E_STATE;
+    }
+    ST3D_CHECK_ARG(p->style_batch == 1 || p->style_batch == n);
+    if (p->guide_n != 0 && p->guide_n != n) {
+        st3d::set_error("st3d_plan_loss: the style guidance was set for %d images, this call brings %d", p->guide_n, n);
+        return ST3D_E_STATE;
+    }
+    bool fresh = false;
+    const int slot = p->epochs.take(epoch, n, &fresh);
+    st3d_plan::ListSet *ls = &p->sets[1 + slot];
+    if (fresh) ls->have_need = ls->have_flat = false;
+    Keyed key{epoch, cover, flat_rgb, 0};
+    p->ls = ls;
+    p->clean = held;            // what forward() compares this call with, and clears
+    const int rc = plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, flat_color,
+                                     st3d::as_stream(stream), &key);
+    p->ls = &p->sets[0];
+    if (rc != ST3D_OK) {        // whatever the slot holds may be half built, and so may the buffers
+        p->epochs.drop(slot);
+        p->clean.clear();
+        return rc;
+    }
+    if (key.flat_done > 0) p->clean.set(epoch, n, key.flat_done, flat_rgb, p->vgg->sets);
+    return ST3D_OK;
+}
+
 static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batch_denom, float style_weight,
-                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, const float *flat_color, hipStream_t s) {
+                             float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, const float *flat_color, hipStream_t s,
+                             Keyed *key) {
     {
         st3d::TraceRange tr("vgg_forward");
-        ST3D_TRY(forward(p, current, n, 28, false, s, flat_color));
+        ST3D_TRY(forward(p, current, n, 28, false, s, flat_color, key));
     }
     st3d::TraceRange tr_loss("gram_and_losses");
     const bool guided = p->guide_n != 0;        // (== n: checked by the caller)
@@ -836,15 +975,16 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
 
     // ---- what the consumer of the image gradient needs (need.hip): with a mask, the bottom launches walk these lists
     const int need = need_mask ? p->need_levels : 0;
-    if (need > 0) {
+    if (need > 0 && !(key && p->ls->have_need)) {       // (a keyed call builds them once per epoch)
         Scope sc(p, F_ELEM, s);
         if (p->need_blocks && need >= 2)
-            ST3D_TRY(st3d_need_blocks_build(need_mask, n, p->S, need - 1, p->need_cols, p->need_seg, p->need_flags, p->need_flags_bytes,
-                                            p->need_list, p->need_cnt, need >= 3 && p->need_gram ? p->need_gram_list : nullptr,
-                                            p->need_gram_cnt, s));
+            ST3D_TRY(st3d_need_blocks_build(need_mask, n, p->S, need - 1, p->need_cols, p->ls->need_seg, p->need_flags, p->need_flags_bytes,
+                                            p->ls->need_list, p->ls->need_cnt, need >= 3 && p->need_gram ? p->ls->need_gram_list : nullptr,
+                                            p->ls->need_gram_cnt, s));
         else
-            ST3D_TRY(st3d_need_build(need_mask, n, p->S, need, p->need_seg, p->need_flags, p->need_flags_bytes, p->need_list[0],
-                                     p->need_list[1], p->need_cnt, s));
+            ST3D_TRY(st3d_need_build(need_mask, n, p->S, need, p->ls->need_seg, p->need_flags, p->need_flags_bytes, p->ls->need_list[0],
+                                     p->ls->need_list[1], p->ls->need_cnt, s));
+        if (key) p->ls->have_need = true;
     }
 
     // ---- backward: gradient w.r.t. the post-ReLU output of each conv, top down
@@ -864,11 +1004,11 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
             if (guided && st >= 0)
                 ST3D_TRY(st3d_conv1_bwd_weighted(have_g ? g : nullptr, p->act[m], p->D[st], style_coef[st], p->vgg->wd[0], gn,
                                                  p->gbuf_floats * sizeof(float), grad_current, n, H, W, p->guide_w0,
-                                                 need >= 1 ? p->need_seg : nullptr, need >= 1 ? need_mask : nullptr, s));
+                                                 need >= 1 ? p->ls->need_seg : nullptr, need >= 1 ? need_mask : nullptr, s));
             else if (need >= 1)
                 ST3D_TRY(st3d_conv1_bwd_masked(have_g ? g : nullptr, p->act[m], st >= 0 ? p->D[st] : nullptr,
                                                st >= 0 ? style_coef[st] : 0.f, p->vgg->wd[0], gn, p->gbuf_floats * sizeof(float),
-                                               grad_current, n, H, W, p->need_seg, need_mask, s));
+                                               grad_current, n, H, W, p->ls->need_seg, need_mask, s));
             else
             ST3D_TRY(st3d_conv1_bwd(have_g ? g : nullptr, p->act[m], st >= 0 ? p->D[st] : nullptr, st >= 0 ? style_coef[st] : 0.f,
                                     p->vgg->wd[0], gn, p->gbuf_floats * sizeof(float), grad_current, n, H, W, s));
@@ -878,7 +1018,7 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
         if (st >= 0 && cs == 2 && need >= 3 && p->need_gram && chain) {        // relu2_1 over the runs conv2_1's input gradient reads
             Scope sc(p, F_GRAM_BWD_NEED, s, m);
             ST3D_TRY(st3d_gram_bwd_gated_segs(p->D[st], p->act[m], guided ? p->guide_plane(st) : nullptr, n, C, H * W, style_coef[st],
-                                              have_g ? 1 : 0, p->need_gram_list, p->need_gram_cnt, g, s));
+                                              have_g ? 1 : 0, p->ls->need_gram_list, p->ls->need_gram_cnt, g, s));
             g_gated = true;
             have_g = true;
         } else if (st >= 0) {
@@ -919,8 +1059,8 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
             content_done = true;
         }
         if (cs >= 1 && cs <= ST3D_NEED_MAX_LISTS && need >= cs + 1) {   // conv1_2 .. conv3_3 over their need lists
-            o.tile_list = p->need_list[cs - 1];
-            o.n_active = p->need_cnt + (cs - 1);
+            o.tile_list = p->ls->need_list[cs - 1];
+            o.n_active = p->ls->need_cnt + (cs - 1);
             o.tile_cols = p->need_cols[cs - 1];
         }
         ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, o));

@@ -29,10 +29,11 @@ device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
 class _PerceptualFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, current, plan, style_weight, content_weight, batch_denom, need_mask=None, flat_color=None, style_mask=None):
+    def forward(ctx, current, plan, style_weight, content_weight, batch_denom, need_mask=None, flat_color=None, style_mask=None,
+                epoch=0):
         loss, grad = plan.loss(current, style_weight, content_weight, batch_denom=batch_denom,
                                want_grad=current.requires_grad, need_mask=need_mask, flat_color=flat_color,
-                               style_mask=style_mask)
+                               style_mask=style_mask, epoch=epoch)
         ctx.grad = grad
         ctx.parts = loss.clone()
         return loss[0].clone()
@@ -40,7 +41,7 @@ class _PerceptualFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         g = ctx.grad * grad_out if ctx.grad is not None else None
-        return g, None, None, None, None, None, None, None
+        return g, None, None, None, None, None, None, None, None
 
 
 #method for the second approach
@@ -89,8 +90,15 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
     # style / noise background and pixels optimised directly carry no tag and take the full forward.
     flat = _render.flat_of(current_imgs)
 
+    # A render whose fragments came from its rasteriser's cache also names the geometry epoch of its coverage tag
+    # (st3d.render.FragmentCache): views whose vertices, faces and cameras have not changed since the tag was made.  The plan
+    # then keeps what depends on the coverage alone -- its need lists, its flat-field lists, the background it has copied into
+    # the shallow buffers -- from one step to the next (PerceptualPlan.loss(epoch=...)); 0 = no epoch, every call rebuilds.
+    # ST3D_EPOCHS=0 (read per call): the A/B switch -- every call rebuilds and fills.
+    epoch = 0 if os.environ.get("ST3D_EPOCHS", "1") == "0" else _render.epoch_of(current_imgs, need)
+
     # batch_denom: the batch the means divide by -- the GLOBAL batch when views are sharded over ranks
-    return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need, flat, style_masks)
+    return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need, flat, style_masks, epoch)
 
 
 def compute_nnfm_loss(current_imgs, style_imgs, model, layers=('conv3_1',), *, masks=None, batch_denom=None):

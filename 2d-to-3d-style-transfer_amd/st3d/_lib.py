@@ -131,6 +131,9 @@ SIGNATURES = {
     "st3d_conv3x3_packed_floats": (c_size, [c_int, c_int]),
     "st3d_conv3x3_pack": (c_int, [c_f32p, c_int, c_int, c_f32p, c_f32p, c_stream]),
     "st3d_conv3x3_fwd": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_stream]),
+    "st3d_conv1_skip_tiles": (c_size, [c_int, c_int, c_int]),
+    "st3d_conv1_skip_build": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, c_stream]),
+    "st3d_conv3x3_fwd_skip": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_u8p, c_stream]),
     "st3d_conv3x3_dgrad": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_stream]),
     "st3d_conv3x3_dgrad_unpool": (c_int, [c_f32p, c_u8p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int,
                                           c_stream]),
@@ -170,6 +173,9 @@ SIGNATURES = {
     "st3d_flat_build": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_i32p, c_i32p, c_i32p, c_i32p,
                                 c_i32p, c_i32p, c_i32p, c_stream]),
     "st3d_flat_fill": (c_int, [c_i32p, c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_stream]),
+    "st3d_flat_build_cover": (c_int, [c_u8p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p,
+                                      c_i32p, c_i32p, c_stream]),
+    "st3d_flat_check_cover": (c_int, [c_f32p, c_f32p, c_u8p, c_int, c_int, ctypes.c_void_p, c_size, c_i32p, c_stream]),
     "st3d_need_levels": (c_int, [c_int]),
     "st3d_need_workspace_bytes": (c_size, [c_int, c_int]),
     "st3d_need_build": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, ctypes.c_void_p, c_size, c_i32p, c_i32p, c_i32p, c_stream]),
@@ -254,6 +260,8 @@ SIGNATURES = {
     "st3d_plan_loss_masked": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_u8p, c_stream]),
     "st3d_plan_loss_flat": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_u8p, c_f32p,
                                     c_stream]),
+    "st3d_plan_loss_keyed": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_int, c_float, c_float, c_f32p, c_f32p, c_u8p, c_f32p,
+                                     ctypes.POINTER(c_float), ctypes.c_uint64, c_stream]),
     "st3d_plan_graph": (c_int, [ctypes.c_void_p, c_int]),
     "st3d_plan_backward": (c_int, [ctypes.c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_void_p), c_f32p, c_stream]),
     "st3d_comm_unique_id": (c_int, [ctypes.c_char_p]),

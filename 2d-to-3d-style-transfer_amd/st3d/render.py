@@ -32,8 +32,10 @@ is the barycentric interpolation of the three vertex colours of the fragment's f
 Texel atlas: a mesh whose textures are a TexturesAtlas renders on csrc/atlas.hip (hard settings, unlit, supersample 1...4):
 the colour is the nearest texel of the R x R block its face owns, differentiable in the atlas alone.
 """
+import itertools
 import math
 import os
+from collections import OrderedDict
 
 import torch
 
@@ -709,9 +711,68 @@ def _lit_vertex_grad(lit, gverts, gnp, p2f, bary):
     return ops.vertex_normals_bwd(lit.verts, lit.faces_i32, lit.incidence, lit.unnormalised, s[1], s[0], gverts)
 
 
+_EPOCH_IDS = itertools.count(1)
+
+
+class FragmentCache:
+    """The fragments of the last few (vertices, faces, cameras, size) batches one rasteriser has seen on the hard K = 1 path.
+
+    In a texture-only run the geometry of a view batch never changes, so projecting and rasterising it again every step
+    recomputes the same fragments.  An entry holds the projected vertices, the fragments, the uint8 coverage tag (made
+    when first asked for) and a fresh geometry-epoch id, under a key of the identity and version of the vertex, face, R and
+    T tensors plus the image size -- the style of key ``reaches_near_plane`` uses; the keyed tensors are held, so their
+    addresses cannot be handed to other tensors while the entry lives.  Vertices that require a gradient never enter.
+
+    One entry is 24 bytes per pixel of fragments (+ 1 of coverage): 50 MB for 8 views at 512^2.  ENTRIES = 4 keeps the content
+    render and two or three alternating view batches of one run, 0.2 GB next to a plan's 4.4 GB; least recently used first
+    out.  The cache belongs to its MeshRasterizer: a new renderer starts empty."""
+    ENTRIES = 4
+
+    class Entry:
+        __slots__ = ("ndc", "frag", "cover", "cover_version", "epoch", "held")
+
+        def coverage(self):
+            """the entry's uint8 coverage tensor, made when first asked for.  It names the epoch, so one that somebody has
+            written to since is replaced, under a new epoch id"""
+            if self.cover is None or self.cover._version != self.cover_version:
+                if self.cover is not None:
+                    self.epoch = next(_EPOCH_IDS)
+                self.cover = (self.frag[0] >= 0).view(torch.uint8)
+                self.cover_version = self.cover._version
+            return self.cover
+
+    def __init__(self):
+        self._entries = OrderedDict()
+
+    @staticmethod
+    def key(verts, faces_i32, R, T, S):
+        return tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in (verts, faces_i32, R, T)) + (int(S), str(verts.device))
+
+    def get(self, key):
+        e = self._entries.get(key)
+        if e is not None:
+            self._entries.move_to_end(key)
+        return e
+
+    def put(self, key, held, ndc, frag):
+        e = FragmentCache.Entry()
+        e.ndc, e.frag, e.cover, e.cover_version, e.epoch, e.held = ndc, frag, None, 0, next(_EPOCH_IDS), held
+        while len(self._entries) >= max(self.ENTRIES, 1):
+            self._entries.popitem(last=False)
+        self._entries[key] = e
+        return e
+
+    def __len__(self):
+        return len(self._entries)
+
+
+_ACTIVE_CACHE = [None]      # innermost last: the FragmentCache _RenderFn.forward may use (None: it rasterises)
+
+
 class MeshRasterizer:
     def __init__(self, cameras=None, raster_settings=None):
         self.cameras, self.raster_settings = cameras, raster_settings or RasterizationSettings()
+        self.fragment_cache = FragmentCache()
 
 
 class SoftPhongShader:
@@ -829,9 +890,21 @@ class _RenderFn(torch.autograd.Function):
         if tex.shape[0] != tex.shape[1]:
             raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
         uvs = verts_uvs.detach().to(torch.float32).reshape(-1, 2).contiguous()
-        ndc = ops.project_verts(v, R, T)
-        # (no near-plane watch here: render_views has looked at the vertices' depths before choosing these kernels)
-        frag = ops.raster_fwd(ndc, faces_i32, S)
+        # the calling rasteriser's FragmentCache (_render_views names it for the length of this call): geometry that is not
+        # being optimised is projected and rasterised once per batch of views
+        cache, entry, key = _ACTIVE_CACHE[-1], None, None
+        if cache is not None and lighting is None and not verts.requires_grad:
+            key = FragmentCache.key(verts, faces_i32, R, T, S)
+            entry = cache.get(key)
+        if entry is None:
+            ndc = ops.project_verts(v, R, T)
+            # (no near-plane watch here: render_views has looked at the vertices' depths before choosing these kernels)
+            frag = ops.raster_fwd(ndc, faces_i32, S)
+            if key is not None:
+                entry = cache.put(key, (verts, faces_i32, R, T), ndc, frag)
+        else:
+            ndc, frag = entry.ndc, entry.frag
+        ctx.entry = entry
         ctx.lit = _lit_setup(lighting, verts, v, faces_i32, R, T)
         if ctx.lit is None:
             rgb, mask = ops.shade_fwd(frag, uvs, faces_uvs_i32, tex)
@@ -1149,11 +1222,31 @@ def tag_need(rgb, p2f):
     return rgb
 
 
-def tag_need_mask(rgb, need):
-    """tag_need for a producer that knows its coverage as a boolean (n,S,S) rather than as fragments"""
+def tag_need_mask(rgb, need, epoch=None):
+    """tag_need for a producer that knows its coverage as a boolean (n,S,S) rather than as fragments.
+    epoch (an id of FragmentCache): `need` is the coverage tensor of that geometry epoch -- the same tensor, unmodified, for
+    every render of the epoch -- and every pixel it does not cover holds the background colour of the render's flat tag bit
+    for bit (the hard path's blend writes the constant there)."""
     if rgb.requires_grad:
-        setattr(rgb, NEED_TAG, need.view(torch.uint8))
+        if need.dtype != torch.uint8:
+            need = need.view(torch.uint8)
+        setattr(rgb, NEED_TAG, need)
+        if epoch:
+            setattr(rgb, EPOCH_TAG, (int(epoch), need, need._version))
     return rgb
+
+
+EPOCH_TAG = "_st3d_epoch"
+
+
+def epoch_of(t, need):
+    """The geometry epoch of `t`'s coverage tag, if `need` (what need_of(t) returned) is that epoch's coverage tensor,
+    unmodified since the tag was made; else 0.  A loss hands it on to PerceptualPlan.loss(epoch=...), which then keeps what
+    depends on the coverage alone from step to step."""
+    tag = getattr(t, EPOCH_TAG, None)
+    if tag is None or need is None or tag[1] is not need or need._version != tag[2]:
+        return 0
+    return tag[0]
 
 
 def need_of(t):
@@ -1224,17 +1317,18 @@ def reaches_near_plane(verts, R, T, z_clip):
     return near
 
 
-def render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None, lights=None, materials=None):
+def render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None, lights=None, materials=None, cache=None):
     """``_render_views`` inside a named range (``ST3D_ROCTX=1``: rocprofv3 --marker-trace shows the step's phases)."""
     with ops.trace("render"):
-        return _render_views(meshes, R, T, image_size, raster_settings, blend_params, lights, materials)
+        return _render_views(meshes, R, T, image_size, raster_settings, blend_params, lights, materials, cache)
 
 
-def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None, lights=None, materials=None):
+def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None, lights=None, materials=None, cache=None):
     """All B views in one batch of launches -> (rgb (B,3,S,S), coverage (B,1,S,S)).  Coverage is the 0/1 mask under
     the reference's hard settings (whichever kernels render them) and softmax_rgb_blend's alpha under soft settings;
     both satisfy ``coverage > 0`` == covered.  lights / materials: the shading (lighting_of: None = today's unlit
-    kernels); both kernel families light, so a batch rerouted to the clipping kernels keeps its lighting."""
+    kernels); both kernel families light, so a batch rerouted to the clipping kernels keeps its lighting.  cache: the calling
+    rasteriser's FragmentCache (None: every call rasterises); only the unlit hard K = 1 path with a texture map uses it."""
     tex = meshes.textures
     dev = meshes.device
     rs, bp = raster_settings, blend_params
@@ -1265,9 +1359,17 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
         rs = RasterizationSettings(image_size=image_size, z_clip_value=RasterizationSettings.Z_CLIP_DEFAULT)
     if uses_hard_path(rs, bp):
         # K=1, blur 0: the blend weight cancels and the pixel is the sampled texel itself
-        rgb, mask = _RenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
-                                    tex.faces_uvs_i32(), R, T, int(image_size), lighting)
-        if rgb.requires_grad:
+        _ACTIVE_CACHE.append(cache if os.environ.get("ST3D_FRAG_CACHE", "1") != "0" else None)    # (the A/B switch, read per render)
+        try:
+            rgb, mask = _RenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
+                                        tex.faces_uvs_i32(), R, T, int(image_size), lighting)
+        finally:
+            _ACTIVE_CACHE.pop()
+        entry = getattr(rgb.grad_fn, "entry", None) if rgb.requires_grad else None
+        if entry is not None:       # fragments of the cache: their coverage tag is made once and names its geometry epoch
+            cover = entry.coverage()
+            tag_need_mask(rgb, cover, epoch=entry.epoch)
+        elif rgb.requires_grad:
             tag_need(rgb, rgb.grad_fn.frag[0])
         tag_flat(rgb, (1.0, 1.0, 1.0))           # (uses_hard_path: the default BlendParams, a white background)
         return rgb, mask
@@ -1467,7 +1569,8 @@ class MeshRenderer:
         lights = lights if lights is not None else getattr(self.shader, "lights", None)
         materials = materials if materials is not None else getattr(self.shader, "materials", None)
         return render_views(meshes_world, R, T, self.image_size, self.rasterizer.raster_settings,
-                            getattr(self.shader, "blend_params", None), lights, materials)
+                            getattr(self.shader, "blend_params", None), lights, materials,
+                            getattr(self.rasterizer, "fragment_cache", None))
 
     def __call__(self, meshes_world, cameras=None, lights=None, materials=None, **kw):
         rgb, cov = self.render(meshes_world, cameras, lights, materials)

@@ -261,11 +261,16 @@ class PerceptualPlan:
             self.generation += 1
             self._style_key, self._style_ref = k, style
 
-    def _color(self, rgb):
-        """The device copy of a background colour (one upload per colour and plan, not per step)."""
+    @staticmethod
+    def _color_key(rgb):
         key = tuple(float(c) for c in rgb)
         if len(key) != 3:
             raise _lib.St3dError(f"flat_color must be 3 floats, got {rgb!r}")
+        return key
+
+    def _color(self, rgb):
+        """The device copy of a background colour (one upload per colour and plan, not per step)."""
+        key = self._color_key(rgb)
         cache = self.__dict__.setdefault("_colors", {})
         if key not in cache:
             if len(cache) > 64:
@@ -294,24 +299,38 @@ class PerceptualPlan:
         self._guided = True
 
     def loss(self, current, style_weight, content_weight, batch_denom=None, want_grad=True, need_mask=None, flat_color=None,
-             style_mask=None):
+             style_mask=None, epoch=0):
         """-> (loss_buf view [total, content, style], grad (n,3,S,S) or None).
         need_mask (n,S,S) uint8: the only pixels at which the caller's consumer reads grad (st3d_plan_loss_masked) -- grad
         is the same there, bit for bit, and 0 elsewhere; the bottom of the VGG backward computes only what they need.
         flat_color (3 floats): `current` holds this colour at many pixels, as a render holds its background
         (st3d_plan_loss_flat): the shallow forward convs compute the tiles that see anything else and copy the rest.  The
         results are the same bits; the colour only decides whether the lists are built.
-        style_mask (n,1,S,S) | (n,S,S) in [0,1]: the guided style loss -- set before the call, cleared when absent."""
+        style_mask (n,1,S,S) | (n,S,S) in [0,1]: the guided style loss -- set before the call, cleared when absent.
+        epoch (with need_mask; 0 = none): the caller's promise that need_mask is the COVERAGE of `current` and has the
+        contents it had at every earlier call with this id, and that every pixel outside it holds flat_color bit for bit
+        (st3d_plan_loss_keyed).  The plan then builds its lists once per epoch, the flat-field lists from the coverage, and
+        leaves out the copies while its buffers still hold the epoch's background.  The results are the same bits."""
         cur = current.detach().to(torch.float32).contiguous()
         n = cur.shape[0]
         self.set_style_guidance(style_mask, n)
         grad = torch.empty_like(cur) if want_grad else None
-        if need_mask is not None and want_grad:
+        cover = need_mask if epoch else None
+        if need_mask is not None and (want_grad or epoch):
             if need_mask.dtype != torch.uint8 or tuple(need_mask.shape) != (n, self.S, self.S):
                 raise _lib.St3dError(f"need_mask must be uint8 ({n},{self.S},{self.S}), got {need_mask.dtype} {tuple(need_mask.shape)}")
-            need_mask = need_mask.contiguous()
+            need_mask = cover = need_mask.contiguous()
+            if not want_grad:
+                need_mask = None
         else:
             need_mask = None
+        if epoch and cover is not None:
+            rgb = (ctypes.c_float * 3)(*self._color_key(flat_color)) if flat_color is not None else None
+            call("st3d_plan_loss_keyed", self._h, dptr(cur), n, int(batch_denom or n), float(style_weight),
+                 float(content_weight), dptr(self.loss_buf), dptr(grad), dptr(cover),
+                 dptr(self._color(flat_color)) if flat_color is not None else None, rgb, int(epoch), stream_ptr())
+            self.generation += 1
+            return self.loss_buf, grad
         if need_mask is not None or flat_color is not None:
             call("st3d_plan_loss_flat", self._h, dptr(cur), n, int(batch_denom or n), float(style_weight),
                  float(content_weight), dptr(self.loss_buf), dptr(grad), dptr(need_mask),
@@ -336,8 +355,10 @@ class PerceptualPlan:
     # conv_*: Winograd F(2x2,3x3) launches; conv43_*: Winograd F(4x4,3x3); convx_*: direct / vector-ALU kernels
     # *_need: launches that ran over a need list (loss(need_mask=...)): a fraction of the full launch's work
     # conv43_fwd_flat / flat_fill: forward launches over a flat-field list (loss(flat_color=...)) and the copies behind them
+    # convx_fwd_flat: the conv1_1 launch of a keyed call that leaves out its background tiles (loss(epoch=...))
     FAMILIES = ("conv_fwd", "conv_dgrad", "pool", "gram_fwd", "gram_bwd", "elementwise", "convx_fwd", "convx_dgrad", "conv43_fwd",
-                "conv43_dgrad", "conv43_dgrad_need", "convx_dgrad_need", "gram_bwd_need", "conv43_fwd_flat", "flat_fill")
+                "conv43_dgrad", "conv43_dgrad_need", "convx_dgrad_need", "gram_bwd_need", "conv43_fwd_flat", "flat_fill",
+                "convx_fwd_flat")
 
     def profile_launches(self):
         """[(family, VGG module index, ms)] for every launch bracket since the last read (profiling on)."""

@@ -48,6 +48,8 @@ def _composite(tensors, masks, background):
     tag = _render.need_of(tensors)
     if tag is not None and out.requires_grad:
         setattr(out, _render.NEED_TAG, tag)
+        if getattr(tensors, _render.EPOCH_TAG, None) is not None:       # (the coverage's geometry epoch with it; not the flat tag)
+            setattr(out, _render.EPOCH_TAG, getattr(tensors, _render.EPOCH_TAG))
     return out
 
 

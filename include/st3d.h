@@ -366,6 +366,15 @@ int st3d_conv3x3_pack(const float *w, int Cout, int Cin, float *w_fwd, float *w_
 /* y = relu?(conv3x3(x, w) + bias): x (N,Cin,H,W), y (N,Cout,H,W) */
 int st3d_conv3x3_fwd(const float *x, const float *w_fwd_packed, const float *bias, float *y,
                      int N, int Cin, int Cout, int H, int W, int relu, st3d_stream_t stream);
+/* The 3-channel forward (conv1_1: one workgroup per 8 x 128-pixel tile, tiles numbered image-major, then row-major;
+ * st3d_conv1_skip_tiles of them) over the tiles whose byte in tile_skip is 0: y keeps what it held at the others, the
+ * computed tiles are bitwise st3d_conv3x3_fwd's.  Any other shape is ST3D_E_INVALID.  st3d_conv1_skip_build: skip = 1 where
+ * cover (N,H,W bytes, non-zero = covered) holds nothing in the tile +- 1, i.e. every 3x3 window of the tile sees background
+ * (or the zero padding) only -- such a tile's output does not change while the background colour and the weights stay. */
+size_t st3d_conv1_skip_tiles(int N, int H, int W);
+int st3d_conv1_skip_build(const uint8_t *cover, int N, int H, int W, uint8_t *skip, st3d_stream_t stream);
+int st3d_conv3x3_fwd_skip(const float *x, const float *w_fwd_packed, const float *bias, float *y, int N, int Cin, int Cout,
+                          int H, int W, int relu, const uint8_t *tile_skip, st3d_stream_t stream);
 /* gx = conv3x3^T(mask(gy)): gradient w.r.t. the conv INPUT (weights are frozen,
  * utils.py:50-51: no wgrad).  gy (N,Cout,H,W) is the gradient w.r.t. the POST-ReLU output;
  * act (same shape, the saved post-ReLU output) gates it (act>0) when non-NULL. */
@@ -527,6 +536,15 @@ int st3d_flat_build(const float *imgs, const float *color, int N, int S, int lev
                     int *list1, int *map1, int *list2, int *map2, int *list3, int *map3, int *counts, st3d_stream_t stream);
 int st3d_flat_fill(const int *tile_map, float *y, float *y_pooled, uint8_t *pool_idx, int N, int C, int H, int W,
                    st3d_stream_t stream);
+/* st3d_flat_build with V0 taken from a coverage mask (N,S,S bytes, non-zero = covered = varying; 16-byte aligned) instead of
+ * the pixels: the lists depend on the geometry alone, so views that do not move build them once.  They list a superset of
+ * the pixel lists' tiles provided every uncovered pixel holds the background colour bit for bit -- the caller's premise.
+ * st3d_flat_check_cover tests it: *bad (device int) = 1 if a pixel of imgs outside cover differs from color, else 0 (it
+ * uses the V0 plane of the workspace, which st3d_flat_build_cover leaves alone). */
+int st3d_flat_build_cover(const uint8_t *cover, int N, int S, int levels, void *workspace, size_t workspace_bytes, int *list1,
+                          int *map1, int *list2, int *map2, int *list3, int *map3, int *counts, st3d_stream_t stream);
+int st3d_flat_check_cover(const float *imgs, const float *color, const uint8_t *cover, int N, int S, void *workspace,
+                          size_t workspace_bytes, int *bad, st3d_stream_t stream);
 /* MaxPool2d(2,2): y (N,C,H,W) -> p (N,C,H/2,W/2) (+ argmax idx, may be NULL) */
 int st3d_maxpool2x2_fwd(const float *y, float *p, uint8_t *idx, int N, int C, int H, int W,
                         st3d_stream_t stream);
@@ -942,6 +960,25 @@ int st3d_plan_loss_masked(st3d_plan *plan, const float *current, int n, int batc
 int st3d_plan_loss_flat(st3d_plan *plan, const float *current, int n, int batch_denom, float style_weight,
                         float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask,
                         const float *flat_color, st3d_stream_t stream);
+/* st3d_plan_loss_flat for views whose geometry stays put while their texture changes.  epoch names a geometry epoch: the
+ * caller promises that `cover` (n,S,S bytes, non-zero = covered; 16-byte aligned; it doubles as the need mask) has the
+ * contents it had at every earlier call with this epoch and n, and -- when flat_color is given -- that every uncovered
+ * pixel of `current` holds that colour bit for bit.  flat_rgb: the colour once more, 3 floats in HOST memory.  The plan then
+ *   - keeps the need lists and the flat-field lists (built from cover: st3d_flat_build_cover) of the last three epochs and
+ *     builds them only for an epoch it does not hold;
+ *   - leaves out the three st3d_flat_fill launches while the buffers they write still hold this epoch's background: the
+ *     previous call that wrote them was a keyed one with the same epoch, n, colour and weights.  Every other writer
+ *     (st3d_plan_forward, st3d_plan_set_content, st3d_plan_set_style, any other st3d_plan_loss* call, a failed call,
+ *     st3d_vgg_set_conv) makes the next keyed call fill again;
+ *   - under the same condition runs conv1_1 over the tiles that see a covered pixel only (st3d_conv3x3_fwd_skip;
+ *     ST3D_FLAT_CONV1=0, read by st3d_plan_create: the full launch).
+ * Every activation, the losses and the gradient are bitwise st3d_plan_loss_flat's.  epoch == 0, cover == NULL or graph
+ * replay on: st3d_plan_loss_flat itself, launch for launch.  ST3D_FLAT_CHECK=1 (read by st3d_plan_create): every keyed call
+ * tests the promise about the uncovered pixels (st3d_flat_check_cover, one host read) and fails with ST3D_E_STATE if it
+ * does not hold. */
+int st3d_plan_loss_keyed(st3d_plan *plan, const float *current, int n, int batch_denom, float style_weight,
+                         float content_weight, float *loss_out, float *grad_current, const uint8_t *cover,
+                         const float *flat_color, const float *flat_rgb, uint64_t epoch, st3d_stream_t stream);
 /* HIP-graph replay of st3d_plan_loss: its ~70 launches form a static sequence, so after one ordinary call it is captured
  * (per n / batch_denom / weights) and replayed with one hipGraphLaunch; inputs and outputs pass through plan-owned staging
  * buffers (three extra device copies per call).  Pays off where the step is launch-bound (small images). */
@@ -959,8 +996,9 @@ int st3d_plan_backward(st3d_plan *plan, int n, int upto_module, const float *con
  * 7 convx_dgrad 8 conv43_fwd 9 conv43_dgrad (Winograd F(4x4,3x3)); launches that ran over a need list
  * (st3d_plan_loss_masked) count under families of their own, their work being a fraction of the full launch's:
  * 10 conv43_dgrad_need 11 convx_dgrad_need (the relu1_1 pass) 12 gram_bwd_need (none yet); likewise the forward launches
- * over a flat-field list (st3d_plan_loss_flat) and the copies behind them: 13 conv43_fwd_flat 14 flat_fill */
-#define ST3D_PROFILE_FAMILIES 15
+ * over a flat-field list (st3d_plan_loss_flat) and the copies behind them: 13 conv43_fwd_flat 14 flat_fill; and the
+ * conv1_1 launch that leaves out its background tiles (st3d_plan_loss_keyed): 15 convx_fwd_flat */
+#define ST3D_PROFILE_FAMILIES 16
 int st3d_plan_profile(st3d_plan *plan, int enable);
 int st3d_plan_profile_read(st3d_plan *plan, float *ms_out /*host [ST3D_PROFILE_FAMILIES]*/,
                            int *launches_out /*host [ST3D_PROFILE_FAMILIES]*/);

@@ -43,21 +43,24 @@ struct EpochSlots {
 
 // What the buffers the flat-field fills write currently hold in their unlisted tiles: the background of `epoch`, filled for
 // n images of this colour under this many listed launches and this state of the weights.  epoch 0 = unknown.
+// kept: how many forward launches above the flat-field levels the same call ran in full or over their kept lists, bottom-up
+// (conv3_1, conv3_2, conv3_3): their buffers hold the epoch's previous call in every tile, so a call that lists that many
+// launches may leave the unlisted tiles alone.  A record made under another depth does not match.
 struct CleanRecord {
     uint64_t epoch = 0;
-    int n = 0, levels = 0;
+    int n = 0, levels = 0, kept = 0;
     uint32_t rgb[3] = {};           // the colour's bits: -0 is not +0, a NaN equals itself
     uint64_t weights = 0;           // st3d_vgg's counter of st3d_vgg_set_conv calls
 
     void clear() { epoch = 0; }
-    void set(uint64_t e, int count, int lv, const float *color, uint64_t w) {
-        epoch = e; n = count; levels = lv; weights = w;
+    void set(uint64_t e, int count, int lv, const float *color, uint64_t w, int kp = 0) {
+        epoch = e; n = count; levels = lv; weights = w; kept = kp;
         memcpy(rgb, color, sizeof(rgb));
     }
-    bool matches(uint64_t e, int count, int lv, const float *color, uint64_t w) const {
+    bool matches(uint64_t e, int count, int lv, const float *color, uint64_t w, int kp = 0) const {
         uint32_t c[3];
         memcpy(c, color, sizeof(c));
-        return e != 0 && epoch == e && n == count && levels == lv && weights == w && c[0] == rgb[0] && c[1] == rgb[1] && c[2] == rgb[2];
+        return e != 0 && epoch == e && n == count && levels == lv && kept == kp && weights == w && c[0] == rgb[0] && c[1] == rgb[1] && c[2] == rgb[2];
     }
 };
 

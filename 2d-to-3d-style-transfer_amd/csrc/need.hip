@@ -143,6 +143,7 @@ constexpr int kListUnpools[kLists] = {1, 0, 1, 0, 0, 0};     // launch k reads i
 
 struct BlockLevels {
     int nlists;
+    int first;                       // workgroup 0 makes list `first` (the kept lists start above the flat-field levels)
     int bw[kLists];                  // blocks per row (and per column) of the map
     int trows[kLists], tcols[kLists];        // a tile in blocks: 1 x 16 or 2 x 8; 1 x 4 = strips, four entries to a step
     int unpools[kLists];
@@ -193,6 +194,29 @@ __global__ __launch_bounds__(256) void need_front_kernel(const uint8_t *__restri
     }
     const u64 bits = __ballot(any != 0);
     if (lane == 0) b0[word] = bits;
+}
+
+// The front launch of the kept lists (st3d_kept_build): K_0 = block4(dilate(cover, 2)), one lane per block and one wave per
+// word as above.  The block may change when its 8x8 patch (rows / columns 4 b - 2 .. 4 b + 5: the 6x6 input patch of the
+// F(4x4,3x3) block, each pixel of it the output of a 3x3 direct conv) holds a covered pixel.  Clamped like the patch above.
+__global__ __launch_bounds__(256) void kept_front_kernel(const uint8_t *__restrict__ cover, int S, int k0_words, u64 *__restrict__ k0) {
+    const int word = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (word >= k0_words) return;                    // (the whole wave)
+    const int bw = S >> 2, W = row_words(bw);
+    const int j = word % W, by = (word / W) % bw, n = word / (W * bw);
+    const int bx = 64 * j + lane;
+    unsigned any = 0;
+    if (bx < bw) {
+        const uint8_t *m = cover + (size_t)n * S * S + 4 * bx;
+        const int l2 = bx > 0 ? -2 : 0, l1 = bx > 0 ? -1 : 0, r1 = bx + 1 < bw ? 4 : 3, r2 = bx + 1 < bw ? 5 : 3;
+#pragma unroll
+        for (int r = -2; r <= 5; ++r) {
+            const uint8_t *row = m + (size_t)min(max(4 * by + r, 0), S - 1) * S;
+            any |= *reinterpret_cast<const unsigned *>(row) | row[l2] | row[l1] | row[r1] | row[r2];
+        }
+    }
+    const u64 bits = __ballot(any != 0);
+    if (lane == 0) k0[word] = bits;
 }
 
 // every second bit of x (bits 0, 2, .. 62) packed into the low half
@@ -282,7 +306,7 @@ __global__ __launch_bounds__(1024) void need_block_lists_kernel(const u64 *__res
     __shared__ u64 map_even[kMapWords], map_odd[kMapWords / 2];
     __shared__ int wave_sum[16];
     __shared__ int img_first[kMapWords / 16 + 2];        // strips: per image of the chunk, the strips listed before its first
-    const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int k = blockIdx.x + L.first, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const bool gram = k == L.nlists;
     int *__restrict__ list = gram ? L.gram_list : L.list[k];
     const int level = gram ? 1 : k;
@@ -499,6 +523,31 @@ extern "C" size_t st3d_need_blocks_workspace_bytes(int N, int S) {
     return b0_words(N, S) * sizeof(u64);
 }
 
+// the levels of lists 0 .. nlists - 1 at side S; lists first .. nlists - 1 are made (and must be given)
+static int fill_levels(BlockLevels *Lp, int N, int S, int first, int nlists, const int *tile_cols, int *const *lists) {
+    BlockLevels &L = *Lp;
+    memset(&L, 0, sizeof(L));
+    L.nlists = nlists;
+    L.first = first;
+    L.N = N;
+    for (int k = 0; k < nlists; ++k) {
+        const int R = S >> kListShift[k];
+        int rows = 0, cols = 0;
+        st3d_wino43_tile_geometry(R, R, &rows, &cols);
+        if (tile_cols && tile_cols[k]) cols = tile_cols[k];
+        ST3D_CHECK_ARG(k < first || lists[k]);
+        ST3D_CHECK_ARG((cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0) || cols == 16);      // (R % 8 == 0, R % 16 == 0 with it: S % 64 == 0)
+        ST3D_CHECK_ARG(k < first || cols != 16 || ((uintptr_t)lists[k] & 15) == 0);
+        L.bw[k] = R / 4;
+        L.trows[k] = cols == 32 ? 2 : 1;
+        L.tcols[k] = cols / 4;
+        L.unpools[k] = kListUnpools[k];
+        L.total[k] = (int)st3d_need_blocks_tiles(N, S, k);
+        L.list[k] = k < first ? nullptr : lists[k];
+    }
+    return ST3D_OK;
+}
+
 extern "C" int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nlists, const int *tile_cols, uint8_t *seg,
                                       void *workspace, size_t workspace_bytes, int *const *lists, int *counts, int *gram_list,
                                       int *gram_count, st3d_stream_t stream) {
@@ -510,24 +559,7 @@ extern "C" int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nli
     ST3D_CHECK_ARG(lists && counts && workspace && workspace_bytes >= st3d_need_blocks_workspace_bytes(N, S));
     ST3D_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
     BlockLevels L;
-    memset(&L, 0, sizeof(L));
-    L.nlists = nlists;
-    L.N = N;
-    for (int k = 0; k < nlists; ++k) {
-        const int R = S >> kListShift[k];
-        int rows = 0, cols = 0;
-        st3d_wino43_tile_geometry(R, R, &rows, &cols);
-        if (tile_cols && tile_cols[k]) cols = tile_cols[k];
-        ST3D_CHECK_ARG(lists[k]);
-        ST3D_CHECK_ARG((cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0) || cols == 16);      // (R % 8 == 0, R % 16 == 0 with it: S % 64 == 0)
-        ST3D_CHECK_ARG(cols != 16 || ((uintptr_t)lists[k] & 15) == 0);
-        L.bw[k] = R / 4;
-        L.trows[k] = cols == 32 ? 2 : 1;
-        L.tcols[k] = cols / 4;
-        L.unpools[k] = kListUnpools[k];
-        L.total[k] = (int)st3d_need_blocks_tiles(N, S, k);
-        L.list[k] = lists[k];
-    }
+    ST3D_TRY(fill_levels(&L, N, S, 0, nlists, tile_cols, lists));
     if (gram_list) {
         L.gram_runs = (int)(st3d_need_blocks_gram_runs(N, S) / N);
         L.gram_list = gram_list;
@@ -541,6 +573,33 @@ extern "C" int st3d_need_blocks_build(const uint8_t *mask, int N, int S, int nli
     need_front_kernel<<<seg_wgs + st3d::cdiv(words, 4), 256, 0, s>>>(mask, S, total, seg_wgs, seg, words, bits);
     ST3D_LAUNCH_CHECK();
     need_block_lists_kernel<<<nlists + (gram_list ? 1 : 0), 1024, 0, s>>>(bits, L, counts);
+    ST3D_LAUNCH_CHECK();
+    return ST3D_OK;
+}
+
+// The kept lists of the forward launches (plan.hip, forward()): list k is the forward of the conv whose input gradient need
+// list k belongs to -- conv1_2, conv2_1, conv2_2, conv3_1, conv3_2, conv3_3 -- and holds the tiles or strips with an output
+// block that may differ between two calls whose images differ on `cover` only:
+//     K_0 = block4(dilate(cover, 2))            conv1_1 is per pixel, conv1_2 per block
+//     K_k+1 = block4(dilate(K_k, 1)), through the 2x2 OR behind a fused pool
+// which from K_0 on is the propagation of the need lists (next_level_word), so the second launch is theirs.  Lists first ..
+// nlists - 1 are made, in the formats of st3d_need_blocks_build; counts[k] belongs to list k.
+extern "C" int st3d_kept_build(const uint8_t *cover, int N, int S, int first, int nlists, const int *tile_cols, void *workspace,
+                               size_t workspace_bytes, int *const *lists, int *counts, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(cover && N > 0);
+    ST3D_CHECK_ARG(first >= 0 && first < nlists && nlists <= st3d_need_blocks_lists(S));
+    ST3D_CHECK_ARG(((uintptr_t)cover & 15) == 0);
+    ST3D_CHECK_ARG((long)N * S * S < (1L << 31));
+    ST3D_CHECK_ARG(lists && counts && workspace && workspace_bytes >= st3d_need_blocks_workspace_bytes(N, S));
+    ST3D_CHECK_ARG(((uintptr_t)workspace & 15) == 0);
+    BlockLevels L;
+    ST3D_TRY(fill_levels(&L, N, S, first, nlists, tile_cols, lists));
+    hipStream_t s = st3d::as_stream(stream);
+    const int words = (int)b0_words(N, S);
+    u64 *bits = reinterpret_cast<u64 *>(workspace);
+    kept_front_kernel<<<st3d::cdiv(words, 4), 256, 0, s>>>(cover, S, words, bits);
+    ST3D_LAUNCH_CHECK();
+    need_block_lists_kernel<<<nlists - first, 1024, 0, s>>>(bits, L, counts);
     ST3D_LAUNCH_CHECK();
     return ST3D_OK;
 }

@@ -233,6 +233,22 @@ struct st3d_plan {
     int flat_levels = 0;
     uint8_t *flat_ws = nullptr;
     size_t flat_ws_bytes = 0;
+    // kept lists of st3d_plan_loss_keyed (st3d_kept_build, need.hip): how many of conv3_1, conv3_2, conv3_3 walk, in a call that
+    // finds the clean record its own, only the tiles or strips holding an output block that the coverage can change -- every
+    // other tile still holds the bits the previous call of the epoch wrote, and the same launch on the same input would write
+    // them again.  Bottom-up like the levels above; keep_cols as need_cols (16 = strips).  ST3D_KEEP_DEPTH / ST3D_KEEP_TILE /
+    // ST3D_KEEP_FORCE, read by st3d_plan_create.
+    static constexpr int kKeepFirst = 3, kKeepMax = 3;      // list 3 = conv slot 4 = conv3_1
+    int keep_levels = 0;
+    int keep_cols[ST3D_NEED_MAX_LISTS] = {};
+    // The flat-field levels in such a call: no fill runs, so nothing needs their lists to name one tile per border class, and
+    // conv1_2, conv2_1 and conv2_2 may walk their kept lists (lists 0 .. 2) in a finer geometry than the flat-field lists'
+    // own.  shallow_cols[k]: 0 = the flat-field list as ever; 32 / 64 tiles, 16 strips (conv2_1 only: the others pool).
+    // keep_first: the lowest list the build makes (kKeepFirst when no shallow level is on).  ST3D_KEEP_SHALLOW.
+    int shallow_cols[3] = {};
+    int keep_first = kKeepFirst;
+    uint8_t *keep_ws = nullptr;
+    size_t keep_ws_bytes = 0;
     // What the list builds write and the launches read: the need lists (segment bytes, tile lists, counts, the Gram run
     // list) and the flat-field lists (tile lists, maps, counts).  sets[0] belongs to the unkeyed calls, which rebuild it
     // every time; sets[1 ..] hold the lists of the last kEpochSlots geometry epochs of st3d_plan_loss_keyed (epochs.h), built
@@ -246,7 +262,9 @@ struct st3d_plan {
         int *need_gram_list = nullptr, *need_gram_cnt = nullptr;
         int *flat_list[3] = {}, *flat_map[3] = {}, *flat_cnt = nullptr;
         uint8_t *c1_skip = nullptr;                     // (keyed sets) conv1_1's tiles that see background only (conv.hip)
+        int *kept_list[ST3D_NEED_MAX_LISTS] = {}, *kept_cnt = nullptr;     // (keyed sets) lists keep_first .. of st3d_kept_build
         bool have_need = false, have_flat = false;      // (keyed sets) built for the slot's epoch
+        bool have_kept = false;                         // (keyed sets) built by the epoch's first clean call
     };
     ListSet sets[1 + kEpochSlots];
     ListSet *ls = &sets[0];
@@ -257,6 +275,9 @@ struct st3d_plan {
     // fill: its lists are the epoch's, so the listed launches rewrite exactly the tiles they wrote before and the rest still
     // hold what the fills of the epoch's first call copied.  Its conv1_1 likewise leaves out the tiles whose windows see
     // background only (c1_skip): the full launch of the epoch's first call wrote them.
+    // The same record vouches for act[10], act[12] and act[14] (conv3_1 .. conv3_3, each a buffer of its own from dev_alloc): a call
+    // that sets it ran those launches in full or over their kept lists, so every tile holds what a full launch of that call
+    // would have written or -- where the coverage cannot reach -- what the epoch's earlier call did, which is the same bits.
     // The only writer of act[] and pidx[] is forward(), which clears the record on entry; its callers are st3d_plan_forward,
     // st3d_plan_set_content, st3d_plan_set_style and plan_loss_enqueue (every st3d_plan_loss* entry, graph capture and
     // replay included: a replay runs forward()'s captured launches, and the keyed entry never replays).  The backward
@@ -340,6 +361,7 @@ struct Keyed {
     const uint8_t *cover;       // (n,S,S) device bytes, non-zero = covered; every other pixel holds the colour bit for bit
     const float *rgb;           // the colour again, 3 floats in HOST memory (what the clean record compares)
     int flat_done;              // out: how many launches ran listed
+    int kept_done;              // out: how many of conv3_1 .. conv3_3 the call leaves whole (in full or over their kept lists)
 };
 int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hipStream_t s, const float *flat_color = nullptr,
             Keyed *key = nullptr) {
@@ -347,7 +369,10 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
     int flat = 0;               // conv slots 1 .. flat run listed
     if (flat_color)
         while (flat < p->flat_levels && kConvIdx[flat + 1] <= upto) ++flat;
-    const bool fill = !(key && flat > 0 && p->clean.matches(key->epoch, n, flat, key->rgb, v->sets));
+    int keep = 0;               // conv slots 4 .. 3 + keep (conv3_1 ..) may run over their kept lists
+    if (key && flat == p->flat_levels)
+        while (keep < p->keep_levels && kConvIdx[st3d_plan::kKeepFirst + 1 + keep] <= upto) ++keep;
+    const bool fill = !(key && flat > 0 && p->clean.matches(key->epoch, n, flat, key->rgb, v->sets, keep));
     p->clean.clear();           // every path below writes act[] / pidx[]; the keyed entry sets the record again when all went well
     if (flat > 0 && !key) {
         Scope sc(p, F_ELEM, s);
@@ -373,7 +398,13 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
             p->ls->have_flat = true;
         }
     }
-    if (key) key->flat_done = flat;
+    if (key) { key->flat_done = flat; key->kept_done = keep; }
+    if (!fill && keep > 0 && !p->ls->have_kept) {       // the epoch's first clean call: a run that changes its geometry every step never gets here
+        Scope sc(p, F_ELEM, s);
+        ST3D_TRY(st3d_kept_build(key->cover, n, p->S, p->keep_first, st3d_plan::kKeepFirst + p->keep_levels, p->keep_cols, p->keep_ws,
+                                 p->keep_ws_bytes, p->ls->kept_list, p->ls->kept_cnt, s));
+        p->ls->have_kept = true;
+    }
     const float *x = imgs;
     for (int m = 0; m <= upto; ++m) {
         const int cs = conv_slot(m), ps = pool_slot(m);
@@ -402,7 +433,17 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
             float *yfull = (pps < 0 || keep_full) ? p->act[m] : nullptr;
             float *yp = pps >= 0 ? p->act[pool_m] : nullptr;
             uint8_t *yi = pps >= 0 ? p->pidx[pps] : nullptr;
-            if (cs >= 1 && cs <= flat) {           // an F(4x4,3x3) launch over its flat-field list, then the copies
+            if (cs >= 1 && cs <= flat && !fill && keep > 0 && p->shallow_cols[cs - 1]) {
+                // a clean keyed call: the kept list in its own geometry; the tiles it leaves out hold the previous call's bits
+                Scope sc(p, F_CONV43_FWD_FLAT, s, m);
+                const int k = cs - 1;
+                if (p->shallow_cols[k] == 16)
+                    ST3D_TRY(st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], yfull, n, Cin, Cout, H, W, 1, p->ls->kept_list[k],
+                                                    p->ls->kept_cnt + k, s));
+                else
+                    ST3D_TRY(st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->shallow_cols[k],
+                                                       p->ls->kept_list[k], p->ls->kept_cnt + k, s));
+            } else if (cs >= 1 && cs <= flat) {    // an F(4x4,3x3) launch over its flat-field list, then the copies
                 {
                     Scope sc(p, F_CONV43_FWD_FLAT, s, m);
                     ST3D_TRY(st3d_wino43_fwd_tiles(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->ls->flat_list[cs - 1],
@@ -412,6 +453,16 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
                     Scope sc(p, F_FLAT_FILL, s, m);
                     ST3D_TRY(st3d_flat_fill(p->ls->flat_map[cs - 1], yfull, yp, yi, n, Cout, H, W, s));
                 }
+            } else if (!fill && cs > st3d_plan::kKeepFirst && cs <= st3d_plan::kKeepFirst + keep) {
+                // a clean keyed call: the tiles the coverage can change; the others keep the previous call's bits (no pool here)
+                Scope sc(p, F_CONV43_FWD_FLAT, s, m);
+                const int k = cs - 1;
+                if (p->keep_cols[k] == 16)
+                    ST3D_TRY(st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], p->act[m], n, Cin, Cout, H, W, 1, p->ls->kept_list[k],
+                                                    p->ls->kept_cnt + k, s));
+                else
+                    ST3D_TRY(st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], p->act[m], nullptr, nullptr, n, Cin, Cout, H, W, 1,
+                                                       p->keep_cols[k], p->ls->kept_list[k], p->ls->kept_cnt + k, s));
             } else if (route == WINO43) {
                 Scope sc(p, F_CONV43_FWD, s, m);
                 ST3D_TRY(st3d_wino43_fwd(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
@@ -613,6 +664,53 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     int flat_ok = 0;
     while (flat_ok < 3 && p->route[flat_ok + 1].fwd == WINO43) ++flat_ok;
     p->flat_levels = capped(std::min(flat_ok, st3d_flat_levels(S)), "ST3D_FLAT_DEPTH");
+    {
+        // The kept lists: conv3_1 .. conv3_3 above a full set of flat-field levels, F(4x4,3x3) launches without a pool, where the
+        // full launch walks at least two tiles per persistent workgroup (the rule of the need lists, with the forward's Cout;
+        // ST3D_KEEP_FORCE=1 lifts it for tests -- ST3D_NEED_FORCE does not).  ST3D_KEEP_TILE as ST3D_NEED_TILE, one value for
+        // every level or one per level from conv3_1 on; measured default: strips.
+        const bool force = flag("ST3D_KEEP_FORCE", false);
+        int cus = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        int keep_ok = 0;
+        const int lists = st3d_need_blocks_lists(S);
+        const char *tile = getenv("ST3D_KEEP_TILE");
+        while (p->flat_levels == 3 && keep_ok < st3d_plan::kKeepMax) {
+            const int k = st3d_plan::kKeepFirst + keep_ok, cs = k + 1, R = p->H[kConvIdx[cs]];
+            if (k >= lists || p->route[cs].fwd != WINO43 || pool_slot(kConvIdx[cs] + 2) >= 0) break;
+            if (!force && (long)B * (R / 4) * (R / 4) / 16 < 2L * (cus / std::max(1, kConvCout[cs] / 64))) break;
+            int cols = 16;
+            if (tile && tile[0]) {
+                cols = atoi(tile);
+                if (const char *c = strchr(tile, ',')) { tile = c + 1; }
+            }
+            int rows0 = 0, cols0 = 0;
+            st3d_wino43_tile_geometry(R, R, &rows0, &cols0);
+            if (cols == 0) cols = cols0;
+            if (!((cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0 && R % 8 == 0) || cols == 16)) break;
+            p->keep_cols[k] = cols;
+            ++keep_ok;
+        }
+        p->keep_levels = capped(keep_ok, "ST3D_KEEP_DEPTH");
+        // ST3D_KEEP_SHALLOW = a,b,c: the geometry of conv1_2, conv2_1, conv2_2 in clean calls (0 = their flat-field lists);
+        // measured default.  Only above a kept conv3_1, and under the same two-rounds rule.
+        static const int kDefaultShallow[3] = {32, 16, 32};
+        const char *sh = getenv("ST3D_KEEP_SHALLOW");
+        for (int k = 0; k < 3 && p->keep_levels >= 1; ++k) {
+            const int cs = k + 1, R = p->H[kConvIdx[cs]];
+            int cols = kDefaultShallow[k];
+            if (sh) {
+                cols = atoi(sh);
+                if (const char *c = strchr(sh, ',')) { sh = c + 1; } else { sh = ""; }
+            }
+            const bool pools = pool_slot(kConvIdx[cs] + 2) >= 0;
+            const bool fits = (cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0 && R % 8 == 0) || (cols == 16 && !pools);
+            if (!fits || (!force && (long)B * (R / 4) * (R / 4) / 16 < 2L * (cus / std::max(1, kConvCout[cs] / 64)))) continue;
+            p->shallow_cols[k] = cols;
+            if (k < p->keep_first) p->keep_first = k;
+        }
+        for (int k = p->keep_first; k < 3; ++k) p->keep_cols[k] = p->shallow_cols[k] ? p->shallow_cols[k] : 16;     // (built, not walked)
+    }
     for (int i = 0; i < 2; ++i) alloc(&p->gbuf[i], gmax);
     alloc(&p->content_target, (size_t)B * p->C[kContentTap] * p->H[kContentTap] * p->W[kContentTap]);
     for (int i = 0; i < 5; ++i) {
@@ -645,6 +743,15 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
         p->flat_ws_bytes = st3d_flat_workspace_bytes(B, S);
         alloc(&p->flat_ws, p->flat_ws_bytes);
         alloc(&p->g_color, (size_t)4);
+    }
+    if (p->keep_levels >= 1) {
+        p->keep_ws_bytes = st3d_need_blocks_workspace_bytes(B, S);
+        alloc(&p->keep_ws, p->keep_ws_bytes);
+        for (int i = 1; i <= st3d_plan::kEpochSlots; ++i) {
+            alloc(&p->sets[i].kept_cnt, (size_t)ST3D_NEED_MAX_LISTS);
+            for (int k = p->keep_first; k < st3d_plan::kKeepFirst + p->keep_levels; ++k)
+                alloc(&p->sets[i].kept_list[k], st3d_need_blocks_entries(B, S, k, p->keep_cols[k]));
+        }
     }
     for (st3d_plan::ListSet &ls : p->sets) {     // the lists themselves: the unkeyed set and one per epoch slot
         if (p->need_levels >= 1) {
@@ -916,8 +1023,8 @@ extern "C" int st3d_plan_loss_keyed(st3d_plan *p, const float *current, int n, i
     bool fresh = false;
     const int slot = p->epochs.take(epoch, n, &fresh);
     st3d_plan::ListSet *ls = &p->sets[1 + slot];
-    if (fresh) ls->have_need = ls->have_flat = false;
-    Keyed key{epoch, cover, flat_rgb, 0};
+    if (fresh) ls->have_need = ls->have_flat = ls->have_kept = false;
+    Keyed key{epoch, cover, flat_rgb, 0, 0};
     p->ls = ls;
     p->clean = held;            // what forward() compares this call with, and clears
     const int rc = plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, flat_color,
@@ -928,7 +1035,7 @@ extern "C" int st3d_plan_loss_keyed(st3d_plan *p, const float *current, int n, i
         p->clean.clear();
         return rc;
     }
-    if (key.flat_done > 0) p->clean.set(epoch, n, key.flat_done, flat_rgb, p->vgg->sets);
+    if (key.flat_done > 0) p->clean.set(epoch, n, key.flat_done, flat_rgb, p->vgg->sets, key.kept_done);
     return ST3D_OK;
 }
 

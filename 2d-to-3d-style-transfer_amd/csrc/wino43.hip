@@ -688,7 +688,7 @@ bool shape_ok43(int Cin, int Cout, int H, int W) {
 }
 
 template <int MODE, int TC>
-int launch_wino43_tc(Wino43Args a, hipStream_t s) {
+int launch_wino43_tc(Wino43Args a, hipStream_t s, bool strip_fwd = false) {
     using G = Geo43<TC>;
     constexpr bool kStrips = TC == 4;       // (the only use of four tile rows: a step is four listed strips of 4 x 16 pixels)
     a.tiles_x = a.W / G::COLS;
@@ -718,10 +718,13 @@ int launch_wino43_tc(Wino43Args a, hipStream_t s) {
         ST3D_LAUNCH_CHECK();
         return ST3D_OK;
     };
-    if constexpr (kStrips) {        // the input-gradient chain over a strip list (need.hip), nothing else
+    if constexpr (kStrips) {        // the input-gradient chain over a strip list (need.hip), and the plain forward over a kept one
         if (!a.tile_list || !a.n_active) { st3d::set_error("wino43: 16-pixel tile columns come with a strip list and its count"); return ST3D_E_INVALID; }
         if (((uintptr_t)a.tile_list & 15) != 0) { st3d::set_error("wino43: a strip list is 16-byte aligned"); return ST3D_E_INVALID; }
-        if (a.yp || a.bias || a.relu) { st3d::set_error("wino43: strip lists are for the input-gradient chain"); return ST3D_E_INVALID; }
+        // (bias and ReLU are runtime arguments of the plain instantiation: st3d_wino43_fwd_strips alone brings them; the fused
+        //  pool is another epilogue, which STRIPS does not have)
+        if (a.yp) { st3d::set_error("wino43: strip lists leave through the plain epilogue, not the fused pool"); return ST3D_E_INVALID; }
+        if ((a.bias || a.relu) && !(strip_fwd && MODE == 0 && !a.gate)) { st3d::set_error("wino43: strip lists are for the input-gradient chain"); return ST3D_E_INVALID; }
         if (a.gate && a.addt) {
             if (MODE != 0) { st3d::set_error("wino43: the content-target term rides on ungated input (MODE 0) only"); return ST3D_E_INVALID; }
             return go(wino43_kernel<0, 0, 2, TC, true, true>);
@@ -756,7 +759,7 @@ int launch_wino43_tc(Wino43Args a, hipStream_t s) {
 // cols: the caller's choice of geometry (listed launches: the lists number the tiles of one geometry) -- 64 or 32 pixels
 // across where the map allows it, 16 = strips (any map the kernel covers: an image's strips fill whole steps), 0 = tc43's
 template <int MODE>
-int launch_wino43(Wino43Args a, hipStream_t s, int cols = 0) {
+int launch_wino43(Wino43Args a, hipStream_t s, int cols = 0, bool strip_fwd = false) {
     const int native = tc43(a.H, a.W);
     if (cols != 0 && !((cols == 64 && native == 16) || (cols == 32 && a.H > 0 && a.W > 0 && (a.H % 8) == 0 && (a.W % 32) == 0) ||
                        (cols == 16 && native != 0))) {
@@ -764,7 +767,7 @@ int launch_wino43(Wino43Args a, hipStream_t s, int cols = 0) {
         return ST3D_E_INVALID;
     }
     const int tc = cols ? cols / 4 : native;
-    if (tc == 4) return launch_wino43_tc<MODE, 4>(a, s);
+    if (tc == 4) return launch_wino43_tc<MODE, 4>(a, s, strip_fwd);
     return tc == 16 ? launch_wino43_tc<MODE, 16>(a, s) : launch_wino43_tc<MODE, 8>(a, s);
 }
 
@@ -823,6 +826,20 @@ extern "C" int st3d_wino43_fwd_tiles_geo(const float *x, const float *u_fwd, con
     a.tile_list = tile_list;
     a.n_active = n_active;
     return launch_wino43<0>(a, st3d::as_stream(stream), tile_cols);
+}
+
+// the forward over a strip list (need.hip, st3d_kept_build with tile_cols = 16): strip_list holds four strips of 4 x 16 pixels
+// of one image per step (or -1), n_steps counts steps; every block of a listed strip gets bitwise what st3d_wino43_fwd gives
+// it, bias and ReLU included, and nothing else is written.  No fused pool: y only.
+extern "C" int st3d_wino43_fwd_strips(const float *x, const float *u_fwd, const float *bias, float *y, int N, int Cin, int Cout,
+                                      int H, int W, int relu, const int *strip_list, const int *n_steps, st3d_stream_t stream) {
+    ST3D_CHECK_ARG(x && u_fwd && y && strip_list && n_steps);
+    ST3D_CHECK_ARG(N > 0 && shape_ok43(Cin, Cout, H, W));
+    ST3D_CHECK_ARG(((uintptr_t)u_fwd & 15) == 0);
+    Wino43Args a{x, nullptr, u_fwd, bias, y, nullptr, nullptr, N, Cin, Cout, H, W, relu, 0, 0, 0, nullptr, nullptr, 0.f};
+    a.tile_list = strip_list;
+    a.n_active = n_steps;
+    return launch_wino43<0>(a, st3d::as_stream(stream), 16, true);
 }
 
 // gy: gradient w.r.t. the conv's output, ALREADY gated by its producer (or, with pool_idx, the pooled-resolution gradient

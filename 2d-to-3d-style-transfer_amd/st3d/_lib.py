@@ -193,6 +193,10 @@ SIGNATURES = {
                                                   c_int, c_int, c_int, c_i32p, c_i32p, c_stream]),
     "st3d_wino43_fwd_tiles_geo": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_i32p, c_i32p, c_stream]),
+    "st3d_wino43_fwd_strips": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, c_int, c_i32p, c_i32p,
+                                       c_stream]),
+    "st3d_kept_build": (c_int, [c_u8p, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.c_void_p, c_size,
+                                ctypes.POINTER(ctypes.c_void_p), c_i32p, c_stream]),
     "st3d_maxpool2x2_fwd": (c_int, [c_f32p, c_f32p, c_u8p, c_int, c_int, c_int, c_int, c_stream]),
     "st3d_gram_workspace_bytes": (c_size, [c_int, c_int, c_int]),
     "st3d_gram_fwd": (c_int, [c_f32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_f32p, c_stream]),

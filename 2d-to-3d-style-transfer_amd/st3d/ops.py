@@ -1293,6 +1293,34 @@ def wino43_fwd_tiles(x, uf, bias, Cout, tile_list, n_active, y=None, yp=None, id
          dptr(idx, U8), N, Cin, Cout, H, W, 1 if relu else 0, dptr(tile_list, I32), dptr(n_active, I32), stream_ptr())
 
 
+def wino43_fwd_strips(x, uf, bias, Cout, strip_list, n_steps, y, relu=True):
+    """wino43_fwd over the first n_steps (device int32 scalar) steps of strip_list (device int32, four strips of 4 x 16 pixels
+    of one image per step, -1 = none), written into y (N,Cout,H,W) in place; nothing else is written (st3d_wino43_fwd_strips)."""
+    N, Cin, H, W = x.shape
+    assert tuple(y.shape) == (N, Cout, H, W)
+    call("st3d_wino43_fwd_strips", dptr(x.contiguous(), F32), dptr(uf, F32), dptr(bias, F32), dptr(y, F32), N, Cin, Cout, H, W,
+         1 if relu else 0, dptr(strip_list, I32), dptr(n_steps, I32), stream_ptr())
+    return y
+
+
+def kept_build(cover, first=0, nlists=None, tile_cols=None):
+    """cover (N,S,S) uint8 -> {k: (list, count)} for k = first .. nlists - 1: the kept lists of the forward launches conv1_2 ..
+    conv3_3 (st3d_kept_build), in the formats of need_blocks_build.  Lists are sized for every tile (strip) and start as -1."""
+    lib = _lib.load()
+    N, S, _ = cover.shape
+    nlists = need_blocks_lists(S) if nlists is None else nlists
+    counts = torch.full((6,), -7, dtype=I32, device=cover.device)       # (ST3D_NEED_MAX_LISTS)
+    tcols = [int(c or 0) for c in (tile_cols or [0] * nlists)]
+    lists = {k: torch.full((lib.st3d_need_blocks_entries(N, S, k, tcols[k]),), -1, dtype=I32, device=cover.device)
+             for k in range(first, nlists)}
+    nb = lib.st3d_need_blocks_workspace_bytes(N, S)
+    ws = torch.empty((max(nb, 1),), dtype=U8, device=cover.device)
+    cols = (ctypes.c_int * max(nlists, 1))(*tcols)
+    ptrs = (ctypes.c_void_p * max(nlists, 1))(*[lists[k].data_ptr() if k in lists else None for k in range(nlists)])
+    call("st3d_kept_build", dptr(cover, U8), N, S, int(first), nlists, cols, dptr(ws), nb, ptrs, dptr(counts), stream_ptr())
+    return {k: (lists[k], counts[k]) for k in lists}
+
+
 def flat_levels(S):
     return _lib.load().st3d_flat_levels(int(S))
 

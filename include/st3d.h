@@ -511,6 +511,20 @@ int st3d_wino43_dgrad_chain_tiles_geo(const float *gy, const uint8_t *pool_idx, 
 int st3d_wino43_fwd_tiles_geo(const float *x, const float *u_fwd, const float *bias, float *y, float *y_pooled, uint8_t *pool_idx,
                               int N, int Cin, int Cout, int H, int W, int relu, int tile_cols, const int *tile_list,
                               const int *n_active, st3d_stream_t stream);
+/* The plain forward over a strip list: strip_list as tile_list with tile_cols = 16 above, *n_steps counts steps.  bias (may be
+ * NULL) and relu as st3d_wino43_fwd; every block of a listed strip of y is bitwise st3d_wino43_fwd's, nothing else is written.
+ * There is no fused pool over strips (st3d_wino43_fwd_tiles_geo refuses tile_cols = 16 with y_pooled, and with bias or relu). */
+int st3d_wino43_fwd_strips(const float *x, const float *u_fwd, const float *bias, float *y, int N, int Cin, int Cout, int H,
+                           int W, int relu, const int *strip_list, const int *n_steps, st3d_stream_t stream);
+/* Kept lists (csrc/need.hip): which output blocks of the forward launches conv1_2 .. conv3_3 (lists 0 .. 5, the maps of
+ * st3d_need_blocks_build) can differ between two calls whose images differ only where cover (N,S,S bytes, 16-byte aligned) is
+ * non-zero.  conv1_1 is per pixel and an F(4x4,3x3) launch per aligned 4x4 block, so K_0 = block4(dilate(cover, 2)) and
+ * K_k+1 = block4(dilate(K_k, 1)), through the 2x2 OR behind a fused pool.  Lists first .. nlists - 1 are made, each holding the
+ * tiles (tile_cols[k] = 64 / 32 / 0) or strips (16) with a block of K_k, in the formats, sizes and alignment of
+ * st3d_need_blocks_build; lists: HOST array of nlists device pointers (entries below first are not read), counts[k] the count
+ * of list k.  workspace: st3d_need_blocks_workspace_bytes(N, S).  Two launches, no atomics. */
+int st3d_kept_build(const uint8_t *cover, int N, int S, int first, int nlists, const int *tile_cols, void *workspace,
+                    size_t workspace_bytes, int *const *lists, int *counts, st3d_stream_t stream);
 /* st3d_wino43_fwd over the first *n_active entries of tile_list only (as above): y, y_pooled and pool_idx of a listed tile
  * are bitwise what st3d_wino43_fwd writes, nothing else is written. */
 int st3d_wino43_fwd_tiles(const float *x, const float *u_fwd, const float *bias, float *y, float *y_pooled, uint8_t *pool_idx,
@@ -971,7 +985,17 @@ int st3d_plan_loss_flat(st3d_plan *plan, const float *current, int n, int batch_
  *     (st3d_plan_forward, st3d_plan_set_content, st3d_plan_set_style, any other st3d_plan_loss* call, a failed call,
  *     st3d_vgg_set_conv) makes the next keyed call fill again;
  *   - under the same condition runs conv1_1 over the tiles that see a covered pixel only (st3d_conv3x3_fwd_skip;
- *     ST3D_FLAT_CONV1=0, read by st3d_plan_create: the full launch).
+ *     ST3D_FLAT_CONV1=0, read by st3d_plan_create: the full launch);
+ *   - under the same condition runs conv3_1, conv3_2 and conv3_3 over their kept lists (st3d_kept_build, built by the first
+ *     such call of an epoch; st3d_wino43_fwd_strips): a tile the coverage cannot reach still holds the bits the previous call
+ *     wrote, which the same launch on the same input would write again.  The first call of an epoch, and the first after any
+ *     of the writers above, runs them in full.  Only where the full launch walks two tiles or more per workgroup.
+ *     ST3D_KEEP_DEPTH = 0..3 (read by st3d_plan_create) lists fewer of them, bottom-up, 0 none; ST3D_KEEP_TILE = 64 | 32 | 16
+ *     (or one value per launch, comma-separated): the geometry, default 16 = strips; ST3D_KEEP_FORCE=1 lifts the two-tiles
+ *     rule (tests).
+ *     In the same calls conv1_2, conv2_1 and conv2_2 walk their kept lists too instead of their flat-field lists, which have to
+ *     name one tile per border class for the fills and are tied to the kernel's own geometry: ST3D_KEEP_SHALLOW = a,b,c, the
+ *     geometry of each (64 | 32, 16 for conv2_1 only, 0 = the flat-field list as before; default 32,16,32).
  * Every activation, the losses and the gradient are bitwise st3d_plan_loss_flat's.  epoch == 0, cover == NULL or graph
  * replay on: st3d_plan_loss_flat itself, launch for launch.  ST3D_FLAT_CHECK=1 (read by st3d_plan_create): every keyed call
  * tests the promise about the uncovered pixels (st3d_flat_check_cover, one host read) and fails with ST3D_E_STATE if it

@@ -170,6 +170,10 @@ struct GraphKey {               // what a captured loss step has baked in
     }
 };
 
+// ST3D_SPLIT_BATCH when the environment does not set it: st3d_plan::SPLIT_FWD, the forward alone (measured, DESIGN.md 6: the
+// backward's share cannot be told from the spread between boxes)
+#define ST3D_SPLIT_BATCH_DEFAULT 1
+
 struct st3d_plan {
     st3d_vgg *vgg = nullptr;
     int B = 0, S = 0;
@@ -256,7 +260,20 @@ struct st3d_plan {
     // views at 512^2 (st3d_need_blocks_entries, st3d_need_blocks_gram_runs, st3d_flat_tiles) next to the plan's 4.4 GB, so
     // three epochs stay: what a run that alternates two or three view batches needs.
     static constexpr int kEpochSlots = 3;
+    // One group's lists of a split call (below): the existing builders on the group's slice of the coverage, so tiles and strips
+    // count images from the group's first.  flat_*: the flat-field lists, walked without fills by the shallow levels that
+    // have no kept list (they name their representatives within the group; every tile they leave out holds the fill of
+    // the epoch's first call, which is what its own launch would write).
+    struct GroupLists {
+        uint8_t *need_seg = nullptr;
+        int *need_list[ST3D_NEED_MAX_LISTS] = {}, *need_cnt = nullptr;
+        int *need_gram_list = nullptr, *need_gram_cnt = nullptr;
+        int *kept_list[ST3D_NEED_MAX_LISTS] = {}, *kept_cnt = nullptr;
+        int *flat_list[3] = {}, *flat_map[3] = {}, *flat_cnt = nullptr;
+    };
     struct ListSet {
+        GroupLists grp[2];                              // (keyed sets, split plans)
+        bool have_grp_fwd = false, have_grp_need = false;       // built by the epoch's first split call, per direction
         uint8_t *need_seg = nullptr;
         int *need_list[ST3D_NEED_MAX_LISTS] = {}, *need_cnt = nullptr;
         int *need_gram_list = nullptr, *need_gram_cnt = nullptr;
@@ -287,6 +304,27 @@ struct st3d_plan {
     st3d::CleanRecord clean;
     bool conv1_skip = false;        // conv1_1 of a clean keyed call runs over its covered tiles only (ST3D_FLAT_CONV1=0: in full)
     bool flat_check = false;        // ST3D_FLAT_CHECK=1 (read by st3d_plan_create): keyed calls test their premise on the pixels
+    // The split batch (ST3D_SPLIT_BATCH, read by st3d_plan_create): a keyed call that finds the clean record its
+    // own runs its n images as two groups of n / 2: the first on the caller's stream, the second on a stream of the plan's.
+    // Image i at layer L + 1 reads only image i at layer L, in both directions, so one group's launch can fill the CUs that
+    // the other group's launch has left while its last workgroups finish.  The plan's stream is forked from the caller's by
+    // an event and joined back by an event before the call returns; the Grams and the loss sums run over the whole batch
+    // between the two forks.  (Both groups on streams of the plan's was measured too and loses: each cross-queue dependency
+    // leaves the chip idle for 20 - 29 us, and that way there are four per step with nothing running under them; this way
+    // the first group's chain starts on the previous launch's end stamp and only the two joins wait.)  A group's slices:
+    // images [i0, i0 + n / 2) of act[], pidx[], D[], the targets and the caller's gradient; one fixed half of each gbuf[]
+    // (the groups are at different layers at the same time, so a slice by the layer's own image size would overlap).
+    // Every launch is per image, tile or block and takes its reduction order from the layer, not from N, so each image
+    // gets the bits of the one-stream call (the listed launches by the premise of their lists).
+    enum { SPLIT_FWD = 1, SPLIT_BWD = 2 };
+    int split_mode = 0;
+    hipStream_t gstream = nullptr;
+    hipEvent_t ev_fork[2] = {}, ev_join[2] = {};    // [forward / backward]
+    int split_calls[2] = {};        // calls whose forward / backward ran split (st3d_plan_split_calls)
+    // the two-rounds rule with a group's count: which kept lists a group walks, how many need levels it lists
+    bool grp_kept_on[ST3D_NEED_MAX_LISTS] = {};
+    int grp_need_levels = 0;
+    bool grp_need_gram = false;
     // guidance of the style term (st3d_plan_set_style_guidance; guide.hip): the q planes of the five taps for guide_n
     // images (0 = off), and w_0 = q_0^2 for the fused bottom pass.  Allocated by the first call that sets a guidance (for B
     // images: the pointers never move, so a captured loss step keeps reading them), rebuilt by every such call.
@@ -362,7 +400,116 @@ struct Keyed {
     const float *rgb;           // the colour again, 3 floats in HOST memory (what the clean record compares)
     int flat_done;              // out: how many launches ran listed
     int kept_done;              // out: how many of conv3_1 .. conv3_3 the call leaves whole (in full or over their kept lists)
+    bool clean_call = false;    // out: the call found the clean record its own (no fill ran; what a split call requires)
 };
+// the lists a forward chain walks: the epoch's whole-batch ones, or one group's (split calls)
+struct FwdLists {
+    const uint8_t *c1_skip;
+    int *const *kept_list; const int *kept_cnt;
+    int *const *flat_list, *const *flat_map; const int *flat_cnt;
+    const bool *kept_on;        // (groups) which kept lists the group walks; nullptr = all the plan has
+};
+
+// fork the plan's stream for the second group from s / join it back (split calls)
+// (dir: 0 the forward's events, 1 the backward's)
+hipStream_t split_stream(st3d_plan *p, int g, hipStream_t s) { return g == 0 ? s : p->gstream; }
+int split_fork(st3d_plan *p, int dir, hipStream_t s) {
+    ST3D_HIP(hipEventRecord(p->ev_fork[dir], s));
+    ST3D_HIP(hipStreamWaitEvent(p->gstream, p->ev_fork[dir], 0));
+    return ST3D_OK;
+}
+int split_join(st3d_plan *p, int dir, hipStream_t s) {
+    ST3D_HIP(hipEventRecord(p->ev_join[dir], p->gstream));
+    ST3D_HIP(hipStreamWaitEvent(s, p->ev_join[dir], 0));
+    return ST3D_OK;
+}
+// may this call run as two groups in direction `dir`?  (what the call itself decides -- a clean record, a mask -- is the caller's)
+bool split_ok(const st3d_plan *p, int dir, int n, bool keyed) {
+    return keyed && (p->split_mode & dir) && p->gstream && !p->prof && !p->use_graph && p->guide_n == 0 && n >= 4 && n % 2 == 0;
+}
+
+// the launches of images [i0, i0 + n) from module 0 to upto on stream s; x: the first of those images
+int forward_chain(st3d_plan *p, const float *x, int i0, int n, int upto, bool keep_full, hipStream_t s, int flat, int keep, bool fill,
+                  const FwdLists &L) {
+    const st3d_vgg *v = p->vgg;
+    auto act = [&](int m) { return p->act[m] + (size_t)i0 * p->C[m] * p->H[m] * p->W[m]; };
+    auto pix = [&](int ps) { const int m = kPoolIdx[ps]; return p->pidx[ps] + (size_t)i0 * p->C[m] * p->H[m] * p->W[m]; };
+    auto on = [&](int k) { return !L.kept_on || L.kept_on[k]; };
+    for (int m = 0; m <= upto; ++m) {
+        const int cs = conv_slot(m), ps = pool_slot(m);
+        if (cs >= 0) {
+            if (!v->set[cs]) {
+                st3d::set_error("st3d_plan_forward: weights of module %d were never set", m);
+                return ST3D_E_STATE;
+            }
+            const int Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
+            const uint8_t route = p->route[cs].fwd;
+            if (route == DIRECT && cs == 0 && !fill && L.c1_skip) {     // conv1_1 of a clean keyed call: the covered tiles
+                Scope sc(p, F_CONVX_FWD_FLAT, s, m);
+                ST3D_TRY(st3d_conv3x3_fwd_skip(x, v->wf[cs], v->bias[cs], act(m), n, Cin, Cout, H, W, 1, L.c1_skip, s));
+                x = act(m);
+                continue;
+            }
+            if (route == DIRECT) {
+                Scope sc(p, F_CONVX_FWD, s, m);
+                ST3D_TRY(st3d_conv3x3_fwd(x, v->wf[cs], v->bias[cs], act(m), n, Cin, Cout, H, W, 1, s));
+                x = act(m);
+                continue;
+            }
+            // the Winograd kernels pool in their epilogue: conv, relu and the pool behind them are one launch
+            const int pool_m = m + 2;
+            const int pps = (pool_m <= upto) ? pool_slot(pool_m) : -1;
+            float *yfull = (pps < 0 || keep_full) ? act(m) : nullptr;
+            float *yp = pps >= 0 ? act(pool_m) : nullptr;
+            uint8_t *yi = pps >= 0 ? pix(pps) : nullptr;
+            if (cs >= 1 && cs <= flat && !fill && keep > 0 && p->shallow_cols[cs - 1] && on(cs - 1)) {
+                // a clean keyed call: the kept list in its own geometry; the tiles it leaves out hold the previous call's bits
+                Scope sc(p, F_CONV43_FWD_FLAT, s, m);
+                const int k = cs - 1;
+                if (p->shallow_cols[k] == 16)
+                    ST3D_TRY(st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], yfull, n, Cin, Cout, H, W, 1, L.kept_list[k],
+                                                    L.kept_cnt + k, s));
+                else
+                    ST3D_TRY(st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->shallow_cols[k],
+                                                       L.kept_list[k], L.kept_cnt + k, s));
+            } else if (cs >= 1 && cs <= flat) {    // an F(4x4,3x3) launch over its flat-field list, then the copies
+                {
+                    Scope sc(p, F_CONV43_FWD_FLAT, s, m);
+                    ST3D_TRY(st3d_wino43_fwd_tiles(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, L.flat_list[cs - 1],
+                                                   L.flat_cnt + (cs - 1), s));
+                }
+                if (fill) {
+                    Scope sc(p, F_FLAT_FILL, s, m);
+                    ST3D_TRY(st3d_flat_fill(L.flat_map[cs - 1], yfull, yp, yi, n, Cout, H, W, s));
+                }
+            } else if (!fill && cs > st3d_plan::kKeepFirst && cs <= st3d_plan::kKeepFirst + keep && on(cs - 1)) {
+                // a clean keyed call: the tiles the coverage can change; the others keep the previous call's bits (no pool here)
+                Scope sc(p, F_CONV43_FWD_FLAT, s, m);
+                const int k = cs - 1;
+                if (p->keep_cols[k] == 16)
+                    ST3D_TRY(st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], act(m), n, Cin, Cout, H, W, 1, L.kept_list[k],
+                                                    L.kept_cnt + k, s));
+                else
+                    ST3D_TRY(st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], act(m), nullptr, nullptr, n, Cin, Cout, H, W, 1,
+                                                       p->keep_cols[k], L.kept_list[k], L.kept_cnt + k, s));
+            } else if (route == WINO43) {
+                Scope sc(p, F_CONV43_FWD, s, m);
+                ST3D_TRY(st3d_wino43_fwd(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
+            } else {
+                Scope sc(p, F_CONV_FWD, s, m);
+                ST3D_TRY(st3d_wino_fwd(x, v->uf[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
+            }
+            x = pps >= 0 ? yp : act(m);
+            if (pps >= 0) m = pool_m;               // modules m+1, m+2 are done
+        } else if (ps >= 0) {                       // (the ReLU before it kept its conv's C, H, W)
+            Scope sc(p, F_POOL, s, m);
+            ST3D_TRY(st3d_maxpool2x2_fwd(x, act(m), pix(ps), n, p->C[m], p->H[m - 1], p->W[m - 1], s));
+            x = act(m);
+        }   // ReLU modules are fused into their conv
+    }
+    return ST3D_OK;
+}
+
 int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hipStream_t s, const float *flat_color = nullptr,
             Keyed *key = nullptr) {
     const st3d_vgg *v = p->vgg;
@@ -398,86 +545,45 @@ int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hi
             p->ls->have_flat = true;
         }
     }
-    if (key) { key->flat_done = flat; key->kept_done = keep; }
+    if (key) { key->flat_done = flat; key->kept_done = keep; key->clean_call = !fill; }
     if (!fill && keep > 0 && !p->ls->have_kept) {       // the epoch's first clean call: a run that changes its geometry every step never gets here
         Scope sc(p, F_ELEM, s);
         ST3D_TRY(st3d_kept_build(key->cover, n, p->S, p->keep_first, st3d_plan::kKeepFirst + p->keep_levels, p->keep_cols, p->keep_ws,
                                  p->keep_ws_bytes, p->ls->kept_list, p->ls->kept_cnt, s));
         p->ls->have_kept = true;
     }
-    const float *x = imgs;
-    for (int m = 0; m <= upto; ++m) {
-        const int cs = conv_slot(m), ps = pool_slot(m);
-        if (cs >= 0) {
-            if (!v->set[cs]) {
-                st3d::set_error("st3d_plan_forward: weights of module %d were never set", m);
-                return ST3D_E_STATE;
+    st3d_plan::ListSet *ls = p->ls;
+    if (!fill && upto == 28 && !keep_full && split_ok(p, st3d_plan::SPLIT_FWD, n, key != nullptr)) {
+        // ---- the clean call as two groups: the first on s, the second on the plan's stream
+        const int h = n / 2;
+        if (!ls->have_grp_fwd) {        // the epoch's first split call: the builders once more, on each group's slice of the coverage
+            for (int g = 0; g < 2; ++g) {
+                st3d_plan::GroupLists &G = ls->grp[g];
+                const uint8_t *cover = key->cover + (size_t)g * h * p->S * p->S;
+                ST3D_TRY(st3d_flat_build_cover(cover, h, p->S, flat, p->flat_ws, p->flat_ws_bytes, G.flat_list[0], G.flat_map[0], G.flat_list[1],
+                                               G.flat_map[1], G.flat_list[2], G.flat_map[2], G.flat_cnt, s));
+                if (keep > 0)
+                    ST3D_TRY(st3d_kept_build(cover, h, p->S, p->keep_first, st3d_plan::kKeepFirst + p->keep_levels, p->keep_cols, p->keep_ws,
+                                             p->keep_ws_bytes, G.kept_list, G.kept_cnt, s));
             }
-            const int Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
-            const uint8_t route = p->route[cs].fwd;
-            if (route == DIRECT && cs == 0 && !fill && p->ls->c1_skip) {     // conv1_1 of a clean keyed call: the covered tiles
-                Scope sc(p, F_CONVX_FWD_FLAT, s, m);
-                ST3D_TRY(st3d_conv3x3_fwd_skip(x, v->wf[cs], v->bias[cs], p->act[m], n, Cin, Cout, H, W, 1, p->ls->c1_skip, s));
-                x = p->act[m];
-                continue;
-            }
-            if (route == DIRECT) {
-                Scope sc(p, F_CONVX_FWD, s, m);
-                ST3D_TRY(st3d_conv3x3_fwd(x, v->wf[cs], v->bias[cs], p->act[m], n, Cin, Cout, H, W, 1, s));
-                x = p->act[m];
-                continue;
-            }
-            // the Winograd kernels pool in their epilogue: conv, relu and the pool behind them are one launch
-            const int pool_m = m + 2;
-            const int pps = (pool_m <= upto) ? pool_slot(pool_m) : -1;
-            float *yfull = (pps < 0 || keep_full) ? p->act[m] : nullptr;
-            float *yp = pps >= 0 ? p->act[pool_m] : nullptr;
-            uint8_t *yi = pps >= 0 ? p->pidx[pps] : nullptr;
-            if (cs >= 1 && cs <= flat && !fill && keep > 0 && p->shallow_cols[cs - 1]) {
-                // a clean keyed call: the kept list in its own geometry; the tiles it leaves out hold the previous call's bits
-                Scope sc(p, F_CONV43_FWD_FLAT, s, m);
-                const int k = cs - 1;
-                if (p->shallow_cols[k] == 16)
-                    ST3D_TRY(st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], yfull, n, Cin, Cout, H, W, 1, p->ls->kept_list[k],
-                                                    p->ls->kept_cnt + k, s));
-                else
-                    ST3D_TRY(st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->shallow_cols[k],
-                                                       p->ls->kept_list[k], p->ls->kept_cnt + k, s));
-            } else if (cs >= 1 && cs <= flat) {    // an F(4x4,3x3) launch over its flat-field list, then the copies
-                {
-                    Scope sc(p, F_CONV43_FWD_FLAT, s, m);
-                    ST3D_TRY(st3d_wino43_fwd_tiles(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->ls->flat_list[cs - 1],
-                                                   p->ls->flat_cnt + (cs - 1), s));
-                }
-                if (fill) {
-                    Scope sc(p, F_FLAT_FILL, s, m);
-                    ST3D_TRY(st3d_flat_fill(p->ls->flat_map[cs - 1], yfull, yp, yi, n, Cout, H, W, s));
-                }
-            } else if (!fill && cs > st3d_plan::kKeepFirst && cs <= st3d_plan::kKeepFirst + keep) {
-                // a clean keyed call: the tiles the coverage can change; the others keep the previous call's bits (no pool here)
-                Scope sc(p, F_CONV43_FWD_FLAT, s, m);
-                const int k = cs - 1;
-                if (p->keep_cols[k] == 16)
-                    ST3D_TRY(st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], p->act[m], n, Cin, Cout, H, W, 1, p->ls->kept_list[k],
-                                                    p->ls->kept_cnt + k, s));
-                else
-                    ST3D_TRY(st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], p->act[m], nullptr, nullptr, n, Cin, Cout, H, W, 1,
-                                                       p->keep_cols[k], p->ls->kept_list[k], p->ls->kept_cnt + k, s));
-            } else if (route == WINO43) {
-                Scope sc(p, F_CONV43_FWD, s, m);
-                ST3D_TRY(st3d_wino43_fwd(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
-            } else {
-                Scope sc(p, F_CONV_FWD, s, m);
-                ST3D_TRY(st3d_wino_fwd(x, v->uf[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
-            }
-            x = pps >= 0 ? yp : p->act[m];
-            if (pps >= 0) m = pool_m;               // modules m+1, m+2 are done
-        } else if (ps >= 0) {                       // (the ReLU before it kept its conv's C, H, W)
-            Scope sc(p, F_POOL, s, m);
-            ST3D_TRY(st3d_maxpool2x2_fwd(x, p->act[m], p->pidx[ps], n, p->C[m], p->H[m - 1], p->W[m - 1], s));
-            x = p->act[m];
-        }   // ReLU modules are fused into their conv
+            ls->have_grp_fwd = true;
+        }
+        ST3D_TRY(split_fork(p, 0, s));
+        int rc = ST3D_OK;
+        for (int g = 0; g < 2 && rc == ST3D_OK; ++g) {
+            const st3d_plan::GroupLists &G = ls->grp[g];
+            const FwdLists L{ls->c1_skip ? ls->c1_skip + st3d_conv1_skip_tiles(1, p->S, p->S) * (size_t)g * h : nullptr,
+                             G.kept_list, G.kept_cnt, G.flat_list, G.flat_map, G.flat_cnt, p->grp_kept_on};
+            rc = forward_chain(p, imgs + (size_t)g * h * 3 * p->S * p->S, g * h, h, upto, keep_full, split_stream(p, g, s), flat, keep, fill, L);
+        }
+        const int rj = split_join(p, 0, s);     // (also after a failure: the caller's stream stays behind whatever was enqueued)
+        if (rc != ST3D_OK || rj != ST3D_OK) return rc != ST3D_OK ? rc : rj;
+        ++p->split_calls[0];
+        p->last_n = n;
+        return ST3D_OK;
     }
+    const FwdLists L{fill ? nullptr : ls->c1_skip, ls->kept_list, ls->kept_cnt, ls->flat_list, ls->flat_map, ls->flat_cnt, nullptr};
+    ST3D_TRY(forward_chain(p, imgs, 0, n, upto, keep_full, s, flat, keep, fill, L));
     p->last_n = n;
     return ST3D_OK;
 }
@@ -530,8 +636,9 @@ struct DgradOpts {
 
 // one input-gradient launch of conv slot cs: g (gradient w.r.t. the conv's post-ReLU output, or w.r.t. the output of
 // the pool behind it when pooled) -> dst (gradient w.r.t. the conv's input)
+// (i0: the first image of g and dst in the plan's buffers -- the gates, pooled values and argmax are read from there on)
 int dgrad_step(st3d_plan *p, int cs, const float *g, bool g_is_pooled, int pool_of_g, float *dst, int n, hipStream_t s,
-               const DgradOpts &o = {}) {
+               const DgradOpts &o = {}, int i0 = 0) {
     const st3d_vgg *v = p->vgg;
     const int m = kConvIdx[cs];
     const int Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
@@ -542,24 +649,26 @@ int dgrad_step(st3d_plan *p, int cs, const float *g, bool g_is_pooled, int pool_
         return ST3D_E_STATE;
     }
     Scope sc(p, o.tile_list ? F_CONV43_DGRAD_NEED : w43 ? F_CONV43_DGRAD : (wino ? F_CONV_DGRAD : F_CONVX_DGRAD), s, m);
-    const uint8_t *pidx = g_is_pooled ? p->pidx[pool_of_g] : nullptr;
-    const float *pooled = g_is_pooled ? p->act[kPoolIdx[pool_of_g]] : nullptr;
+    auto img = [&](int mm) { return (size_t)i0 * p->C[mm] * p->H[mm] * p->W[mm]; };
+    const uint8_t *pidx = g_is_pooled ? p->pidx[pool_of_g] + img(kPoolIdx[pool_of_g]) : nullptr;
+    const float *pooled = g_is_pooled ? p->act[kPoolIdx[pool_of_g]] + img(kPoolIdx[pool_of_g]) : nullptr;
+    const float *act_m = p->act[m] + img(m);
     if (o.tile_list)
         ST3D_TRY(st3d_wino43_dgrad_chain_tiles_geo(g, pidx, v->u6d[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W,
                                                    o.tile_cols, o.tile_list, o.n_active, s));
     else if (w43)
         ST3D_TRY(st3d_wino43_dgrad_chain(g, pidx, v->u6d[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W, s));
     else if (wino && (o.pregated || o.out_gate))
-        ST3D_TRY(st3d_wino_dgrad_chain(g, (g_is_pooled || o.pregated) ? nullptr : p->act[m], pidx, o.pregated ? nullptr : pooled,
+        ST3D_TRY(st3d_wino_dgrad_chain(g, (g_is_pooled || o.pregated) ? nullptr : act_m, pidx, o.pregated ? nullptr : pooled,
                                        v->ud[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W, s));
     else if (g_is_pooled && wino)
         ST3D_TRY(st3d_wino_dgrad_unpool(g, pidx, pooled, v->ud[cs], dst, n, Cin, Cout, H, W, s));
     else if (g_is_pooled)
         ST3D_TRY(st3d_conv3x3_dgrad_unpool(g, pidx, pooled, v->wd[cs], dst, n, Cin, Cout, H, W, s));
     else if (wino)
-        ST3D_TRY(st3d_wino_dgrad(g, p->act[m], v->ud[cs], dst, n, Cin, Cout, H, W, s));
+        ST3D_TRY(st3d_wino_dgrad(g, act_m, v->ud[cs], dst, n, Cin, Cout, H, W, s));
     else
-        ST3D_TRY(st3d_conv3x3_dgrad(g, p->act[m], v->wd[cs], dst, n, Cin, Cout, H, W, s));
+        ST3D_TRY(st3d_conv3x3_dgrad(g, act_m, v->wd[cs], dst, n, Cin, Cout, H, W, s));
     return ST3D_OK;
 }
 
@@ -779,6 +888,65 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
             }
         }
     }
+    {
+        // ST3D_SPLIT_BATCH = 0 | 1 | fwd | bwd: clean keyed calls as two groups, the second on a stream of the plan's, in both directions or one
+        // (measured default: DESIGN.md 6).  The two-rounds rule once more with a group's count: a list that leaves a group's
+        // launch under two tiles per workgroup is not walked by the groups (the launch runs in full, or over its flat-field
+        // list), and the need levels stop below the first such launch.
+        const char *sb = getenv("ST3D_SPLIT_BATCH");
+        if (sb && sb[0]) p->split_mode = strcmp(sb, "fwd") == 0 ? st3d_plan::SPLIT_FWD : strcmp(sb, "bwd") == 0 ? st3d_plan::SPLIT_BWD :
+                                         sb[0] == '1' ? (st3d_plan::SPLIT_FWD | st3d_plan::SPLIT_BWD) : 0;
+        else p->split_mode = ST3D_SPLIT_BATCH_DEFAULT;
+        if (B < 4 || p->flat_levels < 1) p->split_mode = 0;
+        int cus = 0, dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        const int hb = B / 2;
+        auto rounds = [&](int cs, int channels) {       // a group's launch of conv slot cs walks two tiles per workgroup
+            const int R = p->H[kConvIdx[cs]];
+            return (long)hb * (R / 4) * (R / 4) / 16 >= 2L * (cus / std::max(1, channels / 64));
+        };
+        const bool keep_force = flag("ST3D_KEEP_FORCE", false), need_force = flag("ST3D_NEED_FORCE", false);
+        for (int k = 0; k < ST3D_NEED_MAX_LISTS; ++k) {
+            const bool walked = k < 3 ? p->shallow_cols[k] != 0 : k - st3d_plan::kKeepFirst < p->keep_levels;
+            p->grp_kept_on[k] = walked && (keep_force || rounds(k + 1, kConvCout[k + 1]));
+        }
+        p->grp_need_levels = p->need_levels;
+        for (int cs = 3; cs <= ST3D_NEED_MAX_LISTS && cs + 1 <= p->grp_need_levels; ++cs)
+            if (!need_force && !rounds(cs, kConvCin[cs])) p->grp_need_levels = cs;
+        const int m2 = kConvIdx[2];
+        p->grp_need_gram = p->need_gram && (need_force || (long)hb * (p->H[m2] * p->W[m2] / 64) >= 2L * 4 * cus);
+    }
+    if (p->split_mode && rc == ST3D_OK) {
+        const int hb = B / 2;
+        bool ok = true;
+        ok = hipStreamCreateWithFlags(&p->gstream, hipStreamNonBlocking) == hipSuccess;
+        for (int d = 0; d < 2; ++d)
+            ok = ok && hipEventCreateWithFlags(&p->ev_fork[d], hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&p->ev_join[d], hipEventDisableTiming) == hipSuccess;
+        if (!ok) { st3d::set_error("st3d_plan_create: the split batch's stream and events could not be made"); rc = ST3D_E_HIP; }
+        for (int i = 1; i <= st3d_plan::kEpochSlots; ++i)
+            for (st3d_plan::GroupLists &G : p->sets[i].grp) {
+                alloc(&G.flat_cnt, (size_t)4);
+                for (int k = 0; k < p->flat_levels; ++k) {
+                    alloc(&G.flat_list[k], (size_t)st3d_flat_tiles(hb, S, k));
+                    alloc(&G.flat_map[k], (size_t)st3d_flat_tiles(hb, S, k));
+                }
+                if (p->keep_levels >= 1) {
+                    alloc(&G.kept_cnt, (size_t)ST3D_NEED_MAX_LISTS);
+                    for (int k = p->keep_first; k < st3d_plan::kKeepFirst + p->keep_levels; ++k)
+                        alloc(&G.kept_list[k], st3d_need_blocks_entries(hb, S, k, p->keep_cols[k]));
+                }
+                if (p->need_levels >= 1 && p->need_blocks) {
+                    alloc(&G.need_seg, (size_t)hb * S * (S / 64));
+                    alloc(&G.need_cnt, (size_t)ST3D_NEED_MAX_LISTS);
+                    if (p->need_gram) {
+                        alloc(&G.need_gram_list, st3d_need_blocks_gram_runs(hb, S));
+                        alloc(&G.need_gram_cnt, (size_t)1);
+                    }
+                    for (int l = 0; l + 2 <= p->need_levels; ++l) alloc(&G.need_list[l], st3d_need_blocks_entries(hb, S, l, p->need_cols[l]));
+                }
+            }
+    }
     p->flat_check = flag("ST3D_FLAT_CHECK", false);
     p->conv1_skip = p->flat_levels >= 1 && p->route[0].fwd == DIRECT && flag("ST3D_FLAT_CONV1", true);
     if (p->conv1_skip)
@@ -793,6 +961,11 @@ extern "C" int st3d_plan_destroy(st3d_plan *p) {
     for (void *b : p->owned) (void)hipFree(b);
     if (p->gexec) (void)hipGraphExecDestroy(p->gexec);
     if (p->cap_stream) (void)hipStreamDestroy(p->cap_stream);
+    if (p->gstream) (void)hipStreamDestroy(p->gstream);
+    for (int d = 0; d < 2; ++d) {
+        if (p->ev_fork[d]) (void)hipEventDestroy(p->ev_fork[d]);
+        if (p->ev_join[d]) (void)hipEventDestroy(p->ev_join[d]);
+    }
     for (auto &e : p->evs) { (void)hipEventDestroy(e.a); (void)hipEventDestroy(e.b); }
     for (auto &e : p->pool) (void)hipEventDestroy(e);
     delete p;
@@ -1023,7 +1196,7 @@ extern "C" int st3d_plan_loss_keyed(st3d_plan *p, const float *current, int n, i
     bool fresh = false;
     const int slot = p->epochs.take(epoch, n, &fresh);
     st3d_plan::ListSet *ls = &p->sets[1 + slot];
-    if (fresh) ls->have_need = ls->have_flat = ls->have_kept = false;
+    if (fresh) ls->have_need = ls->have_flat = ls->have_kept = ls->have_grp_fwd = ls->have_grp_need = false;
     Keyed key{epoch, cover, flat_rgb, 0, 0};
     p->ls = ls;
     p->clean = held;            // what forward() compares this call with, and clears
@@ -1036,6 +1209,119 @@ extern "C" int st3d_plan_loss_keyed(st3d_plan *p, const float *current, int n, i
         return rc;
     }
     if (key.flat_done > 0) p->clean.set(epoch, n, key.flat_done, flat_rgb, p->vgg->sets, key.kept_done);
+    return ST3D_OK;
+}
+
+// The backward of the loss step for images [i0, i0 + n) of the last forward: the whole batch, or one group of a split call.
+struct BwdArgs {
+    int n, i0, batch_denom;
+    float content_weight;
+    const float *style_coef;            // (host, 5)
+    float *grad;                        // the caller's gradient, from image i0 on
+    const uint8_t *need_mask;           // likewise (NULL: no lists)
+    int need;                           // levels listed
+    bool need_gram;
+    const uint8_t *need_seg;
+    int *const *need_list; const int *need_cnt, *need_gram_list, *need_gram_cnt;     // numbered from image i0
+    float *g0, *g1;                     // the two gradient buffers of this chain and the bytes of each
+    size_t gbytes;
+};
+static int backward_chain(st3d_plan *p, const BwdArgs &b, hipStream_t s) {
+    const int n = b.n, need = b.need;
+    const bool guided = p->guide_n != 0;
+    const int mc = kContentTap;
+    const size_t chw = (size_t)p->C[mc] * p->H[mc] * p->W[mc];
+    auto act = [&](int m) { return p->act[m] + (size_t)b.i0 * p->C[m] * p->H[m] * p->W[m]; };
+    auto Dof = [&](int st) { const int m = kStyleTap[st]; return p->D[st] + (size_t)b.i0 * p->C[m] * p->C[m]; };
+    const float *content_target = p->content_target + (size_t)b.i0 * chw;
+    const float *style_coef = b.style_coef;
+    float *grad_current = b.grad;
+    const uint8_t *need_mask = b.need_mask;
+
+    // ---- backward: gradient w.r.t. the post-ReLU output of each conv, top down
+    float *g = b.g0, *gn = b.g1;
+    bool have_g = false, g_is_pooled = false, g_gated = false, content_done = false;
+    int pool_of_g = -1;
+    const float cc = (float)(2.0 * (double)b.content_weight / ((double)b.batch_denom * (double)chw));       // d content / d conv4_2 = cc * (F - target)
+    for (int cs = 12; cs >= 0; --cs) {          // conv slots 12 (module 28) .. 0
+        const int m = kConvIdx[cs];
+        const int C = p->C[m], H = p->H[m], W = p->W[m];
+        int st = -1;
+        for (int i = 0; i < 5; ++i)
+            if (kStyleTap[i] == m) st = i;
+        const Route &r = p->route[cs];
+        if (cs == 0 && (st >= 0 || have_g) && p->fused_tap0) {       // relu1_1 and conv1_1 in one pass (tap0.hip)
+            Scope sc(p, need >= 1 ? F_CONVX_DGRAD_NEED : F_CONVX_DGRAD, s, m);
+            if (guided && st >= 0)
+                ST3D_TRY(st3d_conv1_bwd_weighted(have_g ? g : nullptr, act(m), Dof(st), style_coef[st], p->vgg->wd[0], gn,
+                                                 b.gbytes, grad_current, n, H, W, p->guide_w0,
+                                                 need >= 1 ? b.need_seg : nullptr, need >= 1 ? need_mask : nullptr, s));
+            else if (need >= 1)
+                ST3D_TRY(st3d_conv1_bwd_masked(have_g ? g : nullptr, act(m), st >= 0 ? Dof(st) : nullptr,
+                                               st >= 0 ? style_coef[st] : 0.f, p->vgg->wd[0], gn, b.gbytes,
+                                               grad_current, n, H, W, b.need_seg, need_mask, s));
+            else
+            ST3D_TRY(st3d_conv1_bwd(have_g ? g : nullptr, act(m), st >= 0 ? Dof(st) : nullptr, st >= 0 ? style_coef[st] : 0.f,
+                                    p->vgg->wd[0], gn, b.gbytes, grad_current, n, H, W, s));
+            break;
+        }
+        const bool chain = r.gate_taps && !g_is_pooled;
+        if (st >= 0 && cs == 2 && need >= 3 && b.need_gram && chain) {        // relu2_1 over the runs conv2_1's input gradient reads
+            Scope sc(p, F_GRAM_BWD_NEED, s, m);
+            ST3D_TRY(st3d_gram_bwd_gated_segs(Dof(st), act(m), guided ? p->guide_plane(st) : nullptr, n, C, H * W, style_coef[st],
+                                              have_g ? 1 : 0, b.need_gram_list, b.need_gram_cnt, g, s));
+            g_gated = true;
+            have_g = true;
+        } else if (st >= 0) {
+            Scope sc(p, F_GRAM_BWD, s, m);
+            if (guided) {
+                ST3D_TRY(st3d_gram_bwd_weighted(Dof(st), act(m), p->guide_plane(st), n, C, H * W, style_coef[st], have_g ? 1 : 0,
+                                                chain ? 1 : 0, g, s));
+                g_gated = chain;
+            } else if (chain) {
+                ST3D_TRY(st3d_gram_bwd_gated(Dof(st), act(m), n, C, H * W, style_coef[st], have_g ? 1 : 0, g, s));
+                g_gated = true;
+            } else {
+                ST3D_TRY(st3d_gram_bwd(Dof(st), act(m), n, C, H * W, style_coef[st], have_g ? 1 : 0, g, s));
+                g_gated = false;
+            }
+            have_g = true;
+        }
+        if (m == kContentTap && !content_done) {
+            Scope sc(p, F_ELEM, s);
+            if (chain) {
+                ST3D_TRY(st3d_axpy_diff_gated(act(m), content_target, (size_t)n * C * H * W, cc, have_g ? 1 : 0, g, s));
+                g_gated = true;
+            } else {
+                ST3D_TRY(st3d_axpy_diff(act(m), content_target, (size_t)n * C * H * W, cc, have_g ? 1 : 0, g, s));
+                g_gated = false;
+            }
+            have_g = true;
+        }
+        if (!have_g) continue;
+        float *dst = (cs == 0) ? grad_current : gn;
+        DgradOpts o;
+        o.pregated = g_gated;
+        // the tensor dst is the gradient of = this conv's forward input (previous post-ReLU output, or the pool's output)
+        if (r.gate_dst) o.out_gate = act(pool_slot(m - 1) >= 0 ? m - 1 : m - 2);
+        if (o.out_gate && m - 2 == kContentTap) {       // dst is the gradient of the content tap: its own term joins in this launch's store
+            o.add_target = content_target;
+            o.add_coef = cc;
+            content_done = true;
+        }
+        if (cs >= 1 && cs <= ST3D_NEED_MAX_LISTS && need >= cs + 1) {   // conv1_2 .. conv3_3 over their need lists
+            o.tile_list = b.need_list[cs - 1];
+            o.n_active = b.need_cnt + (cs - 1);
+            o.tile_cols = p->need_cols[cs - 1];
+        }
+        ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, o, b.i0));
+        g_gated = o.out_gate != nullptr;
+        // dst is the gradient w.r.t. this conv's input: either the previous conv's post-ReLU
+        // output or a pool output (then the next dgrad fuses the unpool)
+        g_is_pooled = (m > 0) && pool_slot(m - 1) >= 0;
+        pool_of_g = g_is_pooled ? pool_slot(m - 1) : -1;
+        float *t = g; g = gn; gn = t;
+    }
     return ST3D_OK;
 }
 
@@ -1093,92 +1379,47 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
                                      p->ls->need_list[1], p->ls->need_cnt, s));
         if (key) p->ls->have_need = true;
     }
-
-    // ---- backward: gradient w.r.t. the post-ReLU output of each conv, top down
-    float *g = p->gbuf[0], *gn = p->gbuf[1];
-    bool have_g = false, g_is_pooled = false, g_gated = false, content_done = false;
-    int pool_of_g = -1;
-    const float cc = (float)(2.0 * (double)content_weight / (bd * (double)chw));       // d content / d conv4_2 = cc * (F - target)
-    for (int cs = 12; cs >= 0; --cs) {          // conv slots 12 (module 28) .. 0
-        const int m = kConvIdx[cs];
-        const int C = p->C[m], H = p->H[m], W = p->W[m];
-        int st = -1;
-        for (int i = 0; i < 5; ++i)
-            if (kStyleTap[i] == m) st = i;
-        const Route &r = p->route[cs];
-        if (cs == 0 && (st >= 0 || have_g) && p->fused_tap0) {       // relu1_1 and conv1_1 in one pass (tap0.hip)
-            Scope sc(p, need >= 1 ? F_CONVX_DGRAD_NEED : F_CONVX_DGRAD, s, m);
-            if (guided && st >= 0)
-                ST3D_TRY(st3d_conv1_bwd_weighted(have_g ? g : nullptr, p->act[m], p->D[st], style_coef[st], p->vgg->wd[0], gn,
-                                                 p->gbuf_floats * sizeof(float), grad_current, n, H, W, p->guide_w0,
-                                                 need >= 1 ? p->ls->need_seg : nullptr, need >= 1 ? need_mask : nullptr, s));
-            else if (need >= 1)
-                ST3D_TRY(st3d_conv1_bwd_masked(have_g ? g : nullptr, p->act[m], st >= 0 ? p->D[st] : nullptr,
-                                               st >= 0 ? style_coef[st] : 0.f, p->vgg->wd[0], gn, p->gbuf_floats * sizeof(float),
-                                               grad_current, n, H, W, p->ls->need_seg, need_mask, s));
-            else
-            ST3D_TRY(st3d_conv1_bwd(have_g ? g : nullptr, p->act[m], st >= 0 ? p->D[st] : nullptr, st >= 0 ? style_coef[st] : 0.f,
-                                    p->vgg->wd[0], gn, p->gbuf_floats * sizeof(float), grad_current, n, H, W, s));
-            break;
-        }
-        const bool chain = r.gate_taps && !g_is_pooled;
-        if (st >= 0 && cs == 2 && need >= 3 && p->need_gram && chain) {        // relu2_1 over the runs conv2_1's input gradient reads
-            Scope sc(p, F_GRAM_BWD_NEED, s, m);
-            ST3D_TRY(st3d_gram_bwd_gated_segs(p->D[st], p->act[m], guided ? p->guide_plane(st) : nullptr, n, C, H * W, style_coef[st],
-                                              have_g ? 1 : 0, p->ls->need_gram_list, p->ls->need_gram_cnt, g, s));
-            g_gated = true;
-            have_g = true;
-        } else if (st >= 0) {
-            Scope sc(p, F_GRAM_BWD, s, m);
-            if (guided) {
-                ST3D_TRY(st3d_gram_bwd_weighted(p->D[st], p->act[m], p->guide_plane(st), n, C, H * W, style_coef[st], have_g ? 1 : 0,
-                                                chain ? 1 : 0, g, s));
-                g_gated = chain;
-            } else if (chain) {
-                ST3D_TRY(st3d_gram_bwd_gated(p->D[st], p->act[m], n, C, H * W, style_coef[st], have_g ? 1 : 0, g, s));
-                g_gated = true;
-            } else {
-                ST3D_TRY(st3d_gram_bwd(p->D[st], p->act[m], n, C, H * W, style_coef[st], have_g ? 1 : 0, g, s));
-                g_gated = false;
+    st3d_plan::ListSet *ls = p->ls;
+    BwdArgs b{n, 0, batch_denom, content_weight, style_coef, grad_current, need_mask, need, need >= 3 && p->need_gram,
+              ls->need_seg, ls->need_list, ls->need_cnt, ls->need_gram_list, ls->need_gram_cnt, p->gbuf[0], p->gbuf[1],
+              p->gbuf_floats * sizeof(float)};
+    // the split is the clean call's (the forward's condition: this call set flat_done / kept_done and cleared nothing since)
+    // The Gram backward's tile height is the one launch parameter written to follow the workgroup count, so B -- but only behind
+    // C % 128 == 0, where the 128 x 64 tiling is chosen first: as the launcher stands the choice depends on C and HW alone.  Its
+    // tuning knob can bring the count back in (gram.hip reads it per call), so a process that sets it keeps the one-stream call.
+    const bool gram_knob = getenv("ST3D_GRAM_BWD_MT") != nullptr;
+    if (key && key->clean_call && need_mask && need >= 1 && p->need_blocks && !gram_knob && split_ok(p, st3d_plan::SPLIT_BWD, n, true)) {
+        const int h = n / 2, gneed = std::min(need, p->grp_need_levels);
+        const bool ggram = gneed >= 3 && p->grp_need_gram;
+        if (!ls->have_grp_need) {
+            for (int g = 0; g < 2; ++g) {
+                st3d_plan::GroupLists &G = ls->grp[g];
+                const uint8_t *mask = need_mask + (size_t)g * h * p->S * p->S;
+                if (gneed >= 2)
+                    ST3D_TRY(st3d_need_blocks_build(mask, h, p->S, gneed - 1, p->need_cols, G.need_seg, p->need_flags, p->need_flags_bytes,
+                                                    G.need_list, G.need_cnt, ggram ? G.need_gram_list : nullptr, G.need_gram_cnt, s));
+                else
+                    ST3D_TRY(st3d_need_build(mask, h, p->S, gneed, G.need_seg, p->need_flags, p->need_flags_bytes, G.need_list[0],
+                                             G.need_list[1], G.need_cnt, s));
             }
-            have_g = true;
+            ls->have_grp_need = true;
         }
-        if (m == kContentTap && !content_done) {
-            Scope sc(p, F_ELEM, s);
-            if (chain) {
-                ST3D_TRY(st3d_axpy_diff_gated(p->act[m], p->content_target, (size_t)n * C * H * W, cc, have_g ? 1 : 0, g, s));
-                g_gated = true;
-            } else {
-                ST3D_TRY(st3d_axpy_diff(p->act[m], p->content_target, (size_t)n * C * H * W, cc, have_g ? 1 : 0, g, s));
-                g_gated = false;
-            }
-            have_g = true;
+        ST3D_TRY(split_fork(p, 1, s));
+        int rc = ST3D_OK;
+        for (int g = 0; g < 2 && rc == ST3D_OK; ++g) {
+            const st3d_plan::GroupLists &G = ls->grp[g];
+            const size_t half = p->gbuf_floats / 2;
+            BwdArgs bg{h, g * h, batch_denom, content_weight, style_coef, grad_current + (size_t)g * h * 3 * p->S * p->S,
+                       need_mask + (size_t)g * h * p->S * p->S, gneed, ggram, G.need_seg, G.need_list, G.need_cnt, G.need_gram_list,
+                       G.need_gram_cnt, p->gbuf[0] + g * half, p->gbuf[1] + g * half, half * sizeof(float)};
+            rc = backward_chain(p, bg, split_stream(p, g, s));
         }
-        if (!have_g) continue;
-        float *dst = (cs == 0) ? grad_current : gn;
-        DgradOpts o;
-        o.pregated = g_gated;
-        // the tensor dst is the gradient of = this conv's forward input (previous post-ReLU output, or the pool's output)
-        if (r.gate_dst) o.out_gate = p->act[pool_slot(m - 1) >= 0 ? m - 1 : m - 2];
-        if (o.out_gate && m - 2 == kContentTap) {       // dst is the gradient of the content tap: its own term joins in this launch's store
-            o.add_target = p->content_target;
-            o.add_coef = cc;
-            content_done = true;
-        }
-        if (cs >= 1 && cs <= ST3D_NEED_MAX_LISTS && need >= cs + 1) {   // conv1_2 .. conv3_3 over their need lists
-            o.tile_list = p->ls->need_list[cs - 1];
-            o.n_active = p->ls->need_cnt + (cs - 1);
-            o.tile_cols = p->need_cols[cs - 1];
-        }
-        ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, o));
-        g_gated = o.out_gate != nullptr;
-        // dst is the gradient w.r.t. this conv's input: either the previous conv's post-ReLU
-        // output or a pool output (then the next dgrad fuses the unpool)
-        g_is_pooled = (m > 0) && pool_slot(m - 1) >= 0;
-        pool_of_g = g_is_pooled ? pool_slot(m - 1) : -1;
-        float *t = g; g = gn; gn = t;
+        const int rj = split_join(p, 1, s);
+        if (rc != ST3D_OK || rj != ST3D_OK) return rc != ST3D_OK ? rc : rj;
+        ++p->split_calls[1];
+        return ST3D_OK;
     }
-    return ST3D_OK;
+    return backward_chain(p, b, s);
 }
 
 // Backward of st3d_plan_forward for external losses on the taps (differentiable get_features, style_transfer.py:61-83):
@@ -1246,6 +1487,14 @@ extern "C" int st3d_plan_backward(st3d_plan *p, int n, int upto_module, const fl
         float *t = g; g = gn; gn = t;
     }
     if (!have_g) ST3D_HIP(hipMemsetAsync(grad_image, 0, (size_t)n * 3 * p->S * p->S * sizeof(float), s));
+    return ST3D_OK;
+}
+
+// how many calls ran their forward / their backward as two groups since the plan was made (either pointer may be NULL)
+extern "C" int st3d_plan_split_calls(const st3d_plan *p, int *forward_calls, int *backward_calls) {
+    ST3D_CHECK_ARG(p);
+    if (forward_calls) *forward_calls = p->split_calls[0];
+    if (backward_calls) *backward_calls = p->split_calls[1];
     return ST3D_OK;
 }
 

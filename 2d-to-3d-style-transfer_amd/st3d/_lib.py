@@ -275,6 +275,7 @@ SIGNATURES = {
     "st3d_trace_push": (c_int, [ctypes.c_char_p]),
     "st3d_trace_pop": (c_int, []),
     "st3d_trace_enabled": (c_int, []),
+    "st3d_plan_split_calls": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "st3d_plan_profile": (c_int, [ctypes.c_void_p, c_int]),
     "st3d_plan_profile_read": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_float), ctypes.POINTER(c_int)]),
     "st3d_plan_profile_launches": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_float), c_int,

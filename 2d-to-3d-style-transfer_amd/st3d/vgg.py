@@ -342,6 +342,12 @@ class PerceptualPlan:
         self.generation += 1
         return self.loss_buf, grad
 
+    def split_calls(self):
+        """(forward, backward): how many loss calls so far ran that direction as two groups, the second on the plan's own stream (ST3D_SPLIT_BATCH)."""
+        f, b = ctypes.c_int(0), ctypes.c_int(0)
+        call("st3d_plan_split_calls", self._h, ctypes.byref(f), ctypes.byref(b))
+        return f.value, b.value
+
     def profile(self, enable):
         call("st3d_plan_profile", self._h, 1 if enable else 0)
 

@@ -1003,6 +1003,15 @@ int st3d_plan_loss_flat(st3d_plan *plan, const float *current, int n, int batch_
 int st3d_plan_loss_keyed(st3d_plan *plan, const float *current, int n, int batch_denom, float style_weight,
                          float content_weight, float *loss_out, float *grad_current, const uint8_t *cover,
                          const float *flat_color, const float *flat_rgb, uint64_t epoch, st3d_stream_t stream);
+/* The split batch (ST3D_SPLIT_BATCH = 0 | 1 | fwd | bwd, read by st3d_plan_create; default fwd): a keyed call that finds the
+ * clean record its own, with n even and at least 4, no guidance, no graph replay and profiling off, runs its images as two
+ * groups of n / 2, the first on the caller's stream and the second on a stream of the plan's -- the forward to conv5_1, then
+ * the Grams and the loss sums over the whole batch on the caller's stream, then the backward (fwd / bwd: that direction
+ * alone, the other as one launch sequence; 1: both).  The plan's stream is forked
+ * from the caller's stream and joined back to it by events before the call returns, so the caller orders its work as ever;
+ * results are bitwise the one-stream call's.
+ * st3d_plan_split_calls: how many calls so far ran their forward / their backward that way (either pointer may be NULL). */
+int st3d_plan_split_calls(const st3d_plan *plan, int *forward_calls, int *backward_calls);
 /* HIP-graph replay of st3d_plan_loss: its ~70 launches form a static sequence, so after one ordinary call it is captured
  * (per n / batch_denom / weights) and replayed with one hipGraphLaunch; inputs and outputs pass through plan-owned staging
  * buffers (three extra device copies per call).  Pays off where the step is launch-bound (small images). */

@@ -51,6 +51,9 @@ SOURCES = {
     # rounding for rounding; the similarities are MFMA fma chains and the explicit fmaf of the merge pass, which the flag
     # leaves alone
     "nnfm.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # nnfm.hip's flags: the projections are MFMA fma chains, the fp64 differences, squares and sums of the loss and its gradient
+    # are compared with their numpy restatement and stay as written
+    "swd.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "texpyr.hip": ["-ffp-contract=off"],       # the roundings its tests count are the ones written in the source
     # shade.hip's flags: its level-0 taps and blend are those of the plain kernels bit for bit, the chain is compared bit for
     # bit with its ordered numpy restatement

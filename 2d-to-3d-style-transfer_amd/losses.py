@@ -126,6 +126,39 @@ def compute_nnfm_loss(current_imgs, style_imgs, model, layers=('conv3_1',), *, m
     return _st._nnfm_term(current_imgs, style_imgs, model, layers, masks, batch_denom)
 
 
+def compute_swd_loss(current_imgs, style_imgs, model, layers=('conv2_1', 'conv3_1', 'conv4_1', 'conv5_1'), *, directions=0,
+                     generator=None, masks=None, batch_denom=None):
+    """The sliced Wasserstein style term (Heitz et al., CVPR 2021; style_transfer.swd_loss) of ``current_imgs`` (B,3,S,S)
+    against ``style_imgs`` ((1 or B,3,Ss,Ss); one image expanded over the batch is one style), summed over ``layers`` (names
+    from conv1_1, conv2_1, conv3_1, conv4_1, conv4_2, conv5_1).  ``directions``: how many random unit directions each tap is
+    projected onto, 0 = as many as it has channels, 1..512; they are drawn from ``generator`` (None: torch's default) in the
+    order of ``layers`` on every call, as the paper redraws them every step -- or a dict {layer: (K,C) tensor} to hand them
+    in.  The style taps are cached on the style tensor's identity and version; their projection and sort follow the
+    directions.  ``masks`` (B,1,S,S) | (B,S,S) in [0,1], e.g. the renders' coverage, select the positions that take part;
+    ``batch_denom`` is the global batch when the views are sharded.  Cost: its own partial VGG forward and backward up to its
+    deepest tap, next to the fused plan's of compute_perceptual_loss."""
+    import style_transfer as _st
+    if not isinstance(model, _vgg.Vgg19Features):
+        raise TypeError("compute_swd_loss needs the st3d VGG returned by utils.get_vgg()")
+    if not torch.is_tensor(current_imgs) or not torch.is_tensor(style_imgs):
+        raise TypeError("current_imgs and style_imgs must be tensors")
+    if not current_imgs.is_cuda or not style_imgs.is_cuda:
+        raise RuntimeError("st3d runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
+    layers = _st.check_swd_layers(layers)
+    if current_imgs.dim() != 4 or current_imgs.shape[1] != 3 or style_imgs.dim() != 4 or style_imgs.shape[1] != 3:
+        raise ValueError("current_imgs and style_imgs must be (B,3,S,S)")
+    B, S = current_imgs.shape[0], current_imgs.shape[2]
+    if style_imgs.shape[0] not in (1, B):
+        raise ValueError(f"style_imgs must hold 1 or {B} images, got {style_imgs.shape[0]}")
+    masks = check_style_masks(masks, B, S)
+    if isinstance(directions, dict):
+        if set(directions) != set(layers) or not all(torch.is_tensor(v) for v in directions.values()):
+            raise ValueError("directions handed in must be one (K,C) tensor per layer")
+    else:
+        directions = _st.swd_draw(layers, _st.check_swd_directions(directions), generator, current_imgs.device)
+    return _st._swd_term(current_imgs, style_imgs, model, layers, masks, batch_denom, directions)
+
+
 class _FusedLossFn(torch.autograd.Function):
     """A loss whose HIP call returns the value and its gradient together: backward only scales."""
 

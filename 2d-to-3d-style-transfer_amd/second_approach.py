@@ -50,6 +50,7 @@ def main(argv=None):
             run.optimizer.zero_grad()
             if vb.hi == vb.lo:                      # more ranks than views in this batch
                 epoch_loss += run.idle_contribution()
+                run.swd_term(None, None, None, vb.size)     # --swd_weight: the step's draw, so the ranks' generators stay in step
                 run.optimizer.step()
                 continue
             cams = run.cameras[vb.lo:vb.hi]
@@ -82,6 +83,10 @@ def main(argv=None):
             if torch.is_tensor(anchor_term):
                 loss = loss + anchor_term
             style_term = run.nnfm_term(current, cov, style, vb.size)    # --nnfm_weight, off by default
+            if torch.is_tensor(style_term):
+                loss = loss + style_term
+
+            style_term = run.swd_term(current, cov, style, vb.size)     # --swd_weight, off by default
             if torch.is_tensor(style_term):
                 loss = loss + style_term
 

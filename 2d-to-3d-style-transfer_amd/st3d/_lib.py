@@ -65,6 +65,14 @@ SIGNATURES = {
     "st3d_nnfm_sum": (c_int, [c_f32p, c_f32p, c_int, c_int, ctypes.c_double, c_f32p, ctypes.c_void_p, c_stream]),
     "st3d_nnfm_bwd": (c_int, [c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, ctypes.c_void_p, c_f32p, c_int, c_int, c_int, c_int,
                               c_int, ctypes.c_double, c_f32p, c_stream]),
+    "st3d_swd_project": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_stream]),
+    "st3d_swd_geometry": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "st3d_swd_workspace_bytes": (c_size, [c_int, c_int, c_int]),
+    "st3d_swd_sort": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_f32p, c_i32p, c_i32p, c_stream]),
+    "st3d_swd_loss": (c_int, [c_f32p, c_i32p, c_f32p, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_void_p, c_size,
+                              c_f32p, c_stream]),
+    "st3d_swd_bwd": (c_int, [c_f32p, c_i32p, c_i32p, c_f32p, c_f32p, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_f32p,
+                             c_stream]),
     "st3d_face_setup": (c_int, [c_f32p, c_i32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_stream]),
     "st3d_clip_records_bytes": (c_size, [c_int, c_int]),
     "st3d_face_setup_clip": (c_int, [c_f32p, c_i32p, c_int, c_int, c_int, c_float, c_int, ctypes.c_void_p, c_size, c_stream]),

@@ -27,6 +27,7 @@ _STYLE_MASKS = ['none', 'object']
 _TEXTURE_TYPES = ['uv', 'vertex']
 _LAPLACIANS = ['uniform', 'cot', 'cotcurv']
 _NNFM_LAYERS = ['conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.NNFM_LAYERS
+_SWD_LAYERS = ['conv1_1', 'conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.SWD_LAYERS
 
 
 def nnfm_layers(text):
@@ -34,6 +35,14 @@ def nnfm_layers(text):
     names = tuple(s.strip() for s in text.split(','))
     if not names or len(set(names)) != len(names) or any(n not in _NNFM_LAYERS for n in names):
         raise argparse.ArgumentTypeError(f"expected a comma list of distinct names from {','.join(_NNFM_LAYERS)}, got {text!r}")
+    return names
+
+
+def swd_layers(text):
+    """--swd_layers: a comma list of distinct names from conv1_1,conv2_1,conv3_1,conv4_1,conv4_2,conv5_1 -> the tuple"""
+    names = tuple(s.strip() for s in text.split(','))
+    if not names or len(set(names)) != len(names) or any(n not in _SWD_LAYERS for n in names):
+        raise argparse.ArgumentTypeError(f"expected a comma list of distinct names from {','.join(_SWD_LAYERS)}, got {text!r}")
     return names
 
 
@@ -123,6 +132,14 @@ SHARED_FLAGS = [
          "step; 0 = off"),
     Flag("nnfm_layers", nnfm_layers, ('conv3_1',), "taps of the NNFM term, a comma list from conv2_1,conv3_1,conv4_1,conv4_2,"
          "conv5_1; their terms are added"),
+    Flag("swd_weight", float, 0.0, "weight of the sliced Wasserstein style term (Heitz et al. 2021): the VGG features of a render "
+         "and of the style image are projected onto random directions, sorted, and matched quantile by quantile -- the whole "
+         "feature distribution, not its second moments.  Joins the Gram term, or replaces it with --style_weight 0.  "
+         "--style_mask object takes the distribution over the object's coverage only.  The directions are redrawn every step "
+         "from a generator seeded with --seed (0 when unset).  Costs its own partial VGG forward and backward per step; 0 = off"),
+    Flag("swd_layers", swd_layers, ('conv2_1', 'conv3_1', 'conv4_1', 'conv5_1'), "taps of the sliced Wasserstein term, a comma "
+         "list from conv1_1,conv2_1,conv3_1,conv4_1,conv4_2,conv5_1; their terms are added"),
+    Flag("swd_directions", int, 0, "directions each tap is projected onto, 1...512; 0 = as many as the tap has channels"),
     Flag("texture_lod_bias", float, 0.0, "added to every pixel's level of detail before it is clamped to the chain "
          "(--texture_mip_levels): negative = sharper, positive = blurrier"),
 ]
@@ -157,6 +174,11 @@ def check_args(args):
     nnfm = getattr(args, "nnfm_weight", 0.0)
     if not (math.isfinite(nnfm) and nnfm >= 0.0):
         return "--nnfm_weight must be finite and >= 0"
+    swd = getattr(args, "swd_weight", 0.0)
+    if not (math.isfinite(swd) and swd >= 0.0):
+        return "--swd_weight must be finite and >= 0"
+    if not 0 <= getattr(args, "swd_directions", 0) <= 512:
+        return "--swd_directions must be 0 (the channels of each tap) or in 1...512"
     if not getattr(args, "silhouette_sigma", 1e-4) > 0.0:
         return "--silhouette_sigma must be positive"
     k = getattr(args, "silhouette_faces_per_pixel", None)
@@ -533,6 +555,9 @@ class Run:
         self.chamfer_generator = self.chamfer_target = None
         if getattr(args, "chamfer_weight", 0.0):        # off (the default): nothing runs, no generator is created
             self.setup_chamfer()
+        self.swd_generator = None
+        if getattr(args, "swd_weight", 0.0):            # off (the default): nothing runs, no generator is created
+            self.swd_generator = torch.Generator().manual_seed(args.seed if args.seed is not None else 0)
         self.progress = 0               # epochs (second approach) / view batches (first approach) already done
         if args.resume:
             self.load_checkpoint(args.resume)
@@ -633,6 +658,9 @@ class Run:
         generator = getattr(self, "chamfer_generator", None)
         if generator is not None:           # --chamfer_weight: where the point draws of the run have got to
             blob["chamfer_generator_state"] = generator.get_state().cpu()
+        generator = getattr(self, "swd_generator", None)
+        if generator is not None:           # --swd_weight: where the direction draws of the run have got to
+            blob["swd_generator_state"] = generator.get_state().cpu()
         tmp = os.path.join(self.out_dir, "checkpoint.pt.tmp")
         torch.save(blob, tmp)
         os.replace(tmp, os.path.join(self.out_dir, "checkpoint.pt"))
@@ -657,6 +685,12 @@ class Run:
                              % (("with", "without") if "chamfer_generator_state" in blob else ("without", "with")))
         if generator is not None:
             generator.set_state(blob["chamfer_generator_state"])
+        generator = getattr(self, "swd_generator", None)
+        if ("swd_generator_state" in blob) != (generator is not None):
+            raise ValueError("checkpoint was written %s --swd_weight, this run is %s it"
+                             % (("with", "without") if "swd_generator_state" in blob else ("without", "with")))
+        if generator is not None:
+            generator.set_state(blob["swd_generator_state"])
         with torch.no_grad():
             if self.pyramid is not None:
                 self.pyramid.load_params(blob["texture_pyramid"].to(self.device))
@@ -710,6 +744,26 @@ class Run:
         masks = cov if getattr(a, "style_mask", "none") == 'object' else None
         return a.nnfm_weight * _l.compute_nnfm_loss(current, style, self.vgg, layers=a.nnfm_layers, masks=masks,
                                                     batch_denom=batch_size)
+
+    def swd_term(self, current, cov, style, batch_size):
+        """--swd_weight x this rank's share of the batch mean of the sliced Wasserstein style term of the `current` renders
+        against `style` over --swd_layers (losses.compute_swd_loss), scaled like nnfm_term: divided by the GLOBAL batch, and
+        --style_mask object hands it the renders' coverage.  The step's directions come from the run's generator (seeded with
+        --seed, 0 when unset, identically on every rank; kept in checkpoints as swd_generator_state).  A rank without views
+        adds nothing but still makes the draw, so that every rank projects onto the same directions in every step.  With
+        weight 0 (the default) nothing runs at all."""
+        a = self.args
+        generator = getattr(self, "swd_generator", None)
+        if not getattr(a, "swd_weight", 0.0) or generator is None:
+            return 0
+        import style_transfer as _st
+        directions = _st.swd_draw(a.swd_layers, a.swd_directions, generator)
+        if current is None or current.shape[0] == 0:
+            return 0
+        import losses as _l
+        masks = cov if getattr(a, "style_mask", "none") == 'object' else None
+        return a.swd_weight * _l.compute_swd_loss(current, style, self.vgg, layers=a.swd_layers, directions=directions,
+                                                  masks=masks, batch_denom=batch_size)
 
     def setup_chamfer(self):
         """--chamfer_weight > 0: the run's generator, seeded with --seed (0 when unset) identically on every rank, and the

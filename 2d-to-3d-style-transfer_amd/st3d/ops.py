@@ -670,6 +670,129 @@ def nnfm_bwd(feat, style_hat, idx, dist, wsum, weights=None, batch_denom=None, g
     return grad
 
 
+# ------------------------------------------------------------------ sliced Wasserstein style loss (csrc/swd.hip)
+SWD_MAX_POSITIONS = 1 << 20
+SWD_MAX_CHANNELS = 512
+
+
+def _swd_size(n, what, hi=SWD_MAX_POSITIONS):
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= hi:
+        raise ValueError(f"{what} must be an integer in 1..{hi}, got {n!r}")
+    return n
+
+
+def _swd_rows(t, what, dtype=F32):
+    """(B,K,N) (or (B,K,H,W)) -> (contiguous tensor (B,K,N), B, K, N)"""
+    if not torch.is_tensor(t):
+        raise TypeError(f"{what} must be a tensor (B,K,N)")
+    if t.dim() not in (3, 4):
+        raise ValueError(f"{what} must be (B,K,N) or (B,K,H,W), got {tuple(t.shape)}")
+    B, K = int(t.shape[0]), int(t.shape[1])
+    N = int(t[0, 0].numel()) if B and K else 0
+    _swd_size(B, f"the batch of {what}", 65535)
+    _swd_size(K, f"the rows of {what}", SWD_MAX_CHANNELS)
+    _swd_size(N, f"the positions of {what}")
+    return t.detach().to(dtype).contiguous().reshape(B, K, N), B, K, N
+
+
+def _swd_weights(weights, B, N):
+    if weights is None:
+        return None
+    if not torch.is_tensor(weights):
+        raise TypeError("weights must be a tensor (B,N) or (B,H,W)")
+    if weights.numel() != B * N or weights.shape[0] != B:
+        raise ValueError(f"weights must hold ({B},{N}) values, got {tuple(weights.shape)}")
+    return _f32c(weights).reshape(B, N)
+
+
+def _swd_style(tsorted, B, K):
+    tsorted, Bs, Ks, M = _swd_rows(tsorted, "tsorted")
+    if Ks != K:
+        raise ValueError(f"tsorted has {Ks} rows per image, sorted {K}")
+    if Bs not in (1, B):
+        raise ValueError(f"tsorted must hold 1 or {B} images, got {Bs}")
+    return tsorted, Bs, M
+
+
+def _swd_count(count, B):
+    if not torch.is_tensor(count) or tuple(count.shape) != (B,):
+        raise ValueError(f"count must be a tensor ({B},)")
+    return count
+
+
+def swd_project(x, a):
+    """x (B,Q,N) | (B,Q,H,W), a (R,Q) -> out (B,R,N) fp32, out_brn = sum_q a_rq x_bqn as ONE ascending fp32 fma chain from 0
+    (the fp32 MFMA), never split over q.  1 <= Q, R <= 512."""
+    x, B, Q, N = _swd_rows(x, "x")
+    if not torch.is_tensor(a):
+        raise TypeError("a must be a tensor (R,Q)")
+    if a.dim() != 2 or int(a.shape[1]) != Q:
+        raise ValueError(f"a must be (R,{Q}), got {tuple(a.shape)}")
+    R = _swd_size(int(a.shape[0]), "the rows of a", SWD_MAX_CHANNELS)
+    a = _f32c(a)
+    out = torch.empty((B, R, N), dtype=F32, device=x.device)
+    call("st3d_swd_project", dptr(x), dptr(a), B, Q, R, N, dptr(out), stream_ptr())
+    return out
+
+
+def swd_geometry(N):
+    """-> (block, passes) of the launch st3d_swd_sort makes for rows of N positions: strides below `block` are sorted in LDS,
+    `passes` launches on tiles strided in memory handle the strides from `block` up, one per level (0 when N <= block)."""
+    block, passes = ctypes.c_int(0), ctypes.c_int(0)
+    call("st3d_swd_geometry", _swd_size(N, "N"), ctypes.byref(block), ctypes.byref(passes))
+    return block.value, passes.value
+
+
+def swd_workspace_bytes(B, K, N):
+    """the workspace st3d_swd_sort needs (0 when the rows fit one block)"""
+    return int(_lib.load().st3d_swd_workspace_bytes(_swd_size(B, "B", 65535), _swd_size(K, "K", SWD_MAX_CHANNELS), _swd_size(N, "N")))
+
+
+def swd_sort(proj, weights=None, want_perm=True):
+    """proj (B,K,N), weights (B,N) | (B,H,W) >= 0 or None -> (sorted (B,K,N) fp32, perm (B,K,N) int32 or None, count (B) int32):
+    every row ascending by (inactive, key, index) -- inactive = not w > 0, key = the order-preserving map of the fp32 bits with
+    every NaN as 0x7FC00000 -- so the result is unique; sorted holds the original values, perm[r] the position of rank r."""
+    proj, B, K, N = _swd_rows(proj, "proj")
+    weights = _swd_weights(weights, B, N)
+    nbytes = swd_workspace_bytes(B, K, N)
+    ws = torch.empty((nbytes // 8,), dtype=torch.int64, device=proj.device) if nbytes else None
+    out = torch.empty_like(proj)
+    perm = torch.empty((B, K, N), dtype=I32, device=proj.device) if want_perm else None
+    count = torch.empty((B,), dtype=I32, device=proj.device)
+    call("st3d_swd_sort", dptr(proj), dptr(weights), B, K, N, dptr(ws), nbytes, dptr(out), dptr(perm), dptr(count), stream_ptr())
+    return out, perm, count
+
+
+def swd_loss(sorted_rows, count, tsorted, batch_denom=None):
+    """sorted_rows (B,K,N), count (B) int32, tsorted (Bs,K,M) -> loss (1) fp32 = (1 / batch_denom) sum_b (1 / (K n_b))
+    sum_k sum_{r<n_b} (sorted_kbr - tsorted_{k,j(r)})^2, j(r) = ((2r+1) M) // (2 n_b); ordered, in fp64, rounded once."""
+    sorted_rows, B, K, N = _swd_rows(sorted_rows, "sorted")
+    tsorted, Bs, M = _swd_style(tsorted, B, K)
+    count = _swd_count(count, B)
+    loss = torch.empty((1,), dtype=F32, device=sorted_rows.device)
+    ws = torch.empty((B * K,), dtype=F64, device=sorted_rows.device)
+    call("st3d_swd_loss", dptr(sorted_rows), dptr(count, I32), dptr(tsorted), B, Bs, K, N, M,
+         1.0 / float(batch_denom if batch_denom is not None else B), dptr(ws), B * K * 8, dptr(loss), stream_ptr())
+    return loss
+
+
+def swd_bwd(sorted_rows, perm, count, tsorted, batch_denom=None, grad_out=None):
+    """-> d loss / d proj (B,K,N), one launch, every element written once through perm: g 2 / (batch_denom K n_b)
+    (sorted_kbr - tsorted_{k,j(r)}) at position perm[r] for r < n_b, an exact +0 elsewhere.  grad_out: the incoming scalar g
+    as a device tensor, or None."""
+    sorted_rows, B, K, N = _swd_rows(sorted_rows, "sorted")
+    tsorted, Bs, M = _swd_style(tsorted, B, K)
+    count = _swd_count(count, B)
+    if not torch.is_tensor(perm) or tuple(perm.shape) != (B, K, N):
+        raise ValueError("perm does not belong to these rows")
+    if grad_out is not None:
+        grad_out = _f32c(grad_out).reshape(1)
+    gproj = torch.empty_like(sorted_rows)
+    call("st3d_swd_bwd", dptr(sorted_rows), dptr(perm, I32), dptr(count, I32), dptr(tsorted), dptr(grad_out), B, Bs, K, N, M,
+         1.0 / float(batch_denom if batch_denom is not None else B), dptr(gproj), stream_ptr())
+    return gproj
+
+
 # ------------------------------------------------------------------ general soft renderer (K faces per pixel, blur)
 def raster_soft_fwd(verts_ndc, faces_i32, S, K, blur_radius=0.0, clip_bary=None, cull_backfaces=False,
                     perspective_correct=True, z_clip=None):

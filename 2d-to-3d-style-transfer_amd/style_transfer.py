@@ -270,8 +270,136 @@ def _nnfm_term(current_imgs, style_imgs, model, layers, masks, batch_denom):
     return total
 
 
+# ---------------------------------------------------------------------------- sliced Wasserstein style loss (csrc/swd.hip)
+SWD_LAYERS = tuple(_DEFAULT_LAYERS.values())                                # every tap may carry the term
+SWD_DEFAULT_LAYERS = ('conv2_1', 'conv3_1', 'conv4_1', 'conv5_1')           # conv1_1 at 512^2 is 64 rows of 262 144 positions per view
+_SWD_CHANNELS = {'conv1_1': 64, 'conv2_1': 128, 'conv3_1': 256, 'conv4_1': 512, 'conv4_2': 512, 'conv5_1': 512}
+
+
+def swd_directions(K, C, generator=None, device=None):
+    """(K,C) fp32 unit rows: a normal draw from ``generator`` (on the generator's device, so a CPU generator gives the same
+    directions on every rank and device) over its norm, moved to ``device``.  Plain torch; a constant of the gradient."""
+    for n, what in ((K, "K"), (C, "C")):
+        if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= _ops.SWD_MAX_CHANNELS:
+            raise ValueError(f"{what} must be an integer in 1..{_ops.SWD_MAX_CHANNELS}, got {n!r}")
+    where = generator.device if generator is not None else (device if device is not None else "cpu")
+    v = torch.randn((K, C), generator=generator, dtype=torch.float32, device=where)
+    v = v / v.norm(dim=1, keepdim=True)
+    return v.to(device) if device is not None else v
+
+
+class _SwdFn(torch.autograd.Function):
+    """One tap: forward = ops.swd_project -> ops.swd_sort of the render tap and of the style tap with the same directions,
+    ops.swd_loss; backward = ops.swd_bwd, then ops.swd_project with the transposed directions.  The permutation, the
+    directions and the weights are constants; the style gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, features, style_features, directions, weights, batch_denom):
+        f = features.detach().to(torch.float32).contiguous()
+        v = directions.detach().to(torch.float32).contiguous()
+        proj = _ops.swd_project(f, v)
+        rows, perm, count = _ops.swd_sort(proj, weights)
+        tsorted, _, _ = _ops.swd_sort(_ops.swd_project(style_features.detach(), v), None, want_perm=False)
+        loss = _ops.swd_loss(rows, count, tsorted, batch_denom)
+        ctx.saved = (rows, perm, count, tsorted, v, batch_denom, tuple(f.shape))
+        return loss[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rows, perm, count, tsorted, v, batch_denom, shape = ctx.saved
+        grad = None
+        if ctx.needs_input_grad[0]:
+            gproj = _ops.swd_bwd(rows, perm, count, tsorted, batch_denom, grad_out)
+            grad = _ops.swd_project(gproj, v.t().contiguous()).reshape(shape)
+        return grad, None, None, None, None
+
+
+def swd_loss(features, style_features, directions, mask=None, batch_denom=None):
+    """The sliced Wasserstein loss of Heitz et al. (CVPR 2021) over one tap: ``features`` (B,C,H,W) and ``style_features``
+    ((Bs,C,Hs,Ws), Bs 1 or B, any resolution) are projected onto the unit rows of ``directions`` (K,C), every projected row is
+    sorted, and the loss is the mean over directions and positions of the squared difference between a render's sorted row
+    and the style's, resampled to as many samples by nearest rank; the per-image means are summed and divided by
+    ``batch_denom`` (default B).  ``mask`` (B,1,S,S) | (B,S,S) in [0,1] selects the positions (``nnfm_pool_mask``): a position
+    takes part iff its pooled weight is > 0, unweighted; the others receive an exact zero gradient.  Gradient to
+    ``features`` only."""
+    if not torch.is_tensor(features):
+        raise TypeError("features must be a tensor (B,C,H,W)")
+    if not torch.is_tensor(style_features) or not torch.is_tensor(directions):
+        raise TypeError("style_features must be a tensor (Bs,C,Hs,Ws) and directions a tensor (K,C)")
+    if not features.is_cuda:
+        raise RuntimeError("st3d swd_loss runs on the GPU (libst3d); got a CPU tensor -- there is no CPU fallback")
+    if features.dim() != 4:
+        raise ValueError(f"features must be (B,C,H,W), got {tuple(features.shape)}")
+    if batch_denom is not None and not (isinstance(batch_denom, int) and not isinstance(batch_denom, bool) and batch_denom >= 1):
+        raise ValueError(f"batch_denom must be a positive integer, got {batch_denom!r}")
+    B, C, H, W = features.shape
+    if style_features.dim() != 4 or style_features.shape[1] != C or style_features.shape[0] not in (1, B):
+        raise ValueError(f"style_features must be (1 or {B},{C},Hs,Ws), got {tuple(style_features.shape)}")
+    if directions.dim() != 2 or directions.shape[1] != C or not 1 <= directions.shape[0] <= _ops.SWD_MAX_CHANNELS:
+        raise ValueError(f"directions must be (1..{_ops.SWD_MAX_CHANNELS},{C}), got {tuple(directions.shape)}")
+    weights = nnfm_pool_mask(mask, B, H, W) if mask is not None else None
+    return _SwdFn.apply(features, style_features, directions, weights, batch_denom)
+
+
+def check_swd_layers(layers):
+    """a non-empty sequence of distinct names from SWD_LAYERS -> the tuple; else ValueError"""
+    if isinstance(layers, str):
+        layers = tuple(s for s in layers.split(',') if s)
+    layers = tuple(layers)
+    if not layers or len(set(layers)) != len(layers) or any(name not in SWD_LAYERS for name in layers):
+        raise ValueError(f"swd layers must be distinct names from {','.join(SWD_LAYERS)}, got {layers!r}")
+    return layers
+
+
+def check_swd_directions(K):
+    """0 (as many directions as the tap has channels) or 1..512 -> K; else ValueError"""
+    if isinstance(K, bool) or not isinstance(K, int) or not 0 <= K <= _ops.SWD_MAX_CHANNELS:
+        raise ValueError(f"swd directions must be 0 (= the channels of each tap) or 1..{_ops.SWD_MAX_CHANNELS}, got {K!r}")
+    return K
+
+
+def swd_draw(layers, K, generator, device=None):
+    """{layer: directions} for one step, drawn from ``generator`` in the order of ``layers`` (K = 0: as many as the tap has
+    channels).  The draw does not look at any image, so a rank without views makes it too and stays in step."""
+    return {name: swd_directions(K or _SWD_CHANNELS[name], _SWD_CHANNELS[name], generator, device) for name in layers}
+
+
+def _swd_tap_map(layers):
+    return {k: v for k, v in _DEFAULT_LAYERS.items() if v in layers}
+
+
+def _swd_style_taps(style_imgs, model, layers):
+    """{layer: the style tap (Bs,C,Hs,Ws)}, cached on the model under the tensor's identity and version as
+    ``_nnfm_style_taps`` does: the style VGG forward runs once per style.  Its projection and sort follow the directions
+    and are redone with every draw."""
+    key = (style_imgs.data_ptr(), style_imgs._version, tuple(style_imgs.shape), tuple(style_imgs.stride()), layers)
+    cache = getattr(model, "_swd_style_cache", None)
+    if cache is not None and cache[0] == key and cache[1].data_ptr() == style_imgs.data_ptr():
+        return cache[2]
+    s = style_imgs.detach()
+    if s.shape[0] > 1 and s.stride(0) == 0:
+        s = s[:1]
+    with torch.no_grad():
+        feats = get_features(s.to(torch.float32).contiguous(), model, _swd_tap_map(layers))
+        taps = {name: feats[name].detach() for name in layers}
+    model._swd_style_cache = (key, style_imgs, taps)
+    return taps
+
+
+def _swd_term(current_imgs, style_imgs, model, layers, masks, batch_denom, directions):
+    """``directions``: {layer: (K,C)} of this step (``swd_draw``)"""
+    taps = _swd_style_taps(style_imgs, model, layers)
+    feats = get_features(current_imgs, model, _swd_tap_map(layers))
+    total = None
+    for name in layers:
+        term = swd_loss(feats[name], taps[name], directions[name].to(feats[name].device), mask=masks, batch_denom=batch_denom)
+        total = term if total is None else total + term
+    return total
+
+
 def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, steps=2000, style_weight=1e6, content_weight=1, lr=0.003,
-                   style_masks=None, nnfm_weight=0.0, nnfm_layers=('conv3_1',)):
+                   style_masks=None, nnfm_weight=0.0, nnfm_layers=('conv3_1',), swd_weight=0.0, swd_layers=SWD_DEFAULT_LAYERS,
+                   swd_directions=0, swd_seed=0):
     # style_masks (B,1,S,S) | (B,S,S) in [0,1], e.g. the coverage of the renders being stylised: the guided style loss --
     # each tap's Gram of the optimised images is taken over the masked region only (default None: the reference's loss)
     # nnfm_weight > 0: every step adds nnfm_weight x the NNFM term over nnfm_layers (its own partial VGG forward and backward
@@ -281,6 +409,18 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
         raise ValueError("nnfm_weight must be finite and >= 0")
     if nnfm_weight:
         nnfm_layers = check_nnfm_layers(nnfm_layers)
+    # swd_weight > 0: every step adds swd_weight x the sliced Wasserstein term over swd_layers in the same way; its directions
+    # (swd_directions per tap, 0 = as many as the tap has channels) are redrawn every step from one generator seeded with
+    # swd_seed, so two calls with the same seed take the same steps.  0: nothing of it runs.
+    swd_weight = float(swd_weight)
+    if not (swd_weight >= 0.0 and swd_weight != float("inf")):
+        raise ValueError("swd_weight must be finite and >= 0")
+    if swd_weight:
+        swd_layers = check_swd_layers(swd_layers)
+        swd_k = check_swd_directions(swd_directions)
+        if isinstance(swd_seed, bool) or not isinstance(swd_seed, int):
+            raise ValueError(f"swd_seed must be an integer, got {swd_seed!r}")
+        swd_generator = torch.Generator().manual_seed(swd_seed)
 
     # Ensure content_imgs and style_imgs are batched tensors
     assert initial_optimized_imgs.shape[0] == content_imgs.shape[0] == style_imgs.shape[0]
@@ -298,6 +438,7 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
     plan.set_content(content_imgs.to(device), force=True)
     plan.set_style(style_imgs.to(device), B, force=True)
     nnfm_style_imgs = style_imgs.to(device) if nnfm_weight else None      # one tensor for the run: its taps are cached on it
+    swd_style_imgs = style_imgs.to(device) if swd_weight else None
 
     # Initialize target images  --> the ones to optimize
     optimized_imgs = initial_optimized_imgs.clone().detach().to(device).contiguous().requires_grad_(True)
@@ -312,6 +453,11 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
             term = _nnfm_term(optimized_imgs, nnfm_style_imgs, model, nnfm_layers, style_masks, None)
             (extra,) = torch.autograd.grad(term, optimized_imgs)
             grad = grad + nnfm_weight * extra
+        if swd_weight:
+            term = _swd_term(optimized_imgs, swd_style_imgs, model, swd_layers, style_masks, None,
+                             swd_draw(swd_layers, swd_k, swd_generator, device))
+            (extra,) = torch.autograd.grad(term, optimized_imgs)
+            grad = grad + swd_weight * extra
         optimized_imgs.grad = grad
         optimizer.step()
 

@@ -58,7 +58,10 @@ def main(argv=None):
                                                          steps=args.n_style_transfer_steps, style_weight=args.style_weight,
                                                          content_weight=args.content_weight, lr=args.style_transfer_lr,
                                                          style_masks=cov if args.style_mask == 'object' else None,
-                                                         nnfm_weight=args.nnfm_weight, nnfm_layers=args.nnfm_layers))
+                                                         nnfm_weight=args.nnfm_weight, nnfm_layers=args.nnfm_layers,
+                                                     swd_weight=args.swd_weight, swd_layers=args.swd_layers,
+                                                     swd_directions=args.swd_directions,
+                                                     swd_seed=args.seed if args.seed is not None else 0))
                 if rnd == args.n_rounds - 1:
                     run.save_views(targets, vb.lo)
             loss = torch.zeros((), device=run.device)

@@ -793,6 +793,53 @@ int st3d_nnfm_bwd(const float *feat, const float *style_hat, const int32_t *idx,
                   const float *weights, const double *wsum, const float *grad_out, int B, int Bs, int C, int N, int M,
                   double inv_denom, float *grad_feat, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ sliced Wasserstein style loss (csrc/swd.hip):
+ * Heitz, Vanhoey, Chambon, Belcour, "A Sliced Wasserstein Loss for Neural Texture Synthesis", CVPR 2021.  A render tap
+ * F (B,C,H,W), fp32, post-ReLU, N = H W positions; a style tap S (Bs,C,Hs,Ws), M = Hs Ws, Bs = 1 or B; K directions V (K,C),
+ * unit rows, constants of the gradient; optional position weights w (B,N), each >= 0.  Position i of image b is ACTIVE iff
+ * w_bi > 0 (without weights every position is); the active positions are unweighted among themselves; n_b = their number.
+ *   projection  p_kbi = sum_c V_kc F_bci, likewise t_kj for the style: ONE fp32 fma chain in ascending c starting from 0 (what
+ *               the fp32 MFMA computes), never split over c, so a value does not depend on the tile it fell into and two
+ *               positions with equal feature vectors get bit-equal projections.
+ *   order       each row (b,k) is sorted ascending by the triple (inactive, key, index).  key = the order-preserving map of
+ *               the fp32 bits to uint32 (all bits flipped if the sign bit is set, else the sign bit flipped: -0 before +0);
+ *               every NaN is first replaced by 0x7FC00000 and so sorts after +Inf.  The triple is a total order: the result is
+ *               unique whatever algorithm and tiling produce it.  sorted (B,K,N) fp32 holds the original values (NaNs as they
+ *               came), perm (B,K,N) int32 the position that has each rank, count (B) int32 = n_b.  The style rows are sorted
+ *               the same way, without weights or perm.
+ *   matching    rank r < n_b meets the style quantile j(r) = ((2r+1) M) / (2 n_b) in integer arithmetic (the nearest-neighbour
+ *               resampling of the sorted style row to n_b samples; j(r) = r when n_b = M).
+ *   loss        L_b = (1 / (K n_b)) sum_k sum_{r<n_b} (sorted_kbr - tsorted_{k,j(r)})^2, differences, squares and sums in fp64
+ *               in a fixed order; L = inv_denom sum_b L_b, rounded once.  An image with n_b = 0 adds 0 and gets no gradient.
+ *   gradient    perm, V and w are constants, S gets none:
+ *               dL/dp_{k,b,perm[r]} = g 2 inv_denom / (K n_b) (sorted_kbr - tsorted_{k,j(r)}) for r < n_b, in fp64, rounded
+ *               once; an exact +0 at inactive positions and in images with n_b = 0; every element of gproj (B,K,N) is written
+ *               exactly once, no atomics.  dL/dF_bci = sum_k V_kc gproj_kbi is st3d_swd_project again with V^T as the matrix.
+ * NaN and Inf propagate as the expressions say.  Two runs are bit-equal.
+ * Every entry point checks its arguments on the host: a bad size or a null pointer is ST3D_E_INVALID with nothing launched;
+ * nothing allocates inside. */
+/* out_brn = sum_q a_rq x_bqn, the chain above.  x (B,Q,N), a (R,Q), out (B,R,N); 1 <= Q, R <= 512, 1 <= N <= 2^20,
+ * 1 <= B <= 65535; every offset is 64-bit. */
+int st3d_swd_project(const float *x, const float *a, int B, int Q, int R, int N, float *out, st3d_stream_t stream);
+/* the launch st3d_swd_sort makes for rows of N positions: a bitonic network on rows padded to a power of two P >= N; every
+ * stride below `block` runs in LDS on `block` consecutive words, `passes` = the launches that take the strides >= block on
+ * tiles strided in memory, one per level of the network above the block: log2(P / block), 0 when P <= block. */
+int st3d_swd_geometry(int N, int *block, int *passes);
+/* B K P 8 bytes when N > block, else 0 (the workspace may then be NULL); 0 for sizes st3d_swd_sort refuses */
+size_t st3d_swd_workspace_bytes(int B, int K, int N);
+/* proj (B,K,N), weights (B,N) or NULL -> sorted (B,K,N), perm (B,K,N) or NULL, count (B) or NULL.  1 <= K <= 512; workspace
+ * 8-byte aligned, contents never read before written. */
+int st3d_swd_sort(const float *proj, const float *weights, int B, int K, int N, void *workspace, size_t workspace_bytes,
+                  float *sorted, int32_t *perm, int32_t *count, st3d_stream_t stream);
+/* loss[0] = L (overwritten).  tsorted (Bs,K,M).  One fp64 sum per row (thread t of 256 adds r = t, t + 256, ... then a fixed
+ * tree), then one workgroup adds the rows of each image the same way and the images in order: the tree is the same whatever
+ * the launch.  workspace: B K doubles for the row sums, 8-byte aligned. */
+int st3d_swd_loss(const float *sorted, const int32_t *count, const float *tsorted, int B, int Bs, int K, int N, int M,
+                  double inv_denom, void *workspace, size_t workspace_bytes, float *loss, st3d_stream_t stream);
+/* gproj (B,K,N): a scatter through perm with one writer per element; grad_out: the incoming scalar g on the device (NULL = 1) */
+int st3d_swd_bwd(const float *sorted, const int32_t *perm, const int32_t *count, const float *tsorted, const float *grad_out,
+                 int B, int Bs, int K, int N, int M, double inv_denom, float *gproj, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ texture pyramid (csrc/texpyr.hip):
  * the texture map (T,T,3) as the sum of L maps of sides T_l = T / 2^l, each upsampled to T x T.  `params` is one flat
  * fp32 tensor of st3d_texpyr_numel(T, L) = 3 * sum_l T_l^2 elements; level l is the (T_l, T_l, 3) row-major block at

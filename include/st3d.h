@@ -278,7 +278,10 @@ int st3d_shade_lit_fwd(const int32_t *pix_to_face, const float *bary, const floa
 /* -> grad_texture (T,T,3) accumulated (may be NULL), grad_bary (B,S,S,3) and grad_np (B,S,S,6) = per pixel d/dN, d/dP
  * (both or neither).  workspace NULL: float atomics; else (>= st3d_shade_bwd_det_workspace_bytes(T), 16-byte aligned,
  * grad_texture given) the fixed-point scatter of st3d_shade_bwd_det, its bound scaled by weight_bound >= max_c (A + D)_c
- * (e.g. max over entries and channels of |ka La| + |kd Ld|). */
+ * (e.g. max over entries and channels of |ka La| + |kd Ld|).
+ * grad_np is written at covered pixels only (pix_to_face >= 0): elsewhere it keeps what the buffer held.  Its one
+ * consumer, st3d_phong_scatter, reads covered fragments only.  The same holds per fragment for st3d_shade_soft_lit_bwd and
+ * st3d_shade_ss_lit_bwd. */
 int st3d_shade_lit_bwd(const float *grad_rgb, const int32_t *pix_to_face, const float *bary, const float *zbuf,
                        const float *dists, const float *verts_uvs, const int32_t *faces_uvs, const float *texture,
                        int B, int S, int T, int F, int VT, const float *verts, const float *normals,
@@ -360,7 +363,9 @@ int st3d_apply_background(const float *img, const float *mask, const float *bg, 
 /* packed-weight sizes in floats for a (Cout,Cin,3,3) filter */
 size_t st3d_conv3x3_packed_floats(int Cout, int Cin);
 /* w (Cout,Cin,3,3) -> w_fwd [9][Cin4][CoutP] and w_dgrad [9][Cout4][CinP] (rotated 180 deg,
- * channel-transposed); either output may be NULL. */
+ * channel-transposed); either output may be NULL.  Both buffers hold st3d_conv3x3_packed_floats floats, the larger of the
+ * two layouts (Cin4, Cout4: rounded up to 4; CoutP, CinP: to 128); the floats behind a pack's own layout are neither
+ * written here nor read by any kernel. */
 int st3d_conv3x3_pack(const float *w, int Cout, int Cin, float *w_fwd, float *w_dgrad,
                       st3d_stream_t stream);
 /* y = relu?(conv3x3(x, w) + bias): x (N,Cin,H,W), y (N,Cout,H,W) */

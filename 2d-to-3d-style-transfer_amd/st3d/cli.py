@@ -140,6 +140,11 @@ SHARED_FLAGS = [
     Flag("swd_layers", swd_layers, ('conv2_1', 'conv3_1', 'conv4_1', 'conv5_1'), "taps of the sliced Wasserstein term, a comma "
          "list from conv1_1,conv2_1,conv3_1,conv4_1,conv4_2,conv5_1; their terms are added"),
     Flag("swd_directions", int, 0, "directions each tap is projected onto, 1...512; 0 = as many as the tap has channels"),
+    Flag("verts_diffusion", float, 0.0, "optimise the vertices through u = (I + lambda L) verts, L the combinatorial Laplacian of "
+         "the mesh (Nicolet et al. 2021, 'Large Steps in Inverse Rendering of Geometry'): Adam steps on u with one denominator "
+         "for the whole tensor, and every step solves for the vertices by conjugate gradients, so the surface moves coherently "
+         "instead of vertex by vertex.  The value is lambda, finite and >= 0 (the paper's examples use about 19); --verts_lr "
+         "is the step size of u.  --optimization_target mesh / both only; 0 = off"),
     Flag("texture_lod_bias", float, 0.0, "added to every pixel's level of detail before it is clamped to the chain "
          "(--texture_mip_levels): negative = sharper, positive = blurrier"),
 ]
@@ -169,6 +174,12 @@ def check_args(args):
     if chamfer and getattr(args, "optimization_target", None) == 'texture':
         return ("--chamfer_weight needs --optimization_target mesh or both: with 'texture' the vertices do not move and the "
                 "term would be a constant")
+    diffusion = getattr(args, "verts_diffusion", 0.0)
+    if not (math.isfinite(diffusion) and diffusion >= 0.0):
+        return "--verts_diffusion must be finite and >= 0"
+    if diffusion and getattr(args, "optimization_target", None) == 'texture':
+        return ("--verts_diffusion needs --optimization_target mesh or both: with 'texture' the vertices do not move and "
+                "there is nothing to precondition")
     if not 1 <= getattr(args, "chamfer_samples", 5000) <= 1 << 20:
         return "--chamfer_samples must be in 1...1048576"
     nnfm = getattr(args, "nnfm_weight", 0.0)
@@ -541,12 +552,27 @@ class Run:
 
         # one optimiser (one Adam state) for the whole run, over all view batches
         levels = getattr(args, "texture_pyramid_levels", 1)
-        if levels == 1:
+        diffusion = float(getattr(args, "verts_diffusion", 0.0))
+        if diffusion:
+            self.opt = _u.setup_optimizations(args.optimization_target, self.content_mesh, lr, texture_pyramid_levels=levels,
+                                              verts_diffusion=diffusion)
+        elif levels == 1:
             self.opt = _u.setup_optimizations(args.optimization_target, self.content_mesh, lr)
         else:
             self.opt = _u.setup_optimizations(args.optimization_target, self.content_mesh, lr, texture_pyramid_levels=levels)
         self.pyramid = self.opt.get('texture_pyramid')      # None: the texture is the plain leaf opt['texture_map']
-        if args.verts_lr is not None and args.optimization_target == 'both':
+        self.diffusion = self.opt.get('verts_diffusion')    # None: the vertices are the plain leaf opt['verts']
+        self._diffusion_warned = False
+        if self.diffusion is not None:
+            self.say(f"Vertex diffusion: lambda {self.diffusion.lam:g}, largest degree {self.diffusion.max_degree}, at most "
+                     f"{self.diffusion.max_iter} CG iterations per solve at tol {self.diffusion.tol:g}")
+            if args.verts_lr is not None:       # --verts_lr is the step size of u, whether or not a texture is optimised too
+                groups = [{"params": [self.diffusion.params], "lr": args.verts_lr, "uniform": True}]
+                if args.optimization_target == 'both':
+                    texture_leaf = self.pyramid.params if self.pyramid is not None else self.opt[self.texture_key]
+                    groups.append({"params": [texture_leaf], "lr": lr})
+                self.opt['optimizer'] = st3d_optim.Adam(groups)
+        elif args.verts_lr is not None and args.optimization_target == 'both':
             texture_leaf = self.pyramid.params if self.pyramid is not None else self.opt[self.texture_key]
             self.opt['optimizer'] = st3d_optim.Adam([{"params": [self.opt['verts']], "lr": args.verts_lr},
                                                      {"params": [texture_leaf], "lr": lr}])
@@ -587,9 +613,22 @@ class Run:
             print(msg)
 
     def log(self, line):
+        self.check_diffusion()          # the caller has just read the loss back: the solves behind it are finished
         if self.main:
             with open(self._log, 'a') as fh:
                 fh.write(line + '\n')
+
+    def check_diffusion(self):
+        """--verts_diffusion: warn, once per run, when the latest forward or backward solve stopped at its iteration cap."""
+        dv = getattr(self, "diffusion", None)
+        if dv is None or self._diffusion_warned:
+            return
+        for name, info in (("forward", dv.last_info()), ("backward", dv.last_info(backward=True))):
+            if info is not None and not all(info["converged"]):
+                self._diffusion_warned = True
+                self.say(f"WARNING: the {name} solve of --verts_diffusion stopped after {max(info['iterations'])} iterations "
+                         f"at a relative residual of {max(info['residual']):.3g} (tol {dv.tol:g}); not reported again")
+                return
 
     def save_views(self, images, first_index):
         """view_<k>.png for this rank's views of the batch, k counted over the whole view set (asynchronous)."""
@@ -597,6 +636,8 @@ class Run:
 
     def current_mesh(self):
         o = self.opt
+        if getattr(self, "diffusion", None) is not None:    # one forward solve per step: the mesh, the regularisers and the
+            o['verts'] = self.diffusion.verts()             # silhouette / Chamfer terms all read this tensor
         if self.atlas_r:
             return self._utils.build_mesh_atlas(o['atlas'], o['verts'], o['faces'])
         if self.vertex_colors:
@@ -652,6 +693,9 @@ class Run:
                 "texture_type": "vertex" if self.vertex_colors else "uv", "texture_atlas": self.atlas_r,
                 self.texture_key: texture.detach().cpu(), "verts": self.opt['verts'].detach().cpu(),
                 "optimizer": self.optimizer.state_dict()}
+        if getattr(self, "diffusion", None) is not None:    # u is the state of record; "verts" is what it stood for when last solved
+            blob["verts_diffusion"] = self.diffusion.params.detach().cpu()
+            blob["verts_diffusion_lambda"] = float(self.diffusion.lam)
         if self.pyramid is not None:        # the flat parameters are the state of record; texture_map is what they sum to
             blob["texture_pyramid"] = self.pyramid.params.detach().cpu()
             blob["texture_pyramid_levels"] = self.pyramid.levels
@@ -679,6 +723,10 @@ class Run:
         want = self.pyramid.levels if self.pyramid is not None else 1
         if have != want:
             raise ValueError("checkpoint was written with %d texture pyramid level(s), this run has %d" % (have, want))
+        dv = getattr(self, "diffusion", None)
+        have_lam, want_lam = float(blob.get("verts_diffusion_lambda", 0.0)), dv.lam if dv is not None else 0.0
+        if have_lam != want_lam:
+            raise ValueError("checkpoint was written with --verts_diffusion %g, this run has %g" % (have_lam, want_lam))
         generator = getattr(self, "chamfer_generator", None)
         if ("chamfer_generator_state" in blob) != (generator is not None):
             raise ValueError("checkpoint was written %s --chamfer_weight, this run is %s it"
@@ -696,7 +744,10 @@ class Run:
                 self.pyramid.load_params(blob["texture_pyramid"].to(self.device))
             else:
                 self.opt[self.texture_key].copy_(blob[self.texture_key])
-            self.opt['verts'].copy_(blob["verts"])
+            if dv is not None:
+                dv.load_params(blob["verts_diffusion"].to(self.device))     # opt['verts'] is solved for again by current_mesh()
+            else:
+                self.opt['verts'].copy_(blob["verts"])
         self.optimizer.load_state_dict(blob["optimizer"])
         self.progress = int(blob["progress"])
         self.say(f"Resumed from {path} at {self.progress}")

@@ -189,7 +189,9 @@ def _term(verts, target, topo, k, mesh=None, method="uniform", target_length=0.0
                                         w, method, target_length, want_grad=True)
         else:
             out, grad = ops.mesh_reg(verts.detach(), tgt.detach(), topo, w, want_grad=True)
-        hit = (out[1 + k], grad)
+        # the entry keeps `verts` alive (like _topology keeps `faces`): while it does, no other tensor can take its address, so
+        # the key cannot name a later tensor -- the vertices of a DiffusedVertices run are a fresh tensor of version 0 each step
+        hit = (out[1 + k], grad, verts)
         _REG_CACHE[key] = hit
     return _TermFn.apply(verts, hit[0], hit[1])
 

@@ -79,7 +79,9 @@ def comm_info(device=None):
 class Adam:
     """``Adam(params, lr)`` as the reference uses it, or ``Adam([{"params": [...], "lr": ...}, ...])`` for one
     learning rate per tensor group (the reference's notes.txt:29 idea; torch.optim's param_groups convention).
-    ``state_dict()`` / ``load_state_dict()`` carry step counts and both moment buffers for checkpoint / resume."""
+    ``state_dict()`` / ``load_state_dict()`` carry step counts and both moment buffers for checkpoint / resume.
+    A group with ``"uniform": True`` takes the update with one denominator for each whole tensor (st3d_adam_step_uniform,
+    the Adam of st3d.largesteps); the moment buffers and the state dict are the same."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, reduce_grads=True):
         params = list(params)
@@ -87,6 +89,9 @@ class Adam:
         if params and isinstance(params[0], dict):
             self.param_groups = [{"params": list(g["params"]), "lr": float(g.get("lr", lr)), "betas": self.betas,
                                   "eps": self.eps} for g in params]
+            for group, g in zip(self.param_groups, params):
+                if g.get("uniform"):        # one second-moment denominator per tensor (st3d.largesteps.adam_step_uniform)
+                    group["uniform"] = True
         else:
             self.param_groups = [{"params": params, "lr": float(lr), "betas": self.betas, "eps": self.eps}]
         self.params = [p for g in self.param_groups for p in g["params"]]
@@ -158,6 +163,11 @@ class Adam:
                     st["step"] += 1
                     if not p.is_contiguous():
                         raise RuntimeError("st3d Adam needs contiguous parameters")
+                    if group.get("uniform"):
+                        from . import largesteps
+                        largesteps.adam_step_uniform(p.data, g, st["exp_avg"], st["exp_avg_sq"], st["step"], group["lr"],
+                                                     self.betas[0], self.betas[1], self.eps)
+                        continue
                     ops.adam_step(p.data, g, st["exp_avg"], st["exp_avg_sq"], st["step"], group["lr"], self.betas[0],
                                   self.betas[1], self.eps)
 

@@ -9,6 +9,7 @@ What differs from the reference, none of it visible in results:
   * ``setup_optimizations`` returns the fused HIP Adam (st3d.optim.Adam), which also sums the gradient
     over ranks when the view batch is sharded across GPUs.
 """
+import math
 import os
 import random
 
@@ -170,7 +171,29 @@ _VERTEX_LEAVES = {'texture': ('verts_features',), 'mesh': ('verts',), 'both': ('
 _ATLAS_LEAVES = {'texture': ('atlas',), 'mesh': ('verts',), 'both': ('verts', 'atlas')}
 
 
-def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1):
+def _diffused_optimizer(parts, lam, colour_leaves, lr):
+    """verts_diffusion > 0: the vertex leaf becomes the parameters of an st3d.largesteps.DiffusedVertices (under
+    'verts_diffusion'), 'verts' the vertices they stand for, and Adam sees them first, in a group of their own."""
+    from st3d.largesteps import DiffusedVertices
+    dv = DiffusedVertices(parts['verts'], parts['faces'], lam)
+    parts['verts_diffusion'] = dv
+    parts['verts'] = dv.verts()
+    groups = [{"params": [dv.params], "uniform": True}]
+    if colour_leaves:
+        groups.append({"params": list(colour_leaves)})
+    return _st3d_optim.Adam(groups, lr=lr)
+
+
+def refresh_verts(parts):
+    """After an optimiser step of a verts_diffusion run: parts['verts'] = the vertices of the stepped parameters (one
+    solve).  Without diffusion 'verts' is the leaf itself and nothing happens.  -> parts['verts']"""
+    dv = parts.get('verts_diffusion')
+    if dv is not None:
+        parts['verts'] = dv.verts()
+    return parts['verts']
+
+
+def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1, verts_diffusion=0.0):
     """Clone the mesh, mark the tensors `optimization_target` names as leaves and put ONE Adam (single lr,
     default betas/eps) over them (:173-204).  Keys of the returned dict are the reference's.
 
@@ -184,7 +207,18 @@ def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1)
 
     A mesh whose textures are a TexturesAtlas: 'atlas' (F,R,R,3) takes that place in the same way ('texture' -> the atlas,
     'mesh' -> the vertices, 'both' -> the vertices, then the atlas; the colour moves no vertex, so under 'mesh' and 'both'
-    the vertices move by the other terms of the loss alone); texture_pyramid_levels != 1 is a ValueError."""
+    the vertices move by the other terms of the loss alone); texture_pyramid_levels != 1 is a ValueError.
+
+    verts_diffusion = lambda > 0 (targets 'mesh' / 'both', any of the three texture kinds): the vertex leaf is the (V,3)
+    parameter tensor u = (I + lambda L) verts of an st3d.largesteps.DiffusedVertices, returned under 'verts_diffusion', in an
+    Adam group with "uniform": True; 'verts' holds verts() of the current parameters (refresh_verts(dict) after a step).
+    0 (the default) is the plain vertex leaf: no object is made and no call is added.  With 'texture', or a negative or
+    non-finite value: ValueError."""
+    lam = float(verts_diffusion)
+    if not (math.isfinite(lam) and lam >= 0.0):
+        raise ValueError(f"verts_diffusion must be finite and >= 0, got {verts_diffusion!r}")
+    if lam > 0.0 and optimization_target == 'texture':
+        raise ValueError("verts_diffusion needs optimization_target 'mesh' or 'both': with 'texture' the vertices do not move")
     if isinstance(mesh.textures, TexturesAtlas):
         if optimization_target not in _ATLAS_LEAVES:
             raise UnboundLocalError("local variable 'optimizer' referenced before assignment "
@@ -194,6 +228,9 @@ def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1)
                              "and no map to build a pyramid of")
         work = mesh.clone()
         parts = {'atlas': work.textures.atlas_packed(), 'verts': work.verts_packed(), 'faces': work.faces_packed()}
+        if lam > 0.0:
+            colour = [parts['atlas'].requires_grad_(True)] if optimization_target == 'both' else []
+            return dict(parts, optimizable_mesh=work, optimizer=_diffused_optimizer(parts, lam, colour, lr))
         leaves = [parts[name].requires_grad_(True) for name in _ATLAS_LEAVES[optimization_target]]
         return dict(parts, optimizable_mesh=work, optimizer=_st3d_optim.Adam(leaves, lr=lr))
     if isinstance(mesh.textures, TexturesVertex):
@@ -206,6 +243,9 @@ def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1)
         work = mesh.clone()
         parts = {'verts_features': work.textures.verts_features_packed(), 'verts': work.verts_packed(),
                  'faces': work.faces_packed()}
+        if lam > 0.0:
+            colour = [parts['verts_features'].requires_grad_(True)] if optimization_target == 'both' else []
+            return dict(parts, optimizable_mesh=work, optimizer=_diffused_optimizer(parts, lam, colour, lr))
         leaves = [parts[name].requires_grad_(True) for name in _VERTEX_LEAVES[optimization_target]]
         return dict(parts, optimizable_mesh=work, optimizer=_st3d_optim.Adam(leaves, lr=lr))
     work = mesh.clone()
@@ -225,8 +265,14 @@ def setup_optimizations(optimization_target, mesh, lr, texture_pyramid_levels=1)
                              "not optimised")
         from st3d.texpyr import TexturePyramid
         parts['texture_pyramid'] = TexturePyramid(parts.pop('texture_map'), texture_pyramid_levels)
+        if lam > 0.0:           # 'both': the target 'mesh' was refused above
+            return dict(parts, optimizable_mesh=work,
+                        optimizer=_diffused_optimizer(parts, lam, [parts['texture_pyramid'].params], lr))
         leaves = [parts['verts'].requires_grad_(True)] if optimization_target == 'both' else []
         leaves.append(parts['texture_pyramid'].params)
         return dict(parts, optimizable_mesh=work, optimizer=_st3d_optim.Adam(leaves, lr=lr))
+    if lam > 0.0:
+        colour = [parts['texture_map'].requires_grad_(True)] if optimization_target == 'both' else []
+        return dict(parts, optimizable_mesh=work, optimizer=_diffused_optimizer(parts, lam, colour, lr))
     leaves = [parts[name].requires_grad_(True) for name in _LEAVES[optimization_target]]
     return dict(parts, optimizable_mesh=work, optimizer=_st3d_optim.Adam(leaves, lr=lr))

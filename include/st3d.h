@@ -1093,6 +1093,35 @@ int st3d_plan_profile_read(st3d_plan *plan, float *ms_out /*host [ST3D_PROFILE_F
 int st3d_plan_profile_launches(st3d_plan *plan, int *tags_out /*host [capacity]*/, float *ms_out /*host [capacity]*/,
                                int capacity, int *count_out);
 
+/* ------------------------------------------------------------------ Laplacian-preconditioned vertex steps (diffuse.hip)
+ * Nicolet, Jacobson, Jakob, "Large Steps in Inverse Rendering of Geometry" (2021): the vertices are v = M^-1 u with
+ * M = I + lambda L, L the combinatorial Laplacian of the static topology, (L x)_i = sum over j in nbr(i) of (x_i - x_j),
+ * accumulated in exactly this form in adjacency order (nbr_off (V+1) / nbr_idx: the CSR adjacency, every index in [0, V) --
+ * the CALLER guarantees it), so that M c = c bit for bit for a constant c.  M is symmetric positive definite, lambda_min >= 1.
+ * st3d_diffuse_apply: y (V,3) = M x (V,3); x and y must not overlap.
+ * st3d_diffuse_solve: x (V,3) = M^-1 b (V,3), the three columns by plain conjugate gradients from x = 0, each column in one
+ * workgroup of 1024 threads with the whole iteration inside the kernel (no synchronisation between workgroups).  A column
+ * stops when ||r||_2 <= tol ||b||_2 on the recursive residual or after max_iter iterations, whichever comes first -- a NaN in
+ * b runs to max_iter and returns NaN in that column alone; b = 0 gives x = 0 after 0 iterations.  Dot products: fp32
+ * products added in fp64 in a fixed order; two calls give the same bits.  The search direction lives in LDS while
+ * 4 V + 256 bytes fit 160 KiB, else in the workspace; x, r and A p live in registers while V <= 4096, else in x and the
+ * workspace.  ST3D_DIFFUSE_LDS=0 puts the search direction, ST3D_DIFFUSE_REGS=0 the other three, in global memory whatever
+ * V is (both read by every call); the result is the same bits in every case.  workspace: st3d_diffuse_workspace_bytes(V) bytes (0 for V < 1), 16-byte
+ * aligned, written before it is read.  info: 3 records {int32 iterations, int32 converged, float ||r|| / ||b||} (36 bytes,
+ * 4-byte aligned), written on the device.  b and x must not overlap. */
+int st3d_diffuse_apply(const int *nbr_off, const int *nbr_idx, int V, float lambda, const float *x, float *y,
+                       st3d_stream_t stream);
+size_t st3d_diffuse_workspace_bytes(int V);
+int st3d_diffuse_solve(const int *nbr_off, const int *nbr_idx, int V, float lambda, const float *b, float *x, float tol,
+                       int max_iter, void *workspace, size_t workspace_bytes, void *info, st3d_stream_t stream);
+/* Adam with ONE second-moment denominator for the whole tensor (the update the paper above runs on u):
+ *   m <- m + (g - m)(1 - beta1);  s <- beta2 s + (1 - beta2) g^2;
+ *   p <- p - lr (m / (1 - beta1^t)) / (eps + max over all elements of sqrt(s / (1 - beta2^t)))
+ * The maximum is order-free, so the result is the same bits from run to run; a NaN moment makes it NaN.  Two launches.
+ * partials: st3d_reduce_partials() floats of scratch, written before they are read. */
+int st3d_adam_step_uniform(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, int step, float lr,
+                           float beta1, float beta2, float eps, float *partials, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-GPU
  * One process per GPU; every rank renders / VGGs its slice of the view batch with the loss means divided by the GLOBAL
  * batch (batch_denom of st3d_plan_loss) and ONE SUM all-reduce of the flat fp32 gradient (3*T*T texture floats

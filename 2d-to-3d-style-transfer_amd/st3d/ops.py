@@ -123,51 +123,60 @@ def raster_fwd(verts_ndc, faces_i32, S, z_clip=None):
     return p2f, zbuf, bary, dists
 
 
-def shade_fwd(frag, verts_uvs, faces_uvs_i32, texture):
+# ---- what the renderer wrappers below share.  These build argument tuples and buffers and never launch: every public
+# wrapper holds its own call("st3d_...") (the guarded suite finds the device wrappers by that text).
+def _frag_head(frag):
+    """the four fragment pointers in the order of the C ABI: p2f, bary, zbuf, dists"""
     p2f, zbuf, bary, dists = frag
-    B, S, _ = p2f.shape
-    T = texture.shape[0]
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
-         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, faces_uvs_i32.shape[0], verts_uvs.shape[0], dptr(rgb),
-         dptr(mask), stream_ptr())
+    return dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32)
+
+
+def _uv_head(verts_uvs, faces_uvs_i32, texture):
+    return dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32)
+
+
+def _rgb_mask(B, S, device):
+    """the (rgb (B,3,S,S), mask (B,1,S,S)) pair every shade_*_fwd fills"""
+    return torch.empty((B, 3, S, S), dtype=F32, device=device), torch.empty((B, 1, S, S), dtype=F32, device=device)
+
+
+def _det_ws(nbytes, device):
+    """-> (workspace of a fixed-point scatter, its size in bytes): whole 16-byte units, as floats"""
+    return torch.empty(((nbytes + 15) // 16 * 4,), dtype=F32, device=device), nbytes
+
+
+def _outputs(first, *optional):
+    """first [, t for every (wanted, t) of optional that is wanted]; a lone output is returned bare"""
+    out = (first,) + tuple(t for wanted, t in optional if wanted)
+    return out if len(out) > 1 else out[0]
+
+
+def shade_fwd(frag, verts_uvs, faces_uvs_i32, texture):
+    B, S, _ = frag[0].shape
+    rgb, mask = _rgb_mask(B, S, frag[0].device)
+    call("st3d_shade_fwd", *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, texture.shape[0],
+         faces_uvs_i32.shape[0], verts_uvs.shape[0], dptr(rgb), dptr(mask), stream_ptr())
     return rgb, mask
 
 
 def shade_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, grad_texture=None, want_uv=False, want_bary=False,
               want_texture=True):
     """-> grad_texture (T,T,3) [, grad_uv (B,S,S,2)] [, grad_bary (B,S,S,3)]"""
-    p2f, zbuf, bary, dists = frag
-    B, S, _ = p2f.shape
-    T = texture.shape[0]
+    B, S, _ = frag[0].shape
+    T, dev = texture.shape[0], frag[0].device
     if grad_texture is None and want_texture:
-        grad_texture = torch.zeros((T, T, 3), dtype=F32, device=p2f.device)
-    guv = torch.empty((B, S, S, 2), dtype=F32, device=p2f.device) if want_uv else None
-    gbary = torch.empty((B, S, S, 3), dtype=F32, device=p2f.device) if want_bary else None
+        grad_texture = torch.zeros((T, T, 3), dtype=F32, device=dev)
+    guv = torch.empty((B, S, S, 2), dtype=F32, device=dev) if want_uv else None
+    gbary = torch.empty((B, S, S, 3), dtype=F32, device=dev) if want_bary else None
     grad_rgb = grad_rgb.contiguous()
+    head = (dptr(grad_rgb, F32), *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, T,
+            faces_uvs_i32.shape[0], verts_uvs.shape[0], dptr(grad_texture, F32), dptr(guv), dptr(gbary))
     if _DETERMINISTIC and grad_texture is not None:
-        nb = _lib.load().st3d_shade_bwd_det_workspace_bytes(T)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=p2f.device)
-        call("st3d_shade_bwd_det", dptr(grad_rgb, F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32),
-             dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, faces_uvs_i32.shape[0],
-             verts_uvs.shape[0], dptr(grad_texture, F32), dptr(guv), dptr(gbary), dptr(ws), nb, stream_ptr())
-        out = (grad_texture,)
-        if want_uv:
-            out += (guv,)
-        if want_bary:
-            out += (gbary,)
-        return out if len(out) > 1 else out[0]
-    call("st3d_shade_bwd", dptr(grad_rgb, F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32),
-         dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, faces_uvs_i32.shape[0],
-         verts_uvs.shape[0], dptr(grad_texture, F32) if grad_texture is not None else None, dptr(guv), dptr(gbary),
-         stream_ptr())
-    out = (grad_texture,)
-    if want_uv:
-        out += (guv,)
-    if want_bary:
-        out += (gbary,)
-    return out if len(out) > 1 else out[0]
+        ws, nb = _det_ws(_lib.load().st3d_shade_bwd_det_workspace_bytes(T), dev)
+        call("st3d_shade_bwd_det", *head, dptr(ws), nb, stream_ptr())
+    else:
+        call("st3d_shade_bwd", *head, stream_ptr())
+    return _outputs(grad_texture, (want_uv, guv), (want_bary, gbary))
 
 
 # ---- per-vertex colours (csrc/vcolor.hip): TexturesVertex on the hard settings, unlit
@@ -183,20 +192,19 @@ def _vc_check(p2f, faces_i32, colours):
 
 def shade_vc_fwd(frag, faces_i32, colours):
     """frag, faces (F,3) int32, colours (V,3) -> rgb (B,3,S,S), mask (B,1,S,S)"""
-    p2f, zbuf, bary, dists = frag
+    p2f = frag[0]
     _vc_check(p2f, faces_i32, colours)
     B, S, _ = p2f.shape
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_vc_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(faces_i32, I32),
-         dptr(colours, F32), B, S, faces_i32.shape[0], colours.shape[0], dptr(rgb), dptr(mask), stream_ptr())
+    rgb, mask = _rgb_mask(B, S, p2f.device)
+    call("st3d_shade_vc_fwd", *_frag_head(frag), dptr(faces_i32, I32), dptr(colours, F32), B, S, faces_i32.shape[0],
+         colours.shape[0], dptr(rgb), dptr(mask), stream_ptr())
     return rgb, mask
 
 
 def shade_vc_bwd(grad_rgb, frag, faces_i32, colours, grad_colours=None, want_colours=True, want_bary=False):
     """-> grad_colours (V,3) (accumulated into `grad_colours` when given) [, grad_bary (B,S,S,3)]; want_colours=False
     (the vertices alone are optimised): grad_bary alone, nothing is scattered.  The scatter follows is_deterministic()."""
-    p2f, zbuf, bary, dists = frag
+    p2f = frag[0]
     _vc_check(p2f, faces_i32, colours)
     B, S, _ = p2f.shape
     V, F = colours.shape[0], faces_i32.shape[0]
@@ -210,11 +218,10 @@ def shade_vc_bwd(grad_rgb, frag, faces_i32, colours, grad_colours=None, want_col
         grad_colours = torch.zeros((V, 3), dtype=F32, device=p2f.device)
     gbary = torch.empty((B, S, S, 3), dtype=F32, device=p2f.device) if want_bary else None
     grad_rgb = grad_rgb.contiguous()
-    head = (dptr(grad_rgb, F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(faces_i32, I32),
-            dptr(colours, F32), B, S, F, V, dptr(grad_colours, F32), dptr(gbary))
+    head = (dptr(grad_rgb, F32), *_frag_head(frag), dptr(faces_i32, I32), dptr(colours, F32), B, S, F, V,
+            dptr(grad_colours, F32), dptr(gbary))
     if _DETERMINISTIC and grad_colours is not None:
-        nb = _lib.load().st3d_shade_vc_bwd_det_workspace_bytes(V)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=p2f.device)
+        ws, nb = _det_ws(_lib.load().st3d_shade_vc_bwd_det_workspace_bytes(V), p2f.device)
         call("st3d_shade_vc_bwd_det", *head, dptr(ws), nb, stream_ptr())
     else:
         call("st3d_shade_vc_bwd", *head, stream_ptr())
@@ -239,22 +246,20 @@ def _atlas_check(p2f, F, R):
 
 def shade_atlas_fwd(frag, atlas):
     """frag, atlas (F,R,R,3) -> rgb (B,3,S,S), mask (B,1,S,S)"""
-    p2f, zbuf, bary, dists = frag
+    p2f = frag[0]
     if atlas.dim() != 4 or atlas.shape[3] != 3 or atlas.shape[1] != atlas.shape[2]:
         raise ValueError(f"atlas must be (F, R, R, 3), got {tuple(atlas.shape)}")
     F, R = atlas.shape[0], atlas.shape[1]
     _atlas_check(p2f, F, R)
     B, S, _ = p2f.shape
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_atlas_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(atlas, F32), B, S,
-         F, R, dptr(rgb), dptr(mask), stream_ptr())
+    rgb, mask = _rgb_mask(B, S, p2f.device)
+    call("st3d_shade_atlas_fwd", *_frag_head(frag), dptr(atlas, F32), B, S, F, R, dptr(rgb), dptr(mask), stream_ptr())
     return rgb, mask
 
 
 def shade_atlas_bwd(grad_rgb, frag, R, F, grad_atlas=None):
     """-> grad_atlas (F,R,R,3) (accumulated into `grad_atlas` when given).  The scatter follows is_deterministic()."""
-    p2f, zbuf, bary, dists = frag
+    p2f = frag[0]
     R, F = int(R), int(F)
     _atlas_check(p2f, F, R)
     B, S, _ = p2f.shape
@@ -265,11 +270,9 @@ def shade_atlas_bwd(grad_rgb, frag, R, F, grad_atlas=None):
     elif tuple(grad_atlas.shape) != (F, R, R, 3):
         raise ValueError(f"grad_atlas must be {(F, R, R, 3)}, got {tuple(grad_atlas.shape)}")
     grad_rgb = grad_rgb.contiguous()
-    head = (dptr(grad_rgb, F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), B, S, F, R,
-            dptr(grad_atlas, F32))
+    head = (dptr(grad_rgb, F32), *_frag_head(frag), B, S, F, R, dptr(grad_atlas, F32))
     if _DETERMINISTIC:
-        nb = _lib.load().st3d_shade_atlas_bwd_det_workspace_bytes(F, R)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=p2f.device)
+        ws, nb = _det_ws(_lib.load().st3d_shade_atlas_bwd_det_workspace_bytes(F, R), p2f.device)
         call("st3d_shade_atlas_bwd_det", *head, dptr(ws), nb, stream_ptr())
     else:
         call("st3d_shade_atlas_bwd", *head, stream_ptr())
@@ -323,45 +326,34 @@ def box_down_bwd(grad_out, a):
 
 def shade_ss_fwd(frag, verts_uvs, faces_uvs_i32, texture, a):
     """frag at side a*S -> rgb (B,3,S,S), coverage (B,1,S,S) in {0, 1/a^2, ..., 1}"""
-    p2f, zbuf, bary, dists = frag
-    B, S = _ss_side(p2f, a)
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    cov = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_ss_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
-         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, a, texture.shape[0], faces_uvs_i32.shape[0], verts_uvs.shape[0],
-         dptr(rgb), dptr(cov), stream_ptr())
+    B, S = _ss_side(frag[0], a)
+    rgb, cov = _rgb_mask(B, S, frag[0].device)
+    call("st3d_shade_ss_fwd", *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, a, texture.shape[0],
+         faces_uvs_i32.shape[0], verts_uvs.shape[0], dptr(rgb), dptr(cov), stream_ptr())
     return rgb, cov
 
 
 def shade_ss_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, a, grad_texture=None, want_uv=False, want_bary=False,
                  want_texture=True):
     """grad_rgb (B,3,S,S), frag at side a*S -> grad_texture (T,T,3) [, grad_uv (B,aS,aS,2)] [, grad_bary (B,aS,aS,3)]"""
-    p2f, zbuf, bary, dists = frag
-    B, S = _ss_side(p2f, a)
+    B, S = _ss_side(frag[0], a)
     SS = a * S
-    T = texture.shape[0]
+    T, dev = texture.shape[0], frag[0].device
     if tuple(grad_rgb.shape) != (B, 3, S, S):
         raise ValueError(f"grad_rgb must be {(B, 3, S, S)}, got {tuple(grad_rgb.shape)}")
     if grad_texture is None and want_texture:
-        grad_texture = torch.zeros((T, T, 3), dtype=F32, device=p2f.device)
-    guv = torch.empty((B, SS, SS, 2), dtype=F32, device=p2f.device) if want_uv else None
-    gbary = torch.empty((B, SS, SS, 3), dtype=F32, device=p2f.device) if want_bary else None
+        grad_texture = torch.zeros((T, T, 3), dtype=F32, device=dev)
+    guv = torch.empty((B, SS, SS, 2), dtype=F32, device=dev) if want_uv else None
+    gbary = torch.empty((B, SS, SS, 3), dtype=F32, device=dev) if want_bary else None
     grad_rgb = grad_rgb.contiguous()
-    head = (dptr(grad_rgb, F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
-            dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, a, T, faces_uvs_i32.shape[0], verts_uvs.shape[0],
-            dptr(grad_texture, F32) if grad_texture is not None else None, dptr(guv), dptr(gbary))
+    head = (dptr(grad_rgb, F32), *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, a, T,
+            faces_uvs_i32.shape[0], verts_uvs.shape[0], dptr(grad_texture, F32), dptr(guv), dptr(gbary))
     if _DETERMINISTIC and grad_texture is not None:
-        nb = _lib.load().st3d_shade_bwd_det_workspace_bytes(T)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=p2f.device)
+        ws, nb = _det_ws(_lib.load().st3d_shade_bwd_det_workspace_bytes(T), dev)
         call("st3d_shade_ss_bwd_det", *head, dptr(ws), nb, stream_ptr())
     else:
         call("st3d_shade_ss_bwd", *head, stream_ptr())
-    out = (grad_texture,)
-    if want_uv:
-        out += (guv,)
-    if want_bary:
-        out += (gbary,)
-    return out if len(out) > 1 else out[0]
+    return _outputs(grad_texture, (want_uv, guv), (want_bary, gbary))
 
 
 def raster_bwd(grad_bary, p2f, verts_ndc, faces_i32):
@@ -369,14 +361,13 @@ def raster_bwd(grad_bary, p2f, verts_ndc, faces_i32):
     B, V, _ = verts_ndc.shape
     S = p2f.shape[1]
     g = torch.empty((B, V, 3), dtype=F32, device=verts_ndc.device)
+    head = (dptr(grad_bary, F32), dptr(p2f, I32), dptr(verts_ndc, F32), dptr(faces_i32, I32), B, V, faces_i32.shape[0], S,
+            dptr(g))
     if _DETERMINISTIC:
-        nb = _lib.load().st3d_raster_bwd_det_workspace_bytes(B, V, S)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=verts_ndc.device)
-        call("st3d_raster_bwd_det", dptr(grad_bary, F32), dptr(p2f, I32), dptr(verts_ndc, F32), dptr(faces_i32, I32), B, V,
-             faces_i32.shape[0], S, dptr(g), dptr(ws), nb, stream_ptr())
-        return g
-    call("st3d_raster_bwd", dptr(grad_bary, F32), dptr(p2f, I32), dptr(verts_ndc, F32), dptr(faces_i32, I32), B, V,
-         faces_i32.shape[0], S, dptr(g), stream_ptr())
+        ws, nb = _det_ws(_lib.load().st3d_raster_bwd_det_workspace_bytes(B, V, S), verts_ndc.device)
+        call("st3d_raster_bwd_det", *head, dptr(ws), nb, stream_ptr())
+    else:
+        call("st3d_raster_bwd", *head, stream_ptr())
     return g
 
 
@@ -830,38 +821,37 @@ def _bg3(background):
 
 
 def shade_soft_fwd(frag, verts_uvs, faces_uvs_i32, texture, sigma=1e-4, gamma=1e-4, background=(1.0, 1.0, 1.0)):
-    p2f, zbuf, bary, dists = frag
-    B, S, _, K = p2f.shape
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    alpha = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_soft_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
-         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, texture.shape[0], K, float(sigma), float(gamma), _bg3(background),
-         dptr(rgb), dptr(alpha), stream_ptr())
+    B, S, _, K = frag[0].shape
+    rgb, alpha = _rgb_mask(B, S, frag[0].device)
+    call("st3d_shade_soft_fwd", *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, texture.shape[0], K,
+         float(sigma), float(gamma), _bg3(background), dptr(rgb), dptr(alpha), stream_ptr())
     return rgb, alpha
+
+
+def _soft_grads(T, B, S, K, want_texture, want_geometry, dev):
+    """-> grad_texture (T,T,3) zeros | None, (grad_bary (B,S,S,K,3), grad_zbuf (B,S,S,K), grad_dists (B,S,S,K)) | None"""
+    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
+    if not want_geometry:
+        return gt, None
+    return gt, (torch.empty((B, S, S, K, 3), dtype=F32, device=dev), torch.empty((B, S, S, K), dtype=F32, device=dev),
+                torch.empty((B, S, S, K), dtype=F32, device=dev))
 
 
 def shade_soft_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, sigma=1e-4, gamma=1e-4, background=(1.0, 1.0, 1.0),
                    want_texture=True, want_geometry=True):
     """-> (grad_texture (T,T,3) | None, (grad_bary, grad_zbuf, grad_dists) | None)"""
-    p2f, zbuf, bary, dists = frag
-    B, S, _, K = p2f.shape
+    B, S, _, K = frag[0].shape
     T = texture.shape[0]
-    dev = p2f.device
-    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
-    gb = torch.empty((B, S, S, K, 3), dtype=F32, device=dev) if want_geometry else None
-    gz = torch.empty((B, S, S, K), dtype=F32, device=dev) if want_geometry else None
-    gd = torch.empty((B, S, S, K), dtype=F32, device=dev) if want_geometry else None
-    if _DETERMINISTIC and gt is not None:       # fixed-point texture scatter: bitwise reproducible (st3d_shade_soft_bwd_det)
-        nb = _lib.load().st3d_shade_soft_bwd_det_workspace_bytes(T)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
-        call("st3d_shade_soft_bwd_det", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
-             dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, K, float(sigma),
-             float(gamma), _bg3(background), dptr(gt), dptr(gb), dptr(gz), dptr(gd), dptr(ws), nb, stream_ptr())
-        return gt, ((gb, gz, gd) if want_geometry else None)
-    call("st3d_shade_soft_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
-         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, K, float(sigma),
-         float(gamma), _bg3(background), dptr(gt), dptr(gb), dptr(gz), dptr(gd), stream_ptr())
-    return gt, ((gb, gz, gd) if want_geometry else None)
+    gt, geo = _soft_grads(T, B, S, K, want_texture, want_geometry, frag[0].device)
+    gb, gz, gd = geo or (None, None, None)
+    head = (dptr(grad_rgb.contiguous(), F32), *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, T, K,
+            float(sigma), float(gamma), _bg3(background), dptr(gt), dptr(gb), dptr(gz), dptr(gd))
+    if _DETERMINISTIC and gt is not None:       # fixed-point texture scatter: bitwise reproducible
+        ws, nb = _det_ws(_lib.load().st3d_shade_soft_bwd_det_workspace_bytes(T), frag[0].device)
+        call("st3d_shade_soft_bwd_det", *head, dptr(ws), nb, stream_ptr())
+    else:
+        call("st3d_shade_soft_bwd", *head, stream_ptr())
+    return gt, geo
 
 
 def raster_soft_bwd(grads, p2f, verts_ndc, faces_i32, clip_bary, perspective_correct=True, slots=None, z_clip=None):
@@ -869,17 +859,14 @@ def raster_soft_bwd(grads, p2f, verts_ndc, faces_i32, clip_bary, perspective_cor
     B, V, _ = verts_ndc.shape
     S, K = p2f.shape[1], p2f.shape[3]
     g = torch.empty((B, V, 3), dtype=F32, device=verts_ndc.device)
-    if _DETERMINISTIC:                          # fixed-point vertex scatter (st3d_raster_soft_bwd_det)
-        nb = _lib.load().st3d_raster_soft_bwd_det_workspace_bytes(B, V, S)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=verts_ndc.device)
-        call("st3d_raster_soft_bwd_det", dptr(gb, F32), dptr(gz, F32), dptr(gd, F32), dptr(p2f, I32), dptr(verts_ndc, F32),
-             dptr(faces_i32, I32), B, V, faces_i32.shape[0], S, K, 1 if clip_bary else 0, 1 if perspective_correct else 0,
-             dptr(slots, I32) if slots is not None else None, float(z_clip) if z_clip is not None else 0.0, dptr(g), dptr(ws), nb,
-             stream_ptr())
-        return g
-    call("st3d_raster_soft_bwd", dptr(gb, F32), dptr(gz, F32), dptr(gd, F32), dptr(p2f, I32), dptr(verts_ndc, F32),
-         dptr(faces_i32, I32), B, V, faces_i32.shape[0], S, K, 1 if clip_bary else 0, 1 if perspective_correct else 0,
-         dptr(slots, I32) if slots is not None else None, float(z_clip) if z_clip is not None else 0.0, dptr(g), stream_ptr())
+    head = (dptr(gb, F32), dptr(gz, F32), dptr(gd, F32), dptr(p2f, I32), dptr(verts_ndc, F32), dptr(faces_i32, I32), B, V,
+            faces_i32.shape[0], S, K, 1 if clip_bary else 0, 1 if perspective_correct else 0, dptr(slots, I32),
+            float(z_clip) if z_clip is not None else 0.0, dptr(g))
+    if _DETERMINISTIC:                          # fixed-point vertex scatter
+        ws, nb = _det_ws(_lib.load().st3d_raster_soft_bwd_det_workspace_bytes(B, V, S), verts_ndc.device)
+        call("st3d_raster_soft_bwd_det", *head, dptr(ws), nb, stream_ptr())
+    else:
+        call("st3d_raster_soft_bwd", *head, stream_ptr())
     return g
 
 
@@ -996,14 +983,10 @@ def silraster_bwd(state, verts_ndc, faces_i32, blur_radius, sigma=1e-4, grad_alp
     rec = _silraster_records(verts_ndc, faces_i32, perspective_correct, z_clip)
     S, blur, clip, cull, persp = _silraster_common(state.shape[2], blur_radius, clip_bary, cull_backfaces, perspective_correct)
     g = torch.empty((B, V, 3), dtype=F32, device=dev)
-    ws, nb = None, 0
-    if _DETERMINISTIC:
-        nb = _lib.load().st3d_silraster_bwd_workspace_bytes(B, V, S)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
+    ws, nb = _det_ws(_lib.load().st3d_silraster_bwd_workspace_bytes(B, V, S), dev) if _DETERMINISTIC else (None, 0)
     ga = grad_alpha.to(F32).contiguous() if grad_alpha is not None else None
     call("st3d_silraster_bwd", dptr(rec), dptr(verts_ndc, F32), dptr(faces_i32, I32), B, V, F, S, blur, clip, cull, persp,
-         float(z_clip), sigma, dptr(state, F32), dptr(ga, F32) if ga is not None else None, float(grad_scale), dptr(g),
-         dptr(ws) if ws is not None else None, nb, stream_ptr())
+         float(z_clip), sigma, dptr(state, F32), dptr(ga, F32), float(grad_scale), dptr(g), dptr(ws), nb, stream_ptr())
     return g
 
 
@@ -1039,103 +1022,80 @@ def _lit_ptrs(lit):
             dptr(lit.faces_i32, I32), dptr(lit.R, F32), dptr(lit.T, F32), dptr(lit.block, F32), lit.block.shape[0], lit.kind)
 
 
+def _lit_grads(T, B, s, want_texture, want_geometry, dev):
+    """-> grad_texture (T,T,3) zeros | None, grad_bary (B,s,s,3) | None, grad_np (B,s,s,6) | None, det workspace | None, its
+    bytes"""
+    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
+    gb = torch.empty((B, s, s, 3), dtype=F32, device=dev) if want_geometry else None
+    gnp = torch.empty((B, s, s, 6), dtype=F32, device=dev) if want_geometry else None
+    if _DETERMINISTIC and gt is not None:
+        return (gt, gb, gnp) + _det_ws(_lib.load().st3d_shade_bwd_det_workspace_bytes(T), dev)
+    return gt, gb, gnp, None, 0
+
+
 def shade_lit_fwd(frag, verts_uvs, faces_uvs_i32, texture, lit):
-    p2f, zbuf, bary, dists = frag
-    B, S, _ = p2f.shape
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_lit_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
-         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, texture.shape[0], faces_uvs_i32.shape[0], verts_uvs.shape[0],
-         *_lit_ptrs(lit), dptr(rgb), dptr(mask), stream_ptr())
+    B, S, _ = frag[0].shape
+    rgb, mask = _rgb_mask(B, S, frag[0].device)
+    call("st3d_shade_lit_fwd", *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, texture.shape[0],
+         faces_uvs_i32.shape[0], verts_uvs.shape[0], *_lit_ptrs(lit), dptr(rgb), dptr(mask), stream_ptr())
     return rgb, mask
 
 
 def shade_lit_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, lit, want_texture=True, want_geometry=False):
     """-> (grad_texture (T,T,3) | None, grad_bary (B,S,S,3) | None, grad_np (B,S,S,6) | None)"""
-    p2f, zbuf, bary, dists = frag
-    B, S, _ = p2f.shape
+    B, S, _ = frag[0].shape
     T = texture.shape[0]
-    dev = p2f.device
-    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
-    gb = torch.empty((B, S, S, 3), dtype=F32, device=dev) if want_geometry else None
-    gnp = torch.empty((B, S, S, 6), dtype=F32, device=dev) if want_geometry else None
-    ws, nb = None, 0
-    if _DETERMINISTIC and gt is not None:
-        nb = _lib.load().st3d_shade_bwd_det_workspace_bytes(T)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
-    call("st3d_shade_lit_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
-         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, faces_uvs_i32.shape[0],
-         verts_uvs.shape[0], *_lit_ptrs(lit), float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gnp), dptr(ws), nb,
-         stream_ptr())
+    gt, gb, gnp, ws, nb = _lit_grads(T, B, S, want_texture, want_geometry, frag[0].device)
+    call("st3d_shade_lit_bwd", dptr(grad_rgb.contiguous(), F32), *_frag_head(frag),
+         *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, T, faces_uvs_i32.shape[0], verts_uvs.shape[0], *_lit_ptrs(lit),
+         float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gnp), dptr(ws), nb, stream_ptr())
     return gt, gb, gnp
 
 
 def shade_ss_lit_fwd(frag, verts_uvs, faces_uvs_i32, texture, lit, a):
-    p2f, zbuf, bary, dists = frag
-    B, S = _ss_side(p2f, a)
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    cov = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_ss_lit_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
-         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, a, texture.shape[0], faces_uvs_i32.shape[0], verts_uvs.shape[0],
-         *_lit_ptrs(lit), dptr(rgb), dptr(cov), stream_ptr())
+    B, S = _ss_side(frag[0], a)
+    rgb, cov = _rgb_mask(B, S, frag[0].device)
+    call("st3d_shade_ss_lit_fwd", *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, a, texture.shape[0],
+         faces_uvs_i32.shape[0], verts_uvs.shape[0], *_lit_ptrs(lit), dptr(rgb), dptr(cov), stream_ptr())
     return rgb, cov
 
 
 def shade_ss_lit_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, lit, a, want_texture=True, want_geometry=False):
     """-> (grad_texture (T,T,3) | None, grad_bary (B,aS,aS,3) | None, grad_np (B,aS,aS,6) | None)"""
-    p2f, zbuf, bary, dists = frag
-    B, S = _ss_side(p2f, a)
-    SS = a * S
+    B, S = _ss_side(frag[0], a)
     T = texture.shape[0]
-    dev = p2f.device
     if tuple(grad_rgb.shape) != (B, 3, S, S):
         raise ValueError(f"grad_rgb must be {(B, 3, S, S)}, got {tuple(grad_rgb.shape)}")
-    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
-    gb = torch.empty((B, SS, SS, 3), dtype=F32, device=dev) if want_geometry else None
-    gnp = torch.empty((B, SS, SS, 6), dtype=F32, device=dev) if want_geometry else None
-    ws, nb = None, 0
-    if _DETERMINISTIC and gt is not None:
-        nb = _lib.load().st3d_shade_bwd_det_workspace_bytes(T)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
-    call("st3d_shade_ss_lit_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
-         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, a, T,
-         faces_uvs_i32.shape[0], verts_uvs.shape[0], *_lit_ptrs(lit), float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gnp),
-         dptr(ws), nb, stream_ptr())
+    gt, gb, gnp, ws, nb = _lit_grads(T, B, a * S, want_texture, want_geometry, frag[0].device)
+    call("st3d_shade_ss_lit_bwd", dptr(grad_rgb.contiguous(), F32), *_frag_head(frag),
+         *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, a, T, faces_uvs_i32.shape[0], verts_uvs.shape[0], *_lit_ptrs(lit),
+         float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gnp), dptr(ws), nb, stream_ptr())
     return gt, gb, gnp
 
 
 def shade_soft_lit_fwd(frag, verts_uvs, faces_uvs_i32, texture, lit, sigma=1e-4, gamma=1e-4, background=(1.0, 1.0, 1.0)):
-    p2f, zbuf, bary, dists = frag
-    B, S, _, K = p2f.shape
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    alpha = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_soft_lit_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
-         dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, texture.shape[0], K, float(sigma), float(gamma), _bg3(background),
-         *_lit_ptrs(lit), dptr(rgb), dptr(alpha), stream_ptr())
+    B, S, _, K = frag[0].shape
+    rgb, alpha = _rgb_mask(B, S, frag[0].device)
+    call("st3d_shade_soft_lit_fwd", *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, texture.shape[0],
+         K, float(sigma), float(gamma), _bg3(background), *_lit_ptrs(lit), dptr(rgb), dptr(alpha), stream_ptr())
     return rgb, alpha
 
 
 def shade_soft_lit_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, texture, lit, sigma=1e-4, gamma=1e-4,
                        background=(1.0, 1.0, 1.0), want_texture=True, want_geometry=True):
     """-> (grad_texture | None, (grad_bary, grad_zbuf, grad_dists) | None, grad_np (B,S,S,K,6) | None)"""
-    p2f, zbuf, bary, dists = frag
-    B, S, _, K = p2f.shape
-    T = texture.shape[0]
-    dev = p2f.device
-    gt = torch.zeros((T, T, 3), dtype=F32, device=dev) if want_texture else None
-    gb = torch.empty((B, S, S, K, 3), dtype=F32, device=dev) if want_geometry else None
-    gz = torch.empty((B, S, S, K), dtype=F32, device=dev) if want_geometry else None
-    gd = torch.empty((B, S, S, K), dtype=F32, device=dev) if want_geometry else None
+    B, S, _, K = frag[0].shape
+    T, dev = texture.shape[0], frag[0].device
+    gt, geo = _soft_grads(T, B, S, K, want_texture, want_geometry, dev)
+    gb, gz, gd = geo or (None, None, None)
     gnp = torch.empty((B, S, S, K, 6), dtype=F32, device=dev) if want_geometry else None
-    ws, nb = None, 0
-    if _DETERMINISTIC and gt is not None:
-        nb = _lib.load().st3d_shade_soft_bwd_det_workspace_bytes(T)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
-    call("st3d_shade_soft_lit_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
-         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(texture, F32), B, S, T, K, float(sigma),
-         float(gamma), _bg3(background), *_lit_ptrs(lit), float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gz), dptr(gd),
-         dptr(gnp), dptr(ws), nb, stream_ptr())
-    return gt, ((gb, gz, gd) if want_geometry else None), gnp
+    ws, nb = (_det_ws(_lib.load().st3d_shade_soft_bwd_det_workspace_bytes(T), dev) if _DETERMINISTIC and gt is not None
+              else (None, 0))
+    call("st3d_shade_soft_lit_bwd", dptr(grad_rgb.contiguous(), F32), *_frag_head(frag),
+         *_uv_head(verts_uvs, faces_uvs_i32, texture), B, S, T, K, float(sigma), float(gamma), _bg3(background),
+         *_lit_ptrs(lit), float(lit.weight_bound), dptr(gt), dptr(gb), dptr(gz), dptr(gd), dptr(gnp), dptr(ws), nb,
+         stream_ptr())
+    return gt, geo, gnp
 
 
 def phong_scatter(grad_np, p2f, bary, faces_i32, V):
@@ -1144,10 +1104,7 @@ def phong_scatter(grad_np, p2f, bary, faces_i32, V):
     K = p2f.shape[3] if p2f.dim() == 4 else 1
     dev = p2f.device
     out = torch.empty((2, V, 3), dtype=F32, device=dev)
-    ws, nb = None, 0
-    if _DETERMINISTIC:
-        nb = _lib.load().st3d_phong_scatter_workspace_bytes(B, V, S)
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
+    ws, nb = _det_ws(_lib.load().st3d_phong_scatter_workspace_bytes(B, V, S), dev) if _DETERMINISTIC else (None, 0)
     call("st3d_phong_scatter", dptr(grad_np, F32), dptr(p2f, I32), dptr(bary, F32), dptr(faces_i32, I32), B, V,
          faces_i32.shape[0], S, K, dptr(out), dptr(ws), nb, stream_ptr())
     return out
@@ -1807,14 +1764,12 @@ def _mip_check_planes(p2f, pyramid, lod, T, L):
 
 def shade_mip_fwd(frag, verts_uvs, faces_uvs_i32, pyramid, lod, T, L):
     """shade_fwd sampling the packed chain trilinearly at lod -> rgb (B,3,S,S), mask (B,1,S,S)"""
-    p2f, zbuf, bary, dists = frag
+    p2f = frag[0]
     B, S, _ = p2f.shape
     _mip_check_planes(p2f, pyramid, lod, T, L)
-    rgb = torch.empty((B, 3, S, S), dtype=F32, device=p2f.device)
-    mask = torch.empty((B, 1, S, S), dtype=F32, device=p2f.device)
-    call("st3d_shade_mip_fwd", dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32), dptr(dists, F32), dptr(verts_uvs, F32),
-         dptr(faces_uvs_i32, I32), dptr(pyramid, F32), dptr(lod, F32), B, S, int(T), int(L), faces_uvs_i32.shape[0],
-         verts_uvs.shape[0], dptr(rgb), dptr(mask), stream_ptr())
+    rgb, mask = _rgb_mask(B, S, p2f.device)
+    call("st3d_shade_mip_fwd", *_frag_head(frag), *_uv_head(verts_uvs, faces_uvs_i32, pyramid), dptr(lod, F32), B, S, int(T),
+         int(L), faces_uvs_i32.shape[0], verts_uvs.shape[0], dptr(rgb), dptr(mask), stream_ptr())
     return rgb, mask
 
 
@@ -1822,7 +1777,7 @@ def shade_mip_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, pyramid, lod, T, L, 
                   want_bary=False, want_texture=True, want_levels=False):
     """-> grad_texture (T,T,3) [, grad_uv (B,S,S,2)] [, grad_bary (B,S,S,3)] [, the per-level gradient (P,) before the
     fold]; lod is a constant.  Fixed point (bitwise reproducible) unless set_deterministic(False)."""
-    p2f, zbuf, bary, dists = frag
+    p2f = frag[0]
     B, S, _ = p2f.shape
     dev = p2f.device
     _mip_check_planes(p2f, pyramid, lod, T, L)
@@ -1833,22 +1788,12 @@ def shade_mip_bwd(grad_rgb, frag, verts_uvs, faces_uvs_i32, pyramid, lod, T, L, 
     gpyr = torch.empty((pyramid.numel(),), dtype=F32, device=dev) if grad_texture is not None else None
     guv = torch.empty((B, S, S, 2), dtype=F32, device=dev) if want_uv else None
     gbary = torch.empty((B, S, S, 3), dtype=F32, device=dev) if want_bary else None
-    ws, nb = None, 0
-    if _DETERMINISTIC and grad_texture is not None:
-        nb = _lib.load().st3d_shade_mip_bwd_workspace_bytes(int(T), int(L))
-        ws = torch.empty(((nb + 15) // 16 * 4,), dtype=F32, device=dev)
-    call("st3d_shade_mip_bwd", dptr(grad_rgb.contiguous(), F32), dptr(p2f, I32), dptr(bary, F32), dptr(zbuf, F32),
-         dptr(dists, F32), dptr(verts_uvs, F32), dptr(faces_uvs_i32, I32), dptr(pyramid, F32), dptr(lod, F32), B, S, int(T),
-         int(L), faces_uvs_i32.shape[0], verts_uvs.shape[0], dptr(gpyr), dptr(grad_texture, F32) if grad_texture is not None
-         else None, dptr(guv), dptr(gbary), dptr(ws), nb, stream_ptr())
-    out = (grad_texture,)
-    if want_uv:
-        out += (guv,)
-    if want_bary:
-        out += (gbary,)
-    if want_levels:
-        out += (gpyr,)
-    return out if len(out) > 1 else out[0]
+    ws, nb = (_det_ws(_lib.load().st3d_shade_mip_bwd_workspace_bytes(int(T), int(L)), dev)
+              if _DETERMINISTIC and grad_texture is not None else (None, 0))
+    call("st3d_shade_mip_bwd", dptr(grad_rgb.contiguous(), F32), *_frag_head(frag),
+         *_uv_head(verts_uvs, faces_uvs_i32, pyramid), dptr(lod, F32), B, S, int(T), int(L), faces_uvs_i32.shape[0],
+         verts_uvs.shape[0], dptr(gpyr), dptr(grad_texture, F32), dptr(guv), dptr(gbary), dptr(ws), nb, stream_ptr())
+    return _outputs(grad_texture, (want_uv, guv), (want_bary, gbary), (want_levels, gpyr))
 
 
 def adam_step(p, g, m, v, step, lr, b1=0.9, b2=0.999, eps=1e-8):

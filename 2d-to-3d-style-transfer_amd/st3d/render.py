@@ -806,19 +806,64 @@ def _refuse_supersampled_silhouette(raster_settings):
         raise NotImplementedError(MIP_REFUSALS["silhouette"])
 
 
+# ---- what the autograd Functions below share: the prologue of every forward (inputs as the kernels take them) and the
+# vertex tail of every backward.  A new shading family is expected to use these rather than copy a neighbour.
+def _verts32(verts):
+    return verts.detach().to(torch.float32).contiguous()
+
+
+def _square_map(tex_map):
+    """a texture map (..., T, T, 3) as the kernels take it: (T,T,3) float32"""
+    tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
+    if tex.shape[0] != tex.shape[1]:
+        raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
+    return tex
+
+
+def _uvs32(verts_uvs):
+    return verts_uvs.detach().to(torch.float32).reshape(-1, 2).contiguous()
+
+
+def _rasterise(v, faces_i32, R, T, side):
+    """-> (projected vertices, hard K = 1 fragments at `side`).  No near-plane watch: the callers of the Functions have looked
+    at the vertices' depths before choosing these kernels."""
+    ndc = ops.project_verts(v, R, T)
+    return ndc, ops.raster_fwd(ndc, faces_i32, side)
+
+
+def _verts_grad(ctx, gbary, gnp=None):
+    """The hard path's vertex tail: d/d(bary) -> raster backward -> projection backward [-> the lighting's
+    direct terms, given the lit kernels' gnp] -> the vertices' own shape.  ctx: frag, geom, verts_shape [, lit]."""
+    v, ndc, faces_i32, R, T = ctx.geom
+    gverts = ops.project_verts_bwd(v, R, T, ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32))
+    if gnp is not None:
+        gverts = _lit_vertex_grad(ctx.lit, gverts, gnp, ctx.frag[0], ctx.frag[2])
+    return gverts.reshape(ctx.verts_shape)
+
+
+def _soft_verts_grad(ctx, geo, gnp=None):
+    """_verts_grad on the general path: geo = (d/d(bary), d/d(zbuf), d/d(dists)), each may be None.  ctx: frag, geom,
+    verts_shape, clip, persp, slots, z_clip [, lit]."""
+    v, ndc, faces_i32, R, T = ctx.geom
+    gndc = ops.raster_soft_bwd(geo, ctx.frag[0], ndc, faces_i32, ctx.clip, ctx.persp, ctx.slots, ctx.z_clip)
+    gverts = ops.project_verts_bwd(v, R, T, gndc)
+    if gnp is not None:
+        gverts = _lit_vertex_grad(ctx.lit, gverts, gnp, ctx.frag[0], ctx.frag[2])
+    return gverts.reshape(ctx.verts_shape)
+
+
 class _SilhouetteFn(torch.autograd.Function):
     """verts -> alpha (B,1,S,S): project, general raster, silhouette_fwd; backward silhouette_bwd -> raster_soft_bwd with
     d/d(dists) alone -> project_verts_bwd."""
 
     @staticmethod
     def forward(ctx, verts, faces_i32, R, T, S, K, blur, clip, sigma, cull, persp, z_clip):
-        v = verts.detach().to(torch.float32).contiguous()
+        v = _verts32(verts)
         ndc = ops.project_verts(v, R, T)
         p2f, _zbuf, _bary, dists, slots = ops.raster_soft_fwd(ndc, faces_i32, S, K, blur, clip, cull, persp, z_clip)
         ctx.frag, ctx.slots = (p2f, dists), slots
-        ctx.args = (clip, sigma, persp, z_clip)
-        ctx.geom = (v, ndc, faces_i32, R, T)
-        ctx.verts_shape = verts.shape
+        ctx.clip, ctx.sigma, ctx.persp, ctx.z_clip = clip, sigma, persp, z_clip
+        ctx.geom, ctx.verts_shape = (v, ndc, faces_i32, R, T), verts.shape
         return ops.silhouette_fwd(p2f, dists, sigma)
 
     @staticmethod
@@ -826,11 +871,8 @@ class _SilhouetteFn(torch.autograd.Function):
         with ops.trace("render_backward"):
             gverts = None
             if ctx.needs_input_grad[0]:
-                clip, sigma, persp, z_clip = ctx.args
-                v, ndc, faces_i32, R, T = ctx.geom
-                gd = ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[1], sigma)
-                gndc = ops.raster_soft_bwd((None, None, gd), ctx.frag[0], ndc, faces_i32, clip, persp, ctx.slots, z_clip)
-                gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
+                gd = ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[1], ctx.sigma)
+                gverts = _soft_verts_grad(ctx, (None, None, gd))
             return (gverts,) + (None,) * 11
 
 
@@ -841,7 +883,7 @@ class _SilhouetteRasterFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, faces_i32, R, T, S, K, blur, clip, sigma, cull, persp, z_clip):
-        v = verts.detach().to(torch.float32).contiguous()
+        v = _verts32(verts)
         ndc = ops.project_verts(v, R, T)
         alpha, state = ops.silraster_fwd(ndc, faces_i32, S, K, blur, sigma, clip, cull, persp, z_clip)
         ctx.saved = (state if verts.requires_grad else None, v, faces_i32, R, T)
@@ -869,14 +911,11 @@ def render_silhouette(meshes, R, T, image_size, raster_settings=None, blend_para
     rs = raster_settings if raster_settings is not None else RasterizationSettings(image_size=image_size)
     _refuse_supersampled_silhouette(rs)
     bp = blend_params if blend_params is not None else BlendParams()
+    fn = _SilhouetteRasterFn if isinstance(rs, SilhouetteRasterizationSettings) else _SilhouetteFn
     with ops.trace("render"):
-        if isinstance(rs, SilhouetteRasterizationSettings):
-            return _SilhouetteRasterFn.apply(meshes.verts_packed(), meshes.faces_i32(), R.to(dev), T.to(dev), int(image_size),
-                                             rs.faces_per_pixel, rs.blur_radius, rs.clip_barycentric_coords, bp.sigma,
-                                             rs.cull_backfaces, rs.perspective_correct, rs.z_clip)
-        return _SilhouetteFn.apply(meshes.verts_packed(), meshes.faces_i32(), R.to(dev), T.to(dev), int(image_size),
-                                   rs.faces_per_pixel, rs.blur_radius, rs.clip_barycentric_coords, bp.sigma,
-                                   rs.cull_backfaces, rs.perspective_correct, rs.z_clip)
+        return fn.apply(meshes.verts_packed(), meshes.faces_i32(), R.to(dev), T.to(dev), int(image_size), rs.faces_per_pixel,
+                        rs.blur_radius, rs.clip_barycentric_coords, bp.sigma, rs.cull_backfaces, rs.perspective_correct,
+                        rs.z_clip)
 
 
 class _RenderFn(torch.autograd.Function):
@@ -885,11 +924,7 @@ class _RenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, lighting=None):
-        v = verts.detach().to(torch.float32).contiguous()
-        tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
-        if tex.shape[0] != tex.shape[1]:
-            raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
-        uvs = verts_uvs.detach().to(torch.float32).reshape(-1, 2).contiguous()
+        v, tex, uvs = _verts32(verts), _square_map(tex_map), _uvs32(verts_uvs)
         # the calling rasteriser's FragmentCache (_render_views names it for the length of this call): geometry that is not
         # being optimised is projected and rasterised once per batch of views
         cache, entry, key = _ACTIVE_CACHE[-1], None, None
@@ -897,9 +932,7 @@ class _RenderFn(torch.autograd.Function):
             key = FragmentCache.key(verts, faces_i32, R, T, S)
             entry = cache.get(key)
         if entry is None:
-            ndc = ops.project_verts(v, R, T)
-            # (no near-plane watch here: render_views has looked at the vertices' depths before choosing these kernels)
-            frag = ops.raster_fwd(ndc, faces_i32, S)
+            ndc, frag = _rasterise(v, faces_i32, R, T, S)
             if key is not None:
                 entry = cache.put(key, (verts, faces_i32, R, T), ndc, frag)
         else:
@@ -911,43 +944,30 @@ class _RenderFn(torch.autograd.Function):
         else:
             rgb, mask = ops.shade_lit_fwd(frag, uvs, faces_uvs_i32, tex, ctx.lit)
         ctx.frag, ctx.uvs, ctx.fuv, ctx.tex = frag, uvs, faces_uvs_i32, tex
-        ctx.tex_shape = tex_map.shape
+        ctx.tex_shape, ctx.verts_shape = tex_map.shape, verts.shape
         ctx.geom = (v, ndc, faces_i32, R, T)
-        ctx.verts_shape = verts.shape
         ctx.mark_non_differentiable(mask)
         return rgb, mask
 
     @staticmethod
     def backward(ctx, grad_rgb, _grad_mask):
         with ops.trace("render_backward"):
-            return _RenderFn._backward(ctx, grad_rgb, _grad_mask)
-
-    @staticmethod
-    def _backward(ctx, grad_rgb, _grad_mask):
-        need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gtex = gverts = None
-        if ctx.lit is not None and (need_v or need_t):
-            gt, gbary, gnp = ops.shade_lit_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit,
-                                               want_texture=need_t, want_geometry=need_v)
-            if need_t:
-                gtex = gt.reshape(ctx.tex_shape)
-            if need_v:
-                v, ndc, faces_i32, R, T = ctx.geom
-                gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
-                gverts = ops.project_verts_bwd(v, R, T, gndc)
-                gverts = _lit_vertex_grad(ctx.lit, gverts, gnp, ctx.frag[0], ctx.frag[2]).reshape(ctx.verts_shape)
-            return gverts, gtex, None, None, None, None, None, None, None
-        if need_v or need_t:
-            res = ops.shade_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, want_bary=need_v,
-                                want_texture=need_t)
-            gt, gbary = (res if need_v else (res, None))
-            if need_t:
-                gtex = gt.reshape(ctx.tex_shape)
-            if need_v:      # uv -> barycentrics -> projected vertices -> world vertices
-                v, ndc, faces_i32, R, T = ctx.geom
-                gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
-                gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
-        return gverts, gtex, None, None, None, None, None, None, None
+            need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            gtex = gverts = None
+            if need_v or need_t:
+                g = grad_rgb.to(torch.float32)
+                gnp = None
+                if ctx.lit is not None:
+                    gt, gbary, gnp = ops.shade_lit_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit, want_texture=need_t,
+                                                       want_geometry=need_v)
+                else:
+                    res = ops.shade_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, want_bary=need_v, want_texture=need_t)
+                    gt, gbary = (res if need_v else (res, None))
+                if need_t:
+                    gtex = gt.reshape(ctx.tex_shape)
+                if need_v:
+                    gverts = _verts_grad(ctx, gbary, gnp)
+            return (gverts, gtex) + (None,) * 7
 
 
 class _MipRenderFn(torch.autograd.Function):
@@ -958,21 +978,15 @@ class _MipRenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, L, bias):
-        v = verts.detach().to(torch.float32).contiguous()
-        tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
-        if tex.shape[0] != tex.shape[1]:
-            raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
+        v, tex, uvs = _verts32(verts), _square_map(tex_map), _uvs32(verts_uvs)
         side = tex.shape[0]
-        uvs = verts_uvs.detach().to(torch.float32).reshape(-1, 2).contiguous()
-        ndc = ops.project_verts(v, R, T)
-        frag = ops.raster_fwd(ndc, faces_i32, S)
+        ndc, frag = _rasterise(v, faces_i32, R, T, S)
         pyr = ops.mip_build(tex, L)
         lod = ops.mip_lod(frag, ndc, faces_i32, uvs, faces_uvs_i32, side, L, bias)
         rgb, mask = ops.shade_mip_fwd(frag, uvs, faces_uvs_i32, pyr, lod, side, L)
         ctx.frag, ctx.uvs, ctx.fuv, ctx.pyr, ctx.lod, ctx.mip = frag, uvs, faces_uvs_i32, pyr, lod, (side, L)
-        ctx.tex_shape = tex_map.shape
+        ctx.tex_shape, ctx.verts_shape = tex_map.shape, verts.shape
         ctx.geom = (v, ndc, faces_i32, R, T)
-        ctx.verts_shape = verts.shape
         ctx.mark_non_differentiable(mask)
         return rgb, mask
 
@@ -989,9 +1003,7 @@ class _MipRenderFn(torch.autograd.Function):
                 if need_t:
                     gtex = gt.reshape(ctx.tex_shape)
                 if need_v:
-                    v, ndc, faces_i32, R, T = ctx.geom
-                    gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
-                    gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
+                    gverts = _verts_grad(ctx, gbary)
             return (gverts, gtex) + (None,) * 8
 
 
@@ -1002,15 +1014,13 @@ class _VertexColourRenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, colours, faces_i32, R, T, S):
-        v = verts.detach().to(torch.float32).contiguous()
+        v = _verts32(verts)
         col = colours.detach().to(torch.float32).reshape(-1, 3).contiguous()
-        ndc = ops.project_verts(v, R, T)
-        frag = ops.raster_fwd(ndc, faces_i32, S)
+        ndc, frag = _rasterise(v, faces_i32, R, T, S)
         rgb, mask = ops.shade_vc_fwd(frag, faces_i32, col)
         ctx.frag, ctx.col = frag, col
-        ctx.col_shape = colours.shape
+        ctx.col_shape, ctx.verts_shape = colours.shape, verts.shape
         ctx.geom = (v, ndc, faces_i32, R, T)
-        ctx.verts_shape = verts.shape
         ctx.mark_non_differentiable(mask)
         return rgb, mask
 
@@ -1020,15 +1030,13 @@ class _VertexColourRenderFn(torch.autograd.Function):
             need_v, need_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             gcol = gverts = None
             if need_v or need_c:
-                v, ndc, faces_i32, R, T = ctx.geom
-                res = ops.shade_vc_bwd(grad_rgb.to(torch.float32), ctx.frag, faces_i32, ctx.col, want_colours=need_c,
+                res = ops.shade_vc_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.geom[2], ctx.col, want_colours=need_c,
                                        want_bary=need_v)
                 gc, gbary = res if (need_v and need_c) else ((res, None) if need_c else (None, res))
                 if need_c:
                     gcol = gc.reshape(ctx.col_shape)
                 if need_v:
-                    gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
-                    gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
+                    gverts = _verts_grad(ctx, gbary)
             return gverts, gcol, None, None, None, None
 
 
@@ -1039,10 +1047,8 @@ class _AtlasRenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, atlas, faces_i32, R, T, S):
-        v = verts.detach().to(torch.float32).contiguous()
         at = atlas.detach().to(torch.float32).reshape(atlas.shape[-4:]).contiguous()
-        ndc = ops.project_verts(v, R, T)
-        frag = ops.raster_fwd(ndc, faces_i32, S)
+        _ndc, frag = _rasterise(_verts32(verts), faces_i32, R, T, S)
         rgb, mask = ops.shade_atlas_fwd(frag, at)
         ctx.frag = frag
         ctx.atlas_shape = atlas.shape
@@ -1066,53 +1072,39 @@ class _SSRenderFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, a, lighting=None):
-        v = verts.detach().to(torch.float32).contiguous()
-        tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
-        if tex.shape[0] != tex.shape[1]:
-            raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
-        uvs = verts_uvs.detach().to(torch.float32).reshape(-1, 2).contiguous()
-        ndc = ops.project_verts(v, R, T)
-        frag = ops.raster_fwd(ndc, faces_i32, a * S)
+        v, tex, uvs = _verts32(verts), _square_map(tex_map), _uvs32(verts_uvs)
+        ndc, frag = _rasterise(v, faces_i32, R, T, a * S)
         ctx.lit = _lit_setup(lighting, verts, v, faces_i32, R, T)
         if ctx.lit is None:
             rgb, cov = ops.shade_ss_fwd(frag, uvs, faces_uvs_i32, tex, a)
         else:
             rgb, cov = ops.shade_ss_lit_fwd(frag, uvs, faces_uvs_i32, tex, ctx.lit, a)
         ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.a = frag, uvs, faces_uvs_i32, tex, a
-        ctx.tex_shape = tex_map.shape
+        ctx.tex_shape, ctx.verts_shape = tex_map.shape, verts.shape
         ctx.geom = (v, ndc, faces_i32, R, T)
-        ctx.verts_shape = verts.shape
         ctx.mark_non_differentiable(cov)
         return rgb, cov
 
     @staticmethod
     def backward(ctx, grad_rgb, _grad_cov):
         with ops.trace("render_backward"):
-            return _SSRenderFn._backward(ctx, grad_rgb)
-
-    @staticmethod
-    def _backward(ctx, grad_rgb):
-        need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gtex = gverts = None
-        if need_v or need_t:
-            g = grad_rgb.to(torch.float32)
-            gnp = None
-            if ctx.lit is not None:
-                gt, gbary, gnp = ops.shade_ss_lit_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit, ctx.a,
-                                                      want_texture=need_t, want_geometry=need_v)
-            else:
-                res = ops.shade_ss_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.a, want_bary=need_v, want_texture=need_t)
-                gt, gbary = (res if need_v else (res, None))
-            if need_t:
-                gtex = gt.reshape(ctx.tex_shape)
-            if need_v:
-                v, ndc, faces_i32, R, T = ctx.geom
-                gndc = ops.raster_bwd(gbary, ctx.frag[0], ndc, faces_i32)
-                gverts = ops.project_verts_bwd(v, R, T, gndc)
+            need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+            gtex = gverts = None
+            if need_v or need_t:
+                g = grad_rgb.to(torch.float32)
+                gnp = None
                 if ctx.lit is not None:
-                    gverts = _lit_vertex_grad(ctx.lit, gverts, gnp, ctx.frag[0], ctx.frag[2])
-                gverts = gverts.reshape(ctx.verts_shape)
-        return (gverts, gtex) + (None,) * 8
+                    gt, gbary, gnp = ops.shade_ss_lit_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit, ctx.a,
+                                                          want_texture=need_t, want_geometry=need_v)
+                else:
+                    res = ops.shade_ss_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.a, want_bary=need_v,
+                                           want_texture=need_t)
+                    gt, gbary = (res if need_v else (res, None))
+                if need_t:
+                    gtex = gt.reshape(ctx.tex_shape)
+                if need_v:
+                    gverts = _verts_grad(ctx, gbary, gnp)
+            return (gverts, gtex) + (None,) * 8
 
 
 class _BoxDownFn(torch.autograd.Function):
@@ -1141,25 +1133,18 @@ class _SoftRenderFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, verts, tex_map, faces_i32, verts_uvs, faces_uvs_i32, R, T, S, K, blur, clip, sigma, gamma, bg,
                 cull=False, persp=True, z_clip=None, lighting=None):
-        v = verts.detach().to(torch.float32).contiguous()
-        tex = tex_map.detach().to(torch.float32).reshape(tex_map.shape[-3], tex_map.shape[-2], 3).contiguous()
-        if tex.shape[0] != tex.shape[1]:
-            raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
-        uvs = verts_uvs.detach().to(torch.float32).reshape(-1, 2).contiguous()
+        v, tex, uvs = _verts32(verts), _square_map(tex_map), _uvs32(verts_uvs)
         ndc = ops.project_verts(v, R, T)
         frag = ops.raster_soft_fwd(ndc, faces_i32, S, K, blur, clip, cull, persp, z_clip)
         ctx.slots = frag[4] if z_clip is not None else None
-        ctx.z_clip = z_clip
         frag = frag[:4]
         ctx.lit = _lit_setup(lighting, verts, v, faces_i32, R, T)
         if ctx.lit is None:
             rgb, alpha = ops.shade_soft_fwd(frag, uvs, faces_uvs_i32, tex, sigma, gamma, bg)
         else:
             rgb, alpha = ops.shade_soft_lit_fwd(frag, uvs, faces_uvs_i32, tex, ctx.lit, sigma, gamma, bg)
-        ctx.persp = persp
         ctx.frag, ctx.uvs, ctx.fuv, ctx.tex = frag, uvs, faces_uvs_i32, tex
-        ctx.blend = (sigma, gamma, bg)
-        ctx.clip = clip
+        ctx.blend, ctx.clip, ctx.persp, ctx.z_clip = (sigma, gamma, bg), clip, persp, z_clip
         ctx.tex_shape, ctx.verts_shape = tex_map.shape, verts.shape
         ctx.geom = (v, ndc, faces_i32, R, T)
         ctx.set_materialize_grads(False)        # an output nobody differentiates arrives as None, not as zeros
@@ -1168,42 +1153,30 @@ class _SoftRenderFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_rgb, grad_alpha):
         with ops.trace("render_backward"):
-            return _SoftRenderFn._backward(ctx, grad_rgb, grad_alpha)
-
-    @staticmethod
-    def _backward(ctx, grad_rgb, grad_alpha):
-        need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        gtex = gverts = None
-        if grad_rgb is None:
-            # only alpha carries a gradient (or nothing does): no RGB backward, no texture gradient
-            if need_v and grad_alpha is not None:
-                v, ndc, faces_i32, R, T = ctx.geom
-                gd = ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[3], ctx.blend[0])
-                gndc = ops.raster_soft_bwd((None, None, gd), ctx.frag[0], ndc, faces_i32, ctx.clip, ctx.persp, ctx.slots,
-                                           ctx.z_clip)
-                gverts = ops.project_verts_bwd(v, R, T, gndc).reshape(ctx.verts_shape)
-            return (gverts, gtex) + (None,) * 16
-        if need_v or need_t:
+            need_v, need_t = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
             sigma, gamma, bg = ctx.blend
-            gnp = None
-            if ctx.lit is None:
-                gt, geo = ops.shade_soft_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, sigma, gamma, bg,
-                                             want_texture=need_t, want_geometry=need_v)
-            else:
-                gt, geo, gnp = ops.shade_soft_lit_bwd(grad_rgb.to(torch.float32), ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit,
-                                                      sigma, gamma, bg, want_texture=need_t, want_geometry=need_v)
-            if need_t:
-                gtex = gt.reshape(ctx.tex_shape)
-            if need_v:
-                v, ndc, faces_i32, R, T = ctx.geom
-                if grad_alpha is not None:      # d alpha / d dists joins the RGB backward's grad_dists
-                    ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[3], sigma, out=geo[2])
-                gndc = ops.raster_soft_bwd(geo, ctx.frag[0], ndc, faces_i32, ctx.clip, ctx.persp, ctx.slots, ctx.z_clip)
-                gverts = ops.project_verts_bwd(v, R, T, gndc)
-                if ctx.lit is not None:
-                    gverts = _lit_vertex_grad(ctx.lit, gverts, gnp, ctx.frag[0], ctx.frag[2])
-                gverts = gverts.reshape(ctx.verts_shape)
-        return (gverts, gtex) + (None,) * 16
+            gtex = gverts = None
+            if grad_rgb is None:
+                # only alpha carries a gradient (or nothing does): no RGB backward, no texture gradient
+                if need_v and grad_alpha is not None:
+                    gd = ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[3], sigma)
+                    gverts = _soft_verts_grad(ctx, (None, None, gd))
+            elif need_v or need_t:
+                g = grad_rgb.to(torch.float32)
+                gnp = None
+                if ctx.lit is None:
+                    gt, geo = ops.shade_soft_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, sigma, gamma, bg, want_texture=need_t,
+                                                 want_geometry=need_v)
+                else:
+                    gt, geo, gnp = ops.shade_soft_lit_bwd(g, ctx.frag, ctx.uvs, ctx.fuv, ctx.tex, ctx.lit, sigma, gamma, bg,
+                                                          want_texture=need_t, want_geometry=need_v)
+                if need_t:
+                    gtex = gt.reshape(ctx.tex_shape)
+                if need_v:
+                    if grad_alpha is not None:      # d alpha / d dists joins the RGB backward's grad_dists
+                        ops.silhouette_bwd(grad_alpha.to(torch.float32), ctx.frag[0], ctx.frag[3], sigma, out=geo[2])
+                    gverts = _soft_verts_grad(ctx, geo, gnp)
+            return (gverts, gtex) + (None,) * 16
 
 
 NEED_TAG = "_st3d_need"
@@ -1317,6 +1290,58 @@ def reaches_near_plane(verts, R, T, z_clip):
     return near
 
 
+def _near_plane_reached(meshes, R, T):
+    """the specialised kernels must not render this batch: the watch has fired, or a vertex lies nearer than PyTorch3D's plane"""
+    return ops.near_plane_triggered() or reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT)
+
+
+def _tag_hard(rgb):
+    """the tags of a hard-path render whose Function kept its fragments: coverage from p2f, a white background"""
+    if rgb.requires_grad:
+        tag_need(rgb, rgb.grad_fn.frag[0])
+    return tag_flat(rgb, (1.0, 1.0, 1.0))
+
+
+_REFUSAL_CONDITIONS = (         # name in the *_REFUSALS tables, does it hold; in order of precedence
+    ("silhouette", lambda rs, bp, lighting: isinstance(rs, SilhouetteRasterizationSettings)),
+    ("lights", lambda rs, bp, lighting: lighting() is not None),
+    ("supersample", lambda rs, bp, lighting: getattr(rs, "supersample", 1) > 1),
+    ("mip", lambda rs, bp, lighting: getattr(rs, "texture_mip_levels", 1) != 1),
+    ("soft", lambda rs, bp, lighting: not uses_hard_path(rs, bp)),
+)
+
+
+def _refuse(table, refused, rs, bp, lighting):
+    """NotImplementedError with `table`'s message for the first condition named in `refused` that holds (before any launch).
+    lighting: a callable -> Lighting or None, asked only once "lights" is reached (making one validates the lights)."""
+    for name, holds in _REFUSAL_CONDITIONS:
+        if name in refused and holds(rs, bp, lighting):
+            raise NotImplementedError(table[name])
+
+
+def _clipping_settings(image_size):
+    """The specialised kernels do not clip: a mesh at the near plane renders with the same (hard) settings on the general
+    kernels at PyTorch3D's default clipping depth -> those settings, with one warning (ST3D_NEAR_PLANE=raise: an error).
+    Every rank decides for its own views; both kernel families give the same pixels where nothing is clipped, so ranks need
+    not agree."""
+    if ops.NEAR_PLANE_POLICY == "raise":
+        raise RuntimeError(ops.NEAR_PLANE_MESSAGE)
+    ops.note_near_plane()
+    return RasterizationSettings(image_size=image_size, z_clip_value=RasterizationSettings.Z_CLIP_DEFAULT)
+
+
+def _uv_args(meshes, R, T):
+    """what every Function that samples a texture map takes first"""
+    tex = meshes.textures
+    return (meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(), tex.faces_uvs_i32(), R, T)
+
+
+def _soft_args(rs, bp, lighting):
+    """what _SoftRenderFn takes after the image side"""
+    return (rs.faces_per_pixel, rs.blur_radius, rs.clip_barycentric_coords, bp.sigma, bp.gamma, bp.background_color,
+            rs.cull_backfaces, rs.perspective_correct, rs.z_clip, lighting)
+
+
 def render_views(meshes, R, T, image_size, raster_settings=None, blend_params=None, lights=None, materials=None, cache=None):
     """``_render_views`` inside a named range (``ST3D_ROCTX=1``: rocprofv3 --marker-trace shows the step's phases)."""
     with ops.trace("render"):
@@ -1348,37 +1373,25 @@ def _render_views(meshes, R, T, image_size, raster_settings=None, blend_params=N
     if getattr(rs, "supersample", 1) > 1:
         return _render_views_ss(meshes, R, T, int(image_size), rs, bp, lighting)
     hard_settings = uses_hard_path(rs, bp)
-    if hard_settings and (ops.near_plane_triggered() or
-                          reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT)):
-        # the specialised kernels do not clip: a mesh at the near plane renders with the same settings on the general
-        # kernels at PyTorch3D's default clipping depth.  Every rank decides for its own views; both kernel families give
-        # the same pixels where nothing is clipped, so ranks need not agree.
-        if ops.NEAR_PLANE_POLICY == "raise":
-            raise RuntimeError(ops.NEAR_PLANE_MESSAGE)
-        ops.note_near_plane()
-        rs = RasterizationSettings(image_size=image_size, z_clip_value=RasterizationSettings.Z_CLIP_DEFAULT)
+    if hard_settings and _near_plane_reached(meshes, R, T):
+        rs = _clipping_settings(image_size)
+    args = _uv_args(meshes, R, T)
     if uses_hard_path(rs, bp):
         # K=1, blur 0: the blend weight cancels and the pixel is the sampled texel itself
         _ACTIVE_CACHE.append(cache if os.environ.get("ST3D_FRAG_CACHE", "1") != "0" else None)    # (the A/B switch, read per render)
         try:
-            rgb, mask = _RenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
-                                        tex.faces_uvs_i32(), R, T, int(image_size), lighting)
+            rgb, mask = _RenderFn.apply(*args, int(image_size), lighting)
         finally:
             _ACTIVE_CACHE.pop()
         entry = getattr(rgb.grad_fn, "entry", None) if rgb.requires_grad else None
-        if entry is not None:       # fragments of the cache: their coverage tag is made once and names its geometry epoch
-            cover = entry.coverage()
-            tag_need_mask(rgb, cover, epoch=entry.epoch)
-        elif rgb.requires_grad:
-            tag_need(rgb, rgb.grad_fn.frag[0])
-        tag_flat(rgb, (1.0, 1.0, 1.0))           # (uses_hard_path: the default BlendParams, a white background)
-        return rgb, mask
+        if entry is None:
+            return _tag_hard(rgb), mask         # (uses_hard_path: the default BlendParams, a white background)
+        cover = entry.coverage()    # fragments of the cache: their coverage tag is made once and names its geometry epoch
+        tag_need_mask(rgb, cover, epoch=entry.epoch)
+        return tag_flat(rgb, (1.0, 1.0, 1.0)), mask
     bp = bp if bp is not None else BlendParams()
     rs = rs if rs is not None else RasterizationSettings(image_size=image_size)
-    rgb, alpha = _SoftRenderFn.apply(meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(),
-                                     tex.faces_uvs_i32(), R, T, int(image_size), rs.faces_per_pixel,
-                                     rs.blur_radius, rs.clip_barycentric_coords, bp.sigma, bp.gamma, bp.background_color,
-                                     rs.cull_backfaces, rs.perspective_correct, rs.z_clip, lighting)
+    rgb, alpha = _SoftRenderFn.apply(*args, int(image_size), *_soft_args(rs, bp, lighting))
     if rgb.requires_grad:
         tag_need(rgb, rgb.grad_fn.frag[0])
     tag_flat(rgb, bp.background_color)
@@ -1393,27 +1406,16 @@ def _render_views_vertex(meshes, R, T, S, rs, bp, lights, materials):
     """_render_views for a mesh whose textures are a TexturesVertex -> (rgb, 0/1 mask) from csrc/vcolor.hip.  Everything
     the kernels do not cover is refused before any launch; a batch at the near plane is an error whatever ST3D_NEAR_PLANE
     says, never a silent reroute (the clipping kernels have no vertex-colour path)."""
-    if isinstance(rs, SilhouetteRasterizationSettings):
-        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["silhouette"])
     dev = meshes.device
-    if lighting_of(lights, materials, dev) is not None:
-        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["lights"])
-    if getattr(rs, "supersample", 1) > 1:
-        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["supersample"])
-    if getattr(rs, "texture_mip_levels", 1) != 1:
-        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["mip"])
-    if not uses_hard_path(rs, bp):
-        raise NotImplementedError(VERTEX_COLOUR_REFUSALS["soft"])
+    _refuse(VERTEX_COLOUR_REFUSALS, ("silhouette", "lights", "supersample", "mip", "soft"), rs, bp,
+            lambda: lighting_of(lights, materials, dev))
     colours = vertex_colours_of(meshes)
     faces_i32 = meshes.faces_i32()              # range-checked against the vertex count (= the colour count)
     R, T = R.to(dev), T.to(dev)
-    if ops.near_plane_triggered() or reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT):
+    if _near_plane_reached(meshes, R, T):
         raise RuntimeError(VERTEX_COLOUR_NEAR_PLANE_MESSAGE)
     rgb, mask = _VertexColourRenderFn.apply(meshes.verts_packed(), colours, faces_i32, R, T, S)
-    if rgb.requires_grad:
-        tag_need(rgb, rgb.grad_fn.frag[0])
-    tag_flat(rgb, (1.0, 1.0, 1.0))
-    return rgb, mask
+    return _tag_hard(rgb), mask
 
 
 def _render_views_atlas(meshes, R, T, S, rs, bp, lights, materials):
@@ -1422,22 +1424,15 @@ def _render_views_atlas(meshes, R, T, S, rs, bp, lights, materials):
     transpose; the mask through ops.box_down_fwd) -- the composition of the ST3D_SS_FUSED=0 branch of _render_views_ss;
     coverage is then fractional.  Everything the kernels do not cover is refused before any launch; a batch at the near
     plane is an error whatever ST3D_NEAR_PLANE says, never a silent reroute (the clipping kernels have no atlas path)."""
-    if isinstance(rs, SilhouetteRasterizationSettings):
-        raise NotImplementedError(ATLAS_REFUSALS["silhouette"])
     dev = meshes.device
-    if lighting_of(lights, materials, dev) is not None:
-        raise NotImplementedError(ATLAS_REFUSALS["lights"])
-    if getattr(rs, "texture_mip_levels", 1) != 1:
-        raise NotImplementedError(ATLAS_REFUSALS["mip"])
-    if not uses_hard_path(rs, bp):
-        raise NotImplementedError(ATLAS_REFUSALS["soft"])
+    _refuse(ATLAS_REFUSALS, ("silhouette", "lights", "mip", "soft"), rs, bp, lambda: lighting_of(lights, materials, dev))
     a = getattr(rs, "supersample", 1)
     if a > 1:
         a = ops.check_supersample(a, S)
     atlas = atlas_of(meshes)
     faces_i32 = meshes.faces_i32()
     R, T = R.to(dev), T.to(dev)
-    if ops.near_plane_triggered() or reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT):
+    if _near_plane_reached(meshes, R, T):
         raise RuntimeError(ATLAS_NEAR_PLANE_MESSAGE)
     if a > 1:
         rgb_hi, mask_hi = _AtlasRenderFn.apply(meshes.verts_packed(), atlas, faces_i32, R, T, a * S)
@@ -1446,37 +1441,24 @@ def _render_views_atlas(meshes, R, T, S, rs, bp, lights, materials):
         tag_flat(rgb, (1.0, 1.0, 1.0))
         return rgb, cov
     rgb, mask = _AtlasRenderFn.apply(meshes.verts_packed(), atlas, faces_i32, R, T, S)
-    if rgb.requires_grad:
-        tag_need(rgb, rgb.grad_fn.frag[0])
-    tag_flat(rgb, (1.0, 1.0, 1.0))
-    return rgb, mask
+    return _tag_hard(rgb), mask
 
 
 def _render_views_mip(meshes, R, T, S, rs, bp, lighting):
     """_render_views at texture_mip_levels != 1 -> (rgb, 0/1 mask) from the mip-mapped kernels, or None when the map's side
     allows one level only (texture_mip_levels = 0 under an odd side: the plain render).  Everything the kernels do not cover
     is refused before any launch; a batch at the near plane is an error, never a silent unfiltered render."""
-    if lighting is not None:
-        raise NotImplementedError(MIP_REFUSALS["lights"])
-    if getattr(rs, "supersample", 1) > 1:
-        raise NotImplementedError(MIP_REFUSALS["supersample"])
-    if not uses_hard_path(rs, bp):
-        raise NotImplementedError(MIP_REFUSALS["soft"])
-    tex = meshes.textures
-    maps = tex.maps_padded()
+    _refuse(MIP_REFUSALS, ("lights", "supersample", "soft"), rs, bp, lambda: lighting)
+    maps = meshes.textures.maps_padded()
     if maps.shape[-3] != maps.shape[-2]:
         raise NotImplementedError("square texture maps only (the reference resizes to size x size)")
     L = ops.check_mip(rs.texture_mip_levels, maps.shape[-2])
     if L == 1:
         return None
-    if ops.near_plane_triggered() or reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT):
+    if _near_plane_reached(meshes, R, T):
         raise RuntimeError(MIP_NEAR_PLANE_MESSAGE)
-    rgb, mask = _MipRenderFn.apply(meshes.verts_packed(), maps, meshes.faces_i32(), tex.verts_uvs_padded(), tex.faces_uvs_i32(),
-                                   R, T, S, L, rs.texture_lod_bias)
-    if rgb.requires_grad:
-        tag_need(rgb, rgb.grad_fn.frag[0])
-    tag_flat(rgb, (1.0, 1.0, 1.0))
-    return rgb, mask
+    rgb, mask = _MipRenderFn.apply(*_uv_args(meshes, R, T), S, L, rs.texture_lod_bias)
+    return _tag_hard(rgb), mask
 
 
 def ss_fused():
@@ -1492,16 +1474,11 @@ def _render_views_ss(meshes, R, T, S, rs, bp, lighting):
     gradients go back through its transpose.  Coverage is fractional either way; ``coverage > 0`` == some sub-pixel
     covered."""
     a = ops.check_supersample(rs.supersample, S)
-    tex = meshes.textures
     hard_settings = uses_hard_path(rs, bp)
     rs_hi = rs
-    if hard_settings and (ops.near_plane_triggered() or
-                          reaches_near_plane(meshes.verts_packed(), R, T, RasterizationSettings.Z_CLIP_DEFAULT)):
-        if ops.NEAR_PLANE_POLICY == "raise":         # (the decision is about vertices, not pixels: as at a = 1)
-            raise RuntimeError(ops.NEAR_PLANE_MESSAGE)
-        ops.note_near_plane()
-        rs_hi = RasterizationSettings(image_size=S, z_clip_value=RasterizationSettings.Z_CLIP_DEFAULT)
-    args = (meshes.verts_packed(), tex.maps_padded(), meshes.faces_i32(), tex.verts_uvs_padded(), tex.faces_uvs_i32(), R, T)
+    if hard_settings and _near_plane_reached(meshes, R, T):
+        rs_hi = _clipping_settings(S)           # (the decision is about vertices, not pixels: as at a = 1)
+    args = _uv_args(meshes, R, T)
     if uses_hard_path(rs_hi, bp):
         if ss_fused():
             rgb, cov = _SSRenderFn.apply(*args, S, a, lighting)
@@ -1512,9 +1489,7 @@ def _render_views_ss(meshes, R, T, S, rs, bp, lighting):
         tag_flat(rgb, (1.0, 1.0, 1.0))
         return rgb, cov
     bp = bp if bp is not None else BlendParams()
-    rgb_hi, alpha_hi = _SoftRenderFn.apply(*args, a * S, rs_hi.faces_per_pixel, rs_hi.blur_radius,
-                                           rs_hi.clip_barycentric_coords, bp.sigma, bp.gamma, bp.background_color,
-                                           rs_hi.cull_backfaces, rs_hi.perspective_correct, rs_hi.z_clip, lighting)
+    rgb_hi, alpha_hi = _SoftRenderFn.apply(*args, a * S, *_soft_args(rs_hi, bp, lighting))
     if hard_settings:       # thresholded at a * S first, as at a = 1; the filter then hands out the same fractional coverage
         alpha_hi = (alpha_hi.detach() > 0).to(torch.float32)
     rgb, alpha = _BoxDownFn.apply(rgb_hi, a), _BoxDownFn.apply(alpha_hi, a)

@@ -205,6 +205,18 @@ def test_hard_lit_forward_backward_match_fp64(dev, cow, case, det):
             texd.grad, verts.grad = None, None
             rgb2, _ = _render(mesh, R_, T_, S, lights, mats, g=gk)
             assert torch.equal(rgb, rgb2) and torch.equal(texd.grad[0], gtex) and torch.equal(verts.grad, gverts)
+            # one target at a time takes the same backward: its own gradient bit for bit, none for the other
+            for need_v in (True, False):
+                texd.grad, verts.grad = None, None
+                verts.requires_grad_(need_v), texd.requires_grad_(not need_v)
+                try:
+                    _render(mesh, R_, T_, S, lights, mats, g=gk)
+                finally:
+                    verts.requires_grad_(True), texd.requires_grad_(True)
+                if need_v:
+                    assert texd.grad is None and torch.equal(verts.grad, gverts)
+                else:
+                    assert verts.grad is None and torch.equal(texd.grad[0], gtex)
     finally:
         ops.set_deterministic(was)
     covered = frags[0].cpu() >= 0
@@ -299,6 +311,15 @@ def test_default_shading_is_unchanged(dev, cow):
         outs.append((rgb.detach(), cov, texd.grad.clone(), verts.grad.clone()))
     for o in outs[1:]:
         assert all(torch.equal(a, b) for a, b in zip(outs[0], o))
+    # one target at a time takes the same (unlit) backward: its own gradient bit for bit, none for the other
+    for need_v in (True, False):
+        mesh, verts, texd, _ = _scene(cow, dev)
+        verts.requires_grad_(need_v), texd.requires_grad_(not need_v)
+        _render(mesh, R_, T_, S, None, None, g=g)
+        if need_v:
+            assert texd.grad is None and torch.equal(verts.grad, outs[0][3])
+        else:
+            assert verts.grad is None and torch.equal(texd.grad, outs[0][2])
 
 
 def test_per_call_lights_override_the_shader(dev, cow):

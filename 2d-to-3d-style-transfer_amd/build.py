@@ -82,7 +82,7 @@ def build(force=False, jobs=4, verbose=True):
     os.makedirs(OBJDIR, exist_ok=True)
     hdrs = (os.path.join(CSRC, "common.h"), os.path.join(CSRC, "det.h"), os.path.join(CSRC, "phong.h"),
             os.path.join(CSRC, "softgeom.h"), os.path.join(CSRC, "shadek1.h"), os.path.join(CSRC, "tilebins.h"),
-            os.path.join(CSRC, "atlas.h"), os.path.join(CSRC, "epochs.h"),
+            os.path.join(CSRC, "atlas.h"), os.path.join(CSRC, "epochs.h"), os.path.join(CSRC, "planlists.h"),
             os.path.join(CSRC, "lab", "wino8.inc"),
             os.path.join(HERE, "..", "include", "st3d.h"), os.path.abspath(__file__))
     todo = []

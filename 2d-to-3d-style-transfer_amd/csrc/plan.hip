@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "epochs.h"
+#include "planlists.h"
 
 namespace st3d {
 static thread_local char g_err[512] = "";
@@ -39,28 +40,13 @@ extern "C" int st3d_device_info(int device, int *cu_count, size_t *hbm_bytes, ch
     return ST3D_OK;
 }
 
+using namespace st3d;      // the VGG layout, the route table and the list decisions (planlists.h)
+
 namespace {
 
-// torchvision vgg19().features layout: module index -> kind
-constexpr int kModules = 37;
-const int kConvIdx[16] = {0, 2, 5, 7, 10, 12, 14, 16, 19, 21, 23, 25, 28, 30, 32, 34};
-const int kConvCin[16] = {3, 64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512, 512, 512};
-const int kConvCout[16] = {64, 64, 128, 128, 256, 256, 256, 256, 512, 512, 512, 512, 512, 512, 512, 512};
-const int kPoolIdx[5] = {4, 9, 18, 27, 36};
 // style taps (style_transfer.py:12-19 minus conv4_2) and the content tap
 const int kStyleTap[5] = {0, 5, 10, 19, 28};
 constexpr int kContentTap = 21;
-
-int conv_slot(int module_idx) {
-    for (int i = 0; i < 16; ++i)
-        if (kConvIdx[i] == module_idx) return i;
-    return -1;
-}
-int pool_slot(int module_idx) {
-    for (int i = 0; i < 5; ++i)
-        if (kPoolIdx[i] == module_idx) return i;
-    return -1;
-}
 
 }  // namespace
 
@@ -145,20 +131,6 @@ extern "C" int st3d_vgg_destroy(st3d_vgg *vgg) {
     return ST3D_OK;
 }
 
-// which kernel runs conv slot cs, per direction.  Every input is fixed when the plan is made -- the handle's switches, the
-// packs that exist, the layer's channels, the plan's H and W -- so st3d_plan_create fills the table once and every launch
-// site reads it; what a call adds is whether the arriving gradient is pooled or already gated
-enum : uint8_t { DIRECT, WINO, WINO43 };      // conv.hip, wino.hip F(2x2,3x3), wino43.hip F(4x4,3x3)
-struct Route {
-    uint8_t fwd = DIRECT;
-    bool dgrad_wino = false;    // the input gradient runs on wino.hip ...
-    bool dgrad_w43 = false;     // ... and on wino43.hip when its gradient arrives already gated (all F(4x4,3x3) takes)
-    // Producer-side ReLU gates (st3d_wino_dgrad_chain): whoever writes a gradient last zeroes it where its tensor's gate
-    // is closed, so the Winograd input gradient that consumes it streams one operand per stage
-    bool gate_taps = false;     // the style / content terms that join this conv's (unpooled) gradient gate it
-    bool gate_dst = false;      // this launch gates the gradient it writes: the launch below is a Winograd one too
-};
-
 struct GraphKey {               // what a captured loss step has baked in
     int n = 0, denom = 0;
     bool want_grad = false, masked = false, flat = false;
@@ -170,10 +142,6 @@ struct GraphKey {               // what a captured loss step has baked in
     }
 };
 
-// ST3D_SPLIT_BATCH when the environment does not set it: st3d_plan::SPLIT_FWD, the forward alone (measured, DESIGN.md 6: the
-// backward's share cannot be told from the spread between boxes)
-#define ST3D_SPLIT_BATCH_DEFAULT 1
-
 struct st3d_plan {
     st3d_vgg *vgg = nullptr;
     int B = 0, S = 0;
@@ -182,6 +150,8 @@ struct st3d_plan {
     // per module: output activation (conv: post-ReLU; relu: alias of its conv; pool: pooled)
     float *act[kModules] = {};
     int C[kModules] = {}, H[kModules] = {}, W[kModules] = {};
+    // image i0 of a buffer shaped like module m's output (act[m], the argmax of the pool at m)
+    template <typename T> T *at(T *buf, int m, int i0) const { return buf + (size_t)i0 * C[m] * H[m] * W[m]; }
     uint8_t *pidx[5] = {};
     float *gbuf[2] = {};
     size_t gbuf_floats = 0;
@@ -219,40 +189,12 @@ struct st3d_plan {
     uint8_t *g_mask = nullptr;
     GraphKey gkey;
     bool gwarm = false;
-    // need lists of st3d_plan_loss_masked (need.hip), rebuilt by every masked call.  A launch may only be thinned out when
-    // every launch below it is, so the levels count from the bottom: 1 the relu1_1 pass, 2 + the conv1_2 input gradient,
-    // 3 + the conv2_1 input gradient -- as many as the size has, the routes allow and ST3D_NEED_DEPTH leaves.
-    // need_blocks: the lists are the per-block ones (st3d_need_blocks_build; ST3D_NEED_BLOCKS=0: the tile-granular ones of
-    // st3d_need_build).  They stay thin further up, so the levels go on: 4 + conv2_2, 5 + conv3_1, 6 + conv3_2, 7 + conv3_3,
-    // each in the geometry need_cols says (64 / 32 pixels across, 16 = strips; 0 = the kernel's own choice for the map).
-    int need_levels = 0;
-    bool need_blocks = false;
-    uint8_t *need_flags = nullptr;
-    size_t need_flags_bytes = 0;
-    int need_cols[ST3D_NEED_MAX_LISTS] = {};
-    // the Gram backward at relu2_1 over the 64-pixel runs the conv2_1 input gradient reads (level 3 and up; gram.hip)
-    bool need_gram = false;
-    // flat-field lists of st3d_plan_loss_flat (flat.hip), rebuilt by every call that brings a colour: how many of conv1_2,
-    // conv2_1, conv2_2 run listed -- as many as the size has, run F(4x4,3x3) and ST3D_FLAT_DEPTH leaves
-    int flat_levels = 0;
-    uint8_t *flat_ws = nullptr;
-    size_t flat_ws_bytes = 0;
-    // kept lists of st3d_plan_loss_keyed (st3d_kept_build, need.hip): how many of conv3_1, conv3_2, conv3_3 walk, in a call that
-    // finds the clean record its own, only the tiles or strips holding an output block that the coverage can change -- every
-    // other tile still holds the bits the previous call of the epoch wrote, and the same launch on the same input would write
-    // them again.  Bottom-up like the levels above; keep_cols as need_cols (16 = strips).  ST3D_KEEP_DEPTH / ST3D_KEEP_TILE /
-    // ST3D_KEEP_FORCE, read by st3d_plan_create.
-    static constexpr int kKeepFirst = 3, kKeepMax = 3;      // list 3 = conv slot 4 = conv3_1
-    int keep_levels = 0;
-    int keep_cols[ST3D_NEED_MAX_LISTS] = {};
-    // The flat-field levels in such a call: no fill runs, so nothing needs their lists to name one tile per border class, and
-    // conv1_2, conv2_1 and conv2_2 may walk their kept lists (lists 0 .. 2) in a finer geometry than the flat-field lists'
-    // own.  shallow_cols[k]: 0 = the flat-field list as ever; 32 / 64 tiles, 16 strips (conv2_1 only: the others pool).
-    // keep_first: the lowest list the build makes (kKeepFirst when no shallow level is on).  ST3D_KEEP_SHALLOW.
-    int shallow_cols[3] = {};
-    int keep_first = kKeepFirst;
-    uint8_t *keep_ws = nullptr;
-    size_t keep_ws_bytes = 0;
+    // What st3d_plan_create decided about the lists (planlists.h): how many need, flat-field and kept levels, their
+    // geometries, the split mode and what a group of a split call walks.  The need lists are rebuilt by every masked call,
+    // the flat-field lists by every call that brings a colour, the kept lists once per epoch by its first clean call.
+    PlanDecisions d;
+    uint8_t *need_flags = nullptr, *flat_ws = nullptr, *keep_ws = nullptr;      // the builders' workspaces
+    size_t need_flags_bytes = 0, flat_ws_bytes = 0, keep_ws_bytes = 0;
     // What the list builds write and the launches read: the need lists (segment bytes, tile lists, counts, the Gram run
     // list) and the flat-field lists (tile lists, maps, counts).  sets[0] belongs to the unkeyed calls, which rebuild it
     // every time; sets[1 ..] hold the lists of the last kEpochSlots geometry epochs of st3d_plan_loss_keyed (epochs.h), built
@@ -260,28 +202,24 @@ struct st3d_plan {
     // views at 512^2 (st3d_need_blocks_entries, st3d_need_blocks_gram_runs, st3d_flat_tiles) next to the plan's 4.4 GB, so
     // three epochs stay: what a run that alternates two or three view batches needs.
     static constexpr int kEpochSlots = 3;
-    // One group's lists of a split call (below): the existing builders on the group's slice of the coverage, so tiles and strips
-    // count images from the group's first.  flat_*: the flat-field lists, walked without fills by the shallow levels that
-    // have no kept list (they name their representatives within the group; every tile they leave out holds the fill of
-    // the epoch's first call, which is what its own launch would write).
-    struct GroupLists {
+    // One batch's lists, numbered from its first image: the whole batch of a call, or one group of a split call (below) --
+    // the same builders on the group's slice of the coverage.  A group walks its flat_* lists without fills at the shallow
+    // levels that have no kept list (they name their representatives within the group; every tile they leave out holds the
+    // fill of the epoch's first call, which is what its own launch would write).
+    struct Lists {
         uint8_t *need_seg = nullptr;
         int *need_list[ST3D_NEED_MAX_LISTS] = {}, *need_cnt = nullptr;
         int *need_gram_list = nullptr, *need_gram_cnt = nullptr;
-        int *kept_list[ST3D_NEED_MAX_LISTS] = {}, *kept_cnt = nullptr;
+        int *kept_list[ST3D_NEED_MAX_LISTS] = {}, *kept_cnt = nullptr;     // (keyed sets) lists keep_first .. of st3d_kept_build
         int *flat_list[3] = {}, *flat_map[3] = {}, *flat_cnt = nullptr;
     };
     struct ListSet {
-        GroupLists grp[2];                              // (keyed sets, split plans)
-        bool have_grp_fwd = false, have_grp_need = false;       // built by the epoch's first split call, per direction
-        uint8_t *need_seg = nullptr;
-        int *need_list[ST3D_NEED_MAX_LISTS] = {}, *need_cnt = nullptr;
-        int *need_gram_list = nullptr, *need_gram_cnt = nullptr;
-        int *flat_list[3] = {}, *flat_map[3] = {}, *flat_cnt = nullptr;
+        Lists whole;
+        Lists grp[2];                                   // (keyed sets, split plans)
         uint8_t *c1_skip = nullptr;                     // (keyed sets) conv1_1's tiles that see background only (conv.hip)
-        int *kept_list[ST3D_NEED_MAX_LISTS] = {}, *kept_cnt = nullptr;     // (keyed sets) lists keep_first .. of st3d_kept_build
         bool have_need = false, have_flat = false;      // (keyed sets) built for the slot's epoch
         bool have_kept = false;                         // (keyed sets) built by the epoch's first clean call
+        bool have_grp_fwd = false, have_grp_need = false;       // built by the epoch's first split call, per direction
     };
     ListSet sets[1 + kEpochSlots];
     ListSet *ls = &sets[0];
@@ -316,15 +254,9 @@ struct st3d_plan {
     // (the groups are at different layers at the same time, so a slice by the layer's own image size would overlap).
     // Every launch is per image, tile or block and takes its reduction order from the layer, not from N, so each image
     // gets the bits of the one-stream call (the listed launches by the premise of their lists).
-    enum { SPLIT_FWD = 1, SPLIT_BWD = 2 };
-    int split_mode = 0;
     hipStream_t gstream = nullptr;
     hipEvent_t ev_fork[2] = {}, ev_join[2] = {};    // [forward / backward]
     int split_calls[2] = {};        // calls whose forward / backward ran split (st3d_plan_split_calls)
-    // the two-rounds rule with a group's count: which kept lists a group walks, how many need levels it lists
-    bool grp_kept_on[ST3D_NEED_MAX_LISTS] = {};
-    int grp_need_levels = 0;
-    bool grp_need_gram = false;
     // guidance of the style term (st3d_plan_set_style_guidance; guide.hip): the q planes of the five taps for guide_n
     // images (0 = off), and w_0 = q_0^2 for the fused bottom pass.  Allocated by the first call that sets a guidance (for B
     // images: the pointers never move, so a captured loss step keeps reading them), rebuilt by every such call.
@@ -404,37 +336,83 @@ struct Keyed {
 };
 // the lists a forward chain walks: the epoch's whole-batch ones, or one group's (split calls)
 struct FwdLists {
-    const uint8_t *c1_skip;
-    int *const *kept_list; const int *kept_cnt;
-    int *const *flat_list, *const *flat_map; const int *flat_cnt;
+    const st3d_plan::Lists &lists;
+    const uint8_t *c1_skip;     // the chain's first image's slice of the set's (nullptr: none)
     const bool *kept_on;        // (groups) which kept lists the group walks; nullptr = all the plan has
 };
 
-// fork the plan's stream for the second group from s / join it back (split calls)
-// (dir: 0 the forward's events, 1 the backward's)
-hipStream_t split_stream(st3d_plan *p, int g, hipStream_t s) { return g == 0 ? s : p->gstream; }
-int split_fork(st3d_plan *p, int dir, hipStream_t s) {
-    ST3D_HIP(hipEventRecord(p->ev_fork[dir], s));
-    ST3D_HIP(hipStreamWaitEvent(p->gstream, p->ev_fork[dir], 0));
-    return ST3D_OK;
+// may this call run as two groups in direction `dir`?  (what the call itself decides -- a clean record, a mask -- is the caller's)
+bool split_ok(const st3d_plan *p, int dir, int n, bool keyed) {
+    return keyed && (p->d.split_mode & dir) && p->gstream && !p->prof && !p->use_graph && p->guide_n == 0 && n >= 4 && n % 2 == 0;
 }
+// join the plan's stream back into s (dir: 0 the forward's event, 1 the backward's)
 int split_join(st3d_plan *p, int dir, hipStream_t s) {
     ST3D_HIP(hipEventRecord(p->ev_join[dir], p->gstream));
     ST3D_HIP(hipStreamWaitEvent(s, p->ev_join[dir], 0));
     return ST3D_OK;
 }
-// may this call run as two groups in direction `dir`?  (what the call itself decides -- a clean record, a mask -- is the caller's)
-bool split_ok(const st3d_plan *p, int dir, int n, bool keyed) {
-    return keyed && (p->split_mode & dir) && p->gstream && !p->prof && !p->use_graph && p->guide_n == 0 && n >= 4 && n % 2 == 0;
+// A split call's chain: fork the plan's stream from s, then fn(g, stream) for the first group on s and the second on the
+// plan's stream, stopping at the first failure.  The plan's stream is joined back also after a failure (the caller's stream
+// stays behind whatever was enqueued).  -> the first error; split_calls[dir] counts the calls that went through.
+// (dir: 0 the forward's events and count, 1 the backward's)
+template <typename Fn>
+int run_split(st3d_plan *p, int dir, hipStream_t s, Fn fn) {
+    ST3D_HIP(hipEventRecord(p->ev_fork[dir], s));
+    ST3D_HIP(hipStreamWaitEvent(p->gstream, p->ev_fork[dir], 0));
+    int rc = ST3D_OK;
+    for (int g = 0; g < 2 && rc == ST3D_OK; ++g) rc = fn(g, g == 0 ? s : p->gstream);
+    const int rj = split_join(p, dir, s);
+    if (rc != ST3D_OK || rj != ST3D_OK) return rc != ST3D_OK ? rc : rj;
+    ++p->split_calls[dir];
+    return ST3D_OK;
+}
+
+// The lists a keyed call's forward walks, from the coverage of `images` images (the batch, or one group's slice): the
+// flat-field lists (with the set's c1_skip bytes when given) and the kept lists, each when asked for.
+int build_forward_lists(st3d_plan *p, st3d_plan::Lists &L, const uint8_t *cover, int images, int flat, bool want_flat, uint8_t *c1_skip,
+                        bool want_kept, hipStream_t s) {
+    if (want_flat) {
+        Scope sc(p, F_ELEM, s);
+        ST3D_TRY(st3d_flat_build_cover(cover, images, p->S, flat, p->flat_ws, p->flat_ws_bytes, L.flat_list[0], L.flat_map[0], L.flat_list[1],
+                                       L.flat_map[1], L.flat_list[2], L.flat_map[2], L.flat_cnt, s));
+        if (c1_skip) ST3D_TRY(st3d_conv1_skip_build(cover, images, p->S, p->S, c1_skip, s));
+    }
+    if (want_kept) {
+        Scope sc(p, F_ELEM, s);
+        ST3D_TRY(st3d_kept_build(cover, images, p->S, p->d.keep_first, kKeepFirst + p->d.keep_levels, p->d.keep_cols, p->keep_ws,
+                                 p->keep_ws_bytes, L.kept_list, L.kept_cnt, s));
+    }
+    return ST3D_OK;
+}
+
+// The need lists of `need` levels from the mask of `images` images (the batch, or one group's slice): the per-block ones
+// (gram: with the relu2_1 run list), or the tile-granular ones where the plan has no others or a single level asks for none.
+int build_need_lists(st3d_plan *p, st3d_plan::Lists &L, const uint8_t *mask, int images, int need, bool gram, hipStream_t s) {
+    Scope sc(p, F_ELEM, s);
+    if (p->d.need_blocks && need >= 2)
+        return st3d_need_blocks_build(mask, images, p->S, need - 1, p->d.need_cols, L.need_seg, p->need_flags, p->need_flags_bytes, L.need_list,
+                                      L.need_cnt, gram ? L.need_gram_list : nullptr, L.need_gram_cnt, s);
+    return st3d_need_build(mask, images, p->S, need, L.need_seg, p->need_flags, p->need_flags_bytes, L.need_list[0], L.need_list[1], L.need_cnt, s);
+}
+
+// conv slot cs of a clean keyed call over its kept list, in strips (cols = 16) or tiles; yp, yi: the fused pool's outputs
+// (tiles only) or nullptr.  The tiles it leaves out hold the previous call's bits.
+int kept_launch(st3d_plan *p, int cs, const float *x, float *y, float *yp, uint8_t *yi, int n, int cols, const st3d_plan::Lists &L,
+                hipStream_t s) {
+    const st3d_vgg *v = p->vgg;
+    const int m = kConvIdx[cs], k = cs - 1, Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
+    Scope sc(p, F_CONV43_FWD_FLAT, s, m);
+    if (cols == 16) return st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], y, n, Cin, Cout, H, W, 1, L.kept_list[k], L.kept_cnt + k, s);
+    return st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], y, yp, yi, n, Cin, Cout, H, W, 1, cols, L.kept_list[k], L.kept_cnt + k, s);
 }
 
 // the launches of images [i0, i0 + n) from module 0 to upto on stream s; x: the first of those images
 int forward_chain(st3d_plan *p, const float *x, int i0, int n, int upto, bool keep_full, hipStream_t s, int flat, int keep, bool fill,
-                  const FwdLists &L) {
+                  const FwdLists &fl) {
     const st3d_vgg *v = p->vgg;
-    auto act = [&](int m) { return p->act[m] + (size_t)i0 * p->C[m] * p->H[m] * p->W[m]; };
-    auto pix = [&](int ps) { const int m = kPoolIdx[ps]; return p->pidx[ps] + (size_t)i0 * p->C[m] * p->H[m] * p->W[m]; };
-    auto on = [&](int k) { return !L.kept_on || L.kept_on[k]; };
+    const st3d_plan::Lists &L = fl.lists;
+    auto act = [&](int m) { return p->at(p->act[m], m, i0); };
+    auto on = [&](int k) { return !fl.kept_on || fl.kept_on[k]; };
     for (int m = 0; m <= upto; ++m) {
         const int cs = conv_slot(m), ps = pool_slot(m);
         if (cs >= 0) {
@@ -444,9 +422,9 @@ int forward_chain(st3d_plan *p, const float *x, int i0, int n, int upto, bool ke
             }
             const int Cin = kConvCin[cs], Cout = kConvCout[cs], H = p->H[m], W = p->W[m];
             const uint8_t route = p->route[cs].fwd;
-            if (route == DIRECT && cs == 0 && !fill && L.c1_skip) {     // conv1_1 of a clean keyed call: the covered tiles
+            if (route == DIRECT && cs == 0 && !fill && fl.c1_skip) {     // conv1_1 of a clean keyed call: the covered tiles
                 Scope sc(p, F_CONVX_FWD_FLAT, s, m);
-                ST3D_TRY(st3d_conv3x3_fwd_skip(x, v->wf[cs], v->bias[cs], act(m), n, Cin, Cout, H, W, 1, L.c1_skip, s));
+                ST3D_TRY(st3d_conv3x3_fwd_skip(x, v->wf[cs], v->bias[cs], act(m), n, Cin, Cout, H, W, 1, fl.c1_skip, s));
                 x = act(m);
                 continue;
             }
@@ -461,17 +439,14 @@ int forward_chain(st3d_plan *p, const float *x, int i0, int n, int upto, bool ke
             const int pps = (pool_m <= upto) ? pool_slot(pool_m) : -1;
             float *yfull = (pps < 0 || keep_full) ? act(m) : nullptr;
             float *yp = pps >= 0 ? act(pool_m) : nullptr;
-            uint8_t *yi = pps >= 0 ? pix(pps) : nullptr;
-            if (cs >= 1 && cs <= flat && !fill && keep > 0 && p->shallow_cols[cs - 1] && on(cs - 1)) {
-                // a clean keyed call: the kept list in its own geometry; the tiles it leaves out hold the previous call's bits
-                Scope sc(p, F_CONV43_FWD_FLAT, s, m);
-                const int k = cs - 1;
-                if (p->shallow_cols[k] == 16)
-                    ST3D_TRY(st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], yfull, n, Cin, Cout, H, W, 1, L.kept_list[k],
-                                                    L.kept_cnt + k, s));
-                else
-                    ST3D_TRY(st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, p->shallow_cols[k],
-                                                       L.kept_list[k], L.kept_cnt + k, s));
+            uint8_t *yi = pps >= 0 ? p->at(p->pidx[pps], pool_m, i0) : nullptr;
+            // a clean keyed call: the geometry of the kept list this launch walks (0: none) -- a shallow level's own, or the
+            // tiles of conv3_1 .. that the coverage can change (no pool there: yfull is the output, yp and yi are null)
+            // (the range first: only conv slots 1 .. flat and kKeepFirst + 1 .. kKeepFirst + keep name a list)
+            const bool listed = cs >= 1 && (cs <= flat || (cs > kKeepFirst && cs <= kKeepFirst + keep));
+            const int kept_cols = !(listed && !fill && keep > 0 && on(cs - 1)) ? 0 : cs <= flat ? p->d.shallow_cols[cs - 1] : p->d.keep_cols[cs - 1];
+            if (kept_cols) {
+                ST3D_TRY(kept_launch(p, cs, x, yfull, yp, yi, n, kept_cols, L, s));
             } else if (cs >= 1 && cs <= flat) {    // an F(4x4,3x3) launch over its flat-field list, then the copies
                 {
                     Scope sc(p, F_CONV43_FWD_FLAT, s, m);
@@ -482,16 +457,6 @@ int forward_chain(st3d_plan *p, const float *x, int i0, int n, int upto, bool ke
                     Scope sc(p, F_FLAT_FILL, s, m);
                     ST3D_TRY(st3d_flat_fill(L.flat_map[cs - 1], yfull, yp, yi, n, Cout, H, W, s));
                 }
-            } else if (!fill && cs > st3d_plan::kKeepFirst && cs <= st3d_plan::kKeepFirst + keep && on(cs - 1)) {
-                // a clean keyed call: the tiles the coverage can change; the others keep the previous call's bits (no pool here)
-                Scope sc(p, F_CONV43_FWD_FLAT, s, m);
-                const int k = cs - 1;
-                if (p->keep_cols[k] == 16)
-                    ST3D_TRY(st3d_wino43_fwd_strips(x, v->u6f[cs], v->bias[cs], act(m), n, Cin, Cout, H, W, 1, L.kept_list[k],
-                                                    L.kept_cnt + k, s));
-                else
-                    ST3D_TRY(st3d_wino43_fwd_tiles_geo(x, v->u6f[cs], v->bias[cs], act(m), nullptr, nullptr, n, Cin, Cout, H, W, 1,
-                                                       p->keep_cols[k], L.kept_list[k], L.kept_cnt + k, s));
             } else if (route == WINO43) {
                 Scope sc(p, F_CONV43_FWD, s, m);
                 ST3D_TRY(st3d_wino43_fwd(x, v->u6f[cs], v->bias[cs], yfull, yp, yi, n, Cin, Cout, H, W, 1, s));
@@ -503,7 +468,7 @@ int forward_chain(st3d_plan *p, const float *x, int i0, int n, int upto, bool ke
             if (pps >= 0) m = pool_m;               // modules m+1, m+2 are done
         } else if (ps >= 0) {                       // (the ReLU before it kept its conv's C, H, W)
             Scope sc(p, F_POOL, s, m);
-            ST3D_TRY(st3d_maxpool2x2_fwd(x, act(m), pix(ps), n, p->C[m], p->H[m - 1], p->W[m - 1], s));
+            ST3D_TRY(st3d_maxpool2x2_fwd(x, act(m), p->at(p->pidx[ps], m, i0), n, p->C[m], p->H[m - 1], p->W[m - 1], s));
             x = act(m);
         }   // ReLU modules are fused into their conv
     }
@@ -513,77 +478,54 @@ int forward_chain(st3d_plan *p, const float *x, int i0, int n, int upto, bool ke
 int forward(st3d_plan *p, const float *imgs, int n, int upto, bool keep_full, hipStream_t s, const float *flat_color = nullptr,
             Keyed *key = nullptr) {
     const st3d_vgg *v = p->vgg;
+    st3d_plan::ListSet *ls = p->ls;
     int flat = 0;               // conv slots 1 .. flat run listed
     if (flat_color)
-        while (flat < p->flat_levels && kConvIdx[flat + 1] <= upto) ++flat;
+        while (flat < p->d.flat_levels && kConvIdx[flat + 1] <= upto) ++flat;
     int keep = 0;               // conv slots 4 .. 3 + keep (conv3_1 ..) may run over their kept lists
-    if (key && flat == p->flat_levels)
-        while (keep < p->keep_levels && kConvIdx[st3d_plan::kKeepFirst + 1 + keep] <= upto) ++keep;
+    if (key && flat == p->d.flat_levels)
+        while (keep < p->d.keep_levels && kConvIdx[kKeepFirst + 1 + keep] <= upto) ++keep;
     const bool fill = !(key && flat > 0 && p->clean.matches(key->epoch, n, flat, key->rgb, v->sets, keep));
     p->clean.clear();           // every path below writes act[] / pidx[]; the keyed entry sets the record again when all went well
     if (flat > 0 && !key) {
         Scope sc(p, F_ELEM, s);
-        ST3D_TRY(st3d_flat_build(imgs, flat_color, n, p->S, flat, p->flat_ws, p->flat_ws_bytes, p->ls->flat_list[0], p->ls->flat_map[0],
-                                 p->ls->flat_list[1], p->ls->flat_map[1], p->ls->flat_list[2], p->ls->flat_map[2], p->ls->flat_cnt, s));
-    } else if (flat > 0) {
-        if (p->flat_check) {    // the premise on this call's pixels: one host read, debug runs only
-            int bad = 0;
-            ST3D_TRY(st3d_flat_check_cover(imgs, flat_color, key->cover, n, p->S, p->flat_ws, p->flat_ws_bytes, p->sets[0].flat_cnt + 3, s));
-            ST3D_HIP(hipMemcpyAsync(&bad, p->sets[0].flat_cnt + 3, sizeof(int), hipMemcpyDeviceToHost, s));
-            ST3D_HIP(hipStreamSynchronize(s));
-            if (bad) {
-                st3d::set_error("st3d_plan_loss_keyed: a pixel outside the coverage differs from the background colour");
-                return ST3D_E_STATE;
-            }
-        }
-        if (!p->ls->have_flat) {
-            Scope sc(p, F_ELEM, s);
-            ST3D_TRY(st3d_flat_build_cover(key->cover, n, p->S, flat, p->flat_ws, p->flat_ws_bytes, p->ls->flat_list[0], p->ls->flat_map[0],
-                                           p->ls->flat_list[1], p->ls->flat_map[1], p->ls->flat_list[2], p->ls->flat_map[2],
-                                           p->ls->flat_cnt, s));
-            if (p->ls->c1_skip) ST3D_TRY(st3d_conv1_skip_build(key->cover, n, p->S, p->S, p->ls->c1_skip, s));
-            p->ls->have_flat = true;
+        st3d_plan::Lists &L = ls->whole;
+        ST3D_TRY(st3d_flat_build(imgs, flat_color, n, p->S, flat, p->flat_ws, p->flat_ws_bytes, L.flat_list[0], L.flat_map[0], L.flat_list[1],
+                                 L.flat_map[1], L.flat_list[2], L.flat_map[2], L.flat_cnt, s));
+    } else if (flat > 0 && p->flat_check) {     // the premise on this call's pixels: one host read, debug runs only
+        int bad = 0, *cnt = p->sets[0].whole.flat_cnt + 3;
+        ST3D_TRY(st3d_flat_check_cover(imgs, flat_color, key->cover, n, p->S, p->flat_ws, p->flat_ws_bytes, cnt, s));
+        ST3D_HIP(hipMemcpyAsync(&bad, cnt, sizeof(int), hipMemcpyDeviceToHost, s));
+        ST3D_HIP(hipStreamSynchronize(s));
+        if (bad) {
+            st3d::set_error("st3d_plan_loss_keyed: a pixel outside the coverage differs from the background colour");
+            return ST3D_E_STATE;
         }
     }
-    if (key) { key->flat_done = flat; key->kept_done = keep; key->clean_call = !fill; }
-    if (!fill && keep > 0 && !p->ls->have_kept) {       // the epoch's first clean call: a run that changes its geometry every step never gets here
-        Scope sc(p, F_ELEM, s);
-        ST3D_TRY(st3d_kept_build(key->cover, n, p->S, p->keep_first, st3d_plan::kKeepFirst + p->keep_levels, p->keep_cols, p->keep_ws,
-                                 p->keep_ws_bytes, p->ls->kept_list, p->ls->kept_cnt, s));
-        p->ls->have_kept = true;
+    if (key) {
+        // the flat-field lists once per epoch; the kept lists by the epoch's first clean call (a run that changes its
+        // geometry every step never gets there).  Each flag is set as soon as its build is enqueued.
+        const bool want_flat = flat > 0 && !ls->have_flat, want_kept = !fill && keep > 0 && !ls->have_kept;
+        ST3D_TRY(build_forward_lists(p, ls->whole, key->cover, n, flat, want_flat, ls->c1_skip, false, s));
+        ls->have_flat |= want_flat;
+        key->flat_done = flat; key->kept_done = keep; key->clean_call = !fill;
+        ST3D_TRY(build_forward_lists(p, ls->whole, key->cover, n, flat, false, nullptr, want_kept, s));
+        ls->have_kept |= want_kept;
     }
-    st3d_plan::ListSet *ls = p->ls;
-    if (!fill && upto == 28 && !keep_full && split_ok(p, st3d_plan::SPLIT_FWD, n, key != nullptr)) {
-        // ---- the clean call as two groups: the first on s, the second on the plan's stream
+    if (!fill && upto == 28 && !keep_full && split_ok(p, SPLIT_FWD, n, key != nullptr)) {
+        // ---- the clean call as two groups; the epoch's first split call runs the builders once more, on each group's slice
         const int h = n / 2;
-        if (!ls->have_grp_fwd) {        // the epoch's first split call: the builders once more, on each group's slice of the coverage
-            for (int g = 0; g < 2; ++g) {
-                st3d_plan::GroupLists &G = ls->grp[g];
-                const uint8_t *cover = key->cover + (size_t)g * h * p->S * p->S;
-                ST3D_TRY(st3d_flat_build_cover(cover, h, p->S, flat, p->flat_ws, p->flat_ws_bytes, G.flat_list[0], G.flat_map[0], G.flat_list[1],
-                                               G.flat_map[1], G.flat_list[2], G.flat_map[2], G.flat_cnt, s));
-                if (keep > 0)
-                    ST3D_TRY(st3d_kept_build(cover, h, p->S, p->keep_first, st3d_plan::kKeepFirst + p->keep_levels, p->keep_cols, p->keep_ws,
-                                             p->keep_ws_bytes, G.kept_list, G.kept_cnt, s));
-            }
-            ls->have_grp_fwd = true;
-        }
-        ST3D_TRY(split_fork(p, 0, s));
-        int rc = ST3D_OK;
-        for (int g = 0; g < 2 && rc == ST3D_OK; ++g) {
-            const st3d_plan::GroupLists &G = ls->grp[g];
-            const FwdLists L{ls->c1_skip ? ls->c1_skip + st3d_conv1_skip_tiles(1, p->S, p->S) * (size_t)g * h : nullptr,
-                             G.kept_list, G.kept_cnt, G.flat_list, G.flat_map, G.flat_cnt, p->grp_kept_on};
-            rc = forward_chain(p, imgs + (size_t)g * h * 3 * p->S * p->S, g * h, h, upto, keep_full, split_stream(p, g, s), flat, keep, fill, L);
-        }
-        const int rj = split_join(p, 0, s);     // (also after a failure: the caller's stream stays behind whatever was enqueued)
-        if (rc != ST3D_OK || rj != ST3D_OK) return rc != ST3D_OK ? rc : rj;
-        ++p->split_calls[0];
-        p->last_n = n;
-        return ST3D_OK;
+        for (int g = 0; g < 2 && !ls->have_grp_fwd; ++g)
+            ST3D_TRY(build_forward_lists(p, ls->grp[g], key->cover + (size_t)g * h * p->S * p->S, h, flat, true, nullptr, keep > 0, s));
+        ls->have_grp_fwd = true;
+        ST3D_TRY(run_split(p, 0, s, [&](int g, hipStream_t gs) {
+            const FwdLists fl{ls->grp[g], ls->c1_skip ? ls->c1_skip + st3d_conv1_skip_tiles(1, p->S, p->S) * (size_t)g * h : nullptr,
+                              p->d.grp_kept_on};
+            return forward_chain(p, imgs + (size_t)g * h * 3 * p->S * p->S, g * h, h, upto, keep_full, gs, flat, keep, fill, fl);
+        }));
+    } else {
+        ST3D_TRY(forward_chain(p, imgs, 0, n, upto, keep_full, s, flat, keep, fill, FwdLists{ls->whole, ls->c1_skip, nullptr}));
     }
-    const FwdLists L{fill ? nullptr : ls->c1_skip, ls->kept_list, ls->kept_cnt, ls->flat_list, ls->flat_map, ls->flat_cnt, nullptr};
-    ST3D_TRY(forward_chain(p, imgs, 0, n, upto, keep_full, s, flat, keep, fill, L));
     p->last_n = n;
     return ST3D_OK;
 }
@@ -649,10 +591,10 @@ int dgrad_step(st3d_plan *p, int cs, const float *g, bool g_is_pooled, int pool_
         return ST3D_E_STATE;
     }
     Scope sc(p, o.tile_list ? F_CONV43_DGRAD_NEED : w43 ? F_CONV43_DGRAD : (wino ? F_CONV_DGRAD : F_CONVX_DGRAD), s, m);
-    auto img = [&](int mm) { return (size_t)i0 * p->C[mm] * p->H[mm] * p->W[mm]; };
-    const uint8_t *pidx = g_is_pooled ? p->pidx[pool_of_g] + img(kPoolIdx[pool_of_g]) : nullptr;
-    const float *pooled = g_is_pooled ? p->act[kPoolIdx[pool_of_g]] + img(kPoolIdx[pool_of_g]) : nullptr;
-    const float *act_m = p->act[m] + img(m);
+    const int pm = g_is_pooled ? kPoolIdx[pool_of_g] : 0;
+    const uint8_t *pidx = g_is_pooled ? p->at(p->pidx[pool_of_g], pm, i0) : nullptr;
+    const float *pooled = g_is_pooled ? p->at(p->act[pm], pm, i0) : nullptr;
+    const float *act_m = p->at(p->act[m], m, i0);
     if (o.tile_list)
         ST3D_TRY(st3d_wino43_dgrad_chain_tiles_geo(g, pidx, v->u6d[cs], o.out_gate, o.add_target, o.add_coef, dst, n, Cin, Cout, H, W,
                                                    o.tile_cols, o.tile_list, o.n_active, s));
@@ -713,113 +655,21 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
         r.gate_dst = v->pregate && cs > 0 && r.dgrad_wino && p->route[cs - 1].dgrad_wino;
     }
     p->fused_tap0 = v->fuse_tap0 && st3d_conv1_bwd_supported(S, S) && gmax >= (size_t)B * 27 * S * S;
-    // ST3D_NEED_DEPTH=k / ST3D_FLAT_DEPTH=k: at most k levels (A/B runs; the default is all of them: each measured to pay,
-    // DESIGN.md 6)
-    auto capped = [](int levels, const char *name) {
-        const char *e = getenv(name);
-        return (e && atoi(e) >= 0 && atoi(e) < levels) ? atoi(e) : levels;
-    };
-    // a listed conv1_2 / conv2_1 input gradient is an F(4x4,3x3) launch, so its gradient has to arrive gated
-    int need_ok = p->fused_tap0 ? 1 : 0;
-    if (need_ok == 1 && p->route[2].gate_dst && p->route[1].dgrad_w43) need_ok = 2;
-    if (need_ok == 2 && p->route[2].dgrad_w43) need_ok = 3;
-    int need_max = st3d_need_levels(S);
-    auto flag = [](const char *name, bool dflt) { const char *e = getenv(name); return e && e[0] ? e[0] != '0' : dflt; };
-    p->need_blocks = need_ok >= 2 && st3d_need_blocks_lists(S) >= 2 && flag("ST3D_NEED_BLOCKS", true);
-    if (p->need_blocks) {
-        // The per-block lists (need.hip).  Level cs + 1 lists the input gradient of conv slot cs = list cs - 1.  A level above
-        // conv2_1, or a geometry other than the kernel's own, engages only where the full launch walks at least two tiles per
-        // persistent workgroup, N tiles_x tiles_y >= 2 (CUs / n_ct): below that every workgroup has one tile at the most and a
-        // list saves nothing (ST3D_NEED_FORCE=1 lifts the rule: tests reach every level at small sizes).
-        // ST3D_NEED_TILE=64|32|16 (or one value per list, comma-separated): that geometry on every listed level it fits
-        // (16 = strips of 4 x 16 pixels, four to a step: it fits every map the kernel covers).
-        need_max = 1 + st3d_need_blocks_lists(S);
-        const bool force = flag("ST3D_NEED_FORCE", false);
-        int cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        auto two_rounds = [&](int cs) {
-            const int R = p->H[kConvIdx[cs]];
-            return force || (long)B * (R / 4) * (R / 4) / 16 >= 2L * (cus / std::max(1, kConvCin[cs] / 64));
-        };
-        // conv2_2 and conv3_1 .. conv3_3: F(4x4,3x3) launches whose gradient arrives gated (from the launch above, or the taps)
-        for (int cs = 3; cs <= ST3D_NEED_MAX_LISTS && need_ok == cs; ++cs)
-            if (p->route[cs].dgrad_w43 && (cs == 4 ? p->route[cs].gate_taps : p->route[cs + 1].gate_dst) && two_rounds(cs)) need_ok = cs + 1;
-        // measured defaults: strips of 4 x 16 pixels on every level but conv3_1, which no geometry finer than 8 x 32
-        // tiles brings under its three rounds
-        static const int kDefaultCols[ST3D_NEED_MAX_LISTS] = {16, 16, 16, 32, 16, 16};
-        const char *tile = getenv("ST3D_NEED_TILE");
-        for (int k = 0; k < ST3D_NEED_MAX_LISTS; ++k) {
-            const int R = p->H[kConvIdx[k + 1]];
-            int cols = kDefaultCols[k];
-            if (tile && tile[0]) {
-                cols = atoi(tile);
-                if (const char *c = strchr(tile, ',')) { tile = c + 1; }
-            }
-            int rows0 = 0, cols0 = 0;
-            st3d_wino43_tile_geometry(R, R, &rows0, &cols0);
-            const bool fits = (cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0 && R % 8 == 0) || (cols == 16 && rows0 != 0);
-            p->need_cols[k] = (fits && cols != cols0 && two_rounds(k + 1)) ? cols : 0;
-        }
-    }
-    p->need_levels = capped(std::min(need_ok, need_max), "ST3D_NEED_DEPTH");
-    if (p->need_blocks && p->need_levels >= 3) {
-        // the relu2_1 Gram backward listed: one workgroup per 64-pixel run, four to a CU -- the same two-rounds rule
-        const int m = kConvIdx[2], HW = p->H[m] * p->W[m];
-        int cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        p->need_gram = flag("ST3D_NEED_GRAM", true) && p->route[2].gate_taps && st3d_gram_bwd_segs_supported(p->C[m], HW) &&
-                       st3d_need_blocks_gram_runs(B, S) > 0 && (flag("ST3D_NEED_FORCE", false) || (long)B * (HW / 64) >= 2L * 4 * cus);
-    }
-    int flat_ok = 0;
-    while (flat_ok < 3 && p->route[flat_ok + 1].fwd == WINO43) ++flat_ok;
-    p->flat_levels = capped(std::min(flat_ok, st3d_flat_levels(S)), "ST3D_FLAT_DEPTH");
-    {
-        // The kept lists: conv3_1 .. conv3_3 above a full set of flat-field levels, F(4x4,3x3) launches without a pool, where the
-        // full launch walks at least two tiles per persistent workgroup (the rule of the need lists, with the forward's Cout;
-        // ST3D_KEEP_FORCE=1 lifts it for tests -- ST3D_NEED_FORCE does not).  ST3D_KEEP_TILE as ST3D_NEED_TILE, one value for
-        // every level or one per level from conv3_1 on; measured default: strips.
-        const bool force = flag("ST3D_KEEP_FORCE", false);
-        int cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        int keep_ok = 0;
-        const int lists = st3d_need_blocks_lists(S);
-        const char *tile = getenv("ST3D_KEEP_TILE");
-        while (p->flat_levels == 3 && keep_ok < st3d_plan::kKeepMax) {
-            const int k = st3d_plan::kKeepFirst + keep_ok, cs = k + 1, R = p->H[kConvIdx[cs]];
-            if (k >= lists || p->route[cs].fwd != WINO43 || pool_slot(kConvIdx[cs] + 2) >= 0) break;
-            if (!force && (long)B * (R / 4) * (R / 4) / 16 < 2L * (cus / std::max(1, kConvCout[cs] / 64))) break;
-            int cols = 16;
-            if (tile && tile[0]) {
-                cols = atoi(tile);
-                if (const char *c = strchr(tile, ',')) { tile = c + 1; }
-            }
-            int rows0 = 0, cols0 = 0;
-            st3d_wino43_tile_geometry(R, R, &rows0, &cols0);
-            if (cols == 0) cols = cols0;
-            if (!((cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0 && R % 8 == 0) || cols == 16)) break;
-            p->keep_cols[k] = cols;
-            ++keep_ok;
-        }
-        p->keep_levels = capped(keep_ok, "ST3D_KEEP_DEPTH");
-        // ST3D_KEEP_SHALLOW = a,b,c: the geometry of conv1_2, conv2_1, conv2_2 in clean calls (0 = their flat-field lists);
-        // measured default.  Only above a kept conv3_1, and under the same two-rounds rule.
-        static const int kDefaultShallow[3] = {32, 16, 32};
-        const char *sh = getenv("ST3D_KEEP_SHALLOW");
-        for (int k = 0; k < 3 && p->keep_levels >= 1; ++k) {
-            const int cs = k + 1, R = p->H[kConvIdx[cs]];
-            int cols = kDefaultShallow[k];
-            if (sh) {
-                cols = atoi(sh);
-                if (const char *c = strchr(sh, ',')) { sh = c + 1; } else { sh = ""; }
-            }
-            const bool pools = pool_slot(kConvIdx[cs] + 2) >= 0;
-            const bool fits = (cols == 64 && R % 64 == 0) || (cols == 32 && R % 32 == 0 && R % 8 == 0) || (cols == 16 && !pools);
-            if (!fits || (!force && (long)B * (R / 4) * (R / 4) / 16 < 2L * (cus / std::max(1, kConvCout[cs] / 64)))) continue;
-            p->shallow_cols[k] = cols;
-            if (k < p->keep_first) p->keep_first = k;
-        }
-        for (int k = p->keep_first; k < 3; ++k) p->keep_cols[k] = p->shallow_cols[k] ? p->shallow_cols[k] : 16;     // (built, not walked)
-    }
+    // ---- what the lists' decisions rest on (planlists.h), asked once: the CU count and the kernels' answers
+    PlanFacts f;
+    f.B = B; f.S = S;
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&f.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || f.cus <= 0) f.cus = 256;
+    for (int cs = 0; cs < 16; ++cs) { f.H[cs] = p->H[kConvIdx[cs]]; f.route[cs] = p->route[cs]; }
+    f.fused_tap0 = p->fused_tap0;
+    f.need_levels = st3d_need_levels(S);
+    f.blocks_lists = st3d_need_blocks_lists(S);
+    f.flat_levels = st3d_flat_levels(S);
+    for (int k = 0; k < ST3D_NEED_MAX_LISTS; ++k) st3d_wino43_tile_geometry(f.H[k + 1], f.H[k + 1], &f.geo_rows[k], &f.geo_cols[k]);
+    f.gram_segs = st3d_gram_bwd_segs_supported(p->C[kConvIdx[2]], f.H[2] * f.H[2]) != 0;
+    f.gram_runs = st3d_need_blocks_gram_runs(B, S);
+    p->d = decide_lists(f, [](const char *name) -> const char * { return getenv(name); });
+    const PlanDecisions &d = p->d;
     for (int i = 0; i < 2; ++i) alloc(&p->gbuf[i], gmax);
     alloc(&p->content_target, (size_t)B * p->C[kContentTap] * p->H[kContentTap] * p->W[kContentTap]);
     for (int i = 0; i < 5; ++i) {
@@ -843,114 +693,72 @@ extern "C" int st3d_plan_create(st3d_plan **out, st3d_vgg *vgg, int B, int S) {
     alloc(&p->g_in, (size_t)B * 3 * S * S);
     alloc(&p->g_grad, (size_t)B * 3 * S * S);
     alloc(&p->g_loss, (size_t)4);
-    if (p->need_levels >= 1) {
+    if (d.need_levels >= 1) {
         alloc(&p->g_mask, (size_t)B * S * S);
-        p->need_flags_bytes = p->need_blocks ? st3d_need_blocks_workspace_bytes(B, S) : st3d_need_workspace_bytes(B, S);
-        if (p->need_levels >= 2) alloc(&p->need_flags, p->need_flags_bytes);
+        p->need_flags_bytes = d.need_blocks ? st3d_need_blocks_workspace_bytes(B, S) : st3d_need_workspace_bytes(B, S);
+        if (d.need_levels >= 2) alloc(&p->need_flags, p->need_flags_bytes);
     }
-    if (p->flat_levels >= 1) {
+    if (d.flat_levels >= 1) {
         p->flat_ws_bytes = st3d_flat_workspace_bytes(B, S);
         alloc(&p->flat_ws, p->flat_ws_bytes);
         alloc(&p->g_color, (size_t)4);
     }
-    if (p->keep_levels >= 1) {
+    if (d.keep_levels >= 1) {
         p->keep_ws_bytes = st3d_need_blocks_workspace_bytes(B, S);
         alloc(&p->keep_ws, p->keep_ws_bytes);
-        for (int i = 1; i <= st3d_plan::kEpochSlots; ++i) {
-            alloc(&p->sets[i].kept_cnt, (size_t)ST3D_NEED_MAX_LISTS);
-            for (int k = p->keep_first; k < st3d_plan::kKeepFirst + p->keep_levels; ++k)
-                alloc(&p->sets[i].kept_list[k], st3d_need_blocks_entries(B, S, k, p->keep_cols[k]));
-        }
     }
-    for (st3d_plan::ListSet &ls : p->sets) {     // the lists themselves: the unkeyed set and one per epoch slot
-        if (p->need_levels >= 1) {
-            alloc(&ls.need_seg, (size_t)B * S * (S / 64));
-            alloc(&ls.need_cnt, (size_t)ST3D_NEED_MAX_LISTS);
-            if (p->need_gram) {
-                alloc(&ls.need_gram_list, st3d_need_blocks_gram_runs(B, S));
-                alloc(&ls.need_gram_cnt, (size_t)1);
+    // the lists of `images` images: the flat-field ones always, the need and kept ones where the caller says
+    auto alloc_lists = [&](st3d_plan::Lists &L, int images, bool need, bool kept) {
+        if (need) {
+            alloc(&L.need_seg, (size_t)images * S * (S / 64));
+            alloc(&L.need_cnt, (size_t)ST3D_NEED_MAX_LISTS);
+            if (d.need_gram) {
+                alloc(&L.need_gram_list, st3d_need_blocks_gram_runs(images, S));
+                alloc(&L.need_gram_cnt, (size_t)1);
             }
-            for (int l = 0; l + 2 <= p->need_levels; ++l) {
-                if (p->need_blocks) {
-                    alloc(&ls.need_list[l], st3d_need_blocks_entries(B, S, l, p->need_cols[l]));
+            for (int l = 0; l + 2 <= d.need_levels; ++l) {
+                if (d.need_blocks) {
+                    alloc(&L.need_list[l], st3d_need_blocks_entries(images, S, l, d.need_cols[l]));
                     continue;
                 }
                 int rows = 0, cols = 0;
                 st3d_wino43_tile_geometry(S >> l, S >> l, &rows, &cols);
-                alloc(&ls.need_list[l], (size_t)B * ((S >> l) / rows) * ((S >> l) / cols));
+                alloc(&L.need_list[l], (size_t)images * ((S >> l) / rows) * ((S >> l) / cols));
             }
         }
-        if (p->flat_levels >= 1) {
-            alloc(&ls.flat_cnt, (size_t)4);
-            for (int k = 0; k < p->flat_levels; ++k) {
-                alloc(&ls.flat_list[k], (size_t)st3d_flat_tiles(B, S, k));
-                alloc(&ls.flat_map[k], (size_t)st3d_flat_tiles(B, S, k));
+        if (d.flat_levels >= 1) {
+            alloc(&L.flat_cnt, (size_t)4);
+            for (int k = 0; k < d.flat_levels; ++k) {
+                alloc(&L.flat_list[k], (size_t)st3d_flat_tiles(images, S, k));
+                alloc(&L.flat_map[k], (size_t)st3d_flat_tiles(images, S, k));
             }
         }
-    }
-    {
-        // ST3D_SPLIT_BATCH = 0 | 1 | fwd | bwd: clean keyed calls as two groups, the second on a stream of the plan's, in both directions or one
-        // (measured default: DESIGN.md 6).  The two-rounds rule once more with a group's count: a list that leaves a group's
-        // launch under two tiles per workgroup is not walked by the groups (the launch runs in full, or over its flat-field
-        // list), and the need levels stop below the first such launch.
-        const char *sb = getenv("ST3D_SPLIT_BATCH");
-        if (sb && sb[0]) p->split_mode = strcmp(sb, "fwd") == 0 ? st3d_plan::SPLIT_FWD : strcmp(sb, "bwd") == 0 ? st3d_plan::SPLIT_BWD :
-                                         sb[0] == '1' ? (st3d_plan::SPLIT_FWD | st3d_plan::SPLIT_BWD) : 0;
-        else p->split_mode = ST3D_SPLIT_BATCH_DEFAULT;
-        if (B < 4 || p->flat_levels < 1) p->split_mode = 0;
-        int cus = 0, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-        const int hb = B / 2;
-        auto rounds = [&](int cs, int channels) {       // a group's launch of conv slot cs walks two tiles per workgroup
-            const int R = p->H[kConvIdx[cs]];
-            return (long)hb * (R / 4) * (R / 4) / 16 >= 2L * (cus / std::max(1, channels / 64));
-        };
-        const bool keep_force = flag("ST3D_KEEP_FORCE", false), need_force = flag("ST3D_NEED_FORCE", false);
-        for (int k = 0; k < ST3D_NEED_MAX_LISTS; ++k) {
-            const bool walked = k < 3 ? p->shallow_cols[k] != 0 : k - st3d_plan::kKeepFirst < p->keep_levels;
-            p->grp_kept_on[k] = walked && (keep_force || rounds(k + 1, kConvCout[k + 1]));
+        if (kept) {
+            alloc(&L.kept_cnt, (size_t)ST3D_NEED_MAX_LISTS);
+            for (int k = d.keep_first; k < kKeepFirst + d.keep_levels; ++k)
+                alloc(&L.kept_list[k], st3d_need_blocks_entries(images, S, k, d.keep_cols[k]));
         }
-        p->grp_need_levels = p->need_levels;
-        for (int cs = 3; cs <= ST3D_NEED_MAX_LISTS && cs + 1 <= p->grp_need_levels; ++cs)
-            if (!need_force && !rounds(cs, kConvCin[cs])) p->grp_need_levels = cs;
-        const int m2 = kConvIdx[2];
-        p->grp_need_gram = p->need_gram && (need_force || (long)hb * (p->H[m2] * p->W[m2] / 64) >= 2L * 4 * cus);
-    }
-    if (p->split_mode && rc == ST3D_OK) {
-        const int hb = B / 2;
-        bool ok = true;
-        ok = hipStreamCreateWithFlags(&p->gstream, hipStreamNonBlocking) == hipSuccess;
-        for (int d = 0; d < 2; ++d)
-            ok = ok && hipEventCreateWithFlags(&p->ev_fork[d], hipEventDisableTiming) == hipSuccess &&
-                 hipEventCreateWithFlags(&p->ev_join[d], hipEventDisableTiming) == hipSuccess;
+    };
+    if (d.split_mode && rc == ST3D_OK) {
+        bool ok = hipStreamCreateWithFlags(&p->gstream, hipStreamNonBlocking) == hipSuccess;
+        for (int dir = 0; dir < 2; ++dir)
+            ok = ok && hipEventCreateWithFlags(&p->ev_fork[dir], hipEventDisableTiming) == hipSuccess &&
+                 hipEventCreateWithFlags(&p->ev_join[dir], hipEventDisableTiming) == hipSuccess;
         if (!ok) { st3d::set_error("st3d_plan_create: the split batch's stream and events could not be made"); rc = ST3D_E_HIP; }
-        for (int i = 1; i <= st3d_plan::kEpochSlots; ++i)
-            for (st3d_plan::GroupLists &G : p->sets[i].grp) {
-                alloc(&G.flat_cnt, (size_t)4);
-                for (int k = 0; k < p->flat_levels; ++k) {
-                    alloc(&G.flat_list[k], (size_t)st3d_flat_tiles(hb, S, k));
-                    alloc(&G.flat_map[k], (size_t)st3d_flat_tiles(hb, S, k));
-                }
-                if (p->keep_levels >= 1) {
-                    alloc(&G.kept_cnt, (size_t)ST3D_NEED_MAX_LISTS);
-                    for (int k = p->keep_first; k < st3d_plan::kKeepFirst + p->keep_levels; ++k)
-                        alloc(&G.kept_list[k], st3d_need_blocks_entries(hb, S, k, p->keep_cols[k]));
-                }
-                if (p->need_levels >= 1 && p->need_blocks) {
-                    alloc(&G.need_seg, (size_t)hb * S * (S / 64));
-                    alloc(&G.need_cnt, (size_t)ST3D_NEED_MAX_LISTS);
-                    if (p->need_gram) {
-                        alloc(&G.need_gram_list, st3d_need_blocks_gram_runs(hb, S));
-                        alloc(&G.need_gram_cnt, (size_t)1);
-                    }
-                    for (int l = 0; l + 2 <= p->need_levels; ++l) alloc(&G.need_list[l], st3d_need_blocks_entries(hb, S, l, p->need_cols[l]));
-                }
-            }
     }
+    auto flag = [](const char *name, bool dflt) { const char *e = getenv(name); return e && e[0] ? e[0] != '0' : dflt; };
     p->flat_check = flag("ST3D_FLAT_CHECK", false);
-    p->conv1_skip = p->flat_levels >= 1 && p->route[0].fwd == DIRECT && flag("ST3D_FLAT_CONV1", true);
-    if (p->conv1_skip)
-        for (int k = 1; k <= st3d_plan::kEpochSlots; ++k) alloc(&p->sets[k].c1_skip, st3d_conv1_skip_tiles(B, S, S));
+    p->conv1_skip = d.flat_levels >= 1 && p->route[0].fwd == DIRECT && flag("ST3D_FLAT_CONV1", true);
+    // the unkeyed set has the need and flat-field lists of the batch; an epoch's set also its kept lists, conv1_1's skip
+    // bytes and, in a split plan, each group's lists (their need lists only the per-block ones: a group's backward requires them)
+    for (int i = 0; i <= st3d_plan::kEpochSlots; ++i) {
+        st3d_plan::ListSet &ls = p->sets[i];
+        alloc_lists(ls.whole, B, d.need_levels >= 1, i >= 1 && d.keep_levels >= 1);
+        if (i == 0) continue;
+        if (d.split_mode)
+            for (st3d_plan::Lists &G : ls.grp) alloc_lists(G, B / 2, d.need_levels >= 1 && d.need_blocks, d.keep_levels >= 1);
+        if (p->conv1_skip) alloc(&ls.c1_skip, st3d_conv1_skip_tiles(B, S, S));
+    }
     if (rc != ST3D_OK) { st3d_plan_destroy(p); return rc; }
     *out = p;
     return ST3D_OK;
@@ -1077,6 +885,34 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
                              float content_weight, float *loss_out, float *grad_current, const uint8_t *need_mask, const float *flat_color, hipStream_t s,
                              Keyed *key = nullptr);
 
+// What the flat and the keyed entry ask of a call alike (`who`: the entry, as its own argument checks name it).  Drops
+// *flat_color where the forward runs in full: ST3D_FLAT=0 (A/B runs, read per call), a size without lists, an unaligned image.
+static int check_loss_call(const char *who, const st3d_plan *p, const float *current, int n, int batch_denom, const float **flat_color) {
+#define LOSS_CALL_ARG(cond)         /* ST3D_CHECK_ARG, under the entry's name */ \
+    do {                                                                         \
+        if (!(cond)) {                                                           \
+            st3d::set_error("%s: invalid argument: %s", who, #cond);             \
+            return ST3D_E_INVALID;                                               \
+        }                                                                        \
+    } while (0)
+    if (*flat_color) {
+        const char *fl = getenv("ST3D_FLAT");
+        if ((fl && fl[0] == '0') || p->d.flat_levels < 1 || ((uintptr_t)current & 15) != 0) *flat_color = nullptr;
+    }
+    LOSS_CALL_ARG(n > 0 && n <= p->B && batch_denom >= n);
+    if (!p->have_content || !p->have_style) {
+        st3d::set_error("st3d_plan_loss: content/style targets not set");
+        return ST3D_E_STATE;
+    }
+    LOSS_CALL_ARG(p->style_batch == 1 || p->style_batch == n);
+    if (p->guide_n != 0 && p->guide_n != n) {
+        st3d::set_error("st3d_plan_loss: the style guidance was set for %d images, this call brings %d", p->guide_n, n);
+        return ST3D_E_STATE;
+    }
+    return ST3D_OK;
+#undef LOSS_CALL_ARG
+}
+
 extern "C" int st3d_plan_graph(st3d_plan *p, int enable) {
     ST3D_CHECK_ARG(p);
     p->use_graph = enable ? 1 : 0;
@@ -1103,21 +939,8 @@ extern "C" int st3d_plan_loss_flat(st3d_plan *p, const float *current, int n, in
     p->clean.clear();           // (before anything can fail or replay a graph: an unkeyed call fills whatever it lists)
     p->ls = &p->sets[0];
     ST3D_CHECK_ARG(((uintptr_t)need_mask & 15) == 0);
-    if (!grad_current || p->need_levels < 1) need_mask = nullptr;      // nothing to thin out: the ordinary call
-    if (flat_color) {           // ST3D_FLAT=0 (A/B runs, read per call), a size without lists, an unaligned image: the full forward
-        const char *fl = getenv("ST3D_FLAT");
-        if ((fl && fl[0] == '0') || p->flat_levels < 1 || ((uintptr_t)current & 15) != 0) flat_color = nullptr;
-    }
-    ST3D_CHECK_ARG(n > 0 && n <= p->B && batch_denom >= n);
-    if (!p->have_content || !p->have_style) {
-        st3d::set_error("st3d_plan_loss: content/style targets not set");
-        return ST3D_E_STATE;
-    }
-    ST3D_CHECK_ARG(p->style_batch == 1 || p->style_batch == n);
-    if (p->guide_n != 0 && p->guide_n != n) {
-        st3d::set_error("st3d_plan_loss: the style guidance was set for %d images, this call brings %d", p->guide_n, n);
-        return ST3D_E_STATE;
-    }
+    if (!grad_current || p->d.need_levels < 1) need_mask = nullptr;      // nothing to thin out: the ordinary call
+    ST3D_TRY(check_loss_call(__func__, p, current, n, batch_denom, &flat_color));
     hipStream_t s = st3d::as_stream(stream);
     if (!p->use_graph || p->prof)
         return plan_loss_enqueue(p, current, n, batch_denom, style_weight, content_weight, loss_out, grad_current, need_mask, flat_color, s);
@@ -1178,21 +1001,8 @@ extern "C" int st3d_plan_loss_keyed(st3d_plan *p, const float *current, int n, i
     p->ls = &p->sets[0];
     ST3D_CHECK_ARG(current && loss_out && (!flat_color || flat_rgb));
     ST3D_CHECK_ARG(((uintptr_t)cover & 15) == 0);
-    const uint8_t *need_mask = (grad_current && p->need_levels >= 1) ? cover : nullptr;
-    if (flat_color) {
-        const char *fl = getenv("ST3D_FLAT");
-        if ((fl && fl[0] == '0') || p->flat_levels < 1 || ((uintptr_t)current & 15) != 0) flat_color = nullptr;
-    }
-    ST3D_CHECK_ARG(n > 0 && n <= p->B && batch_denom >= n);
-    if (!p->have_content || !p->have_style) {
-        st3d::set_error("st3d_plan_loss: content/style targets not set");
-        return ST3D_E_STATE;
-    }
-    ST3D_CHECK_ARG(p->style_batch == 1 || p->style_batch == n);
-    if (p->guide_n != 0 && p->guide_n != n) {
-        st3d::set_error("st3d_plan_loss: the style guidance was set for %d images, this call brings %d", p->guide_n, n);
-        return ST3D_E_STATE;
-    }
+    const uint8_t *need_mask = (grad_current && p->d.need_levels >= 1) ? cover : nullptr;
+    ST3D_TRY(check_loss_call(__func__, p, current, n, batch_denom, &flat_color));
     bool fresh = false;
     const int slot = p->epochs.take(epoch, n, &fresh);
     st3d_plan::ListSet *ls = &p->sets[1 + slot];
@@ -1221,8 +1031,7 @@ struct BwdArgs {
     const uint8_t *need_mask;           // likewise (NULL: no lists)
     int need;                           // levels listed
     bool need_gram;
-    const uint8_t *need_seg;
-    int *const *need_list; const int *need_cnt, *need_gram_list, *need_gram_cnt;     // numbered from image i0
+    const st3d_plan::Lists &lists;      // the need lists, numbered from image i0
     float *g0, *g1;                     // the two gradient buffers of this chain and the bytes of each
     size_t gbytes;
 };
@@ -1231,7 +1040,7 @@ static int backward_chain(st3d_plan *p, const BwdArgs &b, hipStream_t s) {
     const bool guided = p->guide_n != 0;
     const int mc = kContentTap;
     const size_t chw = (size_t)p->C[mc] * p->H[mc] * p->W[mc];
-    auto act = [&](int m) { return p->act[m] + (size_t)b.i0 * p->C[m] * p->H[m] * p->W[m]; };
+    auto act = [&](int m) { return p->at(p->act[m], m, b.i0); };
     auto Dof = [&](int st) { const int m = kStyleTap[st]; return p->D[st] + (size_t)b.i0 * p->C[m] * p->C[m]; };
     const float *content_target = p->content_target + (size_t)b.i0 * chw;
     const float *style_coef = b.style_coef;
@@ -1255,11 +1064,11 @@ static int backward_chain(st3d_plan *p, const BwdArgs &b, hipStream_t s) {
             if (guided && st >= 0)
                 ST3D_TRY(st3d_conv1_bwd_weighted(have_g ? g : nullptr, act(m), Dof(st), style_coef[st], p->vgg->wd[0], gn,
                                                  b.gbytes, grad_current, n, H, W, p->guide_w0,
-                                                 need >= 1 ? b.need_seg : nullptr, need >= 1 ? need_mask : nullptr, s));
+                                                 need >= 1 ? b.lists.need_seg : nullptr, need >= 1 ? need_mask : nullptr, s));
             else if (need >= 1)
                 ST3D_TRY(st3d_conv1_bwd_masked(have_g ? g : nullptr, act(m), st >= 0 ? Dof(st) : nullptr,
                                                st >= 0 ? style_coef[st] : 0.f, p->vgg->wd[0], gn, b.gbytes,
-                                               grad_current, n, H, W, b.need_seg, need_mask, s));
+                                               grad_current, n, H, W, b.lists.need_seg, need_mask, s));
             else
             ST3D_TRY(st3d_conv1_bwd(have_g ? g : nullptr, act(m), st >= 0 ? Dof(st) : nullptr, st >= 0 ? style_coef[st] : 0.f,
                                     p->vgg->wd[0], gn, b.gbytes, grad_current, n, H, W, s));
@@ -1269,7 +1078,7 @@ static int backward_chain(st3d_plan *p, const BwdArgs &b, hipStream_t s) {
         if (st >= 0 && cs == 2 && need >= 3 && b.need_gram && chain) {        // relu2_1 over the runs conv2_1's input gradient reads
             Scope sc(p, F_GRAM_BWD_NEED, s, m);
             ST3D_TRY(st3d_gram_bwd_gated_segs(Dof(st), act(m), guided ? p->guide_plane(st) : nullptr, n, C, H * W, style_coef[st],
-                                              have_g ? 1 : 0, b.need_gram_list, b.need_gram_cnt, g, s));
+                                              have_g ? 1 : 0, b.lists.need_gram_list, b.lists.need_gram_cnt, g, s));
             g_gated = true;
             have_g = true;
         } else if (st >= 0) {
@@ -1310,9 +1119,9 @@ static int backward_chain(st3d_plan *p, const BwdArgs &b, hipStream_t s) {
             content_done = true;
         }
         if (cs >= 1 && cs <= ST3D_NEED_MAX_LISTS && need >= cs + 1) {   // conv1_2 .. conv3_3 over their need lists
-            o.tile_list = b.need_list[cs - 1];
-            o.n_active = b.need_cnt + (cs - 1);
-            o.tile_cols = p->need_cols[cs - 1];
+            o.tile_list = b.lists.need_list[cs - 1];
+            o.n_active = b.lists.need_cnt + (cs - 1);
+            o.tile_cols = p->d.need_cols[cs - 1];
         }
         ST3D_TRY(dgrad_step(p, cs, g, g_is_pooled, pool_of_g, dst, n, s, o, b.i0));
         g_gated = o.out_gate != nullptr;
@@ -1367,57 +1176,31 @@ static int plan_loss_enqueue(st3d_plan *p, const float *current, int n, int batc
     st3d_trace_push("vgg_backward");
 
     // ---- what the consumer of the image gradient needs (need.hip): with a mask, the bottom launches walk these lists
-    const int need = need_mask ? p->need_levels : 0;
-    if (need > 0 && !(key && p->ls->have_need)) {       // (a keyed call builds them once per epoch)
-        Scope sc(p, F_ELEM, s);
-        if (p->need_blocks && need >= 2)
-            ST3D_TRY(st3d_need_blocks_build(need_mask, n, p->S, need - 1, p->need_cols, p->ls->need_seg, p->need_flags, p->need_flags_bytes,
-                                            p->ls->need_list, p->ls->need_cnt, need >= 3 && p->need_gram ? p->ls->need_gram_list : nullptr,
-                                            p->ls->need_gram_cnt, s));
-        else
-            ST3D_TRY(st3d_need_build(need_mask, n, p->S, need, p->ls->need_seg, p->need_flags, p->need_flags_bytes, p->ls->need_list[0],
-                                     p->ls->need_list[1], p->ls->need_cnt, s));
-        if (key) p->ls->have_need = true;
-    }
+    const int need = need_mask ? p->d.need_levels : 0;
     st3d_plan::ListSet *ls = p->ls;
-    BwdArgs b{n, 0, batch_denom, content_weight, style_coef, grad_current, need_mask, need, need >= 3 && p->need_gram,
-              ls->need_seg, ls->need_list, ls->need_cnt, ls->need_gram_list, ls->need_gram_cnt, p->gbuf[0], p->gbuf[1],
-              p->gbuf_floats * sizeof(float)};
+    if (need > 0 && !(key && ls->have_need)) {          // (a keyed call builds them once per epoch)
+        ST3D_TRY(build_need_lists(p, ls->whole, need_mask, n, need, need >= 3 && p->d.need_gram, s));
+        if (key) ls->have_need = true;
+    }
+    BwdArgs b{n, 0, batch_denom, content_weight, style_coef, grad_current, need_mask, need, need >= 3 && p->d.need_gram, ls->whole,
+              p->gbuf[0], p->gbuf[1], p->gbuf_floats * sizeof(float)};
     // the split is the clean call's (the forward's condition: this call set flat_done / kept_done and cleared nothing since)
     // The Gram backward's tile height is the one launch parameter written to follow the workgroup count, so B -- but only behind
     // C % 128 == 0, where the 128 x 64 tiling is chosen first: as the launcher stands the choice depends on C and HW alone.  Its
     // tuning knob can bring the count back in (gram.hip reads it per call), so a process that sets it keeps the one-stream call.
     const bool gram_knob = getenv("ST3D_GRAM_BWD_MT") != nullptr;
-    if (key && key->clean_call && need_mask && need >= 1 && p->need_blocks && !gram_knob && split_ok(p, st3d_plan::SPLIT_BWD, n, true)) {
-        const int h = n / 2, gneed = std::min(need, p->grp_need_levels);
-        const bool ggram = gneed >= 3 && p->grp_need_gram;
-        if (!ls->have_grp_need) {
-            for (int g = 0; g < 2; ++g) {
-                st3d_plan::GroupLists &G = ls->grp[g];
-                const uint8_t *mask = need_mask + (size_t)g * h * p->S * p->S;
-                if (gneed >= 2)
-                    ST3D_TRY(st3d_need_blocks_build(mask, h, p->S, gneed - 1, p->need_cols, G.need_seg, p->need_flags, p->need_flags_bytes,
-                                                    G.need_list, G.need_cnt, ggram ? G.need_gram_list : nullptr, G.need_gram_cnt, s));
-                else
-                    ST3D_TRY(st3d_need_build(mask, h, p->S, gneed, G.need_seg, p->need_flags, p->need_flags_bytes, G.need_list[0],
-                                             G.need_list[1], G.need_cnt, s));
-            }
-            ls->have_grp_need = true;
-        }
-        ST3D_TRY(split_fork(p, 1, s));
-        int rc = ST3D_OK;
-        for (int g = 0; g < 2 && rc == ST3D_OK; ++g) {
-            const st3d_plan::GroupLists &G = ls->grp[g];
-            const size_t half = p->gbuf_floats / 2;
-            BwdArgs bg{h, g * h, batch_denom, content_weight, style_coef, grad_current + (size_t)g * h * 3 * p->S * p->S,
-                       need_mask + (size_t)g * h * p->S * p->S, gneed, ggram, G.need_seg, G.need_list, G.need_cnt, G.need_gram_list,
-                       G.need_gram_cnt, p->gbuf[0] + g * half, p->gbuf[1] + g * half, half * sizeof(float)};
-            rc = backward_chain(p, bg, split_stream(p, g, s));
-        }
-        const int rj = split_join(p, 1, s);
-        if (rc != ST3D_OK || rj != ST3D_OK) return rc != ST3D_OK ? rc : rj;
-        ++p->split_calls[1];
-        return ST3D_OK;
+    if (key && key->clean_call && need_mask && need >= 1 && p->d.need_blocks && !gram_knob && split_ok(p, SPLIT_BWD, n, true)) {
+        const int h = n / 2, gneed = std::min(need, p->d.grp_need_levels);
+        const bool ggram = gneed >= 3 && p->d.grp_need_gram;
+        const size_t img = (size_t)h * p->S * p->S, half = p->gbuf_floats / 2;
+        for (int g = 0; g < 2 && !ls->have_grp_need; ++g)
+            ST3D_TRY(build_need_lists(p, ls->grp[g], need_mask + g * img, h, gneed, ggram, s));
+        ls->have_grp_need = true;
+        return run_split(p, 1, s, [&](int g, hipStream_t gs) {
+            BwdArgs bg{h, g * h, batch_denom, content_weight, style_coef, grad_current + g * 3 * img, need_mask + g * img, gneed, ggram,
+                       ls->grp[g], p->gbuf[0] + g * half, p->gbuf[1] + g * half, half * sizeof(float)};
+            return backward_chain(p, bg, gs);
+        });
     }
     return backward_chain(p, b, s);
 }

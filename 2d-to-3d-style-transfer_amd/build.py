@@ -66,6 +66,8 @@ SOURCES = {
     # M c = c and a one-iteration solve of a constant right-hand side are tested bit for bit, the solve against its numpy
     # restatement rounding for rounding: the differences, products and sums stay as written
     "diffuse.hip": ["-ffp-contract=off"],
+    # shade.hip's flags: the footprint whose texels it marks is the plain kernels' bit for bit; the rest is integer work
+    "cover.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "plan.hip": [],
     "comm.hip": [],
 }

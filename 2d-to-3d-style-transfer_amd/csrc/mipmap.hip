@@ -233,9 +233,8 @@ __global__ __launch_bounds__(256) void shade_mip_fwd_kernel(const int32_t *__res
         return;
     }
     const float b0 = bary[3 * i], b1 = bary[3 * i + 1], b2 = bary[3 * i + 2];
-    const int u0 = fuv[3 * f], u1 = fuv[3 * f + 1], u2 = fuv[3 * f + 2];
-    const float u = b0 * uvs[2 * u0] + b1 * uvs[2 * u1] + b2 * uvs[2 * u2];
-    const float v = b0 * uvs[2 * u0 + 1] + b1 * uvs[2 * u1 + 1] + b2 * uvs[2 * u2 + 1];
+    const FragUV fu = frag_uv(uvs, fuv, f, b0, b1, b2);
+    const float u = fu.u, v = fu.v;
     const Footprint q0 = uv_footprint(u, v, T);
     const Blend bl = blend_k1(dists[i], zbuf[i]);
     const float lam = safe_lod(lod[i], L);
@@ -323,9 +322,9 @@ __global__ __launch_bounds__(256) void shade_mip_bwd_kernel(const float *__restr
     if (f >= 0) {
         const bool want_uv = guv || gbary;
         const float b0 = bary[3 * i], b1 = bary[3 * i + 1], b2 = bary[3 * i + 2];
-        const int u0 = fuv[3 * f], u1 = fuv[3 * f + 1], u2 = fuv[3 * f + 2];
-        const float u = b0 * uvs[2 * u0] + b1 * uvs[2 * u1] + b2 * uvs[2 * u2];
-        const float v = b0 * uvs[2 * u0 + 1] + b1 * uvs[2 * u1 + 1] + b2 * uvs[2 * u2 + 1];
+        const FragUV fu = frag_uv(uvs, fuv, f, b0, b1, b2);
+        const int u0 = fu.u0, u1 = fu.u1, u2 = fu.u2;
+        const float u = fu.u, v = fu.v;
         const Footprint q0 = uv_footprint(u, v, T);
         const Blend bl = blend_k1(dists[i], zbuf[i]);
         const float k = bl.wnum / bl.denom;

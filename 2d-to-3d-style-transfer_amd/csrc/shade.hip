@@ -42,9 +42,8 @@ __global__ __launch_bounds__(256) void shade_fwd_kernel(const int32_t *__restric
         return;
     }
     const float b0 = bary[3 * i], b1 = bary[3 * i + 1], b2 = bary[3 * i + 2];
-    const int u0 = fuv[3 * f], u1 = fuv[3 * f + 1], u2 = fuv[3 * f + 2];
-    const float u = b0 * uvs[2 * u0] + b1 * uvs[2 * u1] + b2 * uvs[2 * u2];
-    const float v = b0 * uvs[2 * u0 + 1] + b1 * uvs[2 * u1 + 1] + b2 * uvs[2 * u2 + 1];
+    const FragUV fu = frag_uv(uvs, fuv, f, b0, b1, b2);
+    const float u = fu.u, v = fu.v;
     const Footprint q = uv_footprint(u, v, T);
     const Blend bl = blend_k1(dists[i], zbuf[i]);
     const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
@@ -80,9 +79,8 @@ __device__ __forceinline__ float shade_px(const int32_t *__restrict__ p2f, const
         return 0.f;
     }
     const float b0 = bary[3 * i], b1 = bary[3 * i + 1], b2 = bary[3 * i + 2];
-    const int u0 = fuv[3 * f], u1 = fuv[3 * f + 1], u2 = fuv[3 * f + 2];
-    const float u = b0 * uvs[2 * u0] + b1 * uvs[2 * u1] + b2 * uvs[2 * u2];
-    const float v = b0 * uvs[2 * u0 + 1] + b1 * uvs[2 * u1 + 1] + b2 * uvs[2 * u2 + 1];
+    const FragUV fu = frag_uv(uvs, fuv, f, b0, b1, b2);
+    const float u = fu.u, v = fu.v;
     const Footprint q = uv_footprint(u, v, T);
     const Blend bl = blend_k1(dists[i], zbuf[i]);
     const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
@@ -187,9 +185,9 @@ __global__ __launch_bounds__(256) void shade_bwd_kernel(const float *__restrict_
     if (f >= 0) {
         const bool want_uv = guv || gbary;
         const float b0 = bary[3 * i], b1 = bary[3 * i + 1], b2 = bary[3 * i + 2];
-        const int u0 = fuv[3 * f], u1 = fuv[3 * f + 1], u2 = fuv[3 * f + 2];
-        const float u = b0 * uvs[2 * u0] + b1 * uvs[2 * u1] + b2 * uvs[2 * u2];
-        const float v = b0 * uvs[2 * u0 + 1] + b1 * uvs[2 * u1 + 1] + b2 * uvs[2 * u2 + 1];
+        const FragUV fu = frag_uv(uvs, fuv, f, b0, b1, b2);
+        const int u0 = fu.u0, u1 = fu.u1, u2 = fu.u2;
+        const float u = fu.u, v = fu.v;
         const Footprint q = uv_footprint(u, v, T);
         const Blend bl = blend_k1(dists[i], zbuf[i]);
         const float k = bl.wnum / bl.denom;

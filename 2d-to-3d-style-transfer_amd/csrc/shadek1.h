@@ -1,5 +1,6 @@
 // shadek1.h -- the fragment arithmetic every K = 1 shading kernel shares (shade.hip, mipmap.hip, vcolor.hip; soft.hip takes
-// the footprint): the bilinear footprint of a UV position and the softmax blend of one fragment against the background.
+// the footprint; cover.hip marks the footprint's texels): the UV position of a fragment, the bilinear footprint of a UV
+// position and the softmax blend of one fragment against the background.
 // The kernels of these files, oracle/raster_ref.c and the numpy restatements of the tests agree bit for bit, so the
 // expressions below ARE the roundings: their order and parenthesisation are part of the contract, and every including
 // file builds with -ffp-contract=off and the correctly rounded division (build.py).
@@ -35,6 +36,19 @@ __device__ __forceinline__ Footprint uv_footprint(float u, float v, int T) {
     o.vy0 = yf0 >= 0 && yf0 < T;   o.vy1 = yf1 >= 0 && yf1 < T;
     o.r0 = (T - 1) - yf0; o.r1 = (T - 1) - yf1;
     o.ix = ix; o.iy = iy;
+    return o;
+}
+
+// The UV position of a fragment on face f: its barycentrics over the face's three UV corners, the products added from left
+// to right (oracle/raster_ref.c spells the same sum).  u0..u2: the corners' rows of verts_uvs, which the backwards read again.
+struct FragUV { int u0, u1, u2; float u, v; };
+
+__device__ __forceinline__ FragUV frag_uv(const float *__restrict__ uvs, const int32_t *__restrict__ fuv, int f, float b0,
+                                          float b1, float b2) {
+    FragUV o;
+    o.u0 = fuv[3 * f]; o.u1 = fuv[3 * f + 1]; o.u2 = fuv[3 * f + 2];
+    o.u = b0 * uvs[2 * o.u0] + b1 * uvs[2 * o.u1] + b2 * uvs[2 * o.u2];
+    o.v = b0 * uvs[2 * o.u0 + 1] + b1 * uvs[2 * o.u1 + 1] + b2 * uvs[2 * o.u2 + 1];
     return o;
 }
 

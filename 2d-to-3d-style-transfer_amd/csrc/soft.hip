@@ -273,6 +273,8 @@ __global__ __launch_bounds__(256) void raster_k_kernel(const float4 *__restrict_
 // ------------------------------------------------------------------------------------------ shading
 using st3d_k1::Footprint;           // the bilinear footprint of the K = 1 kernels: the same texels and weights
 using st3d_k1::uv_footprint;
+using st3d_k1::FragUV;
+using st3d_k1::frag_uv;
 
 struct SoftArgs {
     const int32_t *p2f; const float *bary, *zbuf, *dists, *uvs; const int32_t *fuv; const float *tex;
@@ -370,9 +372,8 @@ __global__ __launch_bounds__(256) void soft_shade_kernel(const SoftArgs a, float
         const float z_inv = (kZfar - a.zbuf[i * K + k]) * zr;
         const float w = prob * expf((z_inv - z_max) / a.gamma);
         const float b0 = a.bary[3 * (i * K + k)], b1 = a.bary[3 * (i * K + k) + 1], b2 = a.bary[3 * (i * K + k) + 2];
-        const int u0 = a.fuv[3 * f], u1 = a.fuv[3 * f + 1], u2 = a.fuv[3 * f + 2];
-        const float u = b0 * a.uvs[2 * u0] + b1 * a.uvs[2 * u1] + b2 * a.uvs[2 * u2];
-        const float v = b0 * a.uvs[2 * u0 + 1] + b1 * a.uvs[2 * u1 + 1] + b2 * a.uvs[2 * u2 + 1];
+        const FragUV fu = frag_uv(a.uvs, a.fuv, f, b0, b1, b2);
+        const float u = fu.u, v = fu.v;
         const Footprint q = uv_footprint(u, v, T);
         const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
         const float *t00 = a.tex + ((size_t)q.r0 * T + q.x0) * 3, *t01 = a.tex + ((size_t)q.r0 * T + q.x1) * 3;
@@ -422,9 +423,9 @@ __global__ __launch_bounds__(256) void soft_shade_kernel(const SoftArgs a, float
         const float e = expf((z_inv - z_max) / a.gamma);
         const float w = prob * e;
         const float b0 = a.bary[3 * (i * K + k)], b1 = a.bary[3 * (i * K + k) + 1], b2 = a.bary[3 * (i * K + k) + 2];
-        const int u0 = a.fuv[3 * f], u1 = a.fuv[3 * f + 1], u2 = a.fuv[3 * f + 2];
-        const float u = b0 * a.uvs[2 * u0] + b1 * a.uvs[2 * u1] + b2 * a.uvs[2 * u2];
-        const float v = b0 * a.uvs[2 * u0 + 1] + b1 * a.uvs[2 * u1 + 1] + b2 * a.uvs[2 * u2 + 1];
+        const FragUV fu = frag_uv(a.uvs, a.fuv, f, b0, b1, b2);
+        const int u0 = fu.u0, u1 = fu.u1, u2 = fu.u2;
+        const float u = fu.u, v = fu.v;
         const Footprint q = uv_footprint(u, v, T);
         const float w00 = q.wx0 * q.wy0, w01 = q.wx1 * q.wy0, w10 = q.wx0 * q.wy1, w11 = q.wx1 * q.wy1;
         const size_t o00 = ((size_t)q.r0 * T + q.x0) * 3, o01 = ((size_t)q.r0 * T + q.x1) * 3;

@@ -26,6 +26,8 @@ _LIGHTS = ['ambient', 'point', 'directional', 'headlight']
 _STYLE_MASKS = ['none', 'object']
 _TEXTURE_TYPES = ['uv', 'vertex']
 _LAPLACIANS = ['uniform', 'cot', 'cotcurv']
+_VIEW_SELECTIONS = ['random', 'coverage']
+VIEW_CANDIDATES_DEFAULT, VIEW_CANDIDATES_MAX = 256, 4096        # (st3d.cover.MAX_CANDIDATES)
 _NNFM_LAYERS = ['conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.NNFM_LAYERS
 _SWD_LAYERS = ['conv1_1', 'conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.SWD_LAYERS
 
@@ -147,6 +149,14 @@ SHARED_FLAGS = [
          "is the step size of u.  --optimization_target mesh / both only; 0 = off"),
     Flag("texture_lod_bias", float, 0.0, "added to every pixel's level of detail before it is clamped to the chain "
          "(--texture_mip_levels): negative = sharper, positive = blurrier"),
+    Flag("view_selection", str, 'random', "which cameras the run looks through: 'random' = n_views random directions (the "
+         "reference's), 'coverage' = --view_candidates random directions are drawn instead and the n_views of them that "
+         "together touch the most texels of the map are picked greedily, once, on the loaded mesh, so that fewer texels stay "
+         "unseen for the whole run.  The selection always marks the plain bilinear footprint at --size, whatever --supersample "
+         "or --texture_mip_levels say; it writes texel_coverage.png (how many of the picked views touch each texel, over "
+         "n_views).  --texture_type uv without --texture_atlas only", _VIEW_SELECTIONS),
+    Flag("view_candidates", int, VIEW_CANDIDATES_DEFAULT, "candidate directions --view_selection coverage picks from, n_views..."
+         "4096"),
 ]
 
 # regularisers the reference defines but never switches on (losses.py:48-65, notes.txt:36,39); weight 0 = off
@@ -259,6 +269,17 @@ def check_args(args):
         if target_ != "texture":
             return (f"--texture_atlas needs --optimization_target texture: the nearest-texel colour moves no vertex (got "
                     f"--optimization_target {target_})")
+    candidates = getattr(args, "view_candidates", VIEW_CANDIDATES_DEFAULT)
+    if getattr(args, "view_selection", "random") == "coverage":
+        if getattr(args, "texture_type", "uv") == "vertex":
+            return "--view_selection coverage needs --texture_type uv: per-vertex colours have no texels to cover"
+        if atlas:
+            return "--view_selection coverage needs --texture_atlas 0: the selection covers the texels of a UV-mapped texture"
+        if not getattr(args, "n_views", 1) <= candidates <= VIEW_CANDIDATES_MAX:
+            return (f"--view_candidates must be in n_views...{VIEW_CANDIDATES_MAX} (got {candidates} with --n_views "
+                    f"{getattr(args, 'n_views', 1)})")
+    elif candidates != VIEW_CANDIDATES_DEFAULT:
+        return "--view_candidates needs --view_selection coverage"
     return None
 
 
@@ -544,8 +565,11 @@ class Run:
 
         self.say("Building cameras...")
         gen = torch.Generator().manual_seed(args.seed) if args.seed is not None else None
-        self.cameras = (_u.build_random_cameras(args.n_views, generator=gen) if args.randomize_views
-                        else _u.build_fixed_cameras(args.n_views))
+        if getattr(args, "view_selection", "random") == "coverage":
+            self.cameras = self.select_views(gen)
+        else:
+            self.cameras = (_u.build_random_cameras(args.n_views, generator=gen) if args.randomize_views
+                            else _u.build_fixed_cameras(args.n_views))
         if self.world > 1:                      # every rank must look through the same cameras
             torch.distributed.broadcast(self.cameras.R, 0)
             torch.distributed.broadcast(self.cameras.T, 0)
@@ -617,6 +641,21 @@ class Run:
         if self.main:
             with open(self._log, 'a') as fh:
                 fh.write(line + '\n')
+
+    def select_views(self, generator):
+        """--view_selection coverage: n_views of --view_candidates random directions, picked greedily by the texels they add
+        (utils.build_coverage_cameras) on the loaded mesh at --size; one line of figures and texel_coverage.png."""
+        import utils as _u
+        args = self.args
+        cameras, report = _u.build_coverage_cameras(args.n_views, self.content_mesh, args.size,
+                                                    candidates=args.view_candidates, generator=generator)
+        self.say(f"View selection: the {args.n_views} picked of {report['candidates']} candidates reach {report['picked']} of "
+                 f"the {report['pool']} texels the candidates reach together; the first {args.n_views} candidates reach "
+                 f"{report['first_n']}")
+        if self.main:
+            share = report['counts'].to(torch.float32) / float(args.n_views)
+            _u.tensor_to_image(share[None].expand(3, -1, -1)).save(os.path.join(self.out_dir, 'texel_coverage.png'))
+        return cameras
 
     def check_diffusion(self):
         """--verts_diffusion: warn, once per run, when the latest forward or backward solve stopped at its iteration cap."""

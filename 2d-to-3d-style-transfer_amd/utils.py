@@ -165,6 +165,19 @@ def build_random_cameras(n_views, dist=2.10, generator=None):
     return FoVPerspectiveCameras(R=R, T=T, device=device)
 
 
+def build_coverage_cameras(n_views, mesh, image_size, candidates=256, dist=2.10, generator=None):
+    """n_views of `candidates` directions drawn by build_random_cameras(candidates, dist, generator), chosen greedily so that
+    together they touch as many texels of the mesh's map as they can (st3d.cover.select_cameras, rendered at image_size)
+    -> (cameras in pick order, the selection's report).  A TexturesUV mesh only (NotImplementedError otherwise)."""
+    from st3d import cover as _cover
+    if isinstance(n_views, bool) or int(n_views) != n_views or isinstance(candidates, bool) or int(candidates) != candidates \
+            or not 1 <= n_views <= candidates <= _cover.MAX_CANDIDATES:
+        raise ValueError(f"need 1 <= n_views <= candidates <= {_cover.MAX_CANDIDATES}, got n_views = {n_views!r}, "
+                         f"candidates = {candidates!r}")
+    pool = build_random_cameras(int(candidates), dist=dist, generator=generator)
+    return _cover.select_cameras(mesh, pool, int(n_views), image_size)
+
+
 # ------------------------------------------------------------------------------------------ optimiser
 _LEAVES = {'texture': ('texture_map',), 'mesh': ('verts',), 'both': ('verts', 'texture_map')}
 _VERTEX_LEAVES = {'texture': ('verts_features',), 'mesh': ('verts',), 'both': ('verts', 'verts_features')}

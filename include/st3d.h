@@ -1122,6 +1122,31 @@ int st3d_diffuse_solve(const int *nbr_off, const int *nbr_idx, int V, float lamb
 int st3d_adam_step_uniform(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, size_t n, int step, float lr,
                            float beta1, float beta2, float eps, float *partials, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ coverage-driven view selection (cover.hip)
+ * Which texels of a T x T texture map each view touches, and a greedy choice of views by what each adds.  A mask is
+ * W = (T*T + 31) / 32 32-bit words per view: texel (row r, column x) of the map as stored, (1,T,T,3) in original rows, has
+ * index t = r*T + x and is bit t & 31 of word t >> 5; bits at or above T*T are 0.  Integer work only: two calls give the same
+ * bits.  Every argument is checked on the host before any launch (ST3D_E_INVALID, nothing launched); nothing is allocated.
+ * Masks, covered and the workspace are 4-byte aligned (rows are read 16 bytes at a time when W % 4 == 0 and the bases allow).
+ * st3d_cover_mark: the hard K = 1 fragments of st3d_raster_fwd at side S, 1 <= S <= 4096, 1 <= T <= 16384.  For every
+ *   covered pixel the UV is interpolated as st3d_shade_fwd does and each of the four texels of its bilinear footprint that
+ *   lies inside the map with both weights > 0 -- the texels st3d_shade_bwd of a positive gradient adds a non-zero weight to --
+ *   is ORed into view b's row of masks (B x W); bits already set stay.  faces_uvs must index verts_uvs and pix_to_face must
+ *   index faces_uvs: the CALLER guarantees it.
+ * st3d_cover_greedy: n rounds enqueued on the stream with no host read in between, 1 <= n <= C <= 4096, 1 <= W <= 2^26.
+ *   Round k: gain[c] = sum_w popcount(masks[c][w] & ~covered[w]) for every candidate not yet taken; picks[k] = the untaken
+ *   candidate of the largest gain, the lowest index among equals, gains[k] = its gain; covered |= its row; it is taken and
+ *   never picked again (when every remaining gain is 0 the pick is the lowest untaken index, gain 0).  covered (W words): in =
+ *   the texels already counted as seen, out = their union with the picks; it must not overlap masks.  workspace:
+ *   st3d_cover_workspace_bytes(C) bytes (C gains + C taken flags; 0 for C outside 1...4096), written before it is read.
+ * st3d_cover_count: counts (T*T int32)[t] = how many of the C >= 1 rows have bit t set; W must be (T*T + 31) / 32. */
+int st3d_cover_mark(const int32_t *pix_to_face, const float *bary, const float *verts_uvs, const int32_t *faces_uvs, int B,
+                    int S, int T, void *masks /* B x W, ORed into */, st3d_stream_t stream);
+size_t st3d_cover_workspace_bytes(int C);
+int st3d_cover_greedy(const void *masks /* C x W */, int C, int W, int n, void *covered /* W */, int32_t *picks /* n */,
+                      int32_t *gains /* n */, void *workspace, st3d_stream_t stream);
+int st3d_cover_count(const void *masks /* C x W */, int C, int W, int T, int32_t *counts /* T*T */, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-GPU
  * One process per GPU; every rank renders / VGGs its slice of the view batch with the loss means divided by the GLOBAL
  * batch (batch_denom of st3d_plan_loss) and ONE SUM all-reduce of the flat fp32 gradient (3*T*T texture floats

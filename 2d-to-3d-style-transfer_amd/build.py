@@ -68,6 +68,9 @@ SOURCES = {
     "diffuse.hip": ["-ffp-contract=off"],
     # shade.hip's flags: the footprint whose texels it marks is the plain kernels' bit for bit; the rest is integer work
     "cover.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # cover.hip's flags: the texel -> face decisions and the bake's roundings are the ones written in the source, compared with
+    # their fp64 numpy restatement; no float atomics, two runs give the same bits
+    "bake.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "plan.hip": [],
     "comm.hip": [],
 }

@@ -16,7 +16,7 @@ from style_transfer import *  # noqa: F401,F403
 from utils import *  # noqa: F401,F403
 from losses import *  # noqa: F401,F403
 
-from st3d.cli import Flag, Run, make_parser
+from st3d.cli import BAKE_FLAGS, Flag, Run, make_parser
 
 FLAGS = [
     Flag("n_mse_steps", int, 100, "phase-B steps (fit the 3-D parameters to the stylised views) per batch"),
@@ -25,7 +25,7 @@ FLAGS = [
     Flag("style_transfer_init", str, 'content', "what the 2-D style transfer starts from", ['noise', 'current', 'content']),
     Flag("style_transfer_lr", float, 0.01, "Adam step size of phase A"),
     Flag("mse_lr", float, 0.01, "Adam step size of phase B"),
-]
+] + BAKE_FLAGS              # --bake_texture: a closed-form start of phase B
 
 
 def build_parser():
@@ -72,6 +72,7 @@ def main(argv=None):
                                                      swd_directions=args.swd_directions,
                                                      swd_seed=args.seed if args.seed is not None else 0))
             run.save_views(targets, vb.lo)
+            run.bake_targets(targets, cams, f"batch {vb.index}")      # --bake_texture, off by default
 
         # phase B: masked MSE between the renders and the stylised views
         shown = 0

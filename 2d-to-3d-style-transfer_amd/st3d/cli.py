@@ -159,6 +159,22 @@ SHARED_FLAGS = [
          "4096"),
 ]
 
+# the fitting phase of first_approach.py / third_approach.py only: each script adds them to its own table
+_BAKE_MODES = ['off', 'mean', 'best']
+BAKE_POWER_DEFAULT, BAKE_MIN_COS_DEFAULT = 2.0, 0.1
+BAKE_FLAGS = [
+    Flag("bake_texture", str, 'off', "before the fitting steps of a batch, bake the batch's stylised views into the texture map "
+         "by UV-space back-projection (st3d.bake): every texel of the chart takes the colour the views show at its surface "
+         "point, 'mean' = blended by the viewing angle, 'best' = from the squarest view alone.  A closed-form head start worth "
+         "tens of fitting steps, with no optimiser state; --n_mse_steps 0 is then a pure bake.  The bake always reads the plain "
+         "fragments at --size, whatever --supersample or --texture_mip_levels say.  --optimization_target texture / both, "
+         "--texture_type uv without --texture_atlas, --texture_pyramid_levels 1, white ambient light, one process only",
+         _BAKE_MODES),
+    Flag("bake_power", float, BAKE_POWER_DEFAULT, "a view's weight in the bake is |cos of its viewing angle|^N, N >= 0"),
+    Flag("bake_min_cos", float, BAKE_MIN_COS_DEFAULT, "the bake ignores a view that sees the texel's face at |cos| below this, "
+         "0...1"),
+]
+
 # regularisers the reference defines but never switches on (losses.py:48-65, notes.txt:36,39); weight 0 = off
 REGULARISER_FLAGS = [
     Flag("tv_weight", float, 0.0, "weight of the masked total-variation term on the current renders"),
@@ -280,6 +296,28 @@ def check_args(args):
                     f"{getattr(args, 'n_views', 1)})")
     elif candidates != VIEW_CANDIDATES_DEFAULT:
         return "--view_candidates needs --view_selection coverage"
+    power = getattr(args, "bake_power", BAKE_POWER_DEFAULT)
+    if not (math.isfinite(power) and power >= 0.0):
+        return "--bake_power must be finite and >= 0"
+    min_cos = getattr(args, "bake_min_cos", BAKE_MIN_COS_DEFAULT)
+    if not 0.0 <= min_cos <= 1.0:
+        return "--bake_min_cos must be in 0...1"
+    if getattr(args, "bake_texture", "off") != "off":
+        if getattr(args, "optimization_target", "texture") == 'mesh':
+            return ("--bake_texture needs --optimization_target texture or both: with 'mesh' the texture is not optimised and "
+                    "there is no map to bake into")
+        if getattr(args, "texture_type", "uv") == "vertex":
+            return "--bake_texture needs --texture_type uv: per-vertex colours have no texels to bake into"
+        if atlas:
+            return "--bake_texture needs --texture_atlas 0: the bake walks the texels of a UV-mapped texture"
+        if levels != 1:
+            return ("--bake_texture needs --texture_pyramid_levels 1: the bake writes the plain map, a pyramid's levels are not "
+                    "solved for")
+        if getattr(args, "lights", "ambient") != "ambient":
+            return (f"--bake_texture needs --lights ambient: a lit image would bake the lighting into the albedo (got --lights "
+                    f"{args.lights})")
+    elif power != BAKE_POWER_DEFAULT or min_cos != BAKE_MIN_COS_DEFAULT:
+        return "--bake_power / --bake_min_cos need --bake_texture mean or best"
     return None
 
 
@@ -514,8 +552,12 @@ class Run:
         import utils as _u
         self.args = args
         self.rank, self.world, local = st3d_optim.init_distributed()
+        if getattr(args, "bake_texture", "off") != "off" and self.world > 1:
+            raise RuntimeError(f"--bake_texture cannot run under torch.distributed (world size {self.world}): every rank holds "
+                               "only its slice of a batch's views, and sharded baking is not implemented -- run one process")
         if not torch.cuda.is_available():
             raise RuntimeError("st3d needs an MI355X (libst3d has no CPU fallback)")
+        self._bake_surface = None           # --bake_texture: texel_surface of the mesh, computed at the first bake (static UVs)
         # one GPU per rank; only a gloo rehearsal (ST3D_DIST_BACKEND=gloo) may put several ranks on one card
         self.device = torch.device(f"cuda:{local % max(torch.cuda.device_count(), 1)}")
         torch.cuda.set_device(self.device)
@@ -656,6 +698,30 @@ class Run:
             share = report['counts'].to(torch.float32) / float(args.n_views)
             _u.tensor_to_image(share[None].expand(3, -1, -1)).save(os.path.join(self.out_dir, 'texel_coverage.png'))
         return cameras
+
+    def bake_targets(self, targets, cams, label):
+        """--bake_texture: bake the batch's stylised views `targets` (n,3,size,size), seen through `cams` on the current
+        vertices, into the texture leaf: baked_texture(acc, fallback = the leaf), in place under no_grad.  Stateless per
+        batch: Adam's moments and the checkpoints know nothing of it.  One line says how many texels were written.  With the
+        flag off (the default) nothing runs."""
+        a = self.args
+        mode = getattr(a, "bake_texture", "off")
+        if mode == "off" or targets is None or cams is None or len(cams) == 0:
+            return
+        from . import bake as _bake
+        leaf = self.opt['texture_map']
+        with torch.no_grad():
+            mesh = self.current_mesh()
+            if self._bake_surface is None:
+                tex = mesh.textures
+                uvs = tex.verts_uvs_padded().detach().to(torch.float32).reshape(-1, 2).contiguous()
+                self._bake_surface = _bake.texel_surface(uvs, tex.faces_uvs_i32(), int(leaf.shape[-2]))
+            texture, acc = self._utils.bake_texture(mesh, targets, cams, a.size, mode=mode, power=a.bake_power,
+                                                    min_cos=a.bake_min_cos, surface=self._bake_surface)
+            leaf.copy_(texture.reshape(leaf.shape))
+            written = int((acc[..., 3] > 0).sum())
+        self.say(f"Bake ({label}): {written} of {acc.shape[0] * acc.shape[1]} texels written from {len(cams)} views "
+                 f"(--bake_texture {mode})")
 
     def check_diffusion(self):
         """--verts_diffusion: warn, once per run, when the latest forward or backward solve stopped at its iteration cap."""

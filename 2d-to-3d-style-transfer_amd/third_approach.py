@@ -16,7 +16,7 @@ from style_transfer import *  # noqa: F401,F403
 from utils import *  # noqa: F401,F403
 from losses import *  # noqa: F401,F403
 
-from st3d.cli import Flag, Run, make_parser
+from st3d.cli import BAKE_FLAGS, Flag, Run, make_parser
 
 FLAGS = [
     Flag("n_rounds", int, 30, "passes over the whole view set"),
@@ -25,7 +25,7 @@ FLAGS = [
     Flag("output_path", str, "/content/output_third", "folder for log.txt, renders and the final mesh"),
     Flag("style_transfer_lr", float, 0.01, "Adam step size on the pixels"),
     Flag("mse_lr", float, 0.01, "Adam step size on the texture / vertices"),
-]
+] + BAKE_FLAGS              # --bake_texture: a closed-form start of every round's fitting steps
 
 
 def build_parser():
@@ -64,6 +64,7 @@ def main(argv=None):
                                                      swd_seed=args.seed if args.seed is not None else 0))
                 if rnd == args.n_rounds - 1:
                     run.save_views(targets, vb.lo)
+                run.bake_targets(targets, cams, f"round {rnd}, batch {vb.index}")       # --bake_texture, off by default
             loss = torch.zeros((), device=run.device)
             for _ in range(args.n_mse_steps):
                 run.optimizer.zero_grad()

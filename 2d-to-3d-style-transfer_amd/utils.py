@@ -178,6 +178,16 @@ def build_coverage_cameras(n_views, mesh, image_size, candidates=256, dist=2.10,
     return _cover.select_cameras(mesh, pool, int(n_views), image_size)
 
 
+def bake_texture(mesh, images, cameras, image_size, mode='mean', power=2.0, min_cos=0.1, **kwargs):
+    """Bake `images` (B,3,S,S), one per camera of `cameras` at S = image_size, into the texture map of `mesh` by UV-space
+    back-projection (st3d.bake.bake_texture): every texel of the chart takes the colour the views show at its surface
+    point, blended by |cos|^power of the viewing angle ('mean') or from the squarest view alone ('best')
+    -> (texture (T,T,3): baked where a view reached the texel, the mesh's own map elsewhere; acc (T,T,4): weighted colour
+    sums and weights).  A TexturesUV mesh only (NotImplementedError otherwise)."""
+    from st3d import bake as _bake
+    return _bake.bake_texture(mesh, images, cameras, image_size, mode=mode, power=power, min_cos=min_cos, **kwargs)
+
+
 # ------------------------------------------------------------------------------------------ optimiser
 _LEAVES = {'texture': ('texture_map',), 'mesh': ('verts',), 'both': ('verts', 'texture_map')}
 _VERTEX_LEAVES = {'texture': ('verts_features',), 'mesh': ('verts',), 'both': ('verts', 'verts_features')}

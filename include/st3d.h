@@ -1147,6 +1147,40 @@ int st3d_cover_greedy(const void *masks /* C x W */, int C, int W, int n, void *
                       int32_t *gains /* n */, void *workspace, st3d_stream_t stream);
 int st3d_cover_count(const void *masks /* C x W */, int C, int W, int T, int32_t *counts /* T*T */, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ baking views into the texture map (bake.hip)
+ * UV-space back-projection: walk the texels of a T x T map, find each one's point on the surface, project it into every
+ * view, test that it is visible there, read the view's colour and blend the views by how squarely they see it.  Gathers
+ * throughout, no float atomics: two calls give the same bits.  Every argument is checked on the host before any launch
+ * (ST3D_E_INVALID, nothing launched); nothing is allocated.  2 <= T <= 16384.
+ * st3d_bake_surface (once per mesh): texel (row r, column x) of the map as stored sits at (x, T-1-r) in texel units, UV x
+ *   (T-1) -- the inverse of the shading kernels' footprint.  t2f (T*T)[t] = the face whose UV triangle has the smallest squared
+ *   distance d2 to the texel (0 inside or on the triangle, either winding; triangles without area and faces whose corners do
+ *   not index verts_uvs (VT rows) are skipped), the lowest face among equal d2, provided d2 <= pad^2, 0 <= pad <= 8; else -1.
+ *   tbary (T*T*3) = the barycentrics of the triangle's closest point (the texel's own inside, clamped onto an edge outside),
+ *   0 where t2f = -1.  workspace: st3d_bake_workspace_bytes(T) bytes (one 64-bit key per texel; 0 for T outside the range),
+ *   8-byte aligned, written before it is read.  Three enqueues: a memset, the claims (integer atomicMin), the decode.
+ * st3d_bake_views (one launch per batch of views): for every texel with 0 <= t2f < F and every view b in index order:
+ *   P = sum_i tbary_i v_i, n = the face's unit normal; view-space position as st3d_project_verts forms it, rejected at zv <=
+ *   0.5; pixel position ix = ((1 - x_ndc) S - 1) / 2 (iy likewise), nearest pixel (rint) rejected outside the image; visible
+ *   iff that pixel shows a face g >= 0 and (g == t2f or |zv - zbuf| <= depth_tol zv); c = |n . normalize(C - P)|, C = -T R^T,
+ *   rejected below min_cos; colour = bilinear over the four pixels floor / floor + 1 (indices clamped to the image), taps on
+ *   uncovered pixels dropped and the rest renormalised; w = c^power.  mode ST3D_BAKE_MEAN: acc.rgb += w colour, acc.w += w;
+ *   ST3D_BAKE_BEST: acc = (w colour, w) when w > acc.w.  acc (T*T*4) is read and written: zeros start a bake, an earlier
+ *   result continues it.  Texels with t2f outside 0...F-1 are not touched.  images (B,3,S,S); pix_to_face, zbuf (B,S,S): the
+ *   hard K = 1 fragments of st3d_raster_fwd for (R, T) at side S <= 4096.  faces must index verts (V rows; a face that does
+ *   not is skipped).
+ * st3d_bake_resolve: out (T*T*3) = acc.rgb / acc.w where acc.w > 0, fallback (T*T*3) elsewhere, bit for bit. */
+#define ST3D_BAKE_MEAN 0
+#define ST3D_BAKE_BEST 1
+size_t st3d_bake_workspace_bytes(int T);
+int st3d_bake_surface(const float *verts_uvs, const int32_t *faces_uvs, int VT, int F, int T, float pad, void *workspace,
+                      size_t workspace_bytes, int32_t *t2f, float *tbary, st3d_stream_t stream);
+int st3d_bake_views(const float *verts, const int32_t *faces, int V, int F, const int32_t *t2f, const float *tbary, int Tt,
+                    const float *R, const float *T, const float *images, const int32_t *pix_to_face, const float *zbuf, int B,
+                    int S, float inv_tan_half_fov, int mode, float power, float min_cos, float depth_tol, float *acc,
+                    st3d_stream_t stream);
+int st3d_bake_resolve(const float *acc, const float *fallback, int Tt, float *out, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-GPU
  * One process per GPU; every rank renders / VGGs its slice of the view batch with the loss means divided by the GLOBAL
  * batch (batch_denom of st3d_plan_loss) and ONE SUM all-reduce of the flat fp32 gradient (3*T*T texture floats

@@ -71,6 +71,9 @@ SOURCES = {
     # cover.hip's flags: the texel -> face decisions and the bake's roundings are the ones written in the source, compared with
     # their fp64 numpy restatement; no float atomics, two runs give the same bits
     "bake.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # bake.hip's flags: the tail kernel and the per-level launches are compared bit for bit with each other, the filled colours
+    # with their fp64 numpy restatement under a bound that counts the roundings written in the source
+    "fill.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "plan.hip": [],
     "comm.hip": [],
 }

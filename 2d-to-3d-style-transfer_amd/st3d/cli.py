@@ -27,6 +27,7 @@ _STYLE_MASKS = ['none', 'object']
 _TEXTURE_TYPES = ['uv', 'vertex']
 _LAPLACIANS = ['uniform', 'cot', 'cotcurv']
 _VIEW_SELECTIONS = ['random', 'coverage']
+_FILL_MODES = ['off', 'chart', 'map']
 VIEW_CANDIDATES_DEFAULT, VIEW_CANDIDATES_MAX = 256, 4096        # (st3d.cover.MAX_CANDIDATES)
 _NNFM_LAYERS = ['conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.NNFM_LAYERS
 _SWD_LAYERS = ['conv1_1', 'conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.SWD_LAYERS
@@ -157,6 +158,11 @@ SHARED_FLAGS = [
          "n_views).  --texture_type uv without --texture_atlas only", _VIEW_SELECTIONS),
     Flag("view_candidates", int, VIEW_CANDIDATES_DEFAULT, "candidate directions --view_selection coverage picks from, n_views..."
          "4096"),
+    Flag("fill_unseen", str, 'off', "at export, give every texel the run never moved (its bits are still the loaded map's) a "
+         "colour interpolated from the texels it did move, by a pull-push fill of the map (st3d.fill): final_render/, final.obj "
+         "and its PNG show the filled map, texel_filled.png which texels were filled.  'chart' writes only the texels of the "
+         "chart and its 1.5-texel gutter (a square map only), 'map' every texel -- the dilation a mip-mapping viewer needs.  "
+         "--optimization_target texture / both, --texture_type uv without --texture_atlas", _FILL_MODES),
 ]
 
 # the fitting phase of first_approach.py / third_approach.py only: each script adds them to its own table
@@ -318,6 +324,14 @@ def check_args(args):
                     f"{args.lights})")
     elif power != BAKE_POWER_DEFAULT or min_cos != BAKE_MIN_COS_DEFAULT:
         return "--bake_power / --bake_min_cos need --bake_texture mean or best"
+    if getattr(args, "fill_unseen", "off") != "off":
+        if getattr(args, "optimization_target", "texture") == 'mesh':
+            return ("--fill_unseen needs --optimization_target texture or both: with 'mesh' no texel is optimised and there is "
+                    "nothing to fill from")
+        if getattr(args, "texture_type", "uv") == "vertex":
+            return "--fill_unseen needs --texture_type uv: per-vertex colours have no texels to fill"
+        if atlas:
+            return "--fill_unseen needs --texture_atlas 0: the fill walks the texels of a UV-mapped texture"
     return None
 
 
@@ -947,6 +961,19 @@ class Run:
         points = _ml.sample_points_from_meshes(mesh, a.chamfer_samples, generator=self.chamfer_generator)
         return (a.chamfer_weight / self.world) * _ml.chamfer_distance(points, self.chamfer_target)[0]
 
+    def fill_unseen(self, mesh, final):
+        """--fill_unseen chart / map: the texels of `mesh`'s unclamped map whose bits are still the loaded map's never moved;
+        they are filled in the clamped map of `final` from the texels that did (utils.fill_texture) -> the mesh to export.
+        One line of figures and texel_filled.png (white = filled).  Rank 0 only, like the export itself."""
+        u, mode = self._utils, self.args.fill_unseen
+        filled, report = u.fill_texture(final, self.original_map, mode, moved_from=mesh)
+        where = "chart and gutter" if mode == "chart" else "map"
+        self.say(f"Fill: {report['filled']} of the {report['domain']} texels of the {where} never moved and were filled "
+                 f"({report['moved']} texels moved; --fill_unseen {mode})")
+        u.tensor_to_image(report['mask'].to(torch.float32)[None].expand(3, -1, -1)).save(
+            os.path.join(self.out_dir, 'texel_filled.png'))
+        return filled
+
     def export(self, mesh):
         """final_render/view_k.png from 12 turntable cameras + final.obj/.mtl/.png (first_approach.py:219-225)."""
         from . import ops as _ops
@@ -955,6 +982,8 @@ class Run:
         if self.main:
             u = self._utils
             final = u.finalize_mesh(mesh)
+            if getattr(self.args, "fill_unseen", "off") != "off":
+                final = self.fill_unseen(mesh, final)
             u.save_render(self.renderer, final, u.build_fixed_cameras(12), os.path.join(self.out_dir, "final_render"))
             tex = final.textures
             if self.atlas_r:

@@ -188,8 +188,56 @@ def bake_texture(mesh, images, cameras, image_size, mode='mean', power=2.0, min_
     return _bake.bake_texture(mesh, images, cameras, image_size, mode=mode, power=power, min_cos=min_cos, **kwargs)
 
 
+FILL_MODES = ('chart', 'map')
+
+
+def fill_texture(mesh, original_map, mode='chart', moved_from=None):
+    """Fill the texels of `mesh`'s texture map that never moved away from `original_map` ((H,W,3) or (1,H,W,3), the map the
+    run started from) by a pull-push fill from the texels that did (st3d.fill.fill_unseen) -> (a mesh of the same geometry
+    and UVs with the filled map, report).  mode 'chart' writes only texels the chart or its 1.5-texel gutter owns
+    (st3d.bake.texel_surface; a square map only), 'map' every texel -- the dilation a mip-mapping viewer needs.  moved_from:
+    the mesh whose map is compared with original_map bit for bit (a run compares its unclamped leaf and fills the clamped
+    map), None = `mesh` itself.  report: 'moved', 'filled', 'domain' (texel counts: moved at all, filled, open to the fill),
+    'mask' ((H,W) uint8, 1 = filled).  A TexturesUV mesh only (NotImplementedError otherwise)."""
+    from st3d import bake as _bake
+    from st3d import fill as _fill
+    tex = mesh.textures
+    if not isinstance(tex, TexturesUV):
+        raise NotImplementedError(f"the fill needs a TexturesUV mesh (a texture map to fill), got {type(tex).__name__}")
+    if mode not in FILL_MODES:
+        raise ValueError(f"mode must be 'chart' or 'map', got {mode!r}")
+    maps = tex.maps_padded()
+    H, W = int(maps.shape[-3]), int(maps.shape[-2])
+    if mode == 'chart' and H != W:
+        raise NotImplementedError(f"mode 'chart' needs a square texture map (the texel -> surface map is square), got {H} x {W}; "
+                                  "mode 'map' fills any")
+    texture = maps.detach().to(torch.float32).reshape(H, W, 3).contiguous()
+    source = tex if moved_from is None else moved_from.textures
+    if not isinstance(source, TexturesUV) or tuple(source.maps_padded().shape[-3:]) != (H, W, 3):
+        raise ValueError(f"moved_from must be a TexturesUV mesh with a {H} x {W} map")
+    leaf = source.maps_padded().detach().to(torch.float32).reshape(H, W, 3).contiguous()
+    if original_map.numel() != H * W * 3:
+        raise ValueError(f"original_map must be ({H}, {W}, 3), got {tuple(original_map.shape)}")
+    original = original_map.detach().to(torch.float32).reshape(H, W, 3).contiguous()
+    valid = _fill.moved_texels(leaf, original)
+    domain = None
+    if mode == 'chart':
+        uvs = tex.verts_uvs_padded().detach().to(torch.float32).reshape(-1, 2).contiguous()
+        t2f, _ = _bake.texel_surface(uvs, tex.faces_uvs_i32(), H)
+        domain = (t2f >= 0).to(torch.uint8)
+    filled, count = _fill.push_pull(texture, valid, domain)
+    moved = int(valid.sum())
+    open_ = valid == 0 if domain is None else (valid == 0) & (domain != 0)      # filled, unless nothing moved at all
+    report = {"moved": moved, "filled": int(count), "domain": H * W if domain is None else int(domain.sum()),
+              "mask": (open_ if moved else torch.zeros_like(open_)).to(torch.uint8)}
+    out = Meshes(verts=mesh.verts_padded(), faces=mesh.faces_padded(),
+                 textures=TexturesUV(maps=filled.reshape(maps.shape), faces_uvs=tex.faces_uvs_padded(),
+                                     verts_uvs=tex.verts_uvs_padded()))
+    return out, report
+
+
 # ------------------------------------------------------------------------------------------ optimiser
-_LEAVES = {'texture': ('texture_map',), 'mesh': ('verts',), 'both': ('verts', 'texture_map')}
+_LEAVES ={'texture': ('texture_map',), 'mesh': ('verts',), 'both': ('verts', 'texture_map')}
 _VERTEX_LEAVES = {'texture': ('verts_features',), 'mesh': ('verts',), 'both': ('verts', 'verts_features')}
 _ATLAS_LEAVES = {'texture': ('atlas',), 'mesh': ('verts',), 'both': ('verts', 'atlas')}
 

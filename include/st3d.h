@@ -1181,6 +1181,33 @@ int st3d_bake_views(const float *verts, const int32_t *faces, int V, int F, cons
                     st3d_stream_t stream);
 int st3d_bake_resolve(const float *acc, const float *fallback, int Tt, float *out, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ pull-push fill of a texture map (fill.hip)
+ * Every texel of tex (H*W*3) that is not valid (H*W bytes, non-zero = valid) takes a colour interpolated from the valid
+ * ones (Gortler et al. 1996), 1 <= H, W <= 16384.  A gather with fixed-order sums, an integer atomicAdd per wave for the
+ * count and no float atomic: two calls give the same bits.  Every argument is checked on the host before any launch
+ * (ST3D_E_INVALID, nothing launched); nothing is allocated.
+ *   Level 0: w = valid ? 1 : 0, c = valid ? tex : 0 -- a select, never a product: what an invalid texel holds (NaN
+ *     included) reaches no output.
+ *   Pull: level l + 1 has sides ceil(h / 2), ceil(w / 2), down to 1 x 1.  Coarse texel (y, x) takes the children
+ *     (2y + dy, 2x + dx) that exist, in the order (0,0), (0,1), (1,0), (1,1): W = sum w, C = sum w c; it stores c' = C / W
+ *     where W > 0, else 0, and w' = min(W, 1).
+ *   No valid texel anywhere (the 1 x 1 level has w = 0): out = tex bit for bit, count = 0, no error.
+ *   Push, from the coarsest level to the finest: a texel with w >= 1 keeps its colour, any other takes w c + (1 - w) up, up
+ *     = the 2x bilinear upsample of the completed coarser level at the texel's centre: along an axis the taps for index i
+ *     are i/2 - 1 (weight 1/4) and i/2 (3/4) for even i, (i-1)/2 (3/4) and (i+1)/2 (1/4) for odd i, indices clamped to the
+ *     coarser level; the four products (wy wx) c are summed in the order (y0,x0), (y0,x1), (y1,x0), (y1,x1).
+ *   out (H*W*3) = tex bit for bit where valid, or where domain (H*W bytes, NULL = every texel) is given and 0; the pushed
+ *     level-0 colour elsewhere.  count (one device int64, 8-byte aligned) = the texels that took the pushed colour.
+ *   (A sum of weights that are 0 or 1, cut at 1, is 0 or 1: with this level 0 every w is 0 or 1, the pull averages the
+ *   children that know a colour and the push hands a texel without one the upsample alone.)
+ * workspace: st3d_fill_workspace_bytes(H, W) bytes, 16-byte aligned, written before it is read: one (rgb, w) float4 per
+ *   texel of every level above the map, 16 max(1, sum_{l >= 1} h_l w_l) bytes, about H W 16 / 3; 0 for sides outside the
+ *   range.  out must not be tex.  With ST3D_FILL_TAIL=0 in the environment (read per call) every level is a launch of its
+ *   own instead of the coarse levels sharing one workgroup; the results are the same bits. */
+size_t st3d_fill_workspace_bytes(int H, int W);
+int st3d_fill_pushpull(const float *tex, const uint8_t *valid, const uint8_t *domain, int H, int W, void *workspace,
+                       size_t workspace_bytes, float *out, int64_t *count, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-GPU
  * One process per GPU; every rank renders / VGGs its slice of the view batch with the loss means divided by the GLOBAL
  * batch (batch_denom of st3d_plan_loss) and ONE SUM all-reduce of the flat fp32 gradient (3*T*T texture floats

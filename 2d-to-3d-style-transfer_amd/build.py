@@ -74,6 +74,9 @@ SOURCES = {
     # bake.hip's flags: the tail kernel and the per-level launches are compared bit for bit with each other, the filled colours
     # with their fp64 numpy restatement under a bound that counts the roundings written in the source
     "fill.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # the pyramid step and its transpose are compared bit for bit with their fp32 numpy restatement: sums and products in the
+    # order written, none fused; no division or square root in the file
+    "imgpyr.hip": ["-ffp-contract=off"],
     "plan.hip": [],
     "comm.hip": [],
 }

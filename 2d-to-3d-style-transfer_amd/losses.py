@@ -59,11 +59,68 @@ def check_style_masks(style_masks, n, S):
     return style_masks.detach().to(torch.float32)
 
 
+class _MultiScaleFn(torch.autograd.Function):
+    """sum_f w_f L_f over an image pyramid (st3d.imgpyr): L_f is the fused loss of the images reduced by f
+    against the content and style reduced by f, on the plan of side S / f.  Scales are visited in ascending f; the loss is
+    added in that order in fp32, and so is the gradient, w_f x the pyramid's transpose of the coarse plan's gradient.  f = 1
+    is the single-scale call with its need / flat / epoch tags; a coarse plan gets the need mask reduced with the images
+    (reduce_need), no flat colour and no epoch.  A weight of 0 skips its scale: no plan, no launch."""
+
+    @staticmethod
+    def forward(ctx, current, model, content, style, style_weight, content_weight, batch_denom, style_masks, scales, weights,
+                tags):
+        from st3d import imgpyr as _imgpyr
+        need, flat, epoch = tags
+        B, S = current.shape[0], current.shape[2]
+        want = current.requires_grad
+        cur = current.detach().to(torch.float32).contiguous()
+        masks = style_masks.reshape(B, 1, S, S) if style_masks is not None else None
+        total = grad = None
+        for f, w in zip(scales, weights):
+            if w == 0.0:
+                continue
+            plan = model.plan(B, S // f)
+            plan.set_content(_imgpyr.reduced_cached(content, f))
+            plan.set_style(_imgpyr.reduced_cached(style, f), B)
+            if f == 1:
+                loss, g = plan.loss(cur, style_weight, content_weight, batch_denom=batch_denom, want_grad=want, need_mask=need,
+                                    flat_color=flat, style_mask=style_masks, epoch=epoch)
+            else:
+                loss, g = plan.loss(_imgpyr.reduce(cur, f), style_weight, content_weight, batch_denom=batch_denom,
+                                    want_grad=want, need_mask=_imgpyr.reduce_need(need, f) if need is not None else None,
+                                    style_mask=_imgpyr.reduce(masks, f) if masks is not None else None)
+                while g is not None and g.shape[2] < S:
+                    g = _ops.pyr_down_bwd(g)
+            term = loss[0] * w
+            total = term if total is None else total + term
+            if g is not None:
+                g = g * w if w != 1.0 else g
+                grad = g if grad is None else grad + g
+        if total is None:       # every weight is 0
+            total = torch.zeros((), dtype=torch.float32, device=cur.device)
+            grad = torch.zeros_like(cur) if want else None
+        ctx.grad = grad
+        return total.clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g = ctx.grad * grad_out if ctx.grad is not None else None
+        return (g,) + (None,) * 10
+
+
 def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style_weight=1e6, content_weight=1, *,
-                            batch_denom=None, style_masks=None):
+                            batch_denom=None, style_masks=None, scales=(1,), scale_weights=None):
+    # scales / scale_weights: the multi-scale loss (Gatys et al. 2017; Heitz et al. 2021) -- sum_f w_f L_f, L_f this loss
+    # of the images reduced by f in {1, 2, 4} (st3d.imgpyr: the [1 3 3 1] / 8 pyramid) against content and style reduced
+    # alike, on the plan of side S / f: VGG's receptive fields, fixed in pixels, then also cover the large shapes of the
+    # style.  S % f == 0 and S / f >= 32.  The default is the single-scale loss and runs none of this.
 
     # Ensure content_imgs and style_imgs are batched tensors
     assert current_imgs.shape[0] == content_imgs.shape[0] == style_imgs.shape[0]
+    multi_scale = not (isinstance(scales, tuple) and scales == (1,) and scale_weights is None)
+    if multi_scale:
+        from st3d import imgpyr as _imgpyr
+        scales, scale_weights = _imgpyr.check_scales(scales, scale_weights, current_imgs.shape[2])
     if not isinstance(model, _vgg.Vgg19Features):
         raise TypeError("compute_perceptual_loss needs the st3d VGG returned by utils.get_vgg()")
     if not current_imgs.is_cuda:
@@ -74,9 +131,10 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
     # the masked region (the object's coverage), so the background neither takes part in the style term nor draws its
     # gradient; the style targets stay the plain Grams, the content term is unchanged, the masks carry no gradient
     style_masks = check_style_masks(style_masks, B, S)
-    plan = model.plan(B, S)
-    plan.set_content(content_imgs)          # conv4_2 of content      (reference :18)
-    plan.set_style(style_imgs, B)           # Grams of style features (reference :19-25)
+    if not multi_scale:
+        plan = model.plan(B, S)
+        plan.set_content(content_imgs)          # conv4_2 of content      (reference :18)
+        plan.set_style(style_imgs, B)           # Grams of style features (reference :19-25)
 
     # A render tags its colour tensor with its coverage (st3d.render.tag_need): its backward reads the image gradient at
     # covered pixels only, so the plan computes the gradient there (bit for bit) and writes 0 elsewhere, skipping the part
@@ -97,6 +155,10 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
     # ST3D_EPOCHS=0 (read per call): the A/B switch -- every call rebuilds and fills.
     epoch = 0 if os.environ.get("ST3D_EPOCHS", "1") == "0" else _render.epoch_of(current_imgs, need)
 
+    if multi_scale:         # every scale sets the targets of its own plan; the tags above serve f = 1
+        return _MultiScaleFn.apply(current_imgs, model, content_imgs, style_imgs, float(style_weight), float(content_weight),
+                                   batch_denom, style_masks, scales, scale_weights, (need, flat, epoch))
+
     # batch_denom: the batch the means divide by -- the GLOBAL batch when views are sharded over ranks
     return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need, flat, style_masks, epoch)
 
@@ -108,7 +170,8 @@ def compute_nnfm_loss(current_imgs, style_imgs, model, layers=('conv3_1',), *, m
     the current images, without gradient and cached on the style tensor's identity and version for the style.  ``masks``
     (B,1,S,S) | (B,S,S) in [0,1], e.g. the renders' coverage, weight the positions; ``batch_denom`` is the global batch when
     the views are sharded.  Cost: the term makes its own partial VGG forward and backward up to its deepest tap, next to
-    the fused plan's of compute_perceptual_loss."""
+    the fused plan's of compute_perceptual_loss.  The term always looks at the full-resolution images: the image pyramid of
+    compute_perceptual_loss(scales=...) does not reach it."""
     import style_transfer as _st
     if not isinstance(model, _vgg.Vgg19Features):
         raise TypeError("compute_nnfm_loss needs the st3d VGG returned by utils.get_vgg()")
@@ -136,7 +199,8 @@ def compute_swd_loss(current_imgs, style_imgs, model, layers=('conv2_1', 'conv3_
     in.  The style taps are cached on the style tensor's identity and version; their projection and sort follow the
     directions.  ``masks`` (B,1,S,S) | (B,S,S) in [0,1], e.g. the renders' coverage, select the positions that take part;
     ``batch_denom`` is the global batch when the views are sharded.  Cost: its own partial VGG forward and backward up to its
-    deepest tap, next to the fused plan's of compute_perceptual_loss."""
+    deepest tap, next to the fused plan's of compute_perceptual_loss.  The term always looks at the full-resolution images:
+    the image pyramid of compute_perceptual_loss(scales=...) does not reach it."""
     import style_transfer as _st
     if not isinstance(model, _vgg.Vgg19Features):
         raise TypeError("compute_swd_loss needs the st3d VGG returned by utils.get_vgg()")
@@ -382,10 +446,13 @@ def compute_first_approach_loss(rendered, masks, target_rendered, verts, target_
 
 
 def compute_second_approach_loss(current, content, style, model, style_weight, content_weight, verts, target_verts, mesh,
-                                 weights, opt_type, *, batch_denom=None, style_masks=None):
+                                 weights, opt_type, *, batch_denom=None, style_masks=None, style_scales=(1,),
+                                 style_scale_weights=None):
+    # style_scales / style_scale_weights: compute_perceptual_loss's scales / scale_weights (the multi-scale loss)
     if opt_type in ('texture', 'mesh', 'both'):
         perceptual = compute_perceptual_loss(current, content, style, model, style_weight=style_weight,
-                                             content_weight=content_weight, batch_denom=batch_denom, style_masks=style_masks)
+                                             content_weight=content_weight, batch_denom=batch_denom, style_masks=style_masks,
+                                             scales=style_scales, scale_weights=style_scale_weights)
     if opt_type == 'texture':
         loss = perceptual                                   # no main_loss_weight here (reference :103-104)
     elif opt_type in ('mesh', 'both'):

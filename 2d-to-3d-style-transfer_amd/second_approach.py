@@ -72,7 +72,8 @@ def main(argv=None):
                 current=current, content=content, style=style, model=run.vgg, style_weight=args.style_weight,
                 content_weight=args.content_weight, verts=run.opt['verts'], target_verts=run.original_verts, mesh=mesh,
                 weights=run.loss_weights, opt_type=args.optimization_target, batch_denom=vb.size,
-                style_masks=cov if args.style_mask == 'object' else None)      # this rank's views, their own coverage
+                style_masks=cov if args.style_mask == 'object' else None,      # this rank's views, their own coverage
+                style_scales=run.style_scales, style_scale_weights=run.style_scale_weights)    # --style_scales, default (1,)
             extra = run.regularisers(current, cov, mesh, vb.hi - vb.lo, vb.size)
             if torch.is_tensor(extra):              # every weight is 0 by default: nothing is added, as in the reference
                 loss = loss + extra

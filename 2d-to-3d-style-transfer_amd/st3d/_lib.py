@@ -272,6 +272,10 @@ SIGNATURES = {
     "st3d_bake_resolve": (c_int, [c_f32p, c_f32p, c_int, c_f32p, c_stream]),
     "st3d_fill_workspace_bytes": (c_size, [c_int, c_int]),
     "st3d_fill_pushpull": (c_int, [c_f32p, c_u8p, c_u8p, c_int, c_int, ctypes.c_void_p, c_size, c_f32p, ctypes.c_void_p, c_stream]),
+    "st3d_pyr_down_tile": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "st3d_pyr_down_fwd": (c_int, [c_f32p, c_int, c_int, c_int, c_f32p, c_stream]),
+    "st3d_pyr_down_bwd": (c_int, [c_f32p, c_int, c_int, c_int, c_f32p, c_stream]),
+    "st3d_pyr_down_need": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, c_stream]),
     "st3d_vgg_create": (c_int, [ctypes.POINTER(ctypes.c_void_p)]),
     "st3d_vgg_set_conv": (c_int, [ctypes.c_void_p, c_int, c_f32p, c_f32p, c_stream]),
     "st3d_vgg_destroy": (c_int, [ctypes.c_void_p]),

@@ -49,6 +49,32 @@ def swd_layers(text):
     return names
 
 
+_STYLE_SCALES = (1, 2, 4)       # st3d.imgpyr.FACTORS
+_MIN_SCALE_SIDE = 32            # st3d.imgpyr.MIN_PLAN_SIDE
+
+
+def style_scales(text):
+    """--style_scales: a comma list of strictly increasing factors from 1,2,4 -> the tuple"""
+    try:
+        factors = tuple(int(s.strip()) for s in text.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a comma list of factors from 1,2,4, got {text!r}")
+    if any(f not in _STYLE_SCALES for f in factors) or any(b <= a for a, b in zip(factors, factors[1:])):
+        raise argparse.ArgumentTypeError(f"expected strictly increasing factors from 1,2,4, got {text!r}")
+    return factors
+
+
+def style_scale_weights(text):
+    """--style_scale_weights: a comma list of finite weights >= 0 -> the tuple"""
+    try:
+        weights = tuple(float(s.strip()) for s in text.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a comma list of numbers, got {text!r}")
+    if any(not (math.isfinite(w) and w >= 0.0) for w in weights):
+        raise argparse.ArgumentTypeError(f"expected finite weights >= 0, got {text!r}")
+    return weights
+
+
 def edge_target_length(text):
     """--edge_target_length: a length, or the literal 'mean' (the loaded mesh's mean edge length, resolved by Run)"""
     if text == 'mean':
@@ -163,6 +189,14 @@ SHARED_FLAGS = [
          "and its PNG show the filled map, texel_filled.png which texels were filled.  'chart' writes only the texels of the "
          "chart and its 1.5-texel gutter (a square map only), 'map' every texel -- the dilation a mip-mapping viewer needs.  "
          "--optimization_target texture / both, --texture_type uv without --texture_atlas", _FILL_MODES),
+    Flag("style_scales", style_scales, None, "evaluate the style and content terms on the renders and on copies of them reduced "
+         "by these factors, a comma list of strictly increasing values from 1,2,4, and add the terms (an image pyramid: Gatys et "
+         "al. 2017, Heitz et al. 2021): VGG's receptive fields are fixed in pixels, so the reduced copies are where the large "
+         "shapes of the style image are seen.  --size must be divisible by the largest factor and leave a side >= 32.  Each "
+         "factor f costs a VGG pass at side size / f; the NNFM and sliced Wasserstein terms stay at full resolution.  "
+         "Default 1: the single-scale loss"),
+    Flag("style_scale_weights", style_scale_weights, None, "one finite weight >= 0 per factor of --style_scales, a comma list; "
+         "a weight of 0 leaves its scale out.  Default: all 1"),
 ]
 
 # the fitting phase of first_approach.py / third_approach.py only: each script adds them to its own table
@@ -332,6 +366,17 @@ def check_args(args):
             return "--fill_unseen needs --texture_type uv: per-vertex colours have no texels to fill"
         if atlas:
             return "--fill_unseen needs --texture_atlas 0: the fill walks the texels of a UV-mapped texture"
+    scales, scale_weights = getattr(args, "style_scales", None), getattr(args, "style_scale_weights", None)
+    if scales is None:
+        if scale_weights is not None:
+            return "--style_scale_weights needs --style_scales"
+    else:
+        if scale_weights is not None and len(scale_weights) != len(scales):
+            return f"--style_scale_weights must give one weight per factor of --style_scales ({len(scales)}), got {len(scale_weights)}"
+        size = getattr(args, "size", 0)
+        if scales != (1,) and (size % scales[-1] or size // scales[-1] < _MIN_SCALE_SIDE):
+            return (f"--style_scales {','.join(str(f) for f in scales)} needs --size divisible by {scales[-1]} with --size / "
+                    f"{scales[-1]} >= {_MIN_SCALE_SIDE}, got --size {size}")
     return None
 
 
@@ -341,6 +386,8 @@ class _Parser(argparse.ArgumentParser):
         complaint = check_args(parsed)
         if complaint:
             self.error(complaint)
+        if getattr(parsed, "style_scales", (1,)) is None:       # unset: the single-scale loss
+            parsed.style_scales = (1,)
         return parsed
 
 
@@ -664,6 +711,12 @@ class Run:
         self.swd_generator = None
         if getattr(args, "swd_weight", 0.0):            # off (the default): nothing runs, no generator is created
             self.swd_generator = torch.Generator().manual_seed(args.seed if args.seed is not None else 0)
+        self.style_scales = tuple(getattr(args, "style_scales", None) or (1,))
+        self.style_scale_weights = getattr(args, "style_scale_weights", None)
+        if self.multi_scale:            # the default: nothing is said, nothing runs
+            weights = self.style_scale_weights or (1.0,) * len(self.style_scales)
+            self.say("Style scales: " + ", ".join(f"1/{f} (plan side {args.size // f}, weight {w:g})"
+                                                   for f, w in zip(self.style_scales, weights)))
         self.progress = 0               # epochs (second approach) / view batches (first approach) already done
         if args.resume:
             self.load_checkpoint(args.resume)
@@ -687,6 +740,11 @@ class Run:
     @property
     def main(self):
         return self.rank == 0
+
+    @property
+    def multi_scale(self):
+        """--style_scales / --style_scale_weights ask for anything but the single-scale loss"""
+        return self.style_scales != (1,) or self.style_scale_weights is not None
 
     def say(self, msg):
         if self.main:
@@ -824,6 +882,9 @@ class Run:
         generator = getattr(self, "swd_generator", None)
         if generator is not None:           # --swd_weight: where the direction draws of the run have got to
             blob["swd_generator_state"] = generator.get_state().cpu()
+        if getattr(self, "multi_scale", False):     # --style_scales: no state of its own, but Adam's moments belong to that loss
+            blob["style_scales"] = list(self.style_scales)
+            blob["style_scale_weights"] = list(self.style_scale_weights) if self.style_scale_weights is not None else None
         tmp = os.path.join(self.out_dir, "checkpoint.pt.tmp")
         torch.save(blob, tmp)
         os.replace(tmp, os.path.join(self.out_dir, "checkpoint.pt"))
@@ -858,6 +919,12 @@ class Run:
                              % (("with", "without") if "swd_generator_state" in blob else ("without", "with")))
         if generator is not None:
             generator.set_state(blob["swd_generator_state"])
+        want_weights = getattr(self, "style_scale_weights", None)
+        have_scales = (tuple(blob.get("style_scales", (1,))), blob.get("style_scale_weights"))
+        want_scales = (tuple(getattr(self, "style_scales", (1,))), list(want_weights) if want_weights is not None else None)
+        if have_scales != want_scales:
+            raise ValueError("checkpoint was written with --style_scales %s (weights %s), this run has %s (weights %s)"
+                             % (have_scales + want_scales))
         with torch.no_grad():
             if self.pyramid is not None:
                 self.pyramid.load_params(blob["texture_pyramid"].to(self.device))

@@ -1674,6 +1674,12 @@ def texpyr_adjoint(grad_texture, T, L, out=None):
     return out
 
 
+# ------------------------------------------------------------------ image pyramid step (csrc/imgpyr.hip)
+# The device wrappers live in st3d/imgpyr.py, next to the autograd function and the caches built on them (as st3d/fill.py
+# holds those of fill.hip); they are re-exported here so that ops keeps one name per entry point of include/st3d.h.
+from .imgpyr import pyr_down_bwd, pyr_down_fwd, pyr_down_need, pyr_down_tile  # noqa: E402,F401
+
+
 # ------------------------------------------------------------------ mip-mapped sampling (csrc/mipmap.hip)
 MIP_MAX_LEVELS = 16
 

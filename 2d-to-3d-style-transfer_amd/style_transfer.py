@@ -399,7 +399,7 @@ def _swd_term(current_imgs, style_imgs, model, layers, masks, batch_denom, direc
 
 def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, steps=2000, style_weight=1e6, content_weight=1, lr=0.003,
                    style_masks=None, nnfm_weight=0.0, nnfm_layers=('conv3_1',), swd_weight=0.0, swd_layers=SWD_DEFAULT_LAYERS,
-                   swd_directions=0, swd_seed=0):
+                   swd_directions=0, swd_seed=0, style_scales=(1,), style_scale_weights=None):
     # style_masks (B,1,S,S) | (B,S,S) in [0,1], e.g. the coverage of the renders being stylised: the guided style loss --
     # each tap's Gram of the optimised images is taken over the masked region only (default None: the reference's loss)
     # nnfm_weight > 0: every step adds nnfm_weight x the NNFM term over nnfm_layers (its own partial VGG forward and backward
@@ -421,6 +421,14 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
         if isinstance(swd_seed, bool) or not isinstance(swd_seed, int):
             raise ValueError(f"swd_seed must be an integer, got {swd_seed!r}")
         swd_generator = torch.Generator().manual_seed(swd_seed)
+    # style_scales / style_scale_weights: the multi-scale loss (st3d.imgpyr; losses.compute_perceptual_loss(scales=...)) --
+    # every step adds w_f x the pyramid's transpose of the gradient of the fused loss at side S / f, f in {2, 4}, to the
+    # plan's gradient before Adam, in ascending f.  The NNFM and SWD terms stay at full resolution.  (1,): today's loop.
+    multi_scale = not (isinstance(style_scales, tuple) and style_scales == (1,) and style_scale_weights is None)
+    if multi_scale:
+        from st3d import imgpyr as _imgpyr
+        style_scales, style_scale_weights = _imgpyr.check_scales(style_scales, style_scale_weights,
+                                                                 initial_optimized_imgs.shape[2])
 
     # Ensure content_imgs and style_imgs are batched tensors
     assert initial_optimized_imgs.shape[0] == content_imgs.shape[0] == style_imgs.shape[0]
@@ -428,15 +436,27 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
         raise TypeError("style_transfer needs the st3d VGG returned by utils.get_vgg()")
 
     B, S = initial_optimized_imgs.shape[0], initial_optimized_imgs.shape[2]
-    plan = model.plan(B, S)
+    full_weight = 1.0 if not multi_scale else dict(zip(style_scales, style_scale_weights)).get(1, 0.0)
+    plan = model.plan(B, S) if full_weight else None
     if style_masks is not None:
         if not torch.is_tensor(style_masks) or tuple(style_masks.shape) not in ((B, 1, S, S), (B, S, S)):
             raise ValueError(f"style_masks must be ({B},1,{S},{S}) or ({B},{S},{S})")
         style_masks = style_masks.detach().to(device=device, dtype=torch.float32)
 
     # content conv4_2 features and style Grams: computed once (reference :44-51)
-    plan.set_content(content_imgs.to(device), force=True)
-    plan.set_style(style_imgs.to(device), B, force=True)
+    if plan is not None:
+        plan.set_content(content_imgs.to(device), force=True)
+        plan.set_style(style_imgs.to(device), B, force=True)
+    coarse = []             # (f, w_f, the plan of side S / f, the masks reduced by f): targets set once, here
+    if multi_scale:
+        with torch.no_grad():
+            for f, w in zip(style_scales, style_scale_weights):
+                if f == 1 or w == 0.0:
+                    continue
+                p = model.plan(B, S // f)
+                p.set_content(_imgpyr.reduce(content_imgs.to(device).detach(), f), force=True)
+                p.set_style(_imgpyr.reduce(style_imgs.to(device).detach().contiguous(), f), B, force=True)
+                coarse.append((f, w, p, _imgpyr.reduce(style_masks.reshape(B, 1, S, S), f) if style_masks is not None else None))
     nnfm_style_imgs = style_imgs.to(device) if nnfm_weight else None      # one tensor for the run: its taps are cached on it
     swd_style_imgs = style_imgs.to(device) if swd_weight else None
 
@@ -447,7 +467,19 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
     optimizer = _st3d_optim.Adam([optimized_imgs], lr=lr, reduce_grads=False)
 
     for step in tqdm(range(steps), desc="2D Style Transfer"):
-        _, grad = plan.loss(optimized_imgs, style_weight, content_weight, style_mask=style_masks)
+        grad = None
+        if plan is not None:
+            _, grad = plan.loss(optimized_imgs, style_weight, content_weight, style_mask=style_masks)
+            if full_weight != 1.0:
+                grad = grad * full_weight
+        for f, w, p, m in coarse:
+            _, g = p.loss(_imgpyr.reduce(optimized_imgs.detach(), f), style_weight, content_weight, style_mask=m)
+            while g.shape[2] < S:
+                g = _ops.pyr_down_bwd(g)
+            g = g * w if w != 1.0 else g
+            grad = g if grad is None else grad + g
+        if grad is None:        # every scale has weight 0
+            grad = torch.zeros_like(optimized_imgs)
         if nnfm_weight:
             # the term forwards through the same plan: taken after the fused loss has delivered its gradient
             term = _nnfm_term(optimized_imgs, nnfm_style_imgs, model, nnfm_layers, style_masks, None)

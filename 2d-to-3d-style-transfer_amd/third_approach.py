@@ -61,7 +61,9 @@ def main(argv=None):
                                                          nnfm_weight=args.nnfm_weight, nnfm_layers=args.nnfm_layers,
                                                      swd_weight=args.swd_weight, swd_layers=args.swd_layers,
                                                      swd_directions=args.swd_directions,
-                                                     swd_seed=args.seed if args.seed is not None else 0))
+                                                     swd_seed=args.seed if args.seed is not None else 0,
+                                                     style_scales=run.style_scales,
+                                                     style_scale_weights=run.style_scale_weights))
                 if rnd == args.n_rounds - 1:
                     run.save_views(targets, vb.lo)
                 run.bake_targets(targets, cams, f"round {rnd}, batch {vb.index}")       # --bake_texture, off by default

@@ -1208,6 +1208,27 @@ size_t st3d_fill_workspace_bytes(int H, int W);
 int st3d_fill_pushpull(const float *tex, const uint8_t *valid, const uint8_t *domain, int H, int W, void *workspace,
                        size_t workspace_bytes, float *out, int64_t *count, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ image pyramid step (imgpyr.hip)
+ * N planes of H x W fp32 (H, W even, 2...32768) halved with the separable tent filter [1 3 3 1] / 8 -- for sides >= 4 the
+ * filter of an anti-aliased bilinear resize by 1/2, centred on every 2 x 2 block.  Every argument is checked on the host
+ * before any launch (null pointers, N <= 0, odd or < 2 sides: ST3D_E_INVALID, nothing launched); nothing is allocated; the
+ * two buffers of a call must not be the same.
+ *   fwd:  out (N,H/2,W/2).  Coarse (i, j) reads rows 2i-1 ... 2i+2 and columns 2j-1 ... 2j+2, indices clamped to the plane.
+ *         Per row h = (x[-1] + x[2]) + 3 (x[0] + x[1]); over the four h the same; then * (1/64) -- these roundings, in
+ *         this order, no contraction.  NaN / Inf reach exactly the outputs whose footprint holds them.
+ *   bwd:  grad_in (N,H,W), set, never added to: the exact transpose as a gather.  Along an axis fine index y has the near
+ *         coarse index y >> 1 (weight 3) and the far one (y odd: near + 1, else near - 1; weight 1); where the far one is
+ *         off the plane the near weight is 4 (the clamp had doubled that border row).  A fine pixel sums (wy wx / 64) g
+ *         over (near,near), (near,far), (far,near), (far,far) in (row, column), in that order, taps that do not exist
+ *         skipped: at most 4 products and 3 sums.  No atomics: two calls give the same bits.
+ *   need: uint8 planes (Bn,H,W) -> (Bn,H/2,W/2), 1 where any pixel of the coarse pixel's clamped 4 x 4 footprint is
+ *         non-zero, else 0: every coarse pixel a needed fine pixel gathers from in bwd is needed.
+ *   tile: the fine pixels one workgroup owns in fwd and bwd (16 x 128); halos cross tile borders there. */
+int st3d_pyr_down_tile(int *tile_h, int *tile_w);
+int st3d_pyr_down_fwd(const float *in, int N, int H, int W, float *out, st3d_stream_t stream);
+int st3d_pyr_down_bwd(const float *grad_out, int N, int H, int W, float *grad_in, st3d_stream_t stream);
+int st3d_pyr_down_need(const uint8_t *need_in, int Bn, int H, int W, uint8_t *need_out, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-GPU
  * One process per GPU; every rank renders / VGGs its slice of the view batch with the loss means divided by the GLOBAL
  * batch (batch_denom of st3d_plan_loss) and ONE SUM all-reduce of the flat fp32 gradient (3*T*T texture floats

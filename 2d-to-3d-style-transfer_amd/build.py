@@ -77,6 +77,9 @@ SOURCES = {
     # the pyramid step and its transpose are compared bit for bit with their fp32 numpy restatement: sums and products in the
     # order written, none fused; no division or square root in the file
     "imgpyr.hip": ["-ffp-contract=off"],
+    # the luminance, its transpose, the recombination and the affine map are compared bit for bit with their fp32 numpy
+    # restatement: the only fused operations are the fmaf written in the source; no division or square root in the file
+    "color.hip": ["-ffp-contract=off"],
     "plan.hip": [],
     "comm.hip": [],
 }

@@ -68,8 +68,9 @@ def main(argv=None):
             img, cov = render_meshes(run.renderer, mesh, cams)
             current = apply_background(img, cov, background_type=args.current_background, background=style)
 
+            seen, seen_content = run.loss_images(current, content)     # --preserve_color luminance: their luminance
             loss = compute_second_approach_loss(
-                current=current, content=content, style=style, model=run.vgg, style_weight=args.style_weight,
+                current=seen, content=seen_content, style=style, model=run.vgg, style_weight=args.style_weight,
                 content_weight=args.content_weight, verts=run.opt['verts'], target_verts=run.original_verts, mesh=mesh,
                 weights=run.loss_weights, opt_type=args.optimization_target, batch_denom=vb.size,
                 style_masks=cov if args.style_mask == 'object' else None,      # this rank's views, their own coverage
@@ -83,11 +84,11 @@ def main(argv=None):
             anchor_term = run.chamfer_term(mesh)    # --chamfer_weight, off by default
             if torch.is_tensor(anchor_term):
                 loss = loss + anchor_term
-            style_term = run.nnfm_term(current, cov, style, vb.size)    # --nnfm_weight, off by default
+            style_term = run.nnfm_term(seen, cov, style, vb.size)       # --nnfm_weight, off by default
             if torch.is_tensor(style_term):
                 loss = loss + style_term
 
-            style_term = run.swd_term(current, cov, style, vb.size)     # --swd_weight, off by default
+            style_term = run.swd_term(seen, cov, style, vb.size)        # --swd_weight, off by default
             if torch.is_tensor(style_term):
                 loss = loss + style_term
 

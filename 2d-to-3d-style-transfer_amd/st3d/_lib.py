@@ -276,6 +276,12 @@ SIGNATURES = {
     "st3d_pyr_down_fwd": (c_int, [c_f32p, c_int, c_int, c_int, c_f32p, c_stream]),
     "st3d_pyr_down_bwd": (c_int, [c_f32p, c_int, c_int, c_int, c_f32p, c_stream]),
     "st3d_pyr_down_need": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, c_stream]),
+    "st3d_color_stats_chunk": (c_int, []),
+    "st3d_luma_fwd": (c_int, [c_f32p, c_int, c_size, c_f32p, c_stream]),
+    "st3d_luma_bwd": (c_int, [c_f32p, c_int, c_size, c_f32p, c_stream]),
+    "st3d_luma_recombine": (c_int, [c_f32p, c_f32p, c_int, c_size, c_f32p, c_stream]),
+    "st3d_color_affine": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_int, c_size, c_f32p, c_stream]),
+    "st3d_color_stats": (c_int, [c_f32p, c_u8p, c_int, c_size, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
     "st3d_vgg_create": (c_int, [ctypes.POINTER(ctypes.c_void_p)]),
     "st3d_vgg_set_conv": (c_int, [ctypes.c_void_p, c_int, c_f32p, c_f32p, c_stream]),
     "st3d_vgg_destroy": (c_int, [ctypes.c_void_p]),

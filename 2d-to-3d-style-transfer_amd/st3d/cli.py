@@ -28,6 +28,7 @@ _TEXTURE_TYPES = ['uv', 'vertex']
 _LAPLACIANS = ['uniform', 'cot', 'cotcurv']
 _VIEW_SELECTIONS = ['random', 'coverage']
 _FILL_MODES = ['off', 'chart', 'map']
+_COLOR_MODES = ['off', 'match', 'luminance']       # st3d.color.MODES
 VIEW_CANDIDATES_DEFAULT, VIEW_CANDIDATES_MAX = 256, 4096        # (st3d.cover.MAX_CANDIDATES)
 _NNFM_LAYERS = ['conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.NNFM_LAYERS
 _SWD_LAYERS = ['conv1_1', 'conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1']       # style_transfer.SWD_LAYERS
@@ -197,6 +198,11 @@ SHARED_FLAGS = [
          "Default 1: the single-scale loss"),
     Flag("style_scale_weights", style_scale_weights, None, "one finite weight >= 0 per factor of --style_scales, a comma list; "
          "a weight of 0 leaves its scale out.  Default: all 1"),
+    Flag("preserve_color", str, 'off', "keep the asset's own palette and take only the strokes of the style image (Gatys et al. "
+         "2017, section 5): 'match' recolours the style image once, by an affine map, so that its pixel mean and covariance "
+         "equal those of the loaded mesh seen through the run's cameras; 'luminance' shows every style and content term the "
+         "luminance of render, content and style only, and at export puts the optimised luminance back under the loaded "
+         "colours.  Both write style_matched.png.  --optimization_target texture / both", _COLOR_MODES),
 ]
 
 # the fitting phase of first_approach.py / third_approach.py only: each script adds them to its own table
@@ -366,6 +372,9 @@ def check_args(args):
             return "--fill_unseen needs --texture_type uv: per-vertex colours have no texels to fill"
         if atlas:
             return "--fill_unseen needs --texture_atlas 0: the fill walks the texels of a UV-mapped texture"
+    if getattr(args, "preserve_color", "off") != "off" and getattr(args, "optimization_target", "texture") == 'mesh':
+        return ("--preserve_color needs --optimization_target texture or both: with 'mesh' no colour is optimised and there is "
+                "nothing to preserve")
     scales, scale_weights = getattr(args, "style_scales", None), getattr(args, "style_scale_weights", None)
     if scales is None:
         if scale_weights is not None:
@@ -717,15 +726,21 @@ class Run:
             weights = self.style_scale_weights or (1.0,) * len(self.style_scales)
             self.say("Style scales: " + ", ".join(f"1/{f} (plan side {args.size // f}, weight {w:g})"
                                                    for f, w in zip(self.style_scales, weights)))
+        self.color_mode = getattr(args, "preserve_color", "off")
+        self._utils = _u
+        matched_style = None
+        if self.color_mode != "off":        # the default: nothing is said, nothing runs.  Before --resume is read: a resumed
+            matched_style = self.setup_color()      # run sees the same style image
         self.progress = 0               # epochs (second approach) / view batches (first approach) already done
         if args.resume:
             self.load_checkpoint(args.resume)
         self.style_image = _u.load_as_tensor(args.style_path, size=args.size)   # loop-invariant; the reference reloads it
+        if matched_style is not None:
+            self.style_image = matched_style
         self._log = os.path.join(self.out_dir, 'log.txt')
         if self.main:
             with open(self._log, 'w') as fh:
                 fh.write('Logger:\n')
-        self._utils = _u
         self.writer = AsyncImageWriter()
 
     # ---- small helpers
@@ -746,6 +761,11 @@ class Run:
         """--style_scales / --style_scale_weights ask for anything but the single-scale loss"""
         return self.style_scales != (1,) or self.style_scale_weights is not None
 
+    @property
+    def style_color(self):
+        """style_transfer's ``color``: 'luminance' under --preserve_color luminance, else 'rgb' (today's loop)"""
+        return 'luminance' if getattr(self, "color_mode", "off") == "luminance" else 'rgb'
+
     def say(self, msg):
         if self.main:
             print(msg)
@@ -755,6 +775,78 @@ class Run:
         if self.main:
             with open(self._log, 'a') as fh:
                 fh.write(line + '\n')
+
+    def setup_color(self):
+        """--preserve_color match / luminance: the moments of the LOADED mesh as the run sees it -- every rank renders it
+        through all n_views cameras in batches of batch_size under no_grad and takes st3d.color's 10 sums over the covered
+        pixels, added over the batches in fp64 in batch order -- and the style image prepared from them: 'match' recolours
+        it to the content's mean and covariance (match_matrix), 'luminance' takes its luminance and matches that to the
+        content's luminance (luma_match).  Every rank computes the same bits: no communication.  Rank 0 writes
+        style_matched.png; one line of figures.  -> the (3,size,size) style image of the run."""
+        import numpy as np
+        from . import color as _color
+        a, u = self.args, self._utils
+        luminance = self.color_mode == "luminance"
+        if luminance:       # loss_images() asks luma_cached for every view batch's content in turn: all of them must fit
+            _color.reserve_cache(math.ceil(a.n_views / a.batch_size) + 1)
+        style = u.load_as_tensor(a.style_path, size=a.size)[None]
+        sums = np.zeros(10, np.float64)
+        with torch.no_grad():
+            for first in range(0, a.n_views, a.batch_size):
+                cams = self.cameras[first:min(first + a.batch_size, a.n_views)]
+                img, cov = u.render_meshes(self.renderer, self.content_mesh, cams)
+                if luminance:
+                    img = _color.luma_fwd(img)
+                sums += _color.color_sums(img, (cov > 0).reshape(img.shape[0], -1)).cpu().numpy()
+            content = _color.stats_from_sums(sums)
+            if luminance:
+                style = _color.luma_fwd(style)
+                before = _color.color_stats(style)
+                k, b = _color.luma_match(before, content)
+                matched = _color.recolor(style, np.eye(3) * k, np.full(3, b))
+            else:
+                before = _color.color_stats(style)
+                matched = _color.recolor(style, *_color.match_matrix(before, content))
+            after = _color.color_stats(matched)
+        fmt = lambda m: "(" + ", ".join(f"{v:.4f}" for v in m) + ")"
+        self.say(f"Preserve colour ({self.color_mode}): content mean {fmt(content['mean'])} over {content['n']} covered pixels "
+                 f"of {a.n_views} views; style mean {fmt(before['mean'])} -> {fmt(after['mean'])}")
+        if self.main:
+            u.tensor_to_image(matched).save(os.path.join(self.out_dir, 'style_matched.png'))
+        return matched[0].contiguous()
+
+    def loss_images(self, current, content):
+        """-> the (current, content) pair to hand the style terms: the inputs themselves, or under --preserve_color luminance
+        their luminance -- luma(current), which carries the render's need / flat / epoch tags to the loss, and
+        luma_cached(content), the same tensor every step.  The TV term and the view dumps keep the RGB `current`."""
+        if self.color_mode != "luminance":
+            return current, content
+        from . import color as _color
+        return _color.luma(current), _color.luma_cached(content)
+
+    def recombine_leaf(self, mesh):
+        """--preserve_color luminance at export: `mesh` with its colour carrier (the map, the pyramid's synthesised map, the
+        vertex colours or the atlas) replaced by its luminance under the chroma of the loaded one (color.recombine_texture).
+        A texel that never moved has d = 0 and keeps its loaded value.  One line says how many texels changed."""
+        from . import color as _color
+        u, tex = self._utils, mesh.textures
+        with torch.no_grad():
+            if self.atlas_r:
+                leaf = tex.atlas_packed()
+            elif self.vertex_colors:
+                leaf = tex.verts_features_packed()
+            else:
+                leaf = tex.maps_padded()
+            original = self.original_map.reshape(leaf.shape)
+            out = _color.recombine_texture(leaf, original)
+            changed = int((out != original).any(dim=-1).sum())
+        self.say(f"Recombine: {changed} of {out.numel() // 3} texels carry a new luminance under their loaded chroma "
+                 "(--preserve_color luminance)")
+        if self.atlas_r:
+            return u.build_mesh_atlas(out, mesh.verts_packed(), mesh.faces_packed())
+        if self.vertex_colors:
+            return u.build_mesh_vertex(out, mesh.verts_packed(), mesh.faces_packed())
+        return u.build_mesh(tex.verts_uvs_padded(), tex.faces_uvs_padded(), out, mesh.verts_packed(), mesh.faces_packed())
 
     def select_views(self, generator):
         """--view_selection coverage: n_views of --view_candidates random directions, picked greedily by the texels they add
@@ -885,6 +977,8 @@ class Run:
         if getattr(self, "multi_scale", False):     # --style_scales: no state of its own, but Adam's moments belong to that loss
             blob["style_scales"] = list(self.style_scales)
             blob["style_scale_weights"] = list(self.style_scale_weights) if self.style_scale_weights is not None else None
+        if getattr(self, "color_mode", "off") != "off":     # --preserve_color: Adam's moments belong to that style image and loss
+            blob["preserve_color"] = self.color_mode
         tmp = os.path.join(self.out_dir, "checkpoint.pt.tmp")
         torch.save(blob, tmp)
         os.replace(tmp, os.path.join(self.out_dir, "checkpoint.pt"))
@@ -925,6 +1019,9 @@ class Run:
         if have_scales != want_scales:
             raise ValueError("checkpoint was written with --style_scales %s (weights %s), this run has %s (weights %s)"
                              % (have_scales + want_scales))
+        have_color, want_color = blob.get("preserve_color", "off"), getattr(self, "color_mode", "off")
+        if have_color != want_color:
+            raise ValueError("checkpoint was written with --preserve_color %s, this run has %s" % (have_color, want_color))
         with torch.no_grad():
             if self.pyramid is not None:
                 self.pyramid.load_params(blob["texture_pyramid"].to(self.device))
@@ -1048,7 +1145,9 @@ class Run:
         _ops.check_near_plane(block=True)       # a mesh that reached the near clipping plane fails loudly (no clipping at K = 1)
         if self.main:
             u = self._utils
-            final = u.finalize_mesh(mesh)
+            # --preserve_color luminance: recombine -> clamp -> --fill_unseen (which still reads what moved off the
+            # un-recombined mesh: a texel that never moved keeps its loaded bits either way)
+            final = u.finalize_mesh(self.recombine_leaf(mesh) if getattr(self, "color_mode", "off") == "luminance" else mesh)
             if getattr(self.args, "fill_unseen", "off") != "off":
                 final = self.fill_unseen(mesh, final)
             u.save_render(self.renderer, final, u.build_fixed_cameras(12), os.path.join(self.out_dir, "final_render"))

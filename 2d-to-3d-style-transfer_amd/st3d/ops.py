@@ -1680,6 +1680,13 @@ def texpyr_adjoint(grad_texture, T, L, out=None):
 from .imgpyr import pyr_down_bwd, pyr_down_fwd, pyr_down_need, pyr_down_tile  # noqa: E402,F401
 
 
+# ------------------------------------------------------------------ colour control (csrc/color.hip)
+# As above: the device wrappers live in st3d/color.py next to the autograd function, the cache and the host-side match.
+# st3d_color_stats is ``color_sums`` here as there (the ten sums on the device): ``color_stats`` is the name of the public
+# function of st3d.color that returns mean and covariance, and one name does not get two return types.
+from .color import color_affine, color_stats_chunk, color_sums, luma_bwd, luma_fwd, luma_recombine  # noqa: E402,F401
+
+
 # ------------------------------------------------------------------ mip-mapped sampling (csrc/mipmap.hip)
 MIP_MAX_LEVELS = 16
 

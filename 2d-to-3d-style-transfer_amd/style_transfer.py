@@ -399,7 +399,7 @@ def _swd_term(current_imgs, style_imgs, model, layers, masks, batch_denom, direc
 
 def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, steps=2000, style_weight=1e6, content_weight=1, lr=0.003,
                    style_masks=None, nnfm_weight=0.0, nnfm_layers=('conv3_1',), swd_weight=0.0, swd_layers=SWD_DEFAULT_LAYERS,
-                   swd_directions=0, swd_seed=0, style_scales=(1,), style_scale_weights=None):
+                   swd_directions=0, swd_seed=0, style_scales=(1,), style_scale_weights=None, color='rgb'):
     # style_masks (B,1,S,S) | (B,S,S) in [0,1], e.g. the coverage of the renders being stylised: the guided style loss --
     # each tap's Gram of the optimised images is taken over the masked region only (default None: the reference's loss)
     # nnfm_weight > 0: every step adds nnfm_weight x the NNFM term over nnfm_layers (its own partial VGG forward and backward
@@ -430,10 +430,28 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
         style_scales, style_scale_weights = _imgpyr.check_scales(style_scales, style_scale_weights,
                                                                  initial_optimized_imgs.shape[2])
 
+    # color='luminance' (Gatys et al. 2017, section 5.2; st3d.color): content and style are replaced by their luminance once;
+    # every step ONE luma_fwd of the optimised pixels is what the plan(s) and the NNFM / SWD terms see, and each term's
+    # gradient comes back through luma_bwd before it is added; the result is the optimised luminance under the content's
+    # chroma (color.recombine).  'rgb': today's loop, nothing of it runs.
+    if color not in ('rgb', 'luminance'):
+        raise ValueError(f"color must be 'rgb' or 'luminance', got {color!r}")
+    luminance = color == 'luminance'
+
     # Ensure content_imgs and style_imgs are batched tensors
     assert initial_optimized_imgs.shape[0] == content_imgs.shape[0] == style_imgs.shape[0]
     if not isinstance(model, _vgg.Vgg19Features):
         raise TypeError("style_transfer needs the st3d VGG returned by utils.get_vgg()")
+    if luminance:
+        from st3d import color as _color
+        rgb_content = content_imgs.to(device).detach()
+        with torch.no_grad():
+            content_imgs = _color.luma_fwd(rgb_content.to(torch.float32))
+            one_style = style_imgs.shape[0] > 1 and style_imgs.stride(0) == 0      # one image expanded stays one image expanded
+            style_src = (style_imgs[:1] if one_style else style_imgs).to(device).detach().to(torch.float32)
+            style_imgs = _color.luma_fwd(style_src)
+            if one_style:
+                style_imgs = style_imgs.expand(content_imgs.shape[0], -1, -1, -1)
 
     B, S = initial_optimized_imgs.shape[0], initial_optimized_imgs.shape[2]
     full_weight = 1.0 if not multi_scale else dict(zip(style_scales, style_scale_weights)).get(1, 0.0)
@@ -466,31 +484,40 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
     # Define optimizer (fused HIP Adam; pixels are not sharded, so no gradient all-reduce)
     optimizer = _st3d_optim.Adam([optimized_imgs], lr=lr, reduce_grads=False)
 
+    back = _color.luma_bwd if luminance else (lambda g: g)      # how a term's gradient reaches the pixels
+
     for step in tqdm(range(steps), desc="2D Style Transfer"):
         grad = None
+        seen = optimized_imgs       # what the terms see: the pixels themselves, or one luminance image a step for all of them
+        if luminance:
+            seen = _color.luma_fwd(optimized_imgs.detach()).requires_grad_(bool(nnfm_weight or swd_weight))
         if plan is not None:
-            _, grad = plan.loss(optimized_imgs, style_weight, content_weight, style_mask=style_masks)
+            _, grad = plan.loss(seen, style_weight, content_weight, style_mask=style_masks)
+            grad = back(grad)
             if full_weight != 1.0:
                 grad = grad * full_weight
         for f, w, p, m in coarse:
-            _, g = p.loss(_imgpyr.reduce(optimized_imgs.detach(), f), style_weight, content_weight, style_mask=m)
+            _, g = p.loss(_imgpyr.reduce(seen.detach(), f), style_weight, content_weight, style_mask=m)
             while g.shape[2] < S:
                 g = _ops.pyr_down_bwd(g)
+            g = back(g)
             g = g * w if w != 1.0 else g
             grad = g if grad is None else grad + g
         if grad is None:        # every scale has weight 0
             grad = torch.zeros_like(optimized_imgs)
         if nnfm_weight:
             # the term forwards through the same plan: taken after the fused loss has delivered its gradient
-            term = _nnfm_term(optimized_imgs, nnfm_style_imgs, model, nnfm_layers, style_masks, None)
-            (extra,) = torch.autograd.grad(term, optimized_imgs)
-            grad = grad + nnfm_weight * extra
+            term = _nnfm_term(seen, nnfm_style_imgs, model, nnfm_layers, style_masks, None)
+            (extra,) = torch.autograd.grad(term, seen)
+            grad = grad + nnfm_weight * back(extra)
         if swd_weight:
-            term = _swd_term(optimized_imgs, swd_style_imgs, model, swd_layers, style_masks, None,
+            term = _swd_term(seen, swd_style_imgs, model, swd_layers, style_masks, None,
                              swd_draw(swd_layers, swd_k, swd_generator, device))
-            (extra,) = torch.autograd.grad(term, optimized_imgs)
-            grad = grad + swd_weight * extra
+            (extra,) = torch.autograd.grad(term, seen)
+            grad = grad + swd_weight * back(extra)
         optimized_imgs.grad = grad
         optimizer.step()
 
+    if luminance:
+        return _color.recombine(optimized_imgs, rgb_content)
     return optimized_imgs

@@ -1229,6 +1229,39 @@ int st3d_pyr_down_fwd(const float *in, int N, int H, int W, float *out, st3d_str
 int st3d_pyr_down_bwd(const float *grad_out, int N, int H, int W, float *grad_in, st3d_stream_t stream);
 int st3d_pyr_down_need(const uint8_t *need_in, int Bn, int H, int W, uint8_t *need_out, st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ colour control (color.hip)
+ * Gatys et al. 2017, section 5: the luminance the style terms may be restricted to, and the colour matching of the style
+ * image.  Every image is planar (B,3,P) fp32, P = H W pixels per channel plane, any P >= 1 (an odd P leaves channel planes
+ * off 16-byte boundaries: the kernels then take scalar accesses).  Every argument is checked on the host before any launch
+ * (null pointers, B <= 0, P == 0, B > 65535: ST3D_E_INVALID, nothing launched); nothing is allocated; an output must not be
+ * one of the inputs.  All of it is per pixel and in a fixed order: NaN and +-Inf stay in their own pixel, no atomics, two
+ * calls give the same bits.  The arithmetic, with W = (0.299f, 0.587f, 0.114f) (Rec. 601) as fp32 constants and fmaf one
+ * rounding (tests/_colorref.py restates it in numpy):
+ *     Y(r, g, b) = fmaf(W2, b, fmaf(W1, g, W0 * r))
+ *   luma_fwd:   out[b,c,p] = Y(x[b,:,p]) for c = 0, 1, 2 -- a grey image is three equal planes, as the VGG plan takes them.
+ *   luma_bwd:   the exact transpose: s = (g0 + g1) + g2 in fp32, in that order, then out_c = W_c * s.
+ *   luma_recombine:  d = Y(opt) - Y(orig), one fp32 subtraction, then out_c = orig_c + d.  (The inverse YIQ transform has
+ *               (1,1,1) as the column that multiplies Y: a new Y under the old I and Q adds the same d to all three.)
+ *   color_affine:    out_c = fmaf(A[c][2], x2, fmaf(A[c][1], x1, fmaf(A[c][0], x0, b_c))); with clamp != 0 then
+ *               v < 0 ? 0 : (v > 1 ? 1 : v) -- a NaN stays a NaN, as in torch.clamp. 
+ *               A9 (row-major 3 x 3) and b3 are fp32 in HOST memory, read during the call and handed to the kernel by
+ *               value: no upload, nothing to keep alive.
+ *   color_stats:     mask (B,P) bytes, NULL = every pixel.  out10 (10 doubles, device), over the pixels whose mask byte is
+ *               non-zero: [0] the count, [1..3] sum x_c, [4..9] sum x_c x_d for (c,d) = (0,0) (0,1) (0,2) (1,1) (1,2) (2,2).
+ *               The products are formed in fp64 from the fp32 values (exact), the sums are fp64 in a fixed two-stage
+ *               order: a workgroup of 256 threads owns st3d_color_stats_chunk() consecutive pixels of one image, thread
+ *               t adds pixels t, t + 256, ... in ascending order, the 256 sums are folded by halving strides (128 ... 1);
+ *               a second launch adds the partials in index order (image-major, then chunk).
+ *               partials: 10 * B * ceil(P / chunk) doubles of scratch, written before they are read. */
+int st3d_color_stats_chunk(void);
+int st3d_luma_fwd(const float *x, int B, size_t P, float *out, st3d_stream_t stream);
+int st3d_luma_bwd(const float *g, int B, size_t P, float *out, st3d_stream_t stream);
+int st3d_luma_recombine(const float *opt, const float *orig, int B, size_t P, float *out, st3d_stream_t stream);
+int st3d_color_affine(const float *x, const float *A9, const float *b3, int clamp, int B, size_t P, float *out,
+                      st3d_stream_t stream);
+int st3d_color_stats(const float *x, const uint8_t *mask, int B, size_t P, double *partials, double *out10,
+                     st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-GPU
  * One process per GPU; every rank renders / VGGs its slice of the view batch with the loss means divided by the GLOBAL
  * batch (batch_denom of st3d_plan_loss) and ONE SUM all-reduce of the flat fp32 gradient (3*T*T texture floats

@@ -40,6 +40,8 @@ SOURCES = {
     # the guidance planes are compared bit for bit with their numpy restatement: the roundings written in the source, and the
     # correctly rounded division and square root (hipcc's default, stated so that no other flag relaxes it for this file)
     "guide.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # guide.hip's flags: each region's planes are compared bit for bit with guide.hip's for the one-hot mask
+    "regions.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "tap0.hip": [],
     "need.hip": [],
     "flat.hip": [],

@@ -163,6 +163,72 @@ def compute_perceptual_loss(current_imgs, content_imgs, style_imgs, model, style
     return _PerceptualFn.apply(current_imgs, plan, float(style_weight), float(content_weight), batch_denom, need, flat, style_masks, epoch)
 
 
+def _region_content_target(content_imgs, model):
+    """conv4_2 of the content images, computed once: cached on the model under the tensor's identity and version"""
+    import style_transfer as _st
+    key = (content_imgs.data_ptr(), content_imgs._version, tuple(content_imgs.shape), tuple(content_imgs.stride()))
+    cache = model.__dict__.setdefault("_region_content_cache", {})
+    hit = cache.get(key)
+    if hit is not None and hit[0].data_ptr() == content_imgs.data_ptr():
+        return hit[1]
+    with torch.no_grad():
+        tap = {k: v for k, v in _st._DEFAULT_LAYERS.items() if v == _st.REGION_CONTENT_TAP}
+        target = _st.get_features(content_imgs.detach().to(torch.float32).contiguous(), model, tap)[_st.REGION_CONTENT_TAP]
+    if len(cache) >= 8:         # (the alternating view batches of a run, as PerceptualPlan.CONTENT_CACHE)
+        cache.pop(next(iter(cache)))
+    cache[key] = (content_imgs, target)
+    return target
+
+
+def compute_region_style_loss(current_imgs, content_imgs, style_imgs, pix_to_face, face_regions, model, style_weight=1e6,
+                              content_weight=1, *, region_weights=None, batch_denom=None, planes=None):
+    """compute_perceptual_loss with one style image per region of the mesh (st3d.regions; Gatys et al. 2017, spatial
+    control): content_weight x the conv4_2 content term + style_weight x style_transfer.region_style_loss.
+    ``style_imgs`` (R,3,S,S): region r's style image; ``pix_to_face`` (B,S,S) int32: the fragments of the renders that
+    ``current_imgs`` are (st3d.regions.fragments_of gives them); ``face_regions``: the uint8 labels of
+    regions.check_face_regions (R = style_imgs.shape[0]).  For R = 1 with every face in region 0 the value is the one
+    compute_perceptual_loss(style_masks=coverage) defines; background pixels belong to no region.  ``planes``: the
+    (planes, sums) of regions.region_planes for these fragments, when the caller keeps them (unchanged geometry).
+    One differentiable get_features over the current images, the R x 5 guided Grams, the ordered loss sums, per tap R
+    accumulating Gram backwards, then the plan's backward: the term gives up the fused plan's need / flat / epoch
+    shortcuts.  The scalar carries ``parts`` (3,) [total, content, style].  Gradient to ``current_imgs`` only."""
+    import style_transfer as _st
+    from st3d import regions as _regions
+    if not isinstance(model, _vgg.Vgg19Features):
+        raise TypeError("compute_region_style_loss needs the st3d VGG returned by utils.get_vgg()")
+    if not all(torch.is_tensor(t) for t in (current_imgs, content_imgs, style_imgs)):
+        raise TypeError("current_imgs, content_imgs and style_imgs must be tensors")
+    if not (current_imgs.is_cuda and content_imgs.is_cuda and style_imgs.is_cuda):
+        raise RuntimeError("st3d runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
+    if current_imgs.dim() != 4 or current_imgs.shape[1] != 3 or current_imgs.shape[2] != current_imgs.shape[3]:
+        raise ValueError(f"current_imgs must be (B,3,S,S), got {tuple(current_imgs.shape)}")
+    B, S = current_imgs.shape[0], current_imgs.shape[2]
+    if tuple(content_imgs.shape) != (B, 3, S, S):
+        raise ValueError(f"content_imgs must be ({B},3,{S},{S}), got {tuple(content_imgs.shape)}")
+    R = int(style_imgs.shape[0]) if style_imgs.dim() == 4 else 0
+    if tuple(style_imgs.shape) != (R, 3, S, S) or not 1 <= R <= _regions.MAX_REGIONS:
+        raise ValueError(f"style_imgs must be (R,3,{S},{S}) with R in 1..{_regions.MAX_REGIONS}, one image per region; got "
+                         f"{tuple(style_imgs.shape)}")
+    lambdas = _st.check_region_weights(region_weights, R)
+    targets = _regions.region_targets(style_imgs, model)
+    content_target = _region_content_target(content_imgs, model)
+    if planes is None:
+        if tuple(pix_to_face.shape[:3]) != (B, S, S):
+            raise ValueError(f"pix_to_face must be ({B},{S},{S}), got {tuple(pix_to_face.shape)}")
+        planes = _regions.region_planes(pix_to_face, face_regions, R)
+    q, sums = planes
+    layers = dict(_st.REGION_STYLE_TAPS)
+    layers.update({k: v for k, v in _st._DEFAULT_LAYERS.items() if v == _st.REGION_CONTENT_TAP})
+    feats = _st.get_features(current_imgs, model, layers)           # targets first: this forward is the plan's last
+    taps, _, bd = _st._region_check(feats, q, sums, targets, lambdas, batch_denom)
+    masked = _st._region_masked_targets(sums, targets, B)
+    with _ops.trace("region_style_loss"):
+        loss, parts = _st._RegionLossFn.apply((q, masked, lambdas, bd, float(style_weight), float(content_weight),
+                                               content_target), *taps, feats[_st.REGION_CONTENT_TAP])
+    loss.parts = parts
+    return loss
+
+
 def compute_nnfm_loss(current_imgs, style_imgs, model, layers=('conv3_1',), *, masks=None, batch_denom=None):
     """The NNFM style term (Zhang et al., "ARF", ECCV 2022; style_transfer.nnfm_loss) of ``current_imgs`` (B,3,S,S) against
     ``style_imgs`` ((1 or B,3,Ss,Ss); one image expanded over the batch is searched as one style), summed over ``layers``

@@ -21,14 +21,14 @@ from style_transfer import *  # noqa: F401,F403
 from utils import *  # noqa: F401,F403
 from losses import *  # noqa: F401,F403
 
-from st3d.cli import REGULARISER_FLAGS, Flag, Run, load_scene, make_parser  # noqa: F401  (load_scene re-exported)
+from st3d.cli import REGION_FLAGS, REGULARISER_FLAGS, Flag, Run, load_scene, make_parser  # noqa: F401  (load_scene re-exported)
 
 FLAGS = [
     Flag("epochs", int, 3000, "passes over the view set"),
     Flag("output_path", str, "/content/output_second", "folder for log.txt, renders and the final mesh"),
     Flag("lr", float, 0.01, "Adam step size"),
     Flag("save_every", int, 1, "write current_images/*.png every N steps (reference: every step); 0 = never"),
-] + REGULARISER_FLAGS
+] + REGULARISER_FLAGS + REGION_FLAGS      # --style_regions: this script's alone
 
 
 def build_parser():
@@ -69,12 +69,15 @@ def main(argv=None):
             current = apply_background(img, cov, background_type=args.current_background, background=style)
 
             seen, seen_content = run.loss_images(current, content)     # --preserve_color luminance: their luminance
-            loss = compute_second_approach_loss(
-                current=seen, content=seen_content, style=style, model=run.vgg, style_weight=args.style_weight,
-                content_weight=args.content_weight, verts=run.opt['verts'], target_verts=run.original_verts, mesh=mesh,
-                weights=run.loss_weights, opt_type=args.optimization_target, batch_denom=vb.size,
-                style_masks=cov if args.style_mask == 'object' else None,      # this rank's views, their own coverage
-                style_scales=run.style_scales, style_scale_weights=run.style_scale_weights)    # --style_scales, default (1,)
+            if run.regions is not None:             # --style_regions, off by default: one style image per mesh region
+                loss = run.region_loss(seen, seen_content, mesh, vb)
+            else:
+                loss = compute_second_approach_loss(
+                    current=seen, content=seen_content, style=style, model=run.vgg, style_weight=args.style_weight,
+                    content_weight=args.content_weight, verts=run.opt['verts'], target_verts=run.original_verts, mesh=mesh,
+                    weights=run.loss_weights, opt_type=args.optimization_target, batch_denom=vb.size,
+                    style_masks=cov if args.style_mask == 'object' else None,      # this rank's views, their own coverage
+                    style_scales=run.style_scales, style_scale_weights=run.style_scale_weights)    # --style_scales, default (1,)
             extra = run.regularisers(current, cov, mesh, vb.hi - vb.lo, vb.size)
             if torch.is_tensor(extra):              # every weight is 0 by default: nothing is added, as in the reference
                 loss = loss + extra

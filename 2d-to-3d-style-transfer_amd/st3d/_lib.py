@@ -215,6 +215,9 @@ SIGNATURES = {
     "st3d_guidance_floats": (c_size, [c_int, c_int]),
     "st3d_guidance_partials": (c_size, [c_int, c_int]),
     "st3d_guidance_build": (c_int, [c_f32p, c_int, c_int, c_f32p, c_f32p, c_f32p, c_stream]),
+    "st3d_region_planes_floats": (c_size, [c_int, c_int, c_int]),
+    "st3d_region_planes_partials": (c_size, [c_int, c_int, c_int]),
+    "st3d_region_planes": (c_int, [c_i32p, c_u8p, c_int, c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_stream]),
     "st3d_gram_fwd_weighted": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, ctypes.c_void_p, c_size, c_f32p, c_stream]),
     "st3d_gram_fwd_multi_weighted": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, c_size, c_stream]),
     "st3d_gram_bwd_weighted": (c_int, [c_f32p, c_f32p, c_f32p, c_int, c_int, c_int, c_float, c_int, c_int, c_f32p, c_stream]),

@@ -76,6 +76,86 @@ def style_scale_weights(text):
     return weights
 
 
+def style_regions(text):
+    """--style_regions: 'material', an axis with cuts (x:0, y:-0.1,0.2) or a .npy file of one label per face -> the text,
+    once st3d.regions.parse_spec takes it"""
+    from . import regions as _regions
+    try:
+        _regions.parse_spec(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return text
+
+
+# second_approach.py's own flags (the first and third approach have no per-region loss): --style_regions and its two lists
+REGION_FLAGS = [
+    Flag("style_regions", style_regions, None, "one style image per region of the mesh (Gatys et al. 2017, spatial control): "
+         "'material' = the OBJ's usemtl groups in order of first appearance; 'x:c[,c...]' / 'y:...' / 'z:...' = slabs of the "
+         "loaded mesh cut along that axis at the face centroids (k strictly increasing cuts give k + 1 regions, a centroid "
+         "above a cut goes up); a .npy file = one integer label 0...R-1 per face.  At most 8 regions; background pixels "
+         "belong to none.  The style term is then the guided Gram loss of every region against its own image "
+         "(--region_styles), from the fragments of each step's own render; --style_path keeps serving the 'style' "
+         "backgrounds.  Not with --style_mask object, --style_scales other than 1, --nnfm_weight, --swd_weight, "
+         "--preserve_color, --supersample > 1 or several ranks.  Unset = off"),
+    Flag("region_styles", str, None, "with --style_regions: exactly one style image per region, region r takes the r-th path",
+         None, '+'),
+    Flag("region_style_weights", float, None, "with --style_regions: one finite weight >= 0 per region on its style term; "
+         "default all 1", None, '+'),
+]
+
+
+def _check_region_args(args):
+    """check_args for --style_regions / --region_styles / --region_style_weights -> None or the complaint"""
+    spec = getattr(args, "style_regions", None)
+    styles, weights = getattr(args, "region_styles", None), getattr(args, "region_style_weights", None)
+    if spec is None:
+        if styles is not None:
+            return "--region_styles needs --style_regions: without regions there is nothing to give the images to"
+        if weights is not None:
+            return "--region_style_weights needs --style_regions: without regions there is nothing to weight"
+        return None
+    from . import regions as _regions
+    if styles is None:
+        return "--style_regions needs --region_styles: one style image per region"
+    if len(styles) > _regions.MAX_REGIONS:
+        return f"--region_styles names {len(styles)} images; there are at most {_regions.MAX_REGIONS} regions"
+    if weights is not None:
+        if any(not (math.isfinite(w) and w >= 0.0) for w in weights):
+            return "--region_style_weights must be finite and >= 0"
+        if len(weights) != len(styles):
+            return (f"--region_style_weights must give one weight per region: got {len(weights)} for the {len(styles)} images "
+                    "of --region_styles")
+    parsed = _regions.parse_spec(spec)
+    if parsed[0] == "axis" and len(parsed[2]) + 1 != len(styles):
+        return (f"--style_regions {spec} makes {len(parsed[2]) + 1} regions but --region_styles names {len(styles)} images: "
+                "exactly one per region")
+    if getattr(args, "style_mask", "none") == 'object':
+        return ("--style_regions cannot be combined with --style_mask object: the regions already exclude the background, "
+                "and one region over every face is that mask")
+    if tuple(getattr(args, "style_scales", None) or (1,)) != (1,) or getattr(args, "style_scale_weights", None) is not None:
+        return ("--style_regions needs --style_scales 1: the region planes are built at the render's side only, the image "
+                "pyramid has none")
+    if getattr(args, "nnfm_weight", 0.0):
+        return "--style_regions cannot be combined with --nnfm_weight: the NNFM term has no per-region style"
+    if getattr(args, "swd_weight", 0.0):
+        return "--style_regions cannot be combined with --swd_weight: the sliced Wasserstein term has no per-region style"
+    if getattr(args, "preserve_color", "off") != "off":
+        return ("--style_regions needs --preserve_color off: the colour matching prepares one style image, the regions have "
+                "several")
+    if getattr(args, "supersample", 1) > 1:
+        return ("--style_regions needs --supersample 1: a supersampled pixel can see faces of several regions, the planes "
+                "take one face per pixel")
+    if parsed[0] == "material" and os.path.isfile(getattr(args, "obj_path", "")):
+        groups = _regions.count_material_groups(args.obj_path)
+        if groups < 2:
+            return (f"--style_regions material needs an OBJ with at least 2 usemtl groups; {args.obj_path} has {groups}, so the "
+                    "regions would be the whole object (--style_mask object does that)")
+        if groups != len(styles):
+            return (f"--style_regions material finds {groups} usemtl groups in {args.obj_path} but --region_styles names "
+                    f"{len(styles)} images: exactly one per region")
+    return None
+
+
 def edge_target_length(text):
     """--edge_target_length: a length, or the literal 'mean' (the loaded mesh's mean edge length, resolved by Run)"""
     if text == 'mean':
@@ -386,7 +466,7 @@ def check_args(args):
         if scales != (1,) and (size % scales[-1] or size // scales[-1] < _MIN_SCALE_SIDE):
             return (f"--style_scales {','.join(str(f) for f in scales)} needs --size divisible by {scales[-1]} with --size / "
                     f"{scales[-1]} >= {_MIN_SCALE_SIDE}, got --size {size}")
-    return None
+    return _check_region_args(args)
 
 
 class _Parser(argparse.ArgumentParser):
@@ -731,6 +811,9 @@ class Run:
         matched_style = None
         if self.color_mode != "off":        # the default: nothing is said, nothing runs.  Before --resume is read: a resumed
             matched_style = self.setup_color()      # run sees the same style image
+        self.regions = None
+        if getattr(args, "style_regions", None) is not None:    # the default: nothing is said, nothing runs.  Before --resume
+            self.setup_regions(verts, faces)                    # is read: a resumed run must name the same regions
         self.progress = 0               # epochs (second approach) / view batches (first approach) already done
         if args.resume:
             self.load_checkpoint(args.resume)
@@ -814,6 +897,74 @@ class Run:
         if self.main:
             u.tensor_to_image(matched).save(os.path.join(self.out_dir, 'style_matched.png'))
         return matched[0].contiguous()
+
+    def setup_regions(self, verts, faces):
+        """--style_regions: the labels of the LOADED mesh (validated once, here), one style image per region, and -- from the
+        fragments of the loaded mesh through all n_views cameras, rasterised once in batches of batch_size -- each region's
+        share of the covered pixels and the debug pictures regions/view_k.png (rank 0).  Refused under torch.distributed
+        with several ranks: the sharded sums of the term are not implemented."""
+        from . import ops as _ops
+        from . import regions as _regions
+        from . import render as _render
+        a, u = self.args, self._utils
+        if self.world > 1:
+            raise RuntimeError(f"--style_regions cannot run under torch.distributed (world size {self.world}): the per-region "
+                               "sums of a sharded batch are not implemented -- run one process")
+        parsed = _regions.parse_spec(a.style_regions)
+        materials = st3d_io.load_obj(a.obj_path, load_textures=False)[1].materials_idx if parsed[0] == "material" else None
+        labels = _regions.labels_from_spec(parsed, verts, faces, materials)
+        face_regions, R = _regions.check_face_regions(labels, int(faces.shape[0]), device=self.device)
+        if len(a.region_styles) != R:
+            raise ValueError(f"--style_regions {a.style_regions} makes {R} regions on {a.obj_path} but --region_styles names "
+                             f"{len(a.region_styles)} images: exactly one per region")
+        weights = getattr(a, "region_style_weights", None)
+        if weights is not None and len(weights) != R:
+            raise ValueError(f"--region_style_weights must give one weight per region ({R}), got {len(weights)}")
+        styles = torch.stack([u.load_as_tensor(p, size=a.size) for p in a.region_styles]).contiguous()
+        self.regions = {"spec": a.style_regions, "R": R, "labels": face_regions, "styles": styles,
+                        "weights": tuple(float(w) for w in weights) if weights is not None else None, "planes": {}}
+        faces_i32, sums = self.content_mesh.faces_i32(), []
+        v32 = verts.detach().to(torch.float32).contiguous()
+        if self.main:
+            os.makedirs(os.path.join(self.out_dir, "regions"), exist_ok=True)
+        with torch.no_grad():
+            for first in range(0, a.n_views, a.batch_size):
+                Rm, T = _render.join_cameras(self.cameras[first:min(first + a.batch_size, a.n_views)])
+                p2f = _ops.raster_fwd(_ops.project_verts(v32, Rm.to(self.device), T.to(self.device)), faces_i32, a.size)[0]
+                sums.append(_regions.region_planes(p2f, face_regions, R)[1])
+                if self.main:
+                    for k, img in enumerate(_regions.region_preview(p2f, face_regions)):
+                        u.tensor_to_image(img).save(os.path.join(self.out_dir, "regions", f"view_{first + k}.png"))
+        shares = _regions.region_shares(sums)
+        self.say(f"Style regions ({a.style_regions}): R = {R}; share of the covered pixels over {a.n_views} views: "
+                 + ", ".join(f"region {r} {100.0 * s:.1f} %" + (f" (weight {self.regions['weights'][r]:g})"
+                                                                 if weights is not None else "")
+                             for r, s in enumerate(shares)))
+
+    def region_loss(self, current, content, mesh, vb):
+        """--style_regions: compute_second_approach_loss with the per-region style term in the perceptual term's place.  The
+        planes come from the fragments of the step's own render (regions.fragments_of: the render's backward keeps them, the
+        rasteriser's FragmentCache entry when the view came from it) -- nothing is rasterised a second time; with
+        --optimization_target texture the planes of a view batch are built once and kept, with moving vertices every step."""
+        import losses as _l
+        from . import regions as _regions
+        a, g = self.args, self.regions
+        fixed = a.optimization_target == 'texture'
+        planes = g["planes"].get((vb.index, vb.lo, vb.hi)) if fixed else None
+        if planes is None:
+            p2f = _regions.fragments_of(current)
+            if p2f is None or tuple(p2f.shape) != (current.shape[0], current.shape[2], current.shape[3]):
+                raise RuntimeError("--style_regions: the render of this step kept no one-face-per-pixel fragments to label")
+            planes = _regions.region_planes(p2f, g["labels"], g["R"])
+            if fixed:
+                g["planes"][(vb.index, vb.lo, vb.hi)] = planes
+        perceptual = _l.compute_region_style_loss(current, content, g["styles"], None, g["labels"], self.vgg,
+                                                  style_weight=a.style_weight, content_weight=a.content_weight,
+                                                  region_weights=g["weights"], batch_denom=vb.size, planes=planes)
+        if a.optimization_target == 'texture':
+            return perceptual                               # no main_loss_weight here, as compute_second_approach_loss
+        return self.loss_weights['main_loss_weight'] * perceptual + _l._mesh_terms(self.opt['verts'], self.original_verts, mesh,
+                                                                                   self.loss_weights)
 
     def loss_images(self, current, content):
         """-> the (current, content) pair to hand the style terms: the inputs themselves, or under --preserve_color luminance
@@ -979,7 +1130,10 @@ class Run:
             blob["style_scale_weights"] = list(self.style_scale_weights) if self.style_scale_weights is not None else None
         if getattr(self, "color_mode", "off") != "off":     # --preserve_color: Adam's moments belong to that style image and loss
             blob["preserve_color"] = self.color_mode
-        tmp = os.path.join(self.out_dir, "checkpoint.pt.tmp")
+        if getattr(self, "regions", None) is not None:      # --style_regions: Adam's moments belong to these regions' loss
+            blob["style_regions"] = {"spec": self.regions["spec"], "R": self.regions["R"],
+                                     "weights": list(self.regions["weights"]) if self.regions["weights"] is not None else None}
+        tmp =os.path.join(self.out_dir, "checkpoint.pt.tmp")
         torch.save(blob, tmp)
         os.replace(tmp, os.path.join(self.out_dir, "checkpoint.pt"))
 
@@ -1022,6 +1176,14 @@ class Run:
         have_color, want_color = blob.get("preserve_color", "off"), getattr(self, "color_mode", "off")
         if have_color != want_color:
             raise ValueError("checkpoint was written with --preserve_color %s, this run has %s" % (have_color, want_color))
+        g = getattr(self, "regions", None)
+        have_regions = blob.get("style_regions")
+        want_regions = None if g is None else {"spec": g["spec"], "R": g["R"],
+                                               "weights": list(g["weights"]) if g["weights"] is not None else None}
+        if have_regions != want_regions:
+            described = lambda d: "no --style_regions" if d is None else "--style_regions %s (R = %d, weights %s)" % (
+                d["spec"], d["R"], d["weights"])
+            raise ValueError("checkpoint was written with %s, this run has %s" % (described(have_regions), described(want_regions)))
         with torch.no_grad():
             if self.pyramid is not None:
                 self.pyramid.load_params(blob["texture_pyramid"].to(self.device))

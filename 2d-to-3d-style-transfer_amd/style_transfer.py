@@ -141,6 +141,148 @@ def guided_gram_matrix(tensor, mask):
                      f"(sides {[int(p.shape[1]) for p in planes]})")
 
 
+# ---------------------------------------------------------------------------- style regions (csrc/regions.hip)
+REGION_STYLE_TAPS = {k: v for k, v in _DEFAULT_LAYERS.items() if v != 'conv4_2'}       # the five style taps, in module order
+REGION_CONTENT_TAP = 'conv4_2'
+
+
+def region_style_norm(C, H, W, batch_denom):
+    """the plan's normalisation of a style layer: the reference's 1 / (d h w) per layer under the mean over the batch and
+    the Gram's C x C entries"""
+    return 1.0 / (batch_denom * C * C) / (float(C) * C * H * W)
+
+
+def region_grams(taps, planes):
+    """taps: the five style taps (B,C_l,H_l,H_l); planes[r][l] of regions.region_planes -> G^[r][l] (B,C_l,C_l): the R x 5
+    guided Grams, one launch pair per region (st3d_gram_fwd_multi_weighted takes up to 8 items; a region's five are the
+    plan's own shape of call)."""
+    return [_ops.gram_fwd_multi(list(taps), qs=list(planes[r])) for r in range(len(planes))]
+
+
+_REGION_MASKED = {}         # key -> ((sums, targets): held, so the key's addresses stay theirs; the masked targets)
+_REGION_MASKED_ENTRIES = 8  # the alternating view batches of a run
+
+
+def _region_masked_targets(sums, targets, B):
+    """T[r][l] (B,C,C): region r's target Gram for the views in which the region is visible at level l (Sigma_l > 0), zeros
+    for the others -- there G^ is exactly 0 (q = 0), so D = G^ - T = 0: the (view, region, tap) adds exactly nothing to the
+    value and, q being 0, nothing to the gradient.  Kept for as long as the same planes and targets come back (a
+    texture-only run builds them once per view batch)."""
+    key = (sums.data_ptr(), sums._version, tuple(sums.shape), id(targets))
+    hit = _REGION_MASKED.get(key)
+    if hit is not None and hit[0][0] is sums and hit[0][1] is targets:
+        return hit[1]
+    seen = sums > 0                                         # (R,5,B)
+    masked = [[torch.where(seen[r, l][:, None, None], A.expand(B, -1, -1), torch.zeros((), dtype=A.dtype, device=A.device))
+               .contiguous() for l, A in enumerate(targets[r])] for r in range(len(targets))]
+    while len(_REGION_MASKED) >= _REGION_MASKED_ENTRIES:
+        _REGION_MASKED.pop(next(iter(_REGION_MASKED)))
+    _REGION_MASKED[key] = ((sums, targets), masked)
+    return masked
+
+
+class _RegionLossFn(torch.autograd.Function):
+    """(five style taps [, the content tap]) -> content_weight x content + style_weight x sum_r lambda_r sum_l norm_l
+    |G^_{r,l} - A_{r,l}|^2.  Forward: the R x 5 guided Grams, one launch pair per region, the ordered loss sums (st3d_sqdiff_sum_multi,
+    eight items a launch, content first, then r ascending and l ascending inside: the items are folded into their slots
+    in that order in fp32), and, when a gradient is wanted, per tap R calls of the accumulating st3d_gram_bwd_weighted in
+    ascending r.  Backward only scales.  -> (total, parts (3,) [total, content, style])."""
+
+    @staticmethod
+    def forward(ctx, setup, *taps):
+        planes, masked, lambdas, bd, style_weight, content_weight, content_target = setup
+        want = any(t.requires_grad for t in taps)
+        feats = [t.detach().to(torch.float32).contiguous() for t in taps]
+        style_taps, content_tap = feats[:5], (feats[5] if len(feats) > 5 else None)
+        R, B = len(planes), style_taps[0].shape[0]
+        grams = region_grams(style_taps, planes)
+        items, norms = [], []
+        if content_tap is not None:
+            items.append((content_tap, content_target, 1.0 / (bd * content_tap[0].numel()), 1, want))
+        for r in range(R):
+            for l, t in enumerate(style_taps):
+                C, H, W = t.shape[1], t.shape[2], t.shape[3]
+                norms.append(region_style_norm(C, H, W, bd))
+                items.append((grams[r][l], masked[r][l], lambdas[r] * norms[-1], 2, want))
+        out, diffs = None, []
+        for first in range(0, len(items), 8):
+            last = first + 8 >= len(items)
+            out, d = _ops.sqdiff_sum_multi(items[first:first + 8], first == 0, last, style_weight, content_weight, out=out)
+            diffs += d
+        grads = [None] * len(feats)
+        if want:
+            if content_tap is not None:
+                grads[5] = diffs[0] * (2.0 * content_weight / (bd * content_tap[0].numel()))
+                diffs = diffs[1:]
+            for l, t in enumerate(style_taps):
+                g = None
+                for r in range(R):          # ascending r: the first call writes, the others accumulate
+                    coef = 4.0 * style_weight * lambdas[r] * norms[r * 5 + l]
+                    g = _ops.gram_bwd(diffs[r * 5 + l], t, coef, out=g, q=planes[r][l])
+                grads[l] = g
+        ctx.grads = grads
+        ctx.grams = grams
+        parts = out.clone()
+        ctx.mark_non_differentiable(parts)
+        return out[0].clone(), parts
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_parts):
+        return (None,) + tuple(g * grad_out if g is not None and need else None
+                               for g, need in zip(ctx.grads, ctx.needs_input_grad[1:]))
+
+
+def check_region_weights(region_weights, R):
+    """None (all 1) or R finite numbers >= 0 -> tuple of R floats; else ValueError"""
+    if region_weights is None:
+        return (1.0,) * R
+    try:
+        w = tuple(float(x) for x in region_weights)
+    except (TypeError, ValueError):
+        raise ValueError(f"region weights must be numbers, got {region_weights!r}") from None
+    if len(w) != R:
+        raise ValueError(f"{len(w)} region weights for {R} regions: one per region")
+    if not all(x >= 0.0 and x != float("inf") for x in w):
+        raise ValueError(f"region weights must be finite and >= 0, got {w!r}")
+    return w
+
+
+def _region_check(features, planes, sums, targets, region_weights, batch_denom):
+    for name in REGION_STYLE_TAPS.values():
+        if name not in features or not torch.is_tensor(features[name]) or features[name].dim() != 4:
+            raise ValueError(f"features must hold the tap {name} as (B,C,H,W); get_features gives them")
+    taps = [features[name] for name in REGION_STYLE_TAPS.values()]
+    if not taps[0].is_cuda:
+        raise RuntimeError("st3d region_style_loss runs on the GPU (libst3d); got CPU tensors -- there is no CPU fallback")
+    R, B = len(planes), taps[0].shape[0]
+    if not 1 <= R <= 8 or len(targets) != R or any(len(p) != 5 for p in planes) or any(len(t) != 5 for t in targets):
+        raise ValueError("planes and targets must hold five entries for each of the same 1..8 regions")
+    if tuple(sums.shape) != (R, 5, B):
+        raise ValueError(f"sums must be ({R},5,{B}) -- the planes of these {B} views --, got {tuple(sums.shape)}")
+    for l, t in enumerate(taps):
+        if tuple(planes[0][l].shape) != (B, t.shape[2], t.shape[3]):
+            raise ValueError(f"the planes of level {l} are {tuple(planes[0][l].shape)}, the tap {tuple(t.shape)}")
+        if tuple(targets[0][l].shape) != (1, t.shape[1], t.shape[1]):
+            raise ValueError(f"the target of level {l} must be (1,{t.shape[1]},{t.shape[1]}), got {tuple(targets[0][l].shape)}")
+    if batch_denom is not None and not (isinstance(batch_denom, int) and not isinstance(batch_denom, bool) and batch_denom >= 1):
+        raise ValueError(f"batch_denom must be a positive integer, got {batch_denom!r}")
+    return taps, check_region_weights(region_weights, R), int(batch_denom or B)
+
+
+def region_style_loss(features, planes, sums, targets, region_weights=None, batch_denom=None):
+    """The style term over R mesh regions (Gatys et al. 2017, spatial control with one style per region):
+        sum_r lambda_r sum_l norm_l sum_b | G^_{r,l,b} - A_{r,l} |^2,   G^ = sum_p q_r[p]^2 F[:,p] F[:,p]^T,
+    ``features`` the taps of ``get_features`` over the current images, ``planes`` / ``sums`` of st3d.regions.region_planes
+    for the same views, ``targets`` of st3d.regions.region_targets, norm_l the plan's (the reference's layer weights and
+    1 / (d h w); the mean over ``batch_denom``, default B).  For one region that holds every face this is the style term
+    ``compute_perceptual_loss(style_masks=coverage)`` defines.  A (view, region, tap) whose Sigma_l is 0 -- the region is not
+    visible in that view, or vanished at that level -- adds exactly 0 to the value and to the gradient.  The sum runs in
+    ascending r in fp32 in a fixed order: two runs are bit-equal.  Gradient to ``features`` only."""
+    taps, lambdas, bd = _region_check(features, planes, sums, targets, region_weights, batch_denom)
+    masked = _region_masked_targets(sums, targets, taps[0].shape[0])
+    return _RegionLossFn.apply((planes, masked, lambdas, bd, 1.0, 0.0, None), *taps)[0]
+
+
 # ---------------------------------------------------------------------------- NNFM style loss (csrc/nnfm.hip, DESIGN.md 7)
 NNFM_LAYERS = ('conv2_1', 'conv3_1', 'conv4_1', 'conv4_2', 'conv5_1')       # names of _DEFAULT_LAYERS the term may tap
 _NNFM_MASK_RATIOS = (1, 2, 4, 8, 16)

@@ -611,6 +611,19 @@ size_t st3d_guidance_floats(int n, int S);
 size_t st3d_guidance_partials(int n, int S);
 int st3d_guidance_build(const float *mask, int n, int S, float *q_out, float *sums_out, float *partials,
                         st3d_stream_t stream);
+/* ---- style regions (default off): the guidance planes of R regions of a mesh from the fragments of a render.  For region
+ * r the level-0 plane is a_0 = 1 where pix_to_face (n,S,S; < 0 = no face) names a face f with face_region[f] == r, else 0
+ * (background pixels and labels >= R belong to no region); everything after that is st3d_guidance_build's arithmetic in
+ * its pairing and order.  q_out holds R blocks of st3d_guidance_floats(n, S) floats, block r laid out as
+ * st3d_guidance_build lays out its q_out and bit for bit what it gives for that one-hot mask; sums_out is (R,5,n),
+ * [(r * 5 + l) * n + image]; partials: st3d_region_planes_partials(n, S, R) floats of scratch.  One workgroup per 16 x 16
+ * tile and image reads pix_to_face once and takes all regions through the five levels in LDS: no (n,R,S,S) mask exists
+ * anywhere.  1 <= R <= 8, S >= 16, F >= 1; pix_to_face < F is the caller's guarantee (a larger index is read as no face).
+ * Two launches, no atomics, nothing allocated. */
+size_t st3d_region_planes_floats(int n, int S, int R);     /* R * st3d_guidance_floats(n, S); 0 for R outside 1..8 */
+size_t st3d_region_planes_partials(int n, int S, int R);   /* R * st3d_guidance_partials(n, S) */
+int st3d_region_planes(const int32_t *pix_to_face, const uint8_t *face_region, int n, int S, int F, int R, float *q_out,
+                       float *sums_out, float *partials, st3d_stream_t stream);
 /* The guided Gram  gram[b] = sum_p w[b][p] F[:,p] F[:,p]^T  computed as the Gram of q o F, q (B,HW) one plane of
  * st3d_guidance_build: both operand tiles are multiplied by q[p] on their way into LDS (no scaled copy of the activation
  * exists anywhere).  Workspace, splits, kernels' bodies and reduce are those of st3d_gram_fwd: symmetric bit for bit, and

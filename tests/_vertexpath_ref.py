@@ -317,8 +317,9 @@ class BoundNearPowerOfTwo(ValueError):
 MANTISSA_LO, MANTISSA_HI = 0.5 * (1.0 + 2.0 ** -12), 1.0 - 2.0 ** -12
 
 
-def det_scatter(index, values_f32, n_out):
-    """The fixed-point scatter-add of csrc/det.h, exactly: bound = sum |values| over ALL values of the call, scale
+def det_scatter(index, values_f32, n_out, bound=None):
+    """The fixed-point scatter-add of csrc/det.h, exactly: bound = sum |values| over ALL values of the call (or `bound`, for
+    the entry points that take theirs from the upstream gradient: the texture scatters, tests/_texpath_ref.py), scale
     2^(60 - e) with bound = m 2^e, 0.5 <= m < 1; every value quantised with round-to-nearest-even (__double2ll_rn), summed as
     int64 (any order: integer addition), converted back through fp64 to fp32 (nearest even, as the C casts).
 
@@ -331,18 +332,57 @@ def det_scatter(index, values_f32, n_out):
     assert v.dtype == F32, v.dtype
     v = v.reshape(-1).astype(F64)
     assert index.shape == v.shape
-    bound = float(np.abs(v).sum(dtype=F64))
-    assert np.isfinite(bound)
+    own = float(np.abs(v).sum(dtype=F64))
+    bound = own if bound is None else float(bound)
+    assert np.isfinite(bound) and bound >= 0.0
     k = 0
     if bound > 0.0:
         m, e = np.frexp(bound)
         if not (MANTISSA_LO <= m <= MANTISSA_HI):
             raise BoundNearPowerOfTwo(f"bound {bound!r} = {m!r} * 2^{e}")
         k = 60 - int(e)
+    assert np.abs(np.ldexp(v, k)).sum() < 2.0 ** 63              # a bound given from outside covers every partial sum
     q = np.rint(np.ldexp(v, k)).astype(np.int64)
     acc = np.zeros(n_out, np.int64)
     np.add.at(acc, index, q)
     return np.ldexp(acc.astype(F64), -k).astype(F32)
+
+
+def exact_sums(index, values, n_out):
+    """per element of the output: the exact sum of its terms (rounded once to fp64, math.fsum), the exact sum of their
+    magnitudes and the number of nonzero terms"""
+    flat, val = np.asarray(index).ravel(), np.asarray(values).ravel().astype(F64)
+    order = np.argsort(flat, kind="stable")
+    flat, val = flat[order], val[order]
+    total, mag, cnt = np.zeros(n_out, F64), np.zeros(n_out, F64), np.zeros(n_out, np.int64)
+    if flat.size == 0:
+        return total, mag, cnt
+    starts = np.nonzero(np.r_[True, flat[1:] != flat[:-1]])[0]
+    for a, b in zip(starts, np.r_[starts[1:], flat.size]):
+        total[flat[a]] = math.fsum(val[a:b])
+        mag[flat[a]] = math.fsum(np.abs(val[a:b]))
+        cnt[flat[a]] = np.count_nonzero(val[a:b])
+    return total, mag, cnt
+
+
+def assert_within_summation_bound(got, index, values, what, where):
+    """Float atomics: per element |got - sum| <= n 2^-24 sum|c|, n the number of nonzero terms of the element, sum and sum|c|
+    the exact sums of the restated fp32 terms -- the textbook bound of an fp32 summation in any order; elements without a
+    term are exactly 0.  `where(j)` describes element j for the failure message.  -> the largest error / bound ratio."""
+    got = np.asarray(got).reshape(-1)
+    total, mag, cnt = exact_sums(index, values, got.size)
+    assert cnt.max() * (cnt.max() - 1) * 2.0 ** -24 <= 1.0              # where n u sum|c| covers (n-1) u / (1 - (n-1) u)
+    zero = cnt == 0
+    assert (got[zero] == 0).all(), f"{what}: an element without a contribution is not 0"
+    err, bound = np.abs(got.astype(F64) - total), cnt * 2.0 ** -24 * mag
+    ratio = float((err[~zero] / bound[~zero]).max()) if (~zero).any() else 0.0
+    print(f"{what}: float atomics, largest error / bound over {int((~zero).sum())} elements: {ratio:.3f} (most terms: {cnt.max()})")
+    bad = np.nonzero(err > bound)[0]
+    if bad.size:
+        j = int(bad[0])
+        raise AssertionError(f"{what}: {bad.size} elements beyond n 2^-24 sum|c|; first: got {got[j]!r}, sum {total[j]!r}, "
+                             f"bound {bound[j]:.3e}; {where(j)}")
+    return ratio
 
 
 def scatter_index(b, face, faces, V):

@@ -23,8 +23,6 @@ Scenes: cow B = 2, S = 17 / 32 / 48 (partial, 2 x 2, 3 x 3 tiles); quad S = 16 (
 general path at K = 1..4 with blur, clipped barycentrics, without perspective correction, through near-plane clipped
 faces (z_clip = 0.5), and 'overflow': sub at S = 16, K = 8 -- more distinct faces in the single tile than the LDS table has
 slots, so fragments take the direct-to-global branch."""
-import math
-
 import numpy as np
 import pytest
 import torch
@@ -228,35 +226,10 @@ def test_soft_backward_fixed_point_equals_the_restatement_bit_for_bit(dev, ops, 
 
 
 # ------------------------------------------------------------------------------ (c) float atomics, summation-only bound
-def _exact_sums(idx, c9, n):
-    """per element: exact sum (rounded once to fp64), exact sum of magnitudes, number of nonzero terms"""
-    flat, val = idx.ravel(), c9.ravel().astype(F64)
-    order = np.argsort(flat, kind="stable")
-    flat, val = flat[order], val[order]
-    starts = np.nonzero(np.r_[True, flat[1:] != flat[:-1]])[0]
-    total, mag, cnt = np.zeros(n, F64), np.zeros(n, F64), np.zeros(n, np.int64)
-    for a, b in zip(starts, np.r_[starts[1:], flat.size]):
-        total[flat[a]] = math.fsum(val[a:b])
-        mag[flat[a]] = math.fsum(np.abs(val[a:b]))
-        cnt[flat[a]] = np.count_nonzero(val[a:b])
-    return total, mag, cnt
-
-
 def _float_atomics_within_the_summation_bound(ops, dev, d, ref, what):
-    n = d["B"] * d["V"] * 3
     got = _launch(ops, dev, d, ref["grads"]).reshape(-1)
-    total, mag, cnt = _exact_sums(ref["idx"], ref["c9"], n)
-    assert cnt.max() * (cnt.max() - 1) * 2.0 ** -24 <= 1.0              # where n u sum|c| covers (n-1) u / (1 - (n-1) u)
-    zero = cnt == 0
-    assert (got[zero] == 0).all(), f"{what}: an element without a contribution is not 0"
-    err, bound = np.abs(got.astype(F64) - total), cnt * 2.0 ** -24 * mag
-    ratio = float((err[~zero] / bound[~zero]).max())
-    print(f"{what}: float atomics, largest error / bound over {int((~zero).sum())} elements: {ratio:.3f} (most terms: {cnt.max()})")
-    bad = np.nonzero(err > bound)[0]
-    if bad.size:
-        j = int(bad[0])
-        raise AssertionError(f"{what}: {bad.size} elements beyond n 2^-24 sum|c|; first: got {got[j]!r}, sum {total[j]!r}, "
-                             f"bound {bound[j]:.3e}; {_where(d, ref, j)}")
+    assert got.size == d["B"] * d["V"] * 3
+    VP.assert_within_summation_bound(got, ref["idx"], ref["c9"], what, lambda j: _where(d, ref, j))
 
 
 @pytest.mark.parametrize("name,S", VP.HARD_CASES, ids=HARD_IDS)

@@ -82,6 +82,9 @@ SOURCES = {
     # the luminance, its transpose, the recombination and the affine map are compared bit for bit with their fp32 numpy
     # restatement: the only fused operations are the fmaf written in the source; no division or square root in the file
     "color.hip": ["-ffp-contract=off"],
+    # the pool, the stencil, the residual and the gradient are compared bit for bit with their fp32 numpy restatement: sums and
+    # products in the order written, none fused; the only division is by a constant at compile time
+    "lap.hip": ["-ffp-contract=off"],
     "plan.hip": [],
     "comm.hip": [],
 }

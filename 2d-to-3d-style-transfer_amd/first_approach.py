@@ -73,7 +73,8 @@ def main(argv=None):
                                                      swd_seed=args.seed if args.seed is not None else 0,
                                                      style_scales=run.style_scales,
                                                      style_scale_weights=run.style_scale_weights,
-                                                     color=run.style_color))      # --preserve_color luminance
+                                                     color=run.style_color,       # --preserve_color luminance
+                                                     lap_weight=args.lap_weight, lap_pools=args.lap_pools))
             run.save_views(targets, vb.lo)
             run.bake_targets(targets, cams, f"batch {vb.index}")      # --bake_texture, off by default
 

@@ -15,6 +15,7 @@ import os
 import torch
 from torch.nn import functional as F  # noqa: F401  (star-import surface of the reference module)
 
+from st3d import lap as _lap
 from st3d import mesh_losses as _mesh_losses
 from st3d import ops as _ops
 from st3d import render as _render
@@ -338,6 +339,29 @@ def compute_tv_loss(images, masks):
         raise ValueError("compute_tv_loss: a TexturesAtlas mesh has per-face texel blocks, which lie on no pixel grid; total "
                          "variation is defined for images (and texture maps) only")
     return _FusedLossFn.apply(_on_gpu(images), _ops.tv_loss, _on_gpu(masks).detach())
+
+
+def compute_laplacian_loss(current_imgs, content_imgs, pools=(4,), *, batch_denom=None):
+    """The Laplacian content term (Li, Xu, Nie and Chua, "Laplacian-Steered Neural Style Transfer", 2017; st3d.lap) of
+    ``current_imgs`` (B,C,H,W) against ``content_imgs`` of the same shape: for every pool side p of ``pools`` (strictly
+    increasing, from 1, 2, 4, 8, 16, each dividing H and W with pooled sides >= 2) the mean over (batch, channel, pooled pixel)
+    of (D(pool_p(current)) - D(pool_p(content)))^2, D the 5-point Laplacian with a replicate border, every channel on its
+    own; the terms are added in ascending p.  The targets D(pool_p(content)) carry no gradient and are cached on the content
+    tensor's identity and version.  ``batch_denom`` is the global batch when the views are sharded.  Value and
+    d/d current_imgs come from one fused pass per pool side."""
+    if not torch.is_tensor(current_imgs) or not torch.is_tensor(content_imgs):
+        raise TypeError("current_imgs and content_imgs must be tensors")
+    if current_imgs.dim() != 4 or tuple(content_imgs.shape) != tuple(current_imgs.shape):
+        raise ValueError(f"current_imgs and content_imgs must be (B,C,H,W) tensors of one shape, got {tuple(current_imgs.shape)} "
+                         f"and {tuple(content_imgs.shape)}")
+    pools = _lap.check_pools(pools, tuple(current_imgs.shape[2:]))
+    _on_gpu(content_imgs)
+    targets = [_lap.lap_target_cached(content_imgs, p) for p in pools]
+    return _FusedLossFn.apply(_on_gpu(current_imgs), _lap_op, targets, pools, batch_denom)
+
+
+def _lap_op(x, targets, pools, batch_denom, want_grad=True):
+    return _lap.lap_term(x, targets, pools, batch_denom, want_grad)
 
 
 def texture_l2_loss(mesh, original_map):

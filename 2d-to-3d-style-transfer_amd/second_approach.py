@@ -95,6 +95,10 @@ def main(argv=None):
             if torch.is_tensor(style_term):
                 loss = loss + style_term
 
+            detail_term = run.lap_term(seen, seen_content, vb.size)     # --lap_weight, off by default
+            if torch.is_tensor(detail_term):
+                loss = loss + detail_term
+
             if args.save_every and steps_done % args.save_every == 0:
                 run.save_views(current, vb.lo)          # encoded by worker threads, off the step's critical path
 

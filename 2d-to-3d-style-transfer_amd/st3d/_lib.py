@@ -279,6 +279,11 @@ SIGNATURES = {
     "st3d_pyr_down_fwd": (c_int, [c_f32p, c_int, c_int, c_int, c_f32p, c_stream]),
     "st3d_pyr_down_bwd": (c_int, [c_f32p, c_int, c_int, c_int, c_f32p, c_stream]),
     "st3d_pyr_down_need": (c_int, [c_u8p, c_int, c_int, c_int, c_u8p, c_stream]),
+    "st3d_lap_tile": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "st3d_lap_workspace_bytes": (c_size, [c_int, c_int, c_int, c_int]),
+    "st3d_lap_fwd": (c_int, [c_f32p, c_int, c_int, c_int, c_int, c_f32p, c_stream]),
+    "st3d_lap_loss": (c_int, [c_f32p, c_f32p, c_int, c_int, c_int, c_int, ctypes.c_double, ctypes.c_void_p, c_size, c_f32p, c_f32p,
+                              c_stream]),
     "st3d_color_stats_chunk": (c_int, []),
     "st3d_luma_fwd": (c_int, [c_f32p, c_int, c_size, c_f32p, c_stream]),
     "st3d_luma_bwd": (c_int, [c_f32p, c_int, c_size, c_f32p, c_stream]),

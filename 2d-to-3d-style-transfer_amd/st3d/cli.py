@@ -76,6 +76,21 @@ def style_scale_weights(text):
     return weights
 
 
+_LAP_POOLS = (1, 2, 4, 8, 16)       # st3d.lap.POOLS
+LAP_POOLS_DEFAULT = (4,)
+
+
+def lap_pools(text):
+    """--lap_pools: a comma list of strictly increasing pool sides from 1,2,4,8,16 -> the tuple"""
+    try:
+        pools = tuple(int(s.strip()) for s in text.split(','))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected a comma list of pool sides from 1,2,4,8,16, got {text!r}")
+    if any(p not in _LAP_POOLS for p in pools) or any(b <= a for a, b in zip(pools, pools[1:])):
+        raise argparse.ArgumentTypeError(f"expected strictly increasing pool sides from 1,2,4,8,16, got {text!r}")
+    return pools
+
+
 def style_regions(text):
     """--style_regions: 'material', an axis with cuts (x:0, y:-0.1,0.2) or a .npy file of one label per face -> the text,
     once st3d.regions.parse_spec takes it"""
@@ -283,6 +298,16 @@ SHARED_FLAGS = [
          "equal those of the loaded mesh seen through the run's cameras; 'luminance' shows every style and content term the "
          "luminance of render, content and style only, and at export puts the optimised luminance back under the loaded "
          "colours.  Both write style_matched.png.  --optimization_target texture / both", _COLOR_MODES),
+    Flag("lap_weight", float, 0.0, "weight of the Laplacian content term (Li et al. 2017, 'Laplacian-Steered Neural Style "
+         "Transfer'): the mean squared difference between the 5-point Laplacian of the average-pooled render and that of the "
+         "average-pooled content render, per channel.  Keeps the fine detail of the asset (eyes, panel lines, print) that the "
+         "conv4_2 content term does not see, when --nnfm_weight or --swd_weight pull hard.  The term is a mean over residuals "
+         "of [0,1] images, so small weights do nothing: below about 1e3 it cannot matter next to --style_weight 1e6 (the useful "
+         "range is not measured yet, DESIGN.md 7).  Needs --content_background "
+         "equal to --current_background and neither 'noise'.  One fused pass per pool side and step; 0 = off"),
+    Flag("lap_pools", lap_pools, LAP_POOLS_DEFAULT, "pool sides of the Laplacian content term, a comma list of strictly "
+         "increasing values from 1,2,4,8,16; their terms are added.  --size must be divisible by each and leave a pooled side "
+         ">= 2.  Needs --lap_weight"),
 ]
 
 # the fitting phase of first_approach.py / third_approach.py only: each script adds them to its own table
@@ -466,7 +491,32 @@ def check_args(args):
         if scales != (1,) and (size % scales[-1] or size // scales[-1] < _MIN_SCALE_SIDE):
             return (f"--style_scales {','.join(str(f) for f in scales)} needs --size divisible by {scales[-1]} with --size / "
                     f"{scales[-1]} >= {_MIN_SCALE_SIDE}, got --size {size}")
+    complaint = _check_lap_args(args)
+    if complaint:
+        return complaint
     return _check_region_args(args)
+
+
+def _check_lap_args(args):
+    """--lap_weight / --lap_pools against each other, --size and the backgrounds -> None or the complaint"""
+    lap = getattr(args, "lap_weight", 0.0)
+    if not (math.isfinite(lap) and lap >= 0.0):
+        return "--lap_weight must be finite and >= 0"
+    pools = tuple(getattr(args, "lap_pools", None) or LAP_POOLS_DEFAULT)
+    if not lap:
+        if pools != LAP_POOLS_DEFAULT:
+            return "--lap_pools needs --lap_weight"
+        return None
+    size = getattr(args, "size", 0)
+    for p in pools:
+        if size % p or size // p < 2:
+            return (f"--lap_pools {','.join(str(q) for q in pools)} needs --size divisible by {p} with --size / {p} >= 2, got "
+                    f"--size {size}")
+    content_bg, current_bg = getattr(args, "content_background", "white"), getattr(args, "current_background", "white")
+    if content_bg != current_bg or 'noise' in (content_bg, current_bg):
+        return (f"--lap_weight needs --content_background equal to --current_background and neither 'noise' (got {content_bg} "
+                f"and {current_bg}): the term compares whole images, and differing backgrounds would be counted as lost content")
+    return None
 
 
 class _Parser(argparse.ArgumentParser):
@@ -806,6 +856,13 @@ class Run:
             weights = self.style_scale_weights or (1.0,) * len(self.style_scales)
             self.say("Style scales: " + ", ".join(f"1/{f} (plan side {args.size // f}, weight {w:g})"
                                                    for f, w in zip(self.style_scales, weights)))
+        self.lap_pools = None
+        if getattr(args, "lap_weight", 0.0):        # off (the default): nothing is said, nothing runs
+            from . import lap as st3d_lap
+            self.lap_pools = st3d_lap.check_pools(getattr(args, "lap_pools", None) or LAP_POOLS_DEFAULT, args.size)
+            st3d_lap.reserve_cache(len(self.lap_pools) * -(-args.n_views // args.batch_size))
+            self.say("Laplacian content term: weight %g, " % args.lap_weight
+                     + ", ".join(f"pool {p} (pooled side {args.size // p})" for p in self.lap_pools))
         self.color_mode = getattr(args, "preserve_color", "off")
         self._utils = _u
         matched_style = None
@@ -1128,6 +1185,8 @@ class Run:
         if getattr(self, "multi_scale", False):     # --style_scales: no state of its own, but Adam's moments belong to that loss
             blob["style_scales"] = list(self.style_scales)
             blob["style_scale_weights"] = list(self.style_scale_weights) if self.style_scale_weights is not None else None
+        if getattr(self, "lap_pools", None) is not None:    # --lap_weight: no state of its own, but Adam's moments belong to that loss
+            blob["lap_pools"] = list(self.lap_pools)
         if getattr(self, "color_mode", "off") != "off":     # --preserve_color: Adam's moments belong to that style image and loss
             blob["preserve_color"] = self.color_mode
         if getattr(self, "regions", None) is not None:      # --style_regions: Adam's moments belong to these regions' loss
@@ -1173,6 +1232,10 @@ class Run:
         if have_scales != want_scales:
             raise ValueError("checkpoint was written with --style_scales %s (weights %s), this run has %s (weights %s)"
                              % (have_scales + want_scales))
+        have_pools, want_pools = blob.get("lap_pools"), getattr(self, "lap_pools", None)
+        if (list(have_pools) if have_pools is not None else None) != (list(want_pools) if want_pools is not None else None):
+            described = lambda q: "no --lap_weight" if q is None else "--lap_weight and --lap_pools %s" % ",".join(str(p) for p in q)
+            raise ValueError("checkpoint was written with %s, this run has %s" % (described(have_pools), described(want_pools)))
         have_color, want_color = blob.get("preserve_color", "off"), getattr(self, "color_mode", "off")
         if have_color != want_color:
             raise ValueError("checkpoint was written with --preserve_color %s, this run has %s" % (have_color, want_color))
@@ -1240,6 +1303,18 @@ class Run:
         masks = cov if getattr(a, "style_mask", "none") == 'object' else None
         return a.nnfm_weight * _l.compute_nnfm_loss(current, style, self.vgg, layers=a.nnfm_layers, masks=masks,
                                                     batch_denom=batch_size)
+
+    def lap_term(self, seen, seen_content, batch_size):
+        """--lap_weight x this rank's share of the batch mean of the Laplacian content term of the renders `seen` against the
+        content renders `seen_content` over --lap_pools (losses.compute_laplacian_loss) -- both as the other terms see them
+        (loss_images: the luminance under --preserve_color luminance).  An image term like nnfm_term: divided by the GLOBAL
+        batch, nothing on a rank without views, and with weight 0 (the default) nothing runs at all.  The term stays at full
+        resolution.  Checkpoints record the pools (lap_pools)."""
+        a = self.args
+        if not getattr(a, "lap_weight", 0.0) or seen is None or seen.shape[0] == 0:
+            return 0
+        import losses as _l
+        return a.lap_weight * _l.compute_laplacian_loss(seen, seen_content, self.lap_pools, batch_denom=batch_size)
 
     def swd_term(self, current, cov, style, batch_size):
         """--swd_weight x this rank's share of the batch mean of the sliced Wasserstein style term of the `current` renders

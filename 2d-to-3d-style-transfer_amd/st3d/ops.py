@@ -1687,6 +1687,11 @@ from .imgpyr import pyr_down_bwd, pyr_down_fwd, pyr_down_need, pyr_down_tile  # 
 from .color import color_affine, color_stats_chunk, color_sums, luma_bwd, luma_fwd, luma_recombine  # noqa: E402,F401
 
 
+# ------------------------------------------------------------------ Laplacian content term (csrc/lap.hip)
+# As above: the device wrappers live in st3d/lap.py next to the pool checks and the target cache.
+from .lap import lap_fwd, lap_loss, lap_tile  # noqa: E402,F401
+
+
 # ------------------------------------------------------------------ mip-mapped sampling (csrc/mipmap.hip)
 MIP_MAX_LEVELS = 16
 

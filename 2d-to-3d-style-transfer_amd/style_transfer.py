@@ -13,6 +13,7 @@ import torch
 import torch.optim as optim  # noqa: F401  (star-import surface of the reference module)
 from tqdm import tqdm
 
+from st3d import lap as _lap
 from st3d import ops as _ops
 from st3d import optim as _st3d_optim
 from st3d import vgg as _vgg
@@ -539,9 +540,22 @@ def _swd_term(current_imgs, style_imgs, model, layers, masks, batch_denom, direc
     return total
 
 
+def check_lap_pools(pools, side=None):
+    """the pool sides of the Laplacian content term: a non-empty, strictly increasing sequence from (1, 2, 4, 8, 16), each
+    dividing ``side`` (an int or (H, W)) with a pooled side >= 2; -> a tuple of int, else ValueError"""
+    return _lap.check_pools(pools, side)
+
+
+def laplacian_targets(content_imgs, pools):
+    """[D(pool_p(content)) for p in pools] without gradient, cached on the content tensor's identity and version
+    (st3d.lap.lap_target_cached): the targets of the Laplacian content term, computed once per content batch"""
+    return [_lap.lap_target_cached(content_imgs, p) for p in pools]
+
+
 def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, steps=2000, style_weight=1e6, content_weight=1, lr=0.003,
                    style_masks=None, nnfm_weight=0.0, nnfm_layers=('conv3_1',), swd_weight=0.0, swd_layers=SWD_DEFAULT_LAYERS,
-                   swd_directions=0, swd_seed=0, style_scales=(1,), style_scale_weights=None, color='rgb'):
+                   swd_directions=0, swd_seed=0, style_scales=(1,), style_scale_weights=None, color='rgb', lap_weight=0.0,
+                   lap_pools=(4,)):
     # style_masks (B,1,S,S) | (B,S,S) in [0,1], e.g. the coverage of the renders being stylised: the guided style loss --
     # each tap's Gram of the optimised images is taken over the masked region only (default None: the reference's loss)
     # nnfm_weight > 0: every step adds nnfm_weight x the NNFM term over nnfm_layers (its own partial VGG forward and backward
@@ -579,6 +593,14 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
     if color not in ('rgb', 'luminance'):
         raise ValueError(f"color must be 'rgb' or 'luminance', got {color!r}")
     luminance = color == 'luminance'
+    # lap_weight > 0: every step adds lap_weight x the gradient of the Laplacian content term over lap_pools
+    # (losses.compute_laplacian_loss; one fused pass per pool side, targets set once) before Adam.  Under 'luminance' the
+    # term compares the luminance images.  0: nothing of it runs.
+    lap_weight = float(lap_weight)
+    if not (lap_weight >= 0.0 and lap_weight != float("inf")):
+        raise ValueError("lap_weight must be finite and >= 0")
+    if lap_weight:
+        lap_pools = check_lap_pools(lap_pools, tuple(initial_optimized_imgs.shape[2:]))
 
     # Ensure content_imgs and style_imgs are batched tensors
     assert initial_optimized_imgs.shape[0] == content_imgs.shape[0] == style_imgs.shape[0]
@@ -619,6 +641,7 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
                 coarse.append((f, w, p, _imgpyr.reduce(style_masks.reshape(B, 1, S, S), f) if style_masks is not None else None))
     nnfm_style_imgs = style_imgs.to(device) if nnfm_weight else None      # one tensor for the run: its taps are cached on it
     swd_style_imgs = style_imgs.to(device) if swd_weight else None
+    lap_targets = laplacian_targets(content_imgs.to(device), lap_pools) if lap_weight else None
 
     # Initialize target images  --> the ones to optimize
     optimized_imgs = initial_optimized_imgs.clone().detach().to(device).contiguous().requires_grad_(True)
@@ -657,6 +680,9 @@ def style_transfer(initial_optimized_imgs, content_imgs, style_imgs, model, step
                              swd_draw(swd_layers, swd_k, swd_generator, device))
             (extra,) = torch.autograd.grad(term, seen)
             grad = grad + swd_weight * back(extra)
+        if lap_weight:
+            _, extra = _lap.lap_term(seen.detach(), lap_targets, lap_pools)
+            grad = grad + lap_weight * back(extra)
         optimized_imgs.grad = grad
         optimizer.step()
 

@@ -1275,6 +1275,33 @@ int st3d_color_affine(const float *x, const float *A9, const float *b3, int clam
 int st3d_color_stats(const float *x, const uint8_t *mask, int B, size_t P, double *partials, double *out10,
                      st3d_stream_t stream);
 
+/* ------------------------------------------------------------------ Laplacian content term (lap.hip)
+ * Li, Xu, Nie and Chua 2017: the squared difference between the Laplacian of the average-pooled image and a target.  A
+ * stack of N planes (H,W) fp32 (every channel on its own) and a pool side p in {1,2,4,8,16} that divides H and W, with
+ * h = H/p >= 2, w = W/p >= 2 and sides <= 32768.  Every argument is checked on the host before any launch (null or aliased
+ * pointers, bad sides, bad p, a grid that does not fit one dimension, a workspace too small: ST3D_E_INVALID, nothing
+ * launched); nothing is allocated.  No atomics: two calls give the same bits.  The arithmetic, fp32 unless stated, nothing
+ * fused (tests/_lapref.py restates it in numpy):
+ *   pool:  s_r = ((x(ip+r, jp) + x(ip+r, jp+1)) + ...) + x(ip+r, jp+p-1) for the p rows of the block, left to right;
+ *          P(i,j) = ((s_0 + s_1) + ... + s_{p-1}) * (1/p^2), top to bottom, one product with the exact constant.  p = 1: P = x.
+ *   D:     L(i,j) = 4 P(i,j) - ((P(i-1,j) + P(i+1,j)) + (P(i,j-1) + P(i,j+1))), indices clamped to the plane.  D is symmetric.
+ *   lap_fwd:  out (N,h,w) = D(pool_p(x)).
+ *   lap_loss: r = D(pool_p(x)) - target, target (N,h,w);  loss[0] = fp32(scale * sum r^2), the squares and the sum in fp64:
+ *          a workgroup of 256 threads owns one tile of st3d_lap_tile(p) fine pixels, i.e. (tile_h/p) x (tile_w/p) cells
+ *          numbered row-major; thread t adds the cells t, t + 256, ... of the tile that lie on the plane in ascending
+ *          order, the 256 sums are folded by halving strides (128 ... 1); workgroups are numbered plane-major, then tile row,
+ *          then tile column; the finishing launch has thread t add the partials t, t + 256, ... and folds the same way.
+ *          grad (N,H,W), or NULL for the value alone: grad(y,x) = k * D(r)(y/p, x/p), k = fp32(2 scale / p^2) formed on
+ *          the host, one product per cell.  scale is finite and >= 0.
+ *          workspace: st3d_lap_workspace_bytes(N,H,W,p) bytes of device scratch, 8-byte aligned, written before it is
+ *          read (the partials, and r at pooled size).  Launches: 3 with grad, 2 without.
+ *   st3d_lap_workspace_bytes: 0 for arguments the calls refuse. */
+int st3d_lap_tile(int p, int *tile_h, int *tile_w);
+size_t st3d_lap_workspace_bytes(int N, int H, int W, int p);
+int st3d_lap_fwd(const float *x, int N, int H, int W, int p, float *out, st3d_stream_t stream);
+int st3d_lap_loss(const float *x, const float *target, int N, int H, int W, int p, double scale, void *workspace,
+                  size_t workspace_bytes, float *loss, float *grad, st3d_stream_t stream);
+
 /* ------------------------------------------------------------------ multi-GPU
  * One process per GPU; every rank renders / VGGs its slice of the view batch with the loss means divided by the GLOBAL
  * batch (batch_denom of st3d_plan_loss) and ONE SUM all-reduce of the flat fp32 gradient (3*T*T texture floats
